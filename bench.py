@@ -13,8 +13,15 @@ neither several streams nor an environment variable.
 touches the GPU); under torchrun it is one rank.  Prints ONE JSON line on rank 0.
 
 The 8 images of a step are 8 DIFFERENT BBBC039-like images (ellipses at the centres / areas of eight of the reference's per-image
-regression tables, 68 .. 170 objects).  The default run also measures the other BASELINE.json configs (`extras.configs`: GOWT1-like
-frame, NIH3T3-like image set through the stage, synthetic 4096^2), each with its launch time, solves/s and roofline fraction.
+regression tables, 68 .. 170 objects).
+
+A plain run sets up, warms up, times EXACTLY --steps steps once, and prints the line.  --full measures everything else as well: the
+timed region repeated (--repeats, --min-gpu-seconds; median), the kernel timing and roofline, the extras (stage, compute_objects,
+preprocessing, worker processes per card), the other BASELINE.json configs (`extras.configs`: GOWT1-like frame, NIH3T3-like image set
+through the stage, synthetic 4096^2, each with its launch time, solves/s and roofline fraction) and the CPU baseline.
+
+--dump-outputs DIR writes what the last timed step computed (the candidate records and a fixed sample of the foreground masks) as
+.npy files: the inputs are seeded, so two builds can be compared output for output.
 
 Other workloads: --workload {gowt1_like,nih3t3_like,synthetic4096,synthetic512,synthetic256} (one image per step unless --images);
 --mode image_set: BASELINE.json configs[3] -- a set of NIH3T3-like images dealt to the ranks, every rank runs the
@@ -45,16 +52,19 @@ def parse():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--workload', default='bbbc039_like')
     ap.add_argument('--mode', default='solves', choices=['solves', 'image_set', 'sharded'])
-    ap.add_argument('--min-gpu-seconds', type=float, default=2.0, help='the timed regions are repeated until they add up to this much (so that an outside sampler of GPU activity sees the run)')
-    ap.add_argument('--no-configs', action='store_true', help='skip the other BASELINE.json configs in extras')
+    ap.add_argument('--full', action='store_true', help='measure everything beside the headline figure as well: repeated timed regions, kernel timing and roofline, '
+                                                            'extras, the other BASELINE.json configs, the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed to DIR/<name>.npy (float64 / float32)')
+    ap.add_argument('--min-gpu-seconds', type=float, default=2.0, help='--full: the timed regions are repeated until they add up to this much (so that an outside sampler of GPU activity sees the run)')
+    ap.add_argument('--no-configs', action='store_true', help='--full: skip the other BASELINE.json configs in extras')
     ap.add_argument('--same-layout', action='store_true', help='the step of rounds 1-2: 8 copies of ONE BBBC039-like image (layout 0) instead of 8 different ones')
     ap.add_argument('--images', type=int, default=None, help='images per plan = per step (default: 8 for bbbc039_like / synthetic256, else 1)')
     ap.add_argument('--max-size', type=int, default=3, help='candidates = connected atom subsets up to this size + universes')
-    ap.add_argument('--repeats', type=int, default=5, help='the timed region of --steps steps is repeated; the median is reported')
+    ap.add_argument('--repeats', type=int, default=5, help='--full, and the image_set / sharded modes: the timed region of --steps steps is repeated; the median is reported')
     ap.add_argument('--cpu-seconds', type=float, default=12.0, help='budget of each CPU baseline variant')
-    ap.add_argument('--no-cpu', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the stage / compute_objects / preprocessing timings')
-    ap.add_argument('--no-ranks-per-gpu', action='store_true', help='skip the child runs of the stage with 1 / 2 / 4 worker processes on the card (extras)')
+    ap.add_argument('--no-cpu', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='--full: skip the stage / compute_objects / preprocessing timings')
+    ap.add_argument('--no-ranks-per-gpu', action='store_true', help='--full: skip the child runs of the stage with 1 / 2 / 4 worker processes on the card (extras)')
     ap.add_argument('--inflight', type=int, default=1, help='independent steps in flight on separate streams (1 = strictly sequential launches)')
     ap.add_argument('--images-workload-explicit', action='store_true', help='image_set mode: take --workload literally (default: bbbc039_like means the NIH3T3-like set of BASELINE.json configs[3])')
     ap.add_argument('--ranks-per-gpu', type=int, default=1, help='worker processes per GPU (image sets are host bound per process: several processes share a card; gloo moves the small results)')
@@ -150,6 +160,33 @@ def cpu_stage_wall(scene, beta, pruning):
     return dt * 1e3, data['performance'].overall_computed_object_count
 
 
+DUMP_MASK_BYTES = 48 << 20         # float32 mask pixels; the records of a step add a few MB, the whole dump stays under 64 MB
+
+
+def dump_outputs(out_dir, recs, region_boxes, fragments):
+    """--dump-outputs: what a caller of the timed path receives -- every field of the candidate records (records_<field>.npy, float64)
+    and the foreground fragments (offset, bool array).  The fragments of a seeded sample of the candidates are concatenated row-major into
+    masks.npy (float32 0 / 1) with masks_candidates / masks_origin / masks_shape; the sample is drawn from the region boxes of the plan
+    (a fragment lies inside its region's box), which depend on the inputs alone, so every build dumps the same candidates.
+    ``fragments(select)`` returns the (offset, array) pairs of the candidates, at least of those selected."""
+    os.makedirs(out_dir, exist_ok=True)
+    save = lambda name, a: np.save(os.path.join(out_dir, f'{name}.npy'), a)
+    for name in recs.dtype.names:
+        if name != 'reserved':
+            save(f'records_{name}', recs[name].astype(np.float64))
+    n = len(recs)
+    box_bytes = 4 * np.maximum(1, region_boxes[:n, 2].astype(np.int64) * region_boxes[:n, 3])
+    order = np.random.default_rng(0).permutation(n)
+    take = np.sort(order[np.cumsum(box_bytes[order]) <= DUMP_MASK_BYTES])
+    sel = np.zeros(n, bool)
+    sel[take] = True
+    frags = fragments(sel)
+    save('masks_candidates', take.astype(np.float64))
+    save('masks_origin', np.array([frags[i][0] for i in take], np.float64).reshape(-1, 2))
+    save('masks_shape', np.array([frags[i][1].shape for i in take], np.float64).reshape(-1, 2))
+    save('masks', np.concatenate([frags[i][1].ravel() for i in take] + [np.zeros(0, bool)]).astype(np.float32))
+
+
 def source_hash():
     h = hashlib.sha1()
     d = os.path.join(ROOT, 'superdsm_amd', 'csrc')
@@ -241,7 +278,7 @@ def main():
     if args.mode == 'sharded':
         return sharded_mode(args, world, rank, backend, n_gpus_used)
 
-    from superdsm_amd import _capi, engine, testing
+    from superdsm_amd import engine, testing
     from superdsm_amd import dist as sdist
 
     n_images = args.images if args.images else (8 if args.workload in ('bbbc039_like', 'synthetic256') else 1)
@@ -259,8 +296,6 @@ def main():
     streams = [torch.cuda.Stream() for _ in range(nfl)]
     sizes = [[batches[0].records_dev.numel(), batches[0].masks_dev.numel()]] * world       # every rank has the same plan: nothing to exchange
     gathers = [sdist.RecordGather(b, world, rank, sizes=sizes) if world > 1 else None for b in batches]
-    batch = batches[0]
-    L = _capi.lib()
 
     def step(i):
         k = i % nfl
@@ -279,7 +314,7 @@ def main():
         step(i)
     torch.cuda.synchronize()
     region_ms = []
-    n_regions = max(1, args.repeats)
+    n_regions = max(1, args.repeats) if args.full else 1
     while len(region_ms) < n_regions:          # the timed region: EXACTLY --steps steps, barrier + synchronize on both sides
         if world > 1:
             dist.barrier()
@@ -296,28 +331,15 @@ def main():
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt = float(tmax.item())
         region_ms.append(dt * 1e3)
-        if len(region_ms) == n_regions and sum(region_ms) < args.min_gpu_seconds * 1e3 and n_regions < 400:
+        if args.full and len(region_ms) == n_regions and sum(region_ms) < args.min_gpu_seconds * 1e3 and n_regions < 400:
             n_regions = min(400, max(n_regions + 1, int(np.ceil(args.min_gpu_seconds * 1e3 / np.median(region_ms)))))   # (the same count on every rank: the times are all-reduced)
     dt = float(np.median(region_ms)) * 1e-3
-
-    # kernel-level timing with HIP events on the launch stream (one launch at a time)
-    L.sdsm_enable_kernel_timing(1)
-    solve_ms, setup_ms = [], []
-    for _ in range(5):
-        batch.launch()
-        solve_ms.append(L.sdsm_last_solve_kernel_ms())
-        setup_ms.append(L.sdsm_last_setup_kernel_ms())
-    L.sdsm_enable_kernel_timing(0)
-    recs = batch.records()
+    last = batches[(args.steps - 1) % nfl]     # the batch of the last timed step
+    recs = last.records()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, recs, last.mask_info, lambda sel: last.fragments(recs, select=sel))
     n_total = len(fps) * world
     value = n_total * args.steps / dt
-    alg_bytes = engine.algorithmic_bytes(recs, batch.mask_info)
-    kern_ms = float(np.mean(solve_ms))
-    achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
-    evals = recs['evals_value'].astype(np.int64) + recs['evals_full'].astype(np.int64)
-    # FP64-vector cross-check of the Hessian phase: flops_c = E_c N_c (4 (6 + z) + 20) + H_c N_c (6 + z)^2, z ~ 11
-    z = 11.0
-    flops = float((evals * recs['n_pixels'] * (4 * (6 + z) + 20)).sum() + (recs['evals_full'].astype(np.int64) * recs['n_pixels'] * (6 + z) ** 2).sum())
     out = {
         'metric': 'candidate DSM solves/sec', 'value': value, 'unit': 'candidate solves/s', 'n_gpus': n_gpus_used, 'steps': args.steps,
         'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
@@ -334,28 +356,19 @@ def main():
                                   if world > 1 else 'single GPU',
                    'steps_in_flight': nfl, 'timed_regions': len(region_ms), 'timed_regions_ms_min_median_max': [float(np.min(region_ms)), float(np.median(region_ms)), float(np.max(region_ms))],
                    'timed_seconds_total': float(sum(region_ms) * 1e-3), 'value_is': 'median over the timed regions'},
-        'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': 8000.0, 'unit': 'GB/s', 'frac': achieved / 8000.0,
-                     'traffic': measured_traffic(args.workload, n_images),
-                     'kernel': 'sdsm_k_solve: the size classes of one launch, which run concurrently on four queues (class 1 <128, 2560, .., 192> holds '
-                               f'{int(((recs["n_deform"] + 6 <= 128)).sum())} of the {len(recs)} candidates; the longest chains are the workgroup groups of the 10-17 k-pixel clusters and class 1b); '
-                               'kernel_ms = HIP events on the launch stream from the end of sdsm_k_setup to the join of the classes (includes sdsm_k_setup_rows, the rows of G~ of the '
-                               'regions above 4096 pixels); per-class rocprofv3 averages: profiles/r04_kernel_stats.csv',
-                     'kernel_ms': kern_ms, 'setup_kernel_ms': float(np.mean(setup_ms)), 'algorithmic_bytes_per_launch': alg_bytes,
-                     'achieved_in_timed_region': alg_bytes / (dt / args.steps) / 1e9,
-                     'fp64_vector_tflops': flops / (kern_ms * 1e-3) / 1e12, 'fp64_vector_frac_of_78.6': flops / (kern_ms * 1e-3) / 1e12 / 78.6,
-                     'pixel_evaluations_per_launch': int((evals * recs['n_pixels']).sum()),
-                     'pixel_evaluations_per_image': int((evals * recs['n_pixels']).sum() // n_images),
-                     'algorithmic_bytes_definition': 'SURVEY.md 8(d): sum over candidates of E_c (12 N_c + 8 (6 + M_c)) + 12 N_c + ceil(bbox_c / 8) + 128, E_c = passes over the pixels actually made'},
+        'roofline': None,
         'status_counts': {str(k): int(v) for k, v in zip(*np.unique(recs['status'], return_counts=True))},
         # candidates whose region is separable or all but (psi below 1e-4 of the empty model's N ln 2: "no energy"): status optimal, but inf psi = 0 is not attained and the value is the stopping
         # rule's -- what cvxopt would report there is unpinned; they never win a set cover (beta >= 100)
         'near_separable_candidates': int((recs['energy'] < 1e-4 * recs['n_pixels'] * np.log(2)).sum()),
     }
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full:
+        out['roofline'] = roofline(args, batches[0], recs, dt, n_images)
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         out['extras'] = extras(args, scene, imgs[0], n_images, scenes)
         if not args.no_configs and args.workload == 'bbbc039_like':
             out['extras']['configs'] = other_configs(args)
-    if rank == 0 and not args.no_cpu and world == 1:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         out['cpu_baseline'] = cpu_baseline(scenes, args.cpu_seconds)
         if 'extras' in out and args.workload in ('bbbc039_like', 'synthetic256'):
             ms, ncomp = cpu_stage_wall(scene, 150.0, 'isbi24')
@@ -367,6 +380,38 @@ def main():
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+
+
+def roofline(args, batch, recs, dt, n_images):
+    """--full: kernel-level timing with HIP events on the launch stream (one launch at a time) and the roofline figures of the step."""
+    from superdsm_amd import _capi, engine
+    L = _capi.lib()
+    L.sdsm_enable_kernel_timing(1)
+    solve_ms, setup_ms = [], []
+    for _ in range(5):
+        batch.launch()
+        solve_ms.append(L.sdsm_last_solve_kernel_ms())
+        setup_ms.append(L.sdsm_last_setup_kernel_ms())
+    L.sdsm_enable_kernel_timing(0)
+    alg_bytes = engine.algorithmic_bytes(recs, batch.mask_info)
+    kern_ms = float(np.mean(solve_ms))
+    achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
+    evals = recs['evals_value'].astype(np.int64) + recs['evals_full'].astype(np.int64)
+    # FP64-vector cross-check of the Hessian phase (SURVEY.md 8d): flops_c = E_c N_c (4 (6 + z) + 20) + H_c N_c (6 + z)^2, z ~ 11
+    z = 11.0
+    flops = float((evals * recs['n_pixels'] * (4 * (6 + z) + 20)).sum() + (recs['evals_full'].astype(np.int64) * recs['n_pixels'] * (6 + z) ** 2).sum())
+    return {'bound': 'hbm', 'achieved': achieved, 'peak': 8000.0, 'unit': 'GB/s', 'frac': achieved / 8000.0,
+            'traffic': measured_traffic(args.workload, n_images),
+            'kernel': 'sdsm_k_solve: the size classes of one launch, which run concurrently on four queues (class 1 <128, 2560, .., 192> holds '
+                      f'{int(((recs["n_deform"] + 6 <= 128)).sum())} of the {len(recs)} candidates; the longest chains are the workgroup groups of the 10-17 k-pixel clusters and class 1b); '
+                      'kernel_ms = HIP events on the launch stream from the end of sdsm_k_setup to the join of the classes (includes sdsm_k_setup_rows, the rows of G~ of the '
+                      'regions above 4096 pixels); per-class rocprofv3 averages: profiles/r04_kernel_stats.csv',
+            'kernel_ms': kern_ms, 'setup_kernel_ms': float(np.mean(setup_ms)), 'algorithmic_bytes_per_launch': alg_bytes,
+            'achieved_in_timed_region': alg_bytes / (dt / args.steps) / 1e9,
+            'fp64_vector_tflops': flops / (kern_ms * 1e-3) / 1e12, 'fp64_vector_frac_of_78.6': flops / (kern_ms * 1e-3) / 1e12 / 78.6,
+            'pixel_evaluations_per_launch': int((evals * recs['n_pixels']).sum()),
+            'pixel_evaluations_per_image': int((evals * recs['n_pixels']).sum() // n_images),
+            'algorithmic_bytes_definition': 'SURVEY.md 8(d): sum over candidates of E_c (12 N_c + 8 (6 + M_c)) + 12 N_c + ceil(bbox_c / 8) + 128, E_c = passes over the pixels actually made'}
 
 
 def _capi_lib():
@@ -619,8 +664,10 @@ def sharded_mode(args, world, rank, backend, n_gpus_used):
         tmax = torch.tensor([dt], dtype=torch.float64, device='cuda' if backend == 'nccl' else 'cpu')
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         region_ms.append(float(tmax.item()) * 1e3)
-    recs, _ = sb.results()
+    recs, frags = sb.results()
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, recs, sb.mask_info, lambda sel: frags)
         dt = float(np.median(region_ms)) * 1e-3
         n = len(scene['footprints'])
         alg = engine.algorithmic_bytes(recs, sb.mask_info)
@@ -681,6 +728,11 @@ def image_set_mode(args, world, rank, backend, n_gpus_used):
         dt = float(np.median(times))
         flat = sorted(x for part in got for x in part)
         ncand = sum(x[3] for x in flat)
+        if args.dump_outputs:                     # per image: the cost of its cover, and (image, object, atom) rows of the cover's footprints
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, 'cover_costs.npy'), np.array([x[2] for x in flat], np.float64))
+            np.save(os.path.join(args.dump_outputs, 'cover_atoms.npy'),
+                    np.array([(i, k, a) for i, sol, _, _ in flat for k, fp in enumerate(sol) for a in fp], np.float64).reshape(-1, 3))
         print(json.dumps({
             'metric': 'candidate DSM solves/sec', 'value': ncand / dt, 'unit': 'candidate solves/s', 'n_gpus': n_gpus_used, 'steps': 1, 'warmup': 1,
             'ms_per_step': dt * 1e3, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',

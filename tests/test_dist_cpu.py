@@ -156,6 +156,14 @@ def test_sharded_batch_equals_single_rank_world2_gloo():
     assert got == {0: True, 1: True}
 
 
+def _no_gpu_env():
+    """Environment of a bench.py child that sees no GPU, as on a CPU-only machine, also where a GPU is present (a dry run must
+    neither count nor open one): the rank variables of a surrounding launcher removed, no device visible to HIP."""
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
+    env['HIP_VISIBLE_DEVICES'] = '-1'
+    return env
+
+
 def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus 2` with WORLD_SIZE unset starts two child ranks itself (rendezvous on 127.0.0.1, gloo on a box
     without GPUs) and prints ONE JSON line with n_gpus == 2; --dry-run skips the GPU work."""
@@ -163,7 +171,7 @@ def test_bench_starts_its_own_ranks():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
+    env = _no_gpu_env()
     res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--dry-run'],
                          env=env, capture_output=True, timeout=180)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
@@ -179,7 +187,7 @@ def test_bench_ranks_per_gpu_starts_that_many_processes_per_card():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
+    env = _no_gpu_env()
     res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--ranks-per-gpu', '3', '--dry-run'],
                          env=env, capture_output=True, timeout=180)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
@@ -196,7 +204,7 @@ def test_bench_sharded_mode_deals_one_batch_and_gathers_once():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
+    env = _no_gpu_env()
     res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--mode', 'sharded', '--dry-run'],
                          env=env, capture_output=True, timeout=180)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
@@ -216,7 +224,7 @@ def _bench_dry(*flags, timeout=300):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
+    env = _no_gpu_env()
     res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--dry-run'] + list(flags), env=env, capture_output=True, timeout=timeout)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
     lines = [l for l in res.stdout.decode().splitlines() if l.strip()]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turns the rocprofv3 outputs merged under gpurun_out/ into the small committed summaries under profiles/.
+"""Turns the rocprofv3 outputs left under $OUT (default: out/) into the small committed summaries under profiles/.
 usage: python tools/summarize_profiles.py r02 [workload] [images per launch]
 The summary records the hash of the kernel sources it was measured on: bench.py reports its traffic figure only while that
 hash matches the sources that are running."""
@@ -16,14 +16,15 @@ tag = sys.argv[1] if len(sys.argv) > 1 else 'r02'
 workload = sys.argv[2] if len(sys.argv) > 2 else 'bbbc039_like'
 images = int(sys.argv[3]) if len(sys.argv) > 3 else 8
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+out_dir = os.path.join(root, os.environ.get('OUT', 'out'))
 os.makedirs(os.path.join(root, 'profiles'), exist_ok=True)
-stats = glob.glob(os.path.join(root, 'gpurun_out', f'{tag}_trace', '*', '*kernel_stats.csv'))
+stats = glob.glob(os.path.join(out_dir, f'{tag}_trace', '*', '*kernel_stats.csv'))
 if stats:
     shutil.copy(max(stats, key=os.path.getmtime), os.path.join(root, 'profiles', f'{tag}_kernel_stats.csv'))
 
 
 def per_kernel(pattern, counter):
-    files = glob.glob(os.path.join(root, 'gpurun_out', pattern, '*', '*counter_collection.csv'))
+    files = glob.glob(os.path.join(out_dir, pattern, '*', '*counter_collection.csv'))
     agg = collections.defaultdict(lambda: [0, 0.0])
     if not files:
         return {}
@@ -51,7 +52,7 @@ def source_hash():
 
 out = dict(
     source_hash=source_hash(), workload=workload, images_per_launch=images,
-    note=('rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of `python3 bench.py --no-cpu --no-extras --steps 6 --warmup 2 --repeats 2`.  Counters are in KB.  '
+    note=('rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of `python3 bench.py --full --no-cpu --no-extras --steps 6 --warmup 2 --repeats 2`.  Counters are in KB.  '
           'MI355X_MICROARCH.md: on gfx950 FETCH_SIZE reports 1/2 of the bytes of a WIDE (16 B/lane) coalesced stream.  The bulk of what the solve '
           'kernels read is such a stream (the 16-byte weights of the run entries, global_load_dwordx4 at consecutive lanes; beside it the 16-byte halves of the '
           'packed crop and 4-byte index words): the reported traffic is 2 x FETCH_SIZE + WRITE_SIZE (since round 4; rounds 1-3 reported the raw counter, '
@@ -61,7 +62,7 @@ out = dict(
     solve_write_bytes_per_launch=solve_write,
     solve_hbm_bytes_per_launch=2 * solve_fetch + solve_write, solve_hbm_bytes_per_launch_raw=solve_fetch + solve_write)
 sq = {}
-files = glob.glob(os.path.join(root, 'gpurun_out', f'{tag}_sq', '*', '*counter_collection.csv'))
+files = glob.glob(os.path.join(out_dir, f'{tag}_sq', '*', '*counter_collection.csv'))
 if files:
     agg = collections.defaultdict(lambda: collections.defaultdict(list))
     for r in csv.DictReader(open(max(files, key=os.path.getmtime))):
