@@ -205,7 +205,7 @@ size_t sdsm_gaussian_workspace_bytes(int H, int W, double sigma);
 int sdsm_gaussian_filter(const double *d_in, int H, int W, double sigma, double *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
 /* The same with caller-given SYMMETRIC weights per axis (HOST arrays of 2 R + 1 doubles): axis 0 with h_w0, then axis 1 with h_w1,
  * 'reflect' boundary -- e.g. the derivative-of-Gaussian filters of scipy.ndimage.gaussian_laplace used by the scale estimation
- * (superdsm/automation.py:52). */
+ * (superdsm/automation.py:52).  Radii up to R0 = 1240 and R1 = 10048 (the LDS tiles); longer filters fail before anything is launched. */
 size_t sdsm_separable_workspace_bytes(int H, int W, int R0, int R1);
 int sdsm_separable_filter(const double *d_in, int H, int W, const double *h_w0, int R0, const double *h_w1, int R1,
                           double *d_out, void *d_workspace, size_t workspace_bytes, void *stream);

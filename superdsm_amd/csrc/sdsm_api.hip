@@ -791,5 +791,5 @@ extern "C" int sdsm_separable_filter(const double *d_in, int H, int W, const dou
     for (int j = 1; j <= R1; j++) if (h_w1[R1 - j] != h_w1[R1 + j]) return fail(SDSM_ERR_ARGUMENT, "sdsm_separable_filter: weights must be symmetric");
     if (ws_bytes < sdsm_separable_workspace_bytes(H, W, R0, R1)) return fail(SDSM_ERR_WORKSPACE, "sdsm_separable_filter: workspace too small");
     hipError_t e = sdsm_separable_filter_impl(d_in, H, W, h_w0, R0, h_w1, R1, d_out, d_ws, (hipStream_t)stream);
-    return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_separable_filter (a filter radius beyond ~2500 does not fit the LDS tiles)");
+    return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_separable_filter (the LDS tiles take a filter radius of at most 1240 for the column pass and 10048 for the row pass)");
 }

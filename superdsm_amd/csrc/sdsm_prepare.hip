@@ -533,6 +533,9 @@ static hipError_t separable2d(const double *in, int H, int W, const double *d_w0
 {
     hipError_t e;
     CombineArgs none = {};
+    const int span = GR_COLS + 2 * R1 + 1;
+    const size_t lds_rt = (size_t)GR_ROWS * (span + (span >> 3) + 1) * 8;
+    if (lds_rt > GT_LDS_MAX && (cmb || (size_t)(256 + 2 * R1) * 8 > 160 * 1024 - 1024)) return hipErrorInvalidValue;   // (before anything is launched)
     const size_t lds_c32 = (size_t)(8 * GT_K + 2 * R0 + 1) * 32 * 8, lds_c16 = (size_t)(16 * GT_K + 2 * R0 + 1) * 16 * 8;
     if (lds_c32 <= GT_LDS_MAX) {
         if ((e = need_lds((const void *)k_gauss_cols_t<32>, lds_c32)) != hipSuccess) return e;
@@ -553,16 +556,12 @@ static hipError_t separable2d(const double *in, int H, int W, const double *d_w0
             hipLaunchKernelGGL(k_gauss_cols<8>, dim3((W + 7) / 8, (H + GC_ROWS - 1) / GC_ROWS), dim3(256), lds_c, stream, in, H, W, d_w0, R0, tmp);
         }
     }
-    const int span = GR_COLS + 2 * R1 + 1;
-    const size_t lds_rt = (size_t)GR_ROWS * (span + (span >> 3) + 1) * 8;
     if (lds_rt <= GT_LDS_MAX) {
         if ((e = need_lds((const void *)k_gauss_rows_t, lds_rt)) != hipSuccess) return e;
         hipLaunchKernelGGL(k_gauss_rows_t, dim3((W + GR_COLS - 1) / GR_COLS, (H + GR_ROWS - 1) / GR_ROWS), dim3(256), lds_rt, stream, (const double *)tmp, H, W, d_w1, R1, out,
                            cmb ? *cmb : none);
     } else {
-        if (cmb) return hipErrorInvalidValue;
         const size_t lds_r = (size_t)(256 + 2 * R1) * 8;
-        if (lds_r > 160 * 1024 - 1024) return hipErrorInvalidValue;
         if ((e = need_lds((const void *)k_gauss_rows, lds_r)) != hipSuccess) return e;
         hipLaunchKernelGGL(k_gauss_rows, dim3((W + 255) / 256, H), dim3(256), lds_r, stream, (const double *)tmp, H, W, d_w1, R1, out);
     }
