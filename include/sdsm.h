@@ -210,6 +210,34 @@ size_t sdsm_separable_workspace_bytes(int H, int W, int R0, int R1);
 int sdsm_separable_filter(const double *d_in, int H, int W, const double *h_w0, int R0, const double *h_w1, int R1,
                           double *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- scale estimation: determinant-of-Hessian blobs (superdsm/automation.py:13-68) ------------------------------
+ * Bit for bit the host restatement of superdsm_amd/automation.py (_log_negative_masks, _integ, _hessian_matrix_det, _blob_doh).
+ * Laplacian-of-Gaussian sign masks of n_scales scales in one call, without host synchronisation between them:
+ * d_masks[s*H*W + p] = ((d2/dr2 + d2/dc2) im)[p] < 0 (uint8), each term two separable 'reflect' passes as in sdsm_separable_filter.
+ * d_weights (DEVICE): per scale s, 2 R_s + 1 symmetric weights of order 0 and then 2 R_s + 1 of order 2, the scales one after
+ * another; h_radii (host): R_s.  Radii as sdsm_separable_filter takes them. */
+size_t sdsm_log_masks_workspace_bytes(int H, int W);
+int sdsm_log_masks(const double *d_im, int H, int W, int n_scales, const int32_t *h_radii, const double *d_weights, uint8_t *d_masks,
+                   void *d_workspace, size_t workspace_bytes, void *stream);
+/* Integral image d_ii = im.cumsum(0).cumsum(1), every column and then every row summed in index order (numpy's rounding).
+ * d_ii may be d_im. */
+int sdsm_integral_image(const double *d_im, int H, int W, double *d_ii, void *stream);
+/* The determinant-of-Hessian cube of all scales in one launch: d_cube[s*H*W + r*W + c] = mask_s[r, c] * det_s(r, c) with det_s
+ * the box-filter determinant on the integral image d_ii.  h_box (host): n_scales x (size, s2, s3) int32 with size = int(3 sigma),
+ * s2 = (size - 1) // 2, s3 = size // 3; h_w_i (host): n_scales doubles 1.0 / size / size.  d_masks as sdsm_log_masks writes them,
+ * or NULL for none.  n_scales <= SDSM_DOH_MAX_SCALES. */
+#define SDSM_DOH_MAX_SCALES 32
+int sdsm_doh_cube(const double *d_ii, int H, int W, int n_scales, const int32_t *h_box, const double *h_w_i, const uint8_t *d_masks,
+                  double *d_cube, void *stream);
+/* Peaks of the cube: voxels equal to the maximum of their in-bounds 3x3x3 neighbourhood and > threshold.  d_out: a 16-byte header
+ * (int64 total number of peaks, 8 bytes unused) followed by room for `capacity` records; the first min(total, capacity) peaks found
+ * are written, in no particular order.  The total is exact whatever the capacity. */
+typedef struct {
+    int32_t r, c, s, reserved;
+    double value;
+} sdsm_doh_peak;
+int sdsm_doh_peaks(const double *d_cube, int H, int W, int n_scales, double threshold, void *d_out, int64_t capacity, void *stream);
+
 /* ---- host-side combinatorial steps of the stage (no device access) -------------------------------------------------------------
  * Approximate min-weight set cover (superdsm/minsetcover.py:4-88: greedy + merge phase, retried with beta * gamma on up to max_iter
  * levels) and greedy max-weight set packing (superdsm/maxsetpack.py:8-24) over n objects whose footprints are bit sets of `words`

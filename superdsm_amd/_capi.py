@@ -34,6 +34,10 @@ assert RECORD_DTYPE.itemsize == 128
 POST_RECORD_DTYPE = np.dtype([('contrast', 'f8'), ('interior_mean', 'f8'), ('exterior_mean', 'f8'), ('fg_mean', 'f8'), ('fg_std', 'f8'),
                               ('area', 'i4'), ('status', 'i4'), ('r0', 'i4'), ('c0', 'i4'), ('h', 'i4'), ('w', 'i4')])
 assert POST_RECORD_DTYPE.itemsize == 64
+DOH_PEAK_DTYPE = np.dtype([('r', 'i4'), ('c', 'i4'), ('s', 'i4'), ('reserved', 'i4'), ('value', 'f8')])   # sdsm_doh_peak
+assert DOH_PEAK_DTYPE.itemsize == 24
+DOH_PEAKS_HEADER_BYTES = 16
+DOH_MAX_SCALES = 32
 
 # every entry point of include/sdsm.h: name -> (restype, argtypes)
 _vp, _i32, _f64, _sz, _i64 = C.c_void_p, C.c_int, C.c_double, C.c_size_t, C.c_int64
@@ -68,6 +72,11 @@ SYMBOLS = {
     'sdsm_gaussian_filter': (_i32, [_vp, _i32, _i32, _f64, _vp, _vp, _sz, _vp]),
     'sdsm_separable_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32]),
     'sdsm_separable_filter': (_i32, [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
+    'sdsm_log_masks_workspace_bytes': (_sz, [_i32, _i32]),
+    'sdsm_log_masks': (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sdsm_integral_image': (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    'sdsm_doh_cube': (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_doh_peaks': (_i32, [_vp, _i32, _i32, _i32, _f64, _vp, _i64, _vp]),
     'sdsm_minsetcover': (_i32, [_i32, _i32, _vp, _vp, _f64, _i32, _i32, _f64, _vp, _vp]),
     'sdsm_minsetcover_multi': (_i32, [_i32, _vp, _vp, _vp, _vp, _f64, _i32, _i32, _f64, _vp, _vp]),
     'sdsm_maxsetpack': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp]),

@@ -2,13 +2,16 @@
 
 ``create_config`` is automation.py:80-102.  ``_estimate_scale`` restates automation.py:41-68: determinant-of-Hessian blobs on
 11 scales (radii 20 … 200 pixels), restricted to pixels where the Laplacian of Gaussian is negative; the scale is the mean
-radius of the inlier blobs / sqrt(2).  The Laplacian-of-Gaussian masks -- separable filters with up to 1100 taps over the whole
-image, by far the largest part of the reference's cost -- run on the GPU (sdsm_separable_filter with SciPy's own
-derivative-of-Gaussian weights); the box-filter determinant, the 3x3x3 peak search and the overlap pruning are small array
-operations on the host.  PARITY UNPINNED: the reference takes ``_hessian_matrix_det``, ``peak_local_max`` and ``_prune_blobs``
-from scikit-image, which is not available to this build; they are restated from their documented behaviour (box filters on
-the integral image as in SURF; local maxima of a 3x3x3 neighbourhood above the threshold; of two blobs overlapping by more
-than ``overlap`` the smaller one is dropped) and checked on synthetic images of known scale only."""
+radius of the inlier blobs / sqrt(2).  PARITY UNPINNED: the reference takes ``_hessian_matrix_det``, ``peak_local_max`` and
+``_prune_blobs`` from scikit-image, which is not available to this build; they are restated from their documented behaviour (box
+filters on the integral image as in SURF; local maxima of a 3x3x3 neighbourhood above the threshold; of two blobs overlapping by
+more than ``overlap`` the smaller one is dropped) and checked on synthetic images of known scale only.
+
+The host functions below (``_integ``, ``_hessian_matrix_det``, ``_blob_doh``, ``_prune_blobs``) are that restatement; the detector
+that ``_estimate_scale`` and ``estimate_scales`` run is its device twin (``_DohDevice``), bit for bit: the Laplacian-of-Gaussian
+masks (separable filters with up to 1100 taps, SciPy's own derivative-of-Gaussian weights), the integral image, the
+determinant-of-Hessian cube of all scales and the peak compaction are HIP kernels (sdsm_log_masks, sdsm_integral_image,
+sdsm_doh_cube, sdsm_doh_peaks); the host puts the few peaks into ``np.nonzero``'s order and prunes them."""
 import math
 
 import numpy as np
@@ -117,43 +120,181 @@ def _blob_doh(image, sigma_list, threshold=0.01, overlap=.5, mask=None):
     return _prune_blobs(lm, overlap)
 
 
+def _blobs_from_peaks(peaks, total, n_voxels, sigma_list, overlap=.5):
+    """The tail of ``_blob_doh`` from the cube's peaks in any order (``_capi.DOH_PEAK_DTYPE`` records, ``total`` of them, out of
+    ``n_voxels`` voxels): every voxel a peak gives nothing (``peaks.all()``); otherwise the peaks are put into ``np.nonzero``'s order,
+    lexicographic in (r, c, s), then stable-sorted by descending value and pruned."""
+    if total == n_voxels or total == 0:
+        return np.empty((0, 3))
+    assert len(peaks) == total, 'incomplete peak list'
+    coords = np.stack([peaks['r'], peaks['c'], peaks['s']], axis=1).astype(np.intp)
+    order = np.lexsort((coords[:, 2], coords[:, 1], coords[:, 0]))
+    coords, values = coords[order], peaks['value'][order]
+    coords = coords[np.argsort(-values, kind='stable')]
+    lm = coords.astype(np.float64)
+    lm[:, -1] = np.asarray(sigma_list)[coords[:, -1]]
+    return _prune_blobs(lm, overlap)
+
+
+def _log_weights(sigma_list):
+    """SciPy's weights of the two terms of ``ndi.gaussian_laplace`` (``_gaussian_kernel1d`` of order 0 and 2, radius
+    int(4 sigma + 0.5), reversed as ``correlate1d`` applies them; both symmetric): the radii and, per sigma, the 2 R + 1 weights of
+    order 0 followed by the 2 R + 1 of order 2."""
+    from scipy.ndimage._filters import _gaussian_kernel1d
+    radii, parts = [], []
+    for sigma in sigma_list:
+        R = int(4.0 * float(sigma) + 0.5)
+        radii.append(R)
+        parts += [_gaussian_kernel1d(float(sigma), 0, R)[::-1], _gaussian_kernel1d(float(sigma), 2, R)[::-1]]
+    return np.asarray(radii, np.int32), np.ascontiguousarray(np.concatenate(parts), np.float64)
+
+
+def _box_params(sigma_list):
+    """``size``, ``s2``, ``s3`` and ``w_i`` of ``_hessian_matrix_det`` per sigma, computed as it computes them."""
+    box, w_i = np.zeros((len(sigma_list), 3), np.int32), np.zeros(len(sigma_list))
+    for k, sigma in enumerate(sigma_list):
+        size = int(3 * sigma)
+        box[k] = size, (size - 1) // 2, size // 3
+        w_i[k] = 1.0 / size / size
+    return box, w_i
+
+
+class _DohDevice:
+    """The device twin of ``_log_negative_masks`` + ``_blob_doh`` for one sigma list.  The filter weights go to the device once;
+    the workspaces grow on demand and are reused over an image set.  ``load(im)`` uploads an image and computes its LoG masks,
+    integral image and determinant-of-Hessian cube on the current stream without waiting for any of it; ``blobs(threshold)``
+    compacts the cube's peaks and downloads them once.  ``capacity``: peak records downloaded at first; more peaks than that
+    re-run the compaction alone with room for all of them."""
+
+    def __init__(self, sigma_list, capacity=4096):
+        import torch
+        from . import _capi
+        self._torch, self._capi, self._L = torch, _capi, _capi.lib()
+        self.sigma_list = np.asarray(sigma_list, np.float64)
+        if not 1 <= len(self.sigma_list) <= _capi.DOH_MAX_SCALES:
+            raise ValueError(f'the device detector takes 1 to {_capi.DOH_MAX_SCALES} scales')
+        self.radii, weights = _log_weights(self.sigma_list)
+        self.box, self.w_i = _box_params(self.sigma_list)
+        self._d_weights = torch.as_tensor(weights).cuda()
+        self.capacity = max(int(capacity), 1)
+        self._bufs = {}
+        self.shape = None
+
+    def _buf(self, name, nbytes):
+        b = self._bufs.get(name)
+        if b is None or b.numel() < nbytes:
+            self._bufs[name] = b = self._torch.empty(max(int(nbytes), 1), dtype=self._torch.uint8, device=self._d_weights.device)
+        return b
+
+    def _f64(self, name, n):
+        return self._buf(name, 8 * n)[:8 * n].view(self._torch.float64)
+
+    @staticmethod
+    def _p(t):
+        import ctypes as C
+        return C.c_void_p(t.data_ptr())
+
+    def _stream(self):
+        import ctypes as C
+        return C.c_void_p(self._torch.cuda.current_stream().cuda_stream)
+
+    def _masks(self, im):
+        import ctypes as C
+        im = np.ascontiguousarray(im, np.float64)
+        H, W = self.shape = im.shape
+        n, S = H * W, len(self.sigma_list)
+        d_im = self._f64('im', n)
+        d_im.copy_(self._torch.from_numpy(im).reshape(-1))
+        nbytes = self._L.sdsm_log_masks_workspace_bytes(H, W)
+        d_masks = self._buf('masks', S * n)
+        self._capi.check(self._L.sdsm_log_masks(self._p(d_im), H, W, S, self.radii.ctypes.data_as(C.c_void_p), self._p(self._d_weights),
+                                                self._p(d_masks), self._p(self._buf('ws', nbytes)), nbytes, self._stream()), 'sdsm_log_masks')
+        return d_im, d_masks
+
+    def log_masks(self, im):
+        """``{sigma: ndi.gaussian_laplace(im, sigma) < 0}``: one download for all sigmas."""
+        _, d_masks = self._masks(im)
+        H, W = self.shape
+        masks = d_masks[:len(self.sigma_list) * H * W].cpu().numpy().view(bool).reshape(-1, H, W)
+        return {sigma: masks[k] for k, sigma in enumerate(self.sigma_list)}
+
+    def load(self, im):
+        import ctypes as C
+        d_im, d_masks = self._masks(im)
+        H, W = self.shape
+        S, stream = len(self.sigma_list), self._stream()
+        d_ii, d_cube = self._f64('ii', H * W), self._f64('cube', S * H * W)
+        self._capi.check(self._L.sdsm_integral_image(self._p(d_im), H, W, self._p(d_ii), stream), 'sdsm_integral_image')
+        self._capi.check(self._L.sdsm_doh_cube(self._p(d_ii), H, W, S, self.box.ctypes.data_as(C.c_void_p), self.w_i.ctypes.data_as(C.c_void_p),
+                                               self._p(d_masks), self._p(d_cube), stream), 'sdsm_doh_cube')
+        return self
+
+    def integral_image(self):
+        """The integral image of the loaded image (a download: diagnostics and tests)."""
+        return self._f64('ii', self.shape[0] * self.shape[1]).cpu().numpy().reshape(self.shape)
+
+    def cube(self):
+        """The cube of the loaded image as (scale, row, column) (a download: diagnostics and tests)."""
+        return self._f64('cube', len(self.sigma_list) * self.shape[0] * self.shape[1]).cpu().numpy().reshape((-1,) + self.shape)
+
+    def peaks(self, threshold):
+        """The peaks of the loaded image's cube above ``threshold``, in no particular order, and their total."""
+        H, W = self.shape
+        S, hdr = len(self.sigma_list), self._capi.DOH_PEAKS_HEADER_BYTES
+        cap = self.capacity
+        while True:
+            nbytes = hdr + cap * self._capi.DOH_PEAK_DTYPE.itemsize
+            d_out = self._buf('peaks', nbytes)
+            self._capi.check(self._L.sdsm_doh_peaks(self._p(self._f64('cube', S * H * W)), H, W, S, float(threshold), self._p(d_out), cap,
+                                                    self._stream()), 'sdsm_doh_peaks')
+            host = d_out[:nbytes].cpu().numpy()
+            total = int(host[:8].view(np.int64)[0])
+            if total <= cap or total == S * H * W:      # (every voxel a peak: the list is not needed)
+                break
+            cap = total
+        return host[hdr:hdr + min(total, cap) * self._capi.DOH_PEAK_DTYPE.itemsize].view(self._capi.DOH_PEAK_DTYPE), total
+
+    def blobs(self, threshold, overlap=.5):
+        """``_blob_doh(im, sigma_list, threshold, overlap, mask=_log_negative_masks(im, sigma_list))`` of the loaded image."""
+        peaks, total = self.peaks(threshold)
+        return _blobs_from_peaks(peaks, total, len(self.sigma_list) * self.shape[0] * self.shape[1], self.sigma_list, overlap)
+
+
 def _log_negative_masks(im, sigma_list):
     """``{sigma: ndi.gaussian_laplace(im, sigma) < 0}`` (automation.py:52) with the filters on the GPU.  The weights are SciPy's own
     (``_gaussian_kernel1d`` of order 0 and 2: both symmetric), the axes are filtered in SciPy's order."""
-    import ctypes as C
-    import torch
-    from scipy.ndimage._filters import _gaussian_kernel1d
-    from . import _capi
-    L = _capi.lib()
-    H, W = im.shape
-    d_in = torch.as_tensor(np.ascontiguousarray(im, np.float64)).cuda()
-    a, b = torch.empty_like(d_in), torch.empty_like(d_in)
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    out = {}
-    for sigma in sigma_list:
-        R = int(4.0 * float(sigma) + 0.5)
-        w0 = np.ascontiguousarray(_gaussian_kernel1d(float(sigma), 0, R)[::-1])
-        w2 = np.ascontiguousarray(_gaussian_kernel1d(float(sigma), 2, R)[::-1])
-        nbytes = L.sdsm_separable_workspace_bytes(H, W, R, R)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=d_in.device)
-        hp = lambda w: w.ctypes.data_as(C.c_void_p)
-        _capi.check(L.sdsm_separable_filter(p(d_in), H, W, hp(w2), R, hp(w0), R, p(a), p(ws), nbytes, stream), 'sdsm_separable_filter')   # d2/dr2
-        _capi.check(L.sdsm_separable_filter(p(d_in), H, W, hp(w0), R, hp(w2), R, p(b), p(ws), nbytes, stream), 'sdsm_separable_filter')   # d2/dc2
-        out[sigma] = ((a + b) < 0).cpu().numpy()
-    return out
+    return _DohDevice(sigma_list).log_masks(im)
+
+
+def _sigma_list(min_radius, max_radius, num_radii):
+    sigma_list = np.linspace(min_radius, max_radius, num_radii) / math.sqrt(2)
+    return np.concatenate([[sigma_list.min() / 2], sigma_list])
 
 
 def _estimate_scale(im, min_radius=20, max_radius=200, num_radii=10, thresholds=[0.01], inlier_tol=np.inf):
     """Estimates the scale sigma of the objects of an image (automation.py:41-68).  Returns (scale, blobs, inlier mask)."""
-    sigma_list = np.linspace(min_radius, max_radius, num_radii) / math.sqrt(2)
-    sigma_list = np.concatenate([[sigma_list.min() / 2], sigma_list])
-    im_norm = normalize_image(im)
-    im_norm /= im_norm.max()
-    blobs_mask = _log_negative_masks(im_norm, sigma_list)
+    return estimate_scales([im], min_radius, max_radius, num_radii, thresholds, inlier_tol)[0]
+
+
+def estimate_scales(images, min_radius=20, max_radius=200, num_radii=10, thresholds=[0.01], inlier_tol=np.inf):
+    """``_estimate_scale`` of every image of a set (the images may differ in shape): one device detector, its workspaces reused
+    from image to image.  Raises ValueError('scale estimation failed') as soon as an image yields no blobs."""
+    sigma_list = _sigma_list(min_radius, max_radius, num_radii)
+    dev = _DohDevice(sigma_list)
+    out = []
+    for im in images:
+        im_norm = normalize_image(im)
+        im_norm /= im_norm.max()
+        dev.load(im_norm)
+        out.append(_scale_from_blobs(dev.blobs, sigma_list, thresholds))
+    return out
+
+
+def _scale_from_blobs(blob_doh, sigma_list, thresholds):
+    """The rule of automation.py:55-68 over ``blob_doh(threshold)`` -> blobs (rows r, c, sigma)."""
     mean_radius = None
     for threshold in sorted(thresholds, reverse=True):
-        blobs_doh = _blob_doh(im_norm, sigma_list, threshold=threshold, mask=blobs_mask)
+        blobs_doh = blob_doh(threshold)
         blobs_doh = blobs_doh[~np.isclose(blobs_doh[:, 2], sigma_list.min())]
         if len(blobs_doh) == 0:
             continue

@@ -793,3 +793,49 @@ extern "C" int sdsm_separable_filter(const double *d_in, int H, int W, const dou
     hipError_t e = sdsm_separable_filter_impl(d_in, H, W, h_w0, R0, h_w1, R1, d_out, d_ws, (hipStream_t)stream);
     return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_separable_filter (the LDS tiles take a filter radius of at most 1240 for the column pass and 10048 for the row pass)");
 }
+
+// ---- scale estimation (automation.py:13-68): LoG masks, integral image, determinant-of-Hessian cube, peaks ----
+extern "C" hipError_t sdsm_log_masks_impl(const double *d_im, int H, int W, int n_scales, const int32_t *h_radii, const double *d_weights,
+                                          uint8_t *d_masks, void *d_ws, hipStream_t stream);
+extern "C" hipError_t sdsm_integral_image_impl(const double *d_im, int H, int W, double *d_ii, hipStream_t stream);
+extern "C" hipError_t sdsm_doh_cube_impl(const double *d_ii, int H, int W, int n_scales, const int32_t *h_box, const double *h_w_i,
+                                         const uint8_t *d_masks, double *d_cube, hipStream_t stream);
+extern "C" hipError_t sdsm_doh_peaks_impl(const double *d_cube, int H, int W, int n_scales, double threshold, void *d_out, int64_t capacity,
+                                          hipStream_t stream);
+
+extern "C" int sdsm_log_masks(const double *d_im, int H, int W, int n_scales, const int32_t *h_radii, const double *d_weights, uint8_t *d_masks,
+                              void *d_ws, size_t ws_bytes, void *stream)
+{
+    if (!d_im || !d_weights || !d_masks || !d_ws || !h_radii || H < 1 || W < 1 || n_scales < 1) return fail(SDSM_ERR_ARGUMENT, "sdsm_log_masks: bad argument");
+    for (int s = 0; s < n_scales; s++) if (h_radii[s] < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_log_masks: negative radius");
+    if (ws_bytes < sdsm_log_masks_workspace_bytes(H, W)) return fail(SDSM_ERR_WORKSPACE, "sdsm_log_masks: workspace too small");
+    hipError_t e = sdsm_log_masks_impl(d_im, H, W, n_scales, h_radii, d_weights, d_masks, d_ws, (hipStream_t)stream);
+    return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_log_masks (radii as sdsm_separable_filter takes them)");
+}
+
+extern "C" int sdsm_integral_image(const double *d_im, int H, int W, double *d_ii, void *stream)
+{
+    if (!d_im || !d_ii || H < 1 || W < 1) return fail(SDSM_ERR_ARGUMENT, "sdsm_integral_image: bad argument");
+    hipError_t e = sdsm_integral_image_impl(d_im, H, W, d_ii, (hipStream_t)stream);
+    return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_integral_image");
+}
+
+extern "C" int sdsm_doh_cube(const double *d_ii, int H, int W, int n_scales, const int32_t *h_box, const double *h_w_i, const uint8_t *d_masks,
+                             double *d_cube, void *stream)
+{
+    if (!d_ii || !h_box || !h_w_i || !d_cube || H < 1 || W < 1 || n_scales < 1 || n_scales > SDSM_DOH_MAX_SCALES || H > 65535)
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_doh_cube: bad argument");
+    for (int s = 0; s < n_scales; s++) {
+        const int32_t *b = h_box + 3 * s;
+        if (b[0] < 1 || b[0] > (1 << 24) || b[1] < 0 || b[2] < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_doh_cube: bad box sizes");
+    }
+    hipError_t e = sdsm_doh_cube_impl(d_ii, H, W, n_scales, h_box, h_w_i, d_masks, d_cube, (hipStream_t)stream);
+    return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_doh_cube");
+}
+
+extern "C" int sdsm_doh_peaks(const double *d_cube, int H, int W, int n_scales, double threshold, void *d_out, int64_t capacity, void *stream)
+{
+    if (!d_cube || !d_out || H < 1 || W < 1 || n_scales < 1 || capacity < 0 || H > 65535) return fail(SDSM_ERR_ARGUMENT, "sdsm_doh_peaks: bad argument");
+    hipError_t e = sdsm_doh_peaks_impl(d_cube, H, W, n_scales, threshold, d_out, capacity, (hipStream_t)stream);
+    return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_doh_peaks");
+}

@@ -667,3 +667,228 @@ extern "C" hipError_t sdsm_separable_filter_impl(const double *d_in, int H, int 
     if ((e = hipMemcpyAsync(w1, h_w1, (size_t)(2 * R1 + 1) * 8, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
     return separable2d(d_in, H, W, w0, R0, w1, R1, tmp, d_out, stream);
 }
+
+// ---- scale estimation: determinant-of-Hessian blobs (superdsm/automation.py:13-68), bit for bit the host restatement of
+//      superdsm_amd/automation.py (_log_negative_masks, _integ, _hessian_matrix_det, _blob_doh) ----------------------------------
+namespace {
+
+// ndi.gaussian_laplace(im, sigma) < 0 from its two terms (automation.py:52)
+__global__ void k_log_mask(const double *__restrict__ a, const double *__restrict__ b, size_t n, uint8_t *__restrict__ mask)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) mask[i] = (a[i] + b[i]) < 0;
+}
+
+// im.cumsum(0): one thread per column, the rows in index order as numpy accumulates them.  The loads of a block of rows are issued
+// together (the sum is a chain, the loads are not); every element is read before the same thread writes it, so out may be in.
+#define CS_ROWS 16
+__global__ __launch_bounds__(64) void k_cumsum_cols(const double *in, int H, int W, double *out)
+{
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= W) return;
+    const double *p = in + c;
+    double *q = out + c;
+    double s = p[0];
+    q[0] = s;
+    int r = 1;
+    for (; r + CS_ROWS <= H; r += CS_ROWS) {
+        double v[CS_ROWS];
+#pragma unroll
+        for (int k = 0; k < CS_ROWS; k++) v[k] = p[(size_t)(r + k) * W];
+#pragma unroll
+        for (int k = 0; k < CS_ROWS; k++) { s = s + v[k]; q[(size_t)(r + k) * W] = s; }
+    }
+    for (; r < H; r++) { s = s + p[(size_t)r * W]; q[(size_t)r * W] = s; }
+}
+
+// .cumsum(1) in place: a workgroup owns 64 rows and walks along them in tiles of 64 columns, staged through LDS so that the loads
+// and stores stay coalesced; one wavefront scans, a lane per row, the columns in index order with the row's running sum.  The next
+// tile is loaded into registers while the current one is scanned.
+#define CR_TILE 64
+__global__ __launch_bounds__(256) void k_cumsum_rows(double *ii, int H, int W)
+{
+    __shared__ double tile[CR_TILE][CR_TILE + 1];
+    const int tid = threadIdx.x, tx = tid & 63, ty = tid >> 6;          // loads / stores: column tx of rows ty, ty + 4, ...
+    const int r0 = blockIdx.x * CR_TILE;
+    double next[CR_TILE / 4];
+#pragma unroll
+    for (int k = 0; k < CR_TILE / 4; k++) {
+        const int r = r0 + ty + 4 * k;
+        next[k] = r < H && tx < W ? ii[(size_t)r * W + tx] : 0.0;
+    }
+    double carry = 0;                                                   // (wave 0: the running sum of row r0 + tx)
+    for (int c0 = 0; c0 < W; c0 += CR_TILE) {
+#pragma unroll
+        for (int k = 0; k < CR_TILE / 4; k++) tile[ty + 4 * k][tx] = next[k];
+        __syncthreads();
+        const int cn = c0 + CR_TILE + tx;
+#pragma unroll
+        for (int k = 0; k < CR_TILE / 4; k++) {
+            const int r = r0 + ty + 4 * k;
+            next[k] = r < H && cn < W ? ii[(size_t)r * W + cn] : 0.0;
+        }
+        if (ty == 0) {
+            double *row = tile[tx];
+            const int nc = W - c0 < CR_TILE ? W - c0 : CR_TILE;
+            int j = 0;
+            if (c0 == 0) { carry = row[0]; j = 1; }
+            for (; j < nc; j++) { carry = carry + row[j]; row[j] = carry; }
+        }
+        __syncthreads();
+        const int c = c0 + tx;
+#pragma unroll
+        for (int k = 0; k < CR_TILE / 4; k++) {
+            const int r = r0 + ty + 4 * k;
+            if (r < H && c < W) ii[(size_t)r * W + c] = tile[ty + 4 * k][tx];
+        }
+        __syncthreads();
+    }
+}
+
+struct DohScales {
+    int size[SDSM_DOH_MAX_SCALES], s2[SDSM_DOH_MAX_SCALES], s3[SDSM_DOH_MAX_SCALES];
+    double w_i[SDSM_DOH_MAX_SCALES];
+};
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// _integ: the origin is clipped first, the far corner measured from the clipped origin; ((a + b) - c) - d, then np.maximum(0, .)
+// (which keeps a NaN)
+__device__ __forceinline__ double box_sum(const double *__restrict__ ii, int H, int W, int r, int c, int rl, int cl)
+{
+    const int r1 = clampi(r, 0, H - 1), c1 = clampi(c, 0, W - 1);
+    const int r2 = clampi(r1 + rl, 0, H - 1), c2 = clampi(c1 + cl, 0, W - 1);
+    const double *p1 = ii + (size_t)r1 * W, *p2 = ii + (size_t)r2 * W;
+    const double v = ((p1[c1] + p2[c2]) - p1[c2]) - p2[c1];
+    return 0.0 >= v ? 0.0 : v;
+}
+
+// _hessian_matrix_det times the LoG mask, every scale in one launch: thread = (column, row, scale)
+__global__ __launch_bounds__(256) void k_doh_cube(const double *__restrict__ ii, int H, int W, DohScales sc, const uint8_t *__restrict__ masks,
+                                                  double *__restrict__ cube)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y, s = blockIdx.z;
+    if (c >= W) return;
+    const int w = sc.size[s], s2 = sc.s2[s], s3 = sc.s3[s];
+    const double w_i = sc.w_i[s];
+    const double tl = box_sum(ii, H, W, r - s3, c - s3, s3, s3);
+    const double br = box_sum(ii, H, W, r + 1, c + 1, s3, s3);
+    const double bl = box_sum(ii, H, W, r - s3, c + 1, s3, s3);
+    const double tr = box_sum(ii, H, W, r + 1, c - s3, s3, s3);
+    const double dxy = -(((bl + tr) - tl) - br) * w_i;
+    double mid = box_sum(ii, H, W, r - s3 + 1, c - s2, 2 * s3 - 1, w);
+    double side = box_sum(ii, H, W, r - s3 + 1, c - s3 / 2, 2 * s3 - 1, s3);
+    const double dxx = -(mid - 3.0 * side) * w_i;
+    mid = box_sum(ii, H, W, r - s2, c - s3 + 1, w, 2 * s3 - 1);
+    side = box_sum(ii, H, W, r - s3 / 2, c - s3 + 1, s3, 2 * s3 - 1);
+    const double dyy = -(mid - 3.0 * side) * w_i;
+    const double det = dxx * dyy - 0.81 * (dxy * dxy);
+    const size_t p = ((size_t)s * H + r) * W + c;
+    const double m = masks ? (masks[p] ? 1.0 : 0.0) : 1.0;              // mask[s] * det: a bool array times a float array
+    cube[p] = m * det;
+}
+
+__device__ __forceinline__ double max3x3(const double *__restrict__ plane, int H, int W, int r, int c)
+{
+    double m = plane[(size_t)r * W + c];
+#pragma unroll
+    for (int dr = -1; dr <= 1; dr++) {
+        const int rr = r + dr;
+        if (rr < 0 || rr >= H) continue;
+#pragma unroll
+        for (int dc = -1; dc <= 1; dc++) {
+            const int cc = c + dc;
+            if (cc < 0 || cc >= W) continue;
+            const double v = plane[(size_t)rr * W + cc];
+            m = v > m ? v : m;
+        }
+    }
+    return m;
+}
+
+// Peaks: equal to the maximum of the in-bounds 3x3x3 neighbourhood (maximum_filter with mode='nearest') and above the threshold.
+// A thread walks the scales of one pixel with the 3x3 maxima of the planes s - 1, s, s + 1; the peaks of a wavefront take their
+// slots with one atomic.
+__global__ __launch_bounds__(256) void k_doh_peaks(const double *__restrict__ cube, int H, int W, int S, double threshold,
+                                                   unsigned long long *__restrict__ total, sdsm_doh_peak *__restrict__ out, long long capacity)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y, lane = threadIdx.x & 63;
+    const bool inside = c < W;
+    const int cc = inside ? c : W - 1;                                  // (every lane takes part in the ballots)
+    const size_t HW = (size_t)H * W;
+    double m_prev = 0, m_cur = max3x3(cube, H, W, r, cc);
+    for (int s = 0; s < S; s++) {
+        const double m_next = s + 1 < S ? max3x3(cube + (s + 1) * HW, H, W, r, cc) : 0.0;
+        double m = m_cur;
+        if (s > 0) m = m_prev > m ? m_prev : m;
+        if (s + 1 < S) m = m_next > m ? m_next : m;
+        const double v = cube[s * HW + (size_t)r * W + cc];
+        const bool peak = inside && v == m && v > threshold;
+        const unsigned long long bal = __ballot(peak);
+        if (bal) {
+            const int leader = __ffsll((long long)bal) - 1;
+            long long base = 0;
+            if (lane == leader) base = (long long)atomicAdd(total, (unsigned long long)__popcll(bal));
+            base = __shfl(base, leader);
+            if (peak) {
+                const long long idx = base + __popcll(bal & ((1ull << lane) - 1));
+                if (idx < capacity) { sdsm_doh_peak p; p.r = r; p.c = c; p.s = s; p.reserved = 0; p.value = v; out[idx] = p; }
+            }
+        }
+        m_prev = m_cur;
+        m_cur = m_next;
+    }
+}
+
+}  // namespace
+
+extern "C" size_t sdsm_log_masks_workspace_bytes(int H, int W)
+{
+    return 3 * align_up((size_t)H * W * 8, 256);
+}
+
+// Per scale the two terms of the Laplacian (axis 0 with the weights of order 2 and axis 1 with those of order 0, then the other way
+// round) and their sign, all on `stream`: the weights are already on the device.
+extern "C" hipError_t sdsm_log_masks_impl(const double *d_im, int H, int W, int n_scales, const int32_t *h_radii, const double *d_weights,
+                                          uint8_t *d_masks, void *d_ws, hipStream_t stream)
+{
+    const size_t n = (size_t)H * W, nb = align_up(n * 8, 256);
+    double *tmp = (double *)d_ws, *a = (double *)((uint8_t *)d_ws + nb), *b = (double *)((uint8_t *)d_ws + 2 * nb);
+    const double *w = d_weights;
+    for (int s = 0; s < n_scales; s++) {
+        const int R = h_radii[s];
+        const double *w0 = w, *w2 = w + (2 * R + 1);
+        hipError_t e;
+        if ((e = separable2d(d_im, H, W, w2, R, w0, R, tmp, a, stream)) != hipSuccess) return e;      // d2/dr2
+        if ((e = separable2d(d_im, H, W, w0, R, w2, R, tmp, b, stream)) != hipSuccess) return e;      // d2/dc2
+        hipLaunchKernelGGL(k_log_mask, dim3((n + 255) / 256), dim3(256), 0, stream, (const double *)a, (const double *)b, n, d_masks + (size_t)s * n);
+        w += 2 * (2 * R + 1);
+    }
+    return hipGetLastError();
+}
+
+extern "C" hipError_t sdsm_integral_image_impl(const double *d_im, int H, int W, double *d_ii, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_cumsum_cols, dim3((W + 63) / 64), dim3(64), 0, stream, d_im, H, W, d_ii);
+    hipLaunchKernelGGL(k_cumsum_rows, dim3((H + CR_TILE - 1) / CR_TILE), dim3(256), 0, stream, d_ii, H, W);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t sdsm_doh_cube_impl(const double *d_ii, int H, int W, int n_scales, const int32_t *h_box, const double *h_w_i,
+                                         const uint8_t *d_masks, double *d_cube, hipStream_t stream)
+{
+    DohScales sc = {};
+    for (int s = 0; s < n_scales; s++) { sc.size[s] = h_box[3 * s]; sc.s2[s] = h_box[3 * s + 1]; sc.s3[s] = h_box[3 * s + 2]; sc.w_i[s] = h_w_i[s]; }
+    hipLaunchKernelGGL(k_doh_cube, dim3((W + 255) / 256, H, n_scales), dim3(256), 0, stream, d_ii, H, W, sc, d_masks, d_cube);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t sdsm_doh_peaks_impl(const double *d_cube, int H, int W, int n_scales, double threshold, void *d_out, int64_t capacity,
+                                          hipStream_t stream)
+{
+    hipError_t e = hipMemsetAsync(d_out, 0, 16, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_doh_peaks, dim3((W + 255) / 256, H), dim3(256), 0, stream, d_cube, H, W, n_scales, threshold,
+                       (unsigned long long *)d_out, (sdsm_doh_peak *)((uint8_t *)d_out + 16), (long long)capacity);
+    return hipGetLastError();
+}
