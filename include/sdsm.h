@@ -238,6 +238,28 @@ typedef struct {
 } sdsm_doh_peak;
 int sdsm_doh_peaks(const double *d_cube, int H, int W, int n_scales, double threshold, void *d_out, int64_t capacity, void *stream);
 
+/* ---- coarse-to-fine region analysis (superdsm/c2freganal.py:110-126) ------------------------------------------------------------
+ * sdsm_c2f_markers: the cluster markers of y (H x W float64): fg = y > 0, its 4-connected components numbered in raster order of
+ * their first pixel (ndi.label), a component is irregular if (its pixels with an in-image 4-neighbour outside fg) / (its pixels)
+ * > max_irregularity as a float64 division; background counts as one more component with irregularity 0.  d_y_mask (uint8): 0 on
+ * irregular components; d_markers (int32): the regular components relabelled 1 .. n in raster order, 0 elsewhere -- all 0 if no pixel
+ * is background (_normalize_labels_map(first_label=0) without label 0); d_count (device int32): n.  Byte-equal to the SciPy
+ * statement.  H * W < 2^31. */
+size_t sdsm_c2f_markers_workspace_bytes(int H, int W);
+int sdsm_c2f_markers(const double *d_y, int H, int W, double max_irregularity, uint8_t *d_y_mask, int32_t *d_markers, int32_t *d_count,
+                     void *d_ws, size_t ws_bytes, void *stream);
+/* sdsm_edt_exact: d_out[p] (float64) = Euclidean distance of pixel p to the nearest pixel with d_target != 0, unbounded; the exact
+ * integer squared distance, then a correctly rounded sqrt: bit-equal to ndi.distance_transform_edt(d_target == 0).  Without any
+ * target, the distance to (-1, 0), as SciPy reports it.  H, W <= 65535. */
+size_t sdsm_edt_exact_workspace_bytes(int H, int W);
+int sdsm_edt_exact(const uint8_t *d_target, int H, int W, double *d_out, void *d_ws, size_t ws_bytes, void *stream);
+/* sdsm_watershed (host, no device access): the marker flood of the restated rule.  image: H x W float64; markers:
+ * int32 (0 = unlabelled); mask: uint8 or NULL (all admissible).  Markers inside the mask are pushed first, in raster order, with age 0;
+ * the heap pops the smallest (image value, push age, raster index); a popped pixel labels its unlabelled admissible 4-neighbours (up,
+ * left, right, down) with its own label and pushes them with the next age.  out: int32 labels, 0 outside the mask and where no marker
+ * reaches. */
+int sdsm_watershed(const double *image, const int32_t *markers, const uint8_t *mask, int H, int W, int32_t *out);
+
 /* ---- host-side combinatorial steps of the stage (no device access) -------------------------------------------------------------
  * Approximate min-weight set cover (superdsm/minsetcover.py:4-88: greedy + merge phase, retried with beta * gamma on up to max_iter
  * levels) and greedy max-weight set packing (superdsm/maxsetpack.py:8-24) over n objects whose footprints are bit sets of `words`

@@ -10,3 +10,5 @@ import os as _os
 if 'GPU_MAX_HW_QUEUES' not in _os.environ and _os.environ.get('SDSM_SET_HW_QUEUES', '1') != '0':
     _os.environ['GPU_MAX_HW_QUEUES'] = '8'
     _logging.getLogger(__name__).info('GPU_MAX_HW_QUEUES=8 set for this process (SDSM_SET_HW_QUEUES=0: leave the environment alone)')
+
+from .c2freganal import C2F_RegionAnalysis  # noqa: E402,F401

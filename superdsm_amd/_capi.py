@@ -77,6 +77,11 @@ SYMBOLS = {
     'sdsm_integral_image': (_i32, [_vp, _i32, _i32, _vp, _vp]),
     'sdsm_doh_cube': (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     'sdsm_doh_peaks': (_i32, [_vp, _i32, _i32, _i32, _f64, _vp, _i64, _vp]),
+    'sdsm_c2f_markers_workspace_bytes': (_sz, [_i32, _i32]),
+    'sdsm_c2f_markers': (_i32, [_vp, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sdsm_edt_exact_workspace_bytes': (_sz, [_i32, _i32]),
+    'sdsm_edt_exact': (_i32, [_vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    'sdsm_watershed': (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
     'sdsm_minsetcover': (_i32, [_i32, _i32, _vp, _vp, _f64, _i32, _i32, _f64, _vp, _vp]),
     'sdsm_minsetcover_multi': (_i32, [_i32, _vp, _vp, _vp, _vp, _f64, _i32, _i32, _f64, _vp, _vp]),
     'sdsm_maxsetpack': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp]),

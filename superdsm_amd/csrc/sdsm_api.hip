@@ -839,3 +839,37 @@ extern "C" int sdsm_doh_peaks(const double *d_cube, int H, int W, int n_scales, 
     hipError_t e = sdsm_doh_peaks_impl(d_cube, H, W, n_scales, threshold, d_out, capacity, (hipStream_t)stream);
     return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_doh_peaks");
 }
+
+extern "C" size_t sdsm_c2f_markers_workspace_bytes_impl(int H, int W);
+extern "C" hipError_t sdsm_c2f_markers_impl(const double *d_y, int H, int W, double thr, uint8_t *d_y_mask, int32_t *d_markers,
+                                            int32_t *d_count, void *d_ws, hipStream_t stream);
+extern "C" size_t sdsm_edt_exact_workspace_bytes_impl(int H, int W);
+extern "C" hipError_t sdsm_edt_exact_impl(const uint8_t *d_target, int H, int W, double *d_out, void *d_ws, hipStream_t stream);
+
+extern "C" size_t sdsm_c2f_markers_workspace_bytes(int H, int W)
+{
+    return H < 1 || W < 1 ? 0 : sdsm_c2f_markers_workspace_bytes_impl(H, W);
+}
+
+extern "C" int sdsm_c2f_markers(const double *d_y, int H, int W, double max_irregularity, uint8_t *d_y_mask, int32_t *d_markers, int32_t *d_count,
+                                void *d_ws, size_t ws_bytes, void *stream)
+{
+    if (!d_y || !d_y_mask || !d_markers || !d_count || !d_ws || H < 1 || W < 1 || (int64_t)H * W >= INT_MAX)
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_c2f_markers: bad argument");
+    if (ws_bytes < sdsm_c2f_markers_workspace_bytes(H, W)) return fail(SDSM_ERR_WORKSPACE, "sdsm_c2f_markers: workspace too small");
+    hipError_t e = sdsm_c2f_markers_impl(d_y, H, W, max_irregularity, d_y_mask, d_markers, d_count, d_ws, (hipStream_t)stream);
+    return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_c2f_markers");
+}
+
+extern "C" size_t sdsm_edt_exact_workspace_bytes(int H, int W)
+{
+    return H < 1 || W < 1 ? 0 : sdsm_edt_exact_workspace_bytes_impl(H, W);
+}
+
+extern "C" int sdsm_edt_exact(const uint8_t *d_target, int H, int W, double *d_out, void *d_ws, size_t ws_bytes, void *stream)
+{
+    if (!d_target || !d_out || !d_ws || H < 1 || W < 1 || H > 65535 || W > 65535) return fail(SDSM_ERR_ARGUMENT, "sdsm_edt_exact: bad argument");
+    if (ws_bytes < sdsm_edt_exact_workspace_bytes(H, W)) return fail(SDSM_ERR_WORKSPACE, "sdsm_edt_exact: workspace too small");
+    hipError_t e = sdsm_edt_exact_impl(d_target, H, W, d_out, d_ws, (hipStream_t)stream);
+    return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_edt_exact");
+}

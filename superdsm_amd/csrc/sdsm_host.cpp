@@ -7,6 +7,9 @@
 // Footprints are bit sets over the atoms of one cluster: `words` uint64 per object.
 #include <algorithm>
 #include <cstdint>
+#include <functional>
+#include <queue>
+#include <tuple>
 #include <unordered_set>
 #include <vector>
 
@@ -191,6 +194,34 @@ extern "C" int sdsm_count_growth(int n_clusters, const int32_t *offsets, const u
             total += (int64_t)next.size();
             current.assign(next.begin(), next.end());
             size++;
+        }
+    }
+    return SDSM_OK;
+}
+
+// Marker flood of the coarse-to-fine region analysis (the restated rule of scikit-image's heap flood): priority = the
+// pixel's own value, ties by push age, then by raster index (markers only: they all have age 0).
+extern "C" int sdsm_watershed(const double *image, const int32_t *markers, const uint8_t *mask, int H, int W, int32_t *out)
+{
+    if (!image || !markers || !out || H < 1 || W < 1 || (int64_t)H * W >= INT32_MAX) return SDSM_ERR_ARGUMENT;
+    typedef std::tuple<double, int64_t, int32_t> Entry;
+    std::priority_queue<Entry, std::vector<Entry>, std::greater<Entry>> heap;
+    const int32_t n = H * W;
+    for (int32_t p = 0; p < n; p++) {
+        const bool ok = !mask || mask[p];
+        out[p] = ok ? markers[p] : 0;
+        if (ok && markers[p] != 0) heap.emplace(image[p], 0, p);
+    }
+    int64_t age = 0;
+    while (!heap.empty()) {
+        const int32_t p = std::get<2>(heap.top());
+        heap.pop();
+        const int r = p / W, c = p - r * W;
+        const int32_t nb[4] = {r > 0 ? p - W : -1, c > 0 ? p - 1 : -1, c + 1 < W ? p + 1 : -1, r + 1 < H ? p + W : -1};
+        for (int32_t q : nb) {
+            if (q < 0 || out[q] != 0 || (mask && !mask[q])) continue;
+            out[q] = out[p];
+            heap.emplace(image[q], ++age, q);
         }
     }
     return SDSM_OK;

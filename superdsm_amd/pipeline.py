@@ -137,3 +137,14 @@ def create_default_pipeline(extra_stages=()):
     from .globalenergymin import GlobalEnergyMinimization
     from .preprocess import Preprocessing
     return create_pipeline([Preprocessing(), DSM_Config(), *extra_stages, GlobalEnergyMinimization()])
+
+
+def create_reference_pipeline():
+    """The reference's five stages (superdsm/pipeline.py:268-285): Preprocessing -> DSM_Config -> C2F_RegionAnalysis ->
+    GlobalEnergyMinimization -> Postprocessing."""
+    from .c2freganal import C2F_RegionAnalysis
+    from .dsmcfg import DSM_Config
+    from .globalenergymin import GlobalEnergyMinimization
+    from .postprocess import Postprocessing
+    from .preprocess import Preprocessing
+    return create_pipeline([Preprocessing(), DSM_Config(), C2F_RegionAnalysis(), GlobalEnergyMinimization(), Postprocessing()])
