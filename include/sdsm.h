@@ -199,6 +199,24 @@ int sdsm_post_objects(const double *d_g, const double *d_gs, const uint8_t *d_bg
                       const int64_t *d_bits_off, const uint32_t *d_bits, const int64_t *d_new_off, uint32_t *d_new_bits,
                       uint32_t *d_boundary_pool, const int64_t *d_bpool_off, double exterior_scale, double exterior_offset,
                       double contrast_epsilon, double inv_gstd, int max_distance, double stdamp, sdsm_post_record *d_out, void *stream);
+/* sdsm_post_objects for the objects of up to SDSM_MAX_SET_IMAGES images in ONE launch (one workgroup per object).  The per-image inputs
+ * move into a HOST table of sdsm_post_image; the objects of image 0 come first (n_objects of them), then those of image 1, and so on.
+ * Every per-object array (d_boxes, d_bits_off, d_bits, d_new_off, d_new_bits, d_boundary_pool, d_bpool_off, d_out) runs over the
+ * objects of the whole set with the meaning and formats of sdsm_post_objects; a box is in its own image's coordinates.  The shared
+ * parameters hold for every image.  Per object, byte-equal to sdsm_post_objects on its image alone. */
+typedef struct {
+    const double *d_g;      /* raw intensities, H*W float64 */
+    const double *d_gs;     /* smoothed intensities of the mask refinement */
+    const uint8_t *d_bg;    /* background_mask */
+    int32_t H, W;           /* 1 .. 65535 */
+    double inv_gstd;        /* 1 / g.std() */
+    int32_t n_objects;      /* >= 0 */
+    int32_t reserved;
+} sdsm_post_image;
+int sdsm_post_objects_multi(const sdsm_post_image *images, int n_images, const int32_t *d_boxes, const int64_t *d_bits_off,
+                            const uint32_t *d_bits, const int64_t *d_new_off, uint32_t *d_new_bits, uint32_t *d_boundary_pool,
+                            const int64_t *d_bpool_off, double exterior_scale, double exterior_offset, double contrast_epsilon,
+                            int max_distance, double stdamp, sdsm_post_record *d_out, void *stream);
 /* Separable Gaussian filter with SciPy's defaults (mode 'reflect', truncate 4): the smoothing of postprocess.py:165-166 and the
  * building block of sdsm_preprocess. */
 size_t sdsm_gaussian_workspace_bytes(int H, int W, double sigma);
@@ -259,6 +277,30 @@ int sdsm_edt_exact(const uint8_t *d_target, int H, int W, double *d_out, void *d
  * left, right, down) with its own label and pushes them with the next age.  out: int32 labels, 0 outside the mask and where no marker
  * reaches. */
 int sdsm_watershed(const double *image, const int32_t *markers, const uint8_t *mask, int H, int W, int32_t *out);
+
+/* ---- image sets: the image-wide steps above for several images at once ----------------------------------------------------------
+ * A *_multi entry point runs one step for a set of 1 .. SDSM_MAX_SET_IMAGES images: every kernel phase is ONE launch for the whole set,
+ * with no host synchronisation between images (a caller splits larger sets).  The set is described by a HOST table of
+ * sdsm_set_image: image i has H x W pixels (row-major) starting at element `offset` of every packed pixel buffer of the call (counted
+ * in that buffer's element type).  Pixel indices stay local to their image, so only each image is bound by the single-image limits and
+ * the set may hold more than 2^31 pixels.  The images must not overlap in an output buffer.  The table is read on the host; it
+ * reaches the device with the launches, so the caller may free it when the call returns.  Per image, the results are byte-equal to
+ * the single-image entry point.  The workspace sizes grow with the set (adding an image never shrinks them); 0 = bad table. */
+#define SDSM_MAX_SET_IMAGES 32
+typedef struct {
+    int64_t offset;         /* first element of the image in the packed buffers, >= 0 */
+    int32_t H, W;           /* >= 1 */
+} sdsm_set_image;
+/* sdsm_c2f_markers for every image of the set (c2freganal.py:110-123): d_y (float64), d_y_mask (uint8) and d_markers (int32) packed as
+ * the table says; max_irregularity: HOST array, one threshold per image; d_count (device): n_images int32, the markers of each image.
+ * H * W < 2^31 per image. */
+size_t sdsm_c2f_markers_workspace_bytes_multi(const sdsm_set_image *images, int n_images);
+int sdsm_c2f_markers_multi(const sdsm_set_image *images, int n_images, const double *d_y, const double *max_irregularity, uint8_t *d_y_mask,
+                           int32_t *d_markers, int32_t *d_count, void *d_ws, size_t ws_bytes, void *stream);
+/* sdsm_edt_exact for every image of the set: d_target (uint8) and d_out (float64) packed as the table says.  H, W <= 65535 per image. */
+size_t sdsm_edt_exact_workspace_bytes_multi(const sdsm_set_image *images, int n_images);
+int sdsm_edt_exact_multi(const sdsm_set_image *images, int n_images, const uint8_t *d_target, double *d_out, void *d_ws, size_t ws_bytes,
+                         void *stream);
 
 /* ---- host-side combinatorial steps of the stage (no device access) -------------------------------------------------------------
  * Approximate min-weight set cover (superdsm/minsetcover.py:4-88: greedy + merge phase, retried with beta * gamma on up to max_iter

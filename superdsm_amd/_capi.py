@@ -38,6 +38,18 @@ DOH_PEAK_DTYPE = np.dtype([('r', 'i4'), ('c', 'i4'), ('s', 'i4'), ('reserved', '
 assert DOH_PEAK_DTYPE.itemsize == 24
 DOH_PEAKS_HEADER_BYTES = 16
 DOH_MAX_SCALES = 32
+MAX_SET_IMAGES = 32          # SDSM_MAX_SET_IMAGES: images per call of a *_multi entry point
+
+
+class SetImage(C.Structure):
+    """sdsm_set_image: an image of a set in the packed buffers of a *_multi call."""
+    _fields_ = [('offset', C.c_int64), ('H', C.c_int32), ('W', C.c_int32)]
+
+
+class PostImage(C.Structure):
+    """sdsm_post_image: the per-image inputs of sdsm_post_objects_multi."""
+    _fields_ = [('d_g', C.c_void_p), ('d_gs', C.c_void_p), ('d_bg', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32),
+                ('inv_gstd', C.c_double), ('n_objects', C.c_int32), ('reserved', C.c_int32)]
 
 # every entry point of include/sdsm.h: name -> (restype, argtypes)
 _vp, _i32, _f64, _sz, _i64 = C.c_void_p, C.c_int, C.c_double, C.c_size_t, C.c_int64
@@ -68,6 +80,7 @@ SYMBOLS = {
     'sdsm_plan_schedule': (_i32, [_vp, _vp, _vp]),
     'sdsm_plan_set_latency_mode': (_i32, [_vp, _i32]),
     'sdsm_post_objects': (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _f64, _i32, _f64, _vp, _vp]),
+    'sdsm_post_objects_multi': (_i32, [C.POINTER(PostImage), _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _i32, _f64, _vp, _vp]),
     'sdsm_gaussian_workspace_bytes': (_sz, [_i32, _i32, _f64]),
     'sdsm_gaussian_filter': (_i32, [_vp, _i32, _i32, _f64, _vp, _vp, _sz, _vp]),
     'sdsm_separable_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32]),
@@ -82,6 +95,10 @@ SYMBOLS = {
     'sdsm_edt_exact_workspace_bytes': (_sz, [_i32, _i32]),
     'sdsm_edt_exact': (_i32, [_vp, _i32, _i32, _vp, _vp, _sz, _vp]),
     'sdsm_watershed': (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
+    'sdsm_c2f_markers_workspace_bytes_multi': (_sz, [C.POINTER(SetImage), _i32]),
+    'sdsm_c2f_markers_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, C.POINTER(C.c_double), _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sdsm_edt_exact_workspace_bytes_multi': (_sz, [C.POINTER(SetImage), _i32]),
+    'sdsm_edt_exact_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, _vp, _sz, _vp]),
     'sdsm_minsetcover': (_i32, [_i32, _i32, _vp, _vp, _f64, _i32, _i32, _f64, _vp, _vp]),
     'sdsm_minsetcover_multi': (_i32, [_i32, _vp, _vp, _vp, _vp, _f64, _i32, _i32, _f64, _vp, _vp]),
     'sdsm_maxsetpack': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp]),

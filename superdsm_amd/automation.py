@@ -330,8 +330,27 @@ def create_config(pipeline, base_cfg, img=None):
         if img is None:
             raise ValueError('AF_scale is not set and there is no image to estimate the scale from')
         scale = _estimate_scale(img, num_radii=10, thresholds=[0.01])[0]
+    _configure(pipeline, cfg, scale)
+    return cfg, scale
+
+
+def _configure(pipeline, cfg, scale):
     for stage in pipeline.stages:
         for key, spec in stage.configure(scale).items():
             assert len(spec) in (2, 3), f'{type(stage).__name__}.configure returned tuple of unknown length ({len(spec)})'
             _expand(cfg, f'{stage.cfgns}/{key}', spec[0], spec[1], **(spec[2] if len(spec) == 3 else {}))
-    return cfg, scale
+
+
+def create_configs(pipeline, base_cfg, images):
+    """:func:`create_config` for every image of a set: ``(cfg, scale)`` per image.  Without ``AF_scale``, :func:`estimate_scales`
+    estimates the scales of all images in one call."""
+    images = list(images)
+    scale = base_cfg.copy().get('AF_scale', None)
+    scales = [scale] * len(images) if scale is not None else [s[0] for s in estimate_scales(images, num_radii=10, thresholds=[0.01])]
+    result = []
+    for scale in scales:
+        cfg = base_cfg.copy()
+        cfg.get('AF_scale', None)                       # (as create_config: the key is there afterwards, None if it was unset)
+        _configure(pipeline, cfg, scale)
+        result.append((cfg, scale))
+    return result

@@ -29,6 +29,7 @@ from . import _capi, _morph
 from .atoms import AtomAdjacencyGraph
 from .image import Image
 from .objects import CvxprogError, Object
+from .output import get_output
 from .pipeline import Stage
 
 DEFAULTS = dict(seed_connectivity=8, min_atom_radius=15, max_atom_norm_energy=0.05, min_norm_energy_improvement=0.1,
@@ -384,6 +385,82 @@ def edt_exact_gpu(target):
     return out.cpu().numpy()
 
 
+def _set_layout(shapes):
+    """Packed layout of a set: the ``_capi.SetImage`` table and the total of elements (every image 256-element aligned)."""
+    table = (_capi.SetImage * len(shapes))()
+    total = 0
+    for k, (h, w) in enumerate(shapes):
+        table[k].offset, table[k].H, table[k].W = total, int(h), int(w)
+        total += (int(h) * int(w) + _CROP_ALIGN - 1) // _CROP_ALIGN * _CROP_ALIGN
+    return table, total
+
+
+def markers_and_edt_gpu_multi(ys, max_cluster_marker_irregularity):
+    """:func:`cluster_markers_gpu` and then :func:`edt_exact_gpu` of the markers, for a set of images: one packed upload of all ``y``,
+    ``sdsm_c2f_markers_multi`` and ``sdsm_edt_exact_multi`` over up to ``_capi.MAX_SET_IMAGES`` images per call, one download.
+    ``max_cluster_marker_irregularity``: one threshold for all or one per image.  Returns ``(y_mask, cluster_markers, count,
+    distances)`` per image, equal to the single-image functions."""
+    torch = _device()
+    L = _capi.lib()
+    ys = [np.asarray(y, np.float64) for y in ys]
+    thrs = list(max_cluster_marker_irregularity) if np.ndim(max_cluster_marker_irregularity) else [max_cluster_marker_irregularity] * len(ys)
+    results = []
+    for lo in range(0, len(ys), _capi.MAX_SET_IMAGES):
+        part = ys[lo:lo + _capi.MAX_SET_IMAGES]
+        table, total = _set_layout([y.shape for y in part])
+        y_all = np.zeros(total, np.float64)
+        for k, y in enumerate(part):
+            y_all[table[k].offset:table[k].offset + y.size] = y.ravel()
+        d_y = torch.from_numpy(y_all).cuda()
+        n = len(part)
+        # one buffer for everything that comes back: distances (float64), markers (int32), y_mask (uint8), counts (int32)
+        d_res = torch.empty(13 * total + 4 * n, dtype=torch.uint8, device=d_y.device)
+        d_dist = d_res[:8 * total].view(torch.float64)
+        d_markers = d_res[8 * total:12 * total].view(torch.int32)
+        d_mask = d_res[12 * total:13 * total]
+        d_count = d_res[13 * total:].view(torch.int32)
+        thr = (C.c_double * n)(*[float(t) for t in thrs[lo:lo + n]])
+        m_bytes = L.sdsm_c2f_markers_workspace_bytes_multi(table, n)
+        e_bytes = L.sdsm_edt_exact_workspace_bytes_multi(table, n)
+        ws = torch.empty(max(m_bytes, e_bytes), dtype=torch.uint8, device=d_y.device)     # the EDT follows the markers on one stream
+        p = lambda t: C.c_void_p(t.data_ptr())
+        _capi.check(L.sdsm_c2f_markers_multi(table, n, p(d_y), thr, p(d_mask), p(d_markers), p(d_count), p(ws), m_bytes, _stream(torch)),
+                    'sdsm_c2f_markers_multi')
+        d_target = (d_markers != 0).to(torch.uint8)
+        _capi.check(L.sdsm_edt_exact_multi(table, n, p(d_target), p(d_dist), p(ws), e_bytes, _stream(torch)), 'sdsm_edt_exact_multi')
+        res = d_res.cpu().numpy()
+        dist, markers = res[:8 * total].view(np.float64), res[8 * total:12 * total].view(np.int32)
+        mask, count = res[12 * total:13 * total], res[13 * total:].view(np.int32)
+        for k, y in enumerate(part):
+            o, sh = table[k].offset, y.shape
+            results.append((mask[o:o + y.size].reshape(sh).astype(bool), markers[o:o + y.size].reshape(sh).copy(), int(count[k]),
+                            dist[o:o + y.size].reshape(sh).copy()))
+    return results
+
+
+def edt_exact_gpu_multi(targets):
+    """:func:`edt_exact_gpu` of every image of a set (``sdsm_edt_exact_multi``, up to ``_capi.MAX_SET_IMAGES`` images per call)."""
+    torch = _device()
+    L = _capi.lib()
+    targets = [np.asarray(t) != 0 for t in targets]
+    out = []
+    for lo in range(0, len(targets), _capi.MAX_SET_IMAGES):
+        part = targets[lo:lo + _capi.MAX_SET_IMAGES]
+        table, total = _set_layout([t.shape for t in part])
+        t_all = np.zeros(total, np.uint8)
+        for k, t in enumerate(part):
+            t_all[table[k].offset:table[k].offset + t.size] = t.ravel()
+        d_t = torch.from_numpy(t_all).cuda()
+        d_out = torch.empty(total, dtype=torch.float64, device=d_t.device)
+        nbytes = L.sdsm_edt_exact_workspace_bytes_multi(table, len(part))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=d_t.device)
+        _capi.check(L.sdsm_edt_exact_multi(table, len(part), C.c_void_p(d_t.data_ptr()), C.c_void_p(d_out.data_ptr()), C.c_void_p(ws.data_ptr()),
+                                           nbytes, _stream(torch)), 'sdsm_edt_exact_multi')
+        res = d_out.cpu().numpy()
+        out += [res[table[k].offset:table[k].offset + t.size].reshape(t.shape).copy() for k, t in enumerate(part)]
+    return out
+
+
 class _CropImage:
     """What ``engine.Batch`` needs of a ``DeviceImage``, for one cluster crop of a round: views into the round's packed buffers."""
 
@@ -556,6 +633,121 @@ def region_analysis_gpu(y, dsm_cfg, **params):
     return out, stats
 
 
+def _same_config(a, b):
+    try:
+        return bool(a == b)
+    except Exception:                                   # noqa: BLE001 -- values without a truth value of ==: treat as different
+        return False
+
+
+def region_analysis_gpu_multi(ys, dsm_cfgs, params):
+    """:func:`region_analysis_gpu` for a set of images: the markers and EDT of all images in one pass
+    (:func:`markers_and_edt_gpu_multi`), the flood per image, then the split loops of ALL clusters of ALL images in lock step, keyed
+    ``(image, label)``: every round's requests go through one ``EnergyRounds.solve`` per distinct energy configuration (one for a set
+    with one configuration).  A candidate's record does not depend on the plan it is solved in, so every image's
+    outputs equal :func:`region_analysis_gpu` on that image alone, and the set takes as many rounds as its image with the most.
+
+    ``dsm_cfgs`` / ``params``: one per image.  An image whose split fails (``C2FError``, ``CvxprogError``) leaves the set; the others
+    finish.  Returns ``(outputs, stats, set_stats, errors)``: per image its outputs (None where it failed), its phase timings (set-wide
+    phases shared evenly) and its error (or None)."""
+    _device()
+    t_all = time.perf_counter()
+    n = len(ys)
+    params = [_params(**p) for p in params]
+    dsm_cfgs = [dict(c, smooth_amount=np.inf) for c in dsm_cfgs]
+    ys = [np.asarray(y, np.float64) for y in ys]
+    stats = [dict(rounds=[], host_split_s=0.0) for _ in range(n)]
+    errors = [None] * n
+    t0 = time.perf_counter()
+    marked = markers_and_edt_gpu_multi(ys, [p['max_cluster_marker_irregularity'] for p in params])
+    markers_edt_s = time.perf_counter() - t0
+    groups = []                                         # (energy configuration, EnergyRounds, images)
+    for i, c in enumerate(dsm_cfgs):
+        key = _energy_config(c)
+        for g in groups:
+            if _same_config(g[0], key):
+                g[2].append(i)
+                break
+        else:
+            groups.append((key, EnergyRounds(c), [i]))
+    flood_s = 0.0
+    clusters, labels, images = [None] * n, [None] * n, [None] * n
+    for i, (y, (y_mask, cluster_markers, _, distances)) in enumerate(zip(ys, marked)):
+        tf = time.perf_counter()
+        clusters[i] = watershed_native(distances, cluster_markers)
+        stats[i]['flood_s'] = time.perf_counter() - tf
+        flood_s += stats[i]['flood_s']
+        images[i] = Image.create_from_array(y, normalize=False)
+
+    done, pending = [dict() for _ in range(n)], {}
+
+    def fail(i, e):
+        errors[i] = e
+        for k in [k for k in pending if k[0] == i]:
+            del pending[k]
+
+    host_s = 0.0
+    for i in range(n):
+        th = time.perf_counter()
+        boxes = ndi.find_objects(clusters[i])
+        labels[i] = [label for label in range(1, len(boxes) + 1) if boxes[label - 1] is not None]
+        for label in labels[i]:
+            cluster, masked_cluster = _cluster_regions(images[i], marked[i][0], clusters[i], label, boxes[label - 1])
+            steps = _split_cluster(label, cluster, masked_cluster, params[i], watershed_native)
+            try:
+                pending[i, label] = (cluster, masked_cluster, steps, next(steps))
+            except StopIteration as stop:
+                done[i][label] = (cluster, *stop.value)
+            except (C2FError, CvxprogError) as e:
+                fail(i, e)
+                break
+        dt = time.perf_counter() - th
+        stats[i]['host_split_s'] += dt
+        host_s += dt
+    n_rounds = 0
+    while pending:
+        n_rounds += 1
+        order = sorted(pending)
+        for i in sorted({k[0] for k in order}):
+            stats[i]['rounds'].append(dict(crops=sum(1 for k in order if k[0] == i)))
+        for _, rounds, members in groups:
+            keys = [k for k in order if k[0] in members]
+            if not keys:
+                continue
+            requests = [(pending[k][0].model, pending[k][1].mask, pending[k][3][0], pending[k][3][1]) for k in keys]
+            results = rounds.solve(requests)
+            for k, res in zip(keys, results):
+                if k not in pending:                    # its image failed earlier in this round
+                    continue
+                th = time.perf_counter()
+                cluster, masked_cluster, steps, _ = pending.pop(k)
+                try:
+                    pending[k] = (cluster, masked_cluster, steps, steps.send(res))
+                except StopIteration as stop:
+                    done[k[0]][k[1]] = (cluster, *stop.value)
+                except (C2FError, CvxprogError) as e:
+                    fail(k[0], e)
+                dt = time.perf_counter() - th
+                stats[k[0]]['host_split_s'] += dt
+                host_s += dt
+    outputs = [None] * n
+    assemble_s = 0.0
+    for i in range(n):
+        if errors[i] is not None:
+            continue
+        ta = time.perf_counter()
+        outputs[i] = _assemble(ys[i], marked[i][0], clusters[i], [done[i][k] for k in labels[i]])
+        stats[i].update(assemble_s=time.perf_counter() - ta, clusters=len(labels[i]))
+        assemble_s += stats[i]['assemble_s']
+    logs = [r for _, rounds, _ in groups for r in rounds.log]
+    set_stats = dict(images=n, markers_edt_s=markers_edt_s, flood_s=flood_s, host_split_s=host_s, assemble_s=assemble_s, n_rounds=n_rounds,
+                     rounds=logs, launches=sum(rounds.launches for _, rounds, _ in groups), energy_s=sum(r['seconds'] for r in logs),
+                     total_s=time.perf_counter() - t_all)
+    for st in stats:
+        st.update(markers_edt_s=markers_edt_s / max(n, 1), energy_s=set_stats['energy_s'] / max(n, 1))
+    return outputs, stats, set_stats, errors
+
+
 class C2F_RegionAnalysis(Stage):
     """The coarse-to-fine region analysis (c2freganal.py:82-207): requires ``y`` and ``dsm_cfg``, produces ``y_mask``, ``atoms``,
     ``adjacencies``, ``seeds`` and ``clusters``.  Hyper-parameters (``c2f-region-analysis/...``) and defaults as in the reference:
@@ -575,6 +767,34 @@ class C2F_RegionAnalysis(Stage):
         out.write(f'Extracted {self.last_stats["clusters"]} clusters, {int(result["atoms"].max())} atoms '
                   f'({len(self.last_stats["rounds"])} energy rounds)')
         return result
+
+    def process_many(self, datas, cfg, out=None, log_root_dirs=None):
+        """The stage for a set of images (:func:`region_analysis_gpu_multi`), with the contract of
+        ``GlobalEnergyMinimization.process_many``: ``datas`` is a list of pipeline data dicts (inputs read from, outputs written to
+        each), ``cfg`` one config for all or a list; returns the wall time.  The outputs of every image equal those of ``process`` on
+        it alone.  ``last_stats`` becomes the list of the images' stats, ``last_set_stats`` those of the set.  An image that fails
+        (``C2FError``, ``CvxprogError``) gets no outputs; the others do, and then the first failure is raised with ``image_index``,
+        ``image_indices`` (every failed image) and ``image_errors`` (image -> its exception)."""
+        datas = list(datas)
+        cfgs = list(cfg) if isinstance(cfg, (list, tuple)) else [cfg] * len(datas)
+        cfgs = [c.get(self.cfgns, {}) for c in cfgs]
+        out = get_output(out)
+        t0 = time.time()
+        outputs, self.last_stats, self.last_set_stats, errors = region_analysis_gpu_multi(
+            [d['y'] for d in datas], [d['dsm_cfg'] for d in datas], [_params(c) for c in cfgs])
+        for i, (data, result) in enumerate(zip(datas, outputs)):
+            if result is None:
+                continue
+            for inner, outer in self.outputs.items():
+                data[outer] = result[inner]
+            out.write(f'Image {i}: extracted {self.last_stats[i]["clusters"]} clusters, {int(result["atoms"].max())} atoms '
+                      f'({len(self.last_stats[i]["rounds"])} energy rounds)')
+        failed = [i for i, e in enumerate(errors) if e is not None]
+        if failed:
+            e = errors[failed[0]]
+            e.image_index, e.image_indices, e.image_errors = failed[0], failed, {i: errors[i] for i in failed}
+            raise e
+        return time.time() - t0
 
     def configure_ex(self, scale, radius, diameter):
         return {

@@ -873,3 +873,82 @@ extern "C" int sdsm_edt_exact(const uint8_t *d_target, int H, int W, double *d_o
     hipError_t e = sdsm_edt_exact_impl(d_target, H, W, d_out, d_ws, (hipStream_t)stream);
     return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_edt_exact");
 }
+
+// ---- image sets ----------------------------------------------------------------------------------------------------------------
+extern "C" size_t sdsm_c2f_markers_workspace_bytes_multi_impl(const sdsm_set_image *images, int n_images);
+extern "C" hipError_t sdsm_c2f_markers_multi_impl(const sdsm_set_image *images, int n_images, const double *d_y, const double *thr,
+                                                  uint8_t *d_y_mask, int32_t *d_markers, int32_t *d_count, void *d_ws, hipStream_t stream);
+extern "C" size_t sdsm_edt_exact_workspace_bytes_multi_impl(const sdsm_set_image *images, int n_images);
+extern "C" hipError_t sdsm_edt_exact_multi_impl(const sdsm_set_image *images, int n_images, const uint8_t *d_target, double *d_out, void *d_ws,
+                                                hipStream_t stream);
+extern "C" hipError_t sdsm_launch_post_set(const sdsm_post_image *images, int n_images, const int32_t *boxes, const int64_t *bits_off,
+                                           const uint32_t *bits, const int64_t *new_off, uint32_t *new_bits, uint32_t *boundary_pool,
+                                           const int64_t *bpool_off, double exterior_scale, double exterior_offset, double contrast_epsilon,
+                                           int max_distance, double stdamp, sdsm_post_record *out, hipStream_t stream);
+
+// a set table every image of which the single-image entry point takes: 1 .. SDSM_MAX_SET_IMAGES images, offsets >= 0, H, W >= 1, and
+// H * W < 2^31 (markers) or H, W <= 65535 (EDT)
+static bool set_table_ok(const sdsm_set_image *images, int n_images, bool edt)
+{
+    if (!images || n_images < 1 || n_images > SDSM_MAX_SET_IMAGES) return false;
+    for (int i = 0; i < n_images; i++) {
+        const sdsm_set_image &im = images[i];
+        if (im.offset < 0 || im.H < 1 || im.W < 1) return false;
+        if (edt ? (im.H > 65535 || im.W > 65535) : (int64_t)im.H * im.W >= INT_MAX) return false;
+    }
+    return true;
+}
+
+extern "C" size_t sdsm_c2f_markers_workspace_bytes_multi(const sdsm_set_image *images, int n_images)
+{
+    return set_table_ok(images, n_images, false) ? sdsm_c2f_markers_workspace_bytes_multi_impl(images, n_images) : 0;
+}
+
+extern "C" int sdsm_c2f_markers_multi(const sdsm_set_image *images, int n_images, const double *d_y, const double *max_irregularity,
+                                      uint8_t *d_y_mask, int32_t *d_markers, int32_t *d_count, void *d_ws, size_t ws_bytes, void *stream)
+{
+    if (!set_table_ok(images, n_images, false)) return fail(SDSM_ERR_ARGUMENT, "sdsm_c2f_markers_multi: bad image table (1 .. 32 images, offset >= 0, 1 <= H, W, H * W < 2^31)");
+    if (!d_y || !max_irregularity || !d_y_mask || !d_markers || !d_count || !d_ws) return fail(SDSM_ERR_ARGUMENT, "sdsm_c2f_markers_multi: null argument");
+    if (ws_bytes < sdsm_c2f_markers_workspace_bytes_multi(images, n_images)) return fail(SDSM_ERR_WORKSPACE, "sdsm_c2f_markers_multi: workspace too small");
+    hipError_t e = sdsm_c2f_markers_multi_impl(images, n_images, d_y, max_irregularity, d_y_mask, d_markers, d_count, d_ws, (hipStream_t)stream);
+    return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_c2f_markers_multi");
+}
+
+extern "C" size_t sdsm_edt_exact_workspace_bytes_multi(const sdsm_set_image *images, int n_images)
+{
+    return set_table_ok(images, n_images, true) ? sdsm_edt_exact_workspace_bytes_multi_impl(images, n_images) : 0;
+}
+
+extern "C" int sdsm_edt_exact_multi(const sdsm_set_image *images, int n_images, const uint8_t *d_target, double *d_out, void *d_ws, size_t ws_bytes,
+                                    void *stream)
+{
+    if (!set_table_ok(images, n_images, true)) return fail(SDSM_ERR_ARGUMENT, "sdsm_edt_exact_multi: bad image table (1 .. 32 images, offset >= 0, 1 <= H, W <= 65535)");
+    if (!d_target || !d_out || !d_ws) return fail(SDSM_ERR_ARGUMENT, "sdsm_edt_exact_multi: null argument");
+    if (ws_bytes < sdsm_edt_exact_workspace_bytes_multi(images, n_images)) return fail(SDSM_ERR_WORKSPACE, "sdsm_edt_exact_multi: workspace too small");
+    hipError_t e = sdsm_edt_exact_multi_impl(images, n_images, d_target, d_out, d_ws, (hipStream_t)stream);
+    return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_edt_exact_multi");
+}
+
+extern "C" int sdsm_post_objects_multi(const sdsm_post_image *images, int n_images, const int32_t *d_boxes, const int64_t *d_bits_off,
+                                       const uint32_t *d_bits, const int64_t *d_new_off, uint32_t *d_new_bits, uint32_t *d_boundary_pool,
+                                       const int64_t *d_bpool_off, double exterior_scale, double exterior_offset, double contrast_epsilon,
+                                       int max_distance, double stdamp, sdsm_post_record *d_out, void *stream)
+{
+    if (!images || n_images < 1 || n_images > SDSM_MAX_SET_IMAGES) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_objects_multi: 1 .. 32 images per call");
+    int64_t n = 0;
+    for (int j = 0; j < n_images; j++) {
+        const sdsm_post_image &im = images[j];
+        if (im.n_objects < 0 || im.H < 1 || im.W < 1 || im.H > 65535 || im.W > 65535) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_objects_multi: bad image (shape or object count)");
+        if (im.n_objects > 0 && (!im.d_g || !im.d_gs || !im.d_bg)) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_objects_multi: null image input");
+        n += im.n_objects;
+    }
+    if (n >= INT_MAX) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_objects_multi: more than 2^31 - 1 objects");
+    if (n == 0) return SDSM_OK;
+    if (!d_boxes || !d_bits_off || !d_bits || !d_out) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_objects_multi: null argument");
+    if (!(exterior_scale > 0) || !(exterior_offset >= 0) || max_distance < 0 || max_distance > 16) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_objects_multi: exterior_scale > 0, exterior_offset >= 0, 0 <= max_distance <= 16 required");
+    if (max_distance > 0 && stdamp > 0 && (!d_new_off || !d_new_bits)) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_objects_multi: refinement needs the output mask buffers");
+    if ((d_boundary_pool == nullptr) != (d_bpool_off == nullptr)) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_objects_multi: boundary pool and its offsets go together");
+    hipError_t e = sdsm_launch_post_set(images, n_images, d_boxes, d_bits_off, d_bits, d_new_off, d_new_bits, d_boundary_pool, d_bpool_off,
+                                        exterior_scale, exterior_offset, contrast_epsilon, max_distance, stdamp, d_out, (hipStream_t)stream);
+    return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_post_objects_multi");
+}

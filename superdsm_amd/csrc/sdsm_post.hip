@@ -1,4 +1,5 @@
-// Per-object work of the post-processing stage, one workgroup per object, one launch per image.
+// Per-object work of the post-processing stage, one workgroup per object, one launch per image
+// (sdsm_k_post) or per set of images (sdsm_k_post_set: the image of an object comes from the launch's table).
 //
 // Reference behaviour restated here (never its code):
 //   contrast response           superdsm/postprocess.py:254-266  (_compute_contrast)
@@ -42,12 +43,13 @@ __device__ __forceinline__ bool frag_bit(const uint32_t *bits, int h, int w, int
 
 }  // namespace
 
-__global__ __launch_bounds__(POST_WG) void sdsm_k_post(PostParams P)
+// object i of P (one workgroup): the body of sdsm_k_post and of sdsm_k_post_set
+__device__ __forceinline__ void post_object(const PostParams &P, int i)
 {
     __shared__ uint32_t bnd[POST_MAX_BOUNDARY];
     __shared__ double red[POST_WG / 64 * 8];
     __shared__ int nb_sh, ired[POST_WG / 64];
-    const int tid = threadIdx.x, i = blockIdx.x;
+    const int tid = threadIdx.x;
     const int r0 = P.boxes[4 * i], c0 = P.boxes[4 * i + 1], h = P.boxes[4 * i + 2], w = P.boxes[4 * i + 3];
     const uint32_t *bits = P.bits + P.bits_off[i];
     if (tid == 0) nb_sh = 0;
@@ -172,6 +174,62 @@ __global__ __launch_bounds__(POST_WG) void sdsm_k_post(PostParams P)
         if (rmax >= 0) { rec.r0 = rmin; rec.c0 = cmin; rec.h = rmax - rmin + 1; rec.w = cmax - cmin + 1; }
     } else { rec.r0 = r0; rec.c0 = c0; rec.h = h; rec.w = w; rec.status = 3; }   // no refinement on the device
     if (tid == 0) P.out[i] = rec;
+}
+
+__global__ __launch_bounds__(POST_WG) void sdsm_k_post(PostParams P)
+{
+    post_object(P, blockIdx.x);
+}
+
+namespace {
+
+// the objects of a set of images: the shared parameters and per-object arrays in P, the per-image inputs in the table
+struct PostSetParams {
+    PostParams P;
+    int32_t n_images;
+    int32_t first[SDSM_MAX_SET_IMAGES + 1];      // prefix of the images' object counts
+    sdsm_post_image im[SDSM_MAX_SET_IMAGES];
+};
+
+}  // namespace
+
+__global__ __launch_bounds__(POST_WG) void sdsm_k_post_set(PostSetParams S)
+{
+    // the image of this object: the last j with first[j] <= blockIdx.x (images without objects are passed over)
+    int lo = 0, hi = S.n_images - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (S.first[mid] <= (int)blockIdx.x) lo = mid;
+        else hi = mid - 1;
+    }
+    const sdsm_post_image &im = S.im[lo];
+    PostParams P = S.P;
+    P.H = im.H; P.W = im.W; P.n = im.n_objects; P.inv_gstd = im.inv_gstd;
+    P.g = im.d_g; P.gs = im.d_gs; P.bg = im.d_bg;
+    post_object(P, blockIdx.x);
+}
+
+extern "C" hipError_t sdsm_launch_post_set(const sdsm_post_image *images, int n_images, const int32_t *boxes, const int64_t *bits_off,
+                                           const uint32_t *bits, const int64_t *new_off, uint32_t *new_bits, uint32_t *boundary_pool,
+                                           const int64_t *bpool_off, double exterior_scale, double exterior_offset, double contrast_epsilon,
+                                           int max_distance, double stdamp, sdsm_post_record *out, hipStream_t stream)
+{
+    PostSetParams S{};
+    S.n_images = n_images;
+    S.first[0] = 0;
+    for (int j = 0; j < n_images; j++) {
+        S.im[j] = images[j];
+        S.first[j + 1] = S.first[j] + images[j].n_objects;
+    }
+    const int n = S.first[n_images];
+    if (n <= 0) return hipSuccess;
+    PostParams &P = S.P;
+    P.max_distance = max_distance;
+    P.exterior_scale = exterior_scale; P.exterior_offset = exterior_offset; P.contrast_epsilon = contrast_epsilon; P.stdamp = stdamp;
+    P.boxes = boxes; P.bits_off = bits_off; P.bits = bits; P.new_off = new_off; P.new_bits = new_bits;
+    P.boundary_pool = boundary_pool; P.bpool_off = bpool_off; P.out = out;
+    hipLaunchKernelGGL(sdsm_k_post_set, dim3(n), dim3(POST_WG), 0, stream, S);
+    return hipGetLastError();
 }
 
 extern "C" hipError_t sdsm_launch_post(const double *g, const double *gs, const uint8_t *bg, int H, int W, int n, const int32_t *boxes,

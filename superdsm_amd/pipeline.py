@@ -113,6 +113,101 @@ class Pipeline:
                 running = False
         return data, cfg, timings
 
+    def _selected_stages(self, first_stage, last_stage):
+        """The stages ``process_image`` runs for ``first_stage`` (None or a stage name) and ``last_stage``."""
+        running, selected = first_stage is None, []
+        for stage in self.stages:
+            if not running and stage.name == first_stage:
+                running = True
+            if running:
+                selected.append(stage)
+            if stage.name == last_stage:
+                running = False
+        return selected
+
+    def process_images(self, g_raws, cfg, first_stage=None, last_stage=None, datas=None, out=None, log_root_dirs=None):
+        """``process_image`` for a set of images: returns one ``(data, cfg, timings)`` per image, equal to what ``process_image``
+        returns for that image (``cfg``, ``datas`` and ``log_root_dirs``: one for all or one per image).  ``first_stage`` /
+        ``last_stage`` (with the ``+`` suffix), ``histological``, the stages' ``enabled`` setting and the ``start`` / ``end`` /
+        ``skip`` callbacks (fired per image) mean what they mean there.  A stage with a ``process_many`` runs once for the images it
+        is enabled for; its wall time is shared evenly among their ``timings``.  The other stages run image by image.
+
+        An image that fails in a stage (``C2FError``, ``CvxprogError``) leaves the set and the others finish; then the failure of the
+        lowest image index is raised with ``image_index``, ``image_indices`` (every failed image) and ``results`` (everyone's
+        ``(data, cfg, timings)`` so far).  Other exceptions end the call at once."""
+        from .c2freganal import C2FError
+        from .objects import CvxprogError
+        g_raws = list(g_raws)
+        n = len(g_raws)
+        if n == 0:
+            return []
+        per_image = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n
+        cfgs = [c.copy() for c in per_image(cfg)]
+        datas = per_image(datas)
+        logs = per_image(log_root_dirs)
+        assert len(cfgs) == len(datas) == len(logs) == n, 'one config, data and log directory per image'
+        for log in logs:
+            if log is not None:
+                os.makedirs(log, exist_ok=True)
+        # per image, as in process_image: the first stage without data starts from scratch
+        fresh = [first_stage is None or (first_stage == self.stages[0].name and data is None) for data in datas]
+        if first_stage is not None and first_stage.endswith('+'):
+            first_stage = self.stages[1 + self.find(first_stage[:-1])].name
+        if first_stage is not None and last_stage is not None and self.find(first_stage) > self.find(last_stage):
+            return [(data, c, {}) for data, c in zip(datas, cfgs)]
+        out = get_output(out)
+        for i in range(n):
+            if fresh[i]:
+                datas[i] = self.init(g_raws[i], cfgs[i])
+            else:
+                assert datas[i] is not None, 'data argument must be provided if first_stage is used'
+        timings = [{} for _ in range(n)]
+        errors = {}
+        for stage in self._selected_stages(first_stage, last_stage):
+            live = [i for i in range(n) if i not in errors]
+            if hasattr(stage, 'process_many'):
+                enabled = []
+                for i in live:
+                    if cfgs[i].get(stage.cfgns, {}).get('enabled', stage.ENABLED_BY_DEFAULT):
+                        enabled.append(i)
+                    else:
+                        timings[i][stage.name] = stage(datas[i], cfgs[i], out=out, log_root_dir=logs[i])    # skips it
+                if not enabled:
+                    continue
+                for i in enabled:
+                    out.intermediate(f'Starting stage "{stage.name}"')
+                    stage._callback('start', datas[i])
+                # the stage writes its outputs into copies: an image without them afterwards has failed
+                outer = set(stage.outputs.values())
+                subs = [{k: v for k, v in datas[i].items() if k not in outer} for i in enabled]
+                t0 = time.time()
+                try:
+                    dt, error = stage.process_many(subs, [cfgs[i] for i in enabled], out=out, log_root_dirs=[logs[i] for i in enabled]), None
+                except (C2FError, CvxprogError) as e:
+                    dt, error = time.time() - t0, e
+                for j, i in enumerate(enabled):
+                    timings[i][stage.name] = dt / len(enabled)
+                    if outer <= set(subs[j]):
+                        for key in outer:
+                            datas[i][key] = subs[j][key]
+                        stage._callback('end', datas[i])
+                    else:
+                        assert error is not None, f'stage "{stage.name}" generated no output for image {i}'
+                        errors[i] = getattr(error, 'image_errors', {}).get(j, error)
+            else:
+                for i in live:
+                    try:
+                        timings[i][stage.name] = stage(datas[i], cfgs[i], out=out, log_root_dir=logs[i])
+                    except (C2FError, CvxprogError) as e:
+                        errors[i] = e
+        results = [(data, c, t) for data, c, t in zip(datas, cfgs, timings)]
+        if errors:
+            first = min(errors)
+            e = errors[first]
+            e.image_index, e.image_indices, e.results = first, sorted(errors), results
+            raise e
+        return results
+
 
 def create_pipeline(stages):
     """Orders ``stages`` so that every stage's inputs are produced before it runs (``g_raw`` is given)."""

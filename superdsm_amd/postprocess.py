@@ -9,6 +9,7 @@ energy needs no recomputation (``Object.cvxprog_region_size``).  What stays on t
 filling, the glare test, the eccentricity and the accept / discard decisions.  There is no CPU path for the batch."""
 import math
 import os
+import time
 
 import numpy as np
 import scipy.ndimage as ndi
@@ -69,26 +70,19 @@ def gaussian_filter_gpu(g_dev, sigma):
     return out
 
 
-def process_objects_gpu(objects, g, g_mask_processing, background_mask, exterior_scale, exterior_offset, contrast_epsilon,
-                        mask_max_distance, mask_stdamp, device=None):
-    """Contrast response and refined mask (before hole filling) of every object: one launch (sdsm_post_objects).
-    ``g`` / ``g_mask_processing``: float64 device tensors; ``background_mask``: bool array or uint8 device tensor.
-    Returns (records POST_RECORD_DTYPE, list of (offset, fragment) or None where the device did not refine)."""
-    import ctypes as C
-    import torch
-    from . import engine
-    L = _capi.lib()
-    dev = g.device
-    H, W = (int(v) for v in g.shape)
-    n = len(objects)
-    if n == 0:
-        return np.zeros(0, _capi.POST_RECORD_DTYPE), []
-    boxes = np.zeros((n, 4), np.int32)
-    words = np.zeros(n, np.int64)
+def _refinement_radius(mask_max_distance, mask_stdamp):
     if mask_max_distance > 0 and mask_stdamp > 0 and float(mask_max_distance) != int(mask_max_distance):
         # skimage.morphology.disk(r) of a fractional radius (postprocess.py:316-337) is not a disk of int(r): refuse instead of truncating
         raise NotImplementedError(f'mask_max_distance = {mask_max_distance!r}: the GPU mask refinement takes integer radii (<= 16) only, see DESIGN.md "Limits"')
-    m = int(mask_max_distance) if (mask_max_distance > 0 and mask_stdamp > 0) else 0
+    return int(mask_max_distance) if (mask_max_distance > 0 and mask_stdamp > 0) else 0
+
+
+def _pack_objects(objects, H, W, m):
+    """The per-object inputs of sdsm_post_objects: boxes, words of the bit-packed fragments and of the refined windows, the packed
+    fragments, areas."""
+    n = len(objects)
+    boxes = np.zeros((n, 4), np.int32)
+    words = np.zeros(n, np.int64)
     new_words = np.zeros(n, np.int64)
     packed = []
     for k, obj in enumerate(objects):
@@ -104,32 +98,18 @@ def process_objects_gpu(objects, g, g_mask_processing, background_mask, exterior
         nh = min(H, r0 + h + m) - max(0, r0 - m)
         nwid = min(W, c0 + w + m) - max(0, c0 - m)
         new_words[k] = (nh * nwid + 31) // 32
-    bits_off = np.concatenate([[0], np.cumsum(words)[:-1]]).astype(np.int64)
-    new_off = np.concatenate([[0], np.cumsum(new_words)[:-1]]).astype(np.int64)
-    # objects with a very long mask boundary keep their boundary list in global memory (4 B per boundary pixel <= mask pixels)
     areas = np.array([int(o.fg_fragment.sum()) for o in objects], np.int64)
-    need_pool = areas > 12288
-    bpool_off = np.where(need_pool, np.concatenate([[0], np.cumsum(np.where(need_pool, areas, 0))[:-1]]), -1).astype(np.int64)
-    to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    d_boxes, d_bits_off, d_new_off, d_bpool_off = to_dev(boxes), to_dev(bits_off), to_dev(new_off), to_dev(bpool_off)
-    d_bits = to_dev(np.concatenate(packed))
-    d_new = torch.zeros(max(1, int(new_words.sum())) * 4, dtype=torch.uint8, device=dev)
-    d_pool = torch.empty(max(1, int(np.where(need_pool, areas, 0).sum())) * 4, dtype=torch.uint8, device=dev)
-    d_out = torch.zeros(n * 64, dtype=torch.uint8, device=dev)
-    bg = background_mask if torch.is_tensor(background_mask) else to_dev(np.asarray(background_mask, np.uint8))
-    gstd = float(g.std(unbiased=False).item())               # a constant image: 1 / 0 = inf, the contrast comes out NaN and nothing is discarded, as in the reference (postprocess.py:254-266)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        _capi.check(L.sdsm_post_objects(p(g), p(g_mask_processing), p(bg), H, W, n, p(d_boxes), p(d_bits_off), p(d_bits), p(d_new_off), p(d_new),
-                                        p(d_pool), p(d_bpool_off), float(exterior_scale), float(exterior_offset), float(contrast_epsilon),
-                                        (1.0 / gstd) if gstd > 0 else float('inf'), m, float(mask_stdamp), p(d_out), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                    'sdsm_post_objects')
-        recs = d_out.cpu().numpy().view(_capi.POST_RECORD_DTYPE).copy()
-        new_bits = d_new.cpu().numpy() if m > 0 else None
-    if (recs['status'] == 1).any():
-        raise _capi.SdsmError('sdsm_post_objects: boundary list overflow')
+    return boxes, words, new_words, packed, areas
+
+
+def _exclusive(counts):
+    return np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64) if len(counts) else np.zeros(0, np.int64)
+
+
+def _unpack_refined(recs, boxes, new_bits, new_off, new_words, H, W, m):
+    """The refined masks (before hole filling) of the objects of one image: (offset, fragment) or None where the device did not refine."""
     refined = []
-    for k in range(n):
+    for k in range(len(recs)):
         if m == 0:
             refined.append(None)
             continue
@@ -142,7 +122,110 @@ def process_objects_gpu(objects, g, g_mask_processing, background_mask, exterior
         win = np.unpackbits(new_bits[4 * new_off[k]:4 * (new_off[k] + new_words[k])], bitorder='little')[:nh * nwid].reshape(nh, nwid).astype(bool)
         fr, fc = int(recs['r0'][k]) - nr0, int(recs['c0'][k]) - nc0
         refined.append((np.array([int(recs['r0'][k]), int(recs['c0'][k])]), win[fr:fr + int(recs['h'][k]), fc:fc + int(recs['w'][k])]))
-    return recs, refined
+    return refined
+
+
+def _inv_gstd(g):
+    gstd = float(g.std(unbiased=False).item())               # a constant image: 1 / 0 = inf, the contrast comes out NaN and nothing is discarded, as in the reference (postprocess.py:254-266)
+    return (1.0 / gstd) if gstd > 0 else float('inf')
+
+
+def process_objects_gpu(objects, g, g_mask_processing, background_mask, exterior_scale, exterior_offset, contrast_epsilon,
+                        mask_max_distance, mask_stdamp, device=None):
+    """Contrast response and refined mask (before hole filling) of every object: one launch (sdsm_post_objects).
+    ``g`` / ``g_mask_processing``: float64 device tensors; ``background_mask``: bool array or uint8 device tensor.
+    Returns (records POST_RECORD_DTYPE, list of (offset, fragment) or None where the device did not refine)."""
+    import ctypes as C
+    import torch
+    L = _capi.lib()
+    dev = g.device
+    H, W = (int(v) for v in g.shape)
+    n = len(objects)
+    if n == 0:
+        return np.zeros(0, _capi.POST_RECORD_DTYPE), []
+    m = _refinement_radius(mask_max_distance, mask_stdamp)
+    boxes, words, new_words, packed, areas = _pack_objects(objects, H, W, m)
+    bits_off, new_off = _exclusive(words), _exclusive(new_words)
+    # objects with a very long mask boundary keep their boundary list in global memory (4 B per boundary pixel <= mask pixels)
+    need_pool = areas > 12288
+    bpool_off = np.where(need_pool, np.concatenate([[0], np.cumsum(np.where(need_pool, areas, 0))[:-1]]), -1).astype(np.int64)
+    to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    d_boxes, d_bits_off, d_new_off, d_bpool_off = to_dev(boxes), to_dev(bits_off), to_dev(new_off), to_dev(bpool_off)
+    d_bits = to_dev(np.concatenate(packed))
+    d_new = torch.zeros(max(1, int(new_words.sum())) * 4, dtype=torch.uint8, device=dev)
+    d_pool = torch.empty(max(1, int(np.where(need_pool, areas, 0).sum())) * 4, dtype=torch.uint8, device=dev)
+    d_out = torch.zeros(n * 64, dtype=torch.uint8, device=dev)
+    bg = background_mask if torch.is_tensor(background_mask) else to_dev(np.asarray(background_mask, np.uint8))
+    p = lambda t: C.c_void_p(t.data_ptr())
+    with torch.cuda.device(dev):
+        _capi.check(L.sdsm_post_objects(p(g), p(g_mask_processing), p(bg), H, W, n, p(d_boxes), p(d_bits_off), p(d_bits), p(d_new_off), p(d_new),
+                                        p(d_pool), p(d_bpool_off), float(exterior_scale), float(exterior_offset), float(contrast_epsilon),
+                                        _inv_gstd(g), m, float(mask_stdamp), p(d_out), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                    'sdsm_post_objects')
+        recs = d_out.cpu().numpy().view(_capi.POST_RECORD_DTYPE).copy()
+        new_bits = d_new.cpu().numpy() if m > 0 else None
+    if (recs['status'] == 1).any():
+        raise _capi.SdsmError('sdsm_post_objects: boundary list overflow')
+    return recs, _unpack_refined(recs, boxes, new_bits, new_off, new_words, H, W, m)
+
+
+def process_objects_gpu_multi(images, exterior_scale, exterior_offset, contrast_epsilon, mask_max_distance, mask_stdamp):
+    """:func:`process_objects_gpu` for the objects of a set of images, ``images`` = ``(objects, g, g_mask_processing,
+    background_mask)`` per image (one device for all): one sdsm_post_objects_multi launch per ``_capi.MAX_SET_IMAGES`` images.
+    Returns ``(records, refined)`` per image, equal to :func:`process_objects_gpu` on that image."""
+    import ctypes as C
+    import torch
+    L = _capi.lib()
+    m = _refinement_radius(mask_max_distance, mask_stdamp)
+    results = []
+    for lo in range(0, len(images), _capi.MAX_SET_IMAGES):
+        part = images[lo:lo + _capi.MAX_SET_IMAGES]
+        dev = part[0][1].device
+        to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        table = (_capi.PostImage * len(part))()
+        packs, keep = [], []
+        for j, (objects, g, gs, bg) in enumerate(part):
+            H, W = (int(v) for v in g.shape)
+            packs.append(_pack_objects(objects, H, W, m))
+            bg = bg if torch.is_tensor(bg) else to_dev(np.asarray(bg, np.uint8))
+            keep.append(bg)
+            table[j].d_g, table[j].d_gs, table[j].d_bg = g.data_ptr(), gs.data_ptr(), bg.data_ptr()
+            table[j].H, table[j].W, table[j].n_objects = H, W, len(objects)
+            table[j].inv_gstd = _inv_gstd(g) if len(objects) else 0.0
+        n = sum(len(o) for o, *_ in part)
+        if n == 0:
+            results += [(np.zeros(0, _capi.POST_RECORD_DTYPE), []) for _ in part]
+            continue
+        boxes = np.concatenate([pk[0] for pk in packs])
+        words, new_words, areas = (np.concatenate([pk[k] for pk in packs]) for k in (1, 2, 4))
+        bits_off, new_off = _exclusive(words), _exclusive(new_words)
+        need_pool = areas > 12288
+        bpool_off = np.where(need_pool, np.concatenate([[0], np.cumsum(np.where(need_pool, areas, 0))[:-1]]), -1).astype(np.int64)
+        d_boxes, d_bits_off, d_new_off, d_bpool_off = to_dev(boxes), to_dev(bits_off), to_dev(new_off), to_dev(bpool_off)
+        d_bits = to_dev(np.concatenate([b for pk in packs for b in pk[3]]))
+        d_new = torch.zeros(max(1, int(new_words.sum())) * 4, dtype=torch.uint8, device=dev)
+        d_pool = torch.empty(max(1, int(np.where(need_pool, areas, 0).sum())) * 4, dtype=torch.uint8, device=dev)
+        d_out = torch.zeros(n * 64, dtype=torch.uint8, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        with torch.cuda.device(dev):
+            _capi.check(L.sdsm_post_objects_multi(table, len(part), p(d_boxes), p(d_bits_off), p(d_bits), p(d_new_off), p(d_new), p(d_pool),
+                                                  p(d_bpool_off), float(exterior_scale), float(exterior_offset), float(contrast_epsilon), m,
+                                                  float(mask_stdamp), p(d_out), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                        'sdsm_post_objects_multi')
+            recs = d_out.cpu().numpy().view(_capi.POST_RECORD_DTYPE).copy()
+            new_bits = d_new.cpu().numpy() if m > 0 else None
+        if (recs['status'] == 1).any():
+            raise _capi.SdsmError('sdsm_post_objects_multi: boundary list overflow')
+        first = 0
+        for (objects, g, *_), pk in zip(part, packs):
+            H, W = (int(v) for v in g.shape)
+            k = slice(first, first + len(objects))
+            r = recs[k].copy()
+            # the refined windows of this image, offsets relative to its first word
+            refined = _unpack_refined(r, pk[0], new_bits, new_off[k], new_words[k], H, W, m) if len(objects) else []
+            results.append((r, refined))
+            first += len(objects)
+    return results
 
 
 class Postprocessing(Stage):
@@ -153,66 +236,111 @@ class Postprocessing(Stage):
     def __init__(self):
         super().__init__('postprocess', inputs=['cover', 'y_img', 'atoms', 'g_raw', 'dsm_cfg'], outputs=['postprocessed_objects'])
 
-    def process(self, input_data, cfg, out, log_root_dir):
-        import torch
-        out = get_output(out)
-        # simple post-processing
-        max_norm_energy = cfg.get('max_norm_energy', 0.2)
-        discard_image_boundary = cfg.get('discard_image_boundary', False)
-        min_boundary_obj_radius = cfg.get('min_boundary_obj_radius', 0)
-        min_obj_radius = cfg.get('min_object_radius', 0)
-        max_obj_radius = cfg.get('max_object_radius', np.inf)
-        max_eccentricity = cfg.get('max_eccentricity', 0.99)
-        max_boundary_eccentricity = cfg.get('max_boundary_eccentricity', np.inf)
-        if max_boundary_eccentricity is None:
-            max_boundary_eccentricity = max_eccentricity
-        # contrast-based post-processing
-        exterior_scale = cfg.get('exterior_scale', 5)
-        exterior_offset = cfg.get('exterior_offset', 5)
-        min_contrast = cfg.get('min_contrast', 1.35)
-        contrast_epsilon = cfg.get('contrast_epsilon', 1e-4)
-        # mask-based post-processing
-        mask_stdamp = cfg.get('mask_stdamp', 2)
-        mask_max_distance = cfg.get('mask_max_distance', 1)
-        mask_smoothness = cfg.get('mask_smoothness', 3)
-        fill_holes = cfg.get('fill_holes', True)
-        # autofluorescence glare removal
-        glare_detection_smoothness = cfg.get('glare_detection_smoothness', 3)
-        glare_detection_num_layers = cfg.get('glare_detection_num_layers', 5)
-        glare_detection_min_layer = cfg.get('glare_detection_min_layer', 0.5)
-        min_glare_radius = cfg.get('min_glare_radius', np.inf)
-        min_boundary_glare_radius = cfg.get('min_boundary_glare_radius', min_glare_radius)
+    @staticmethod
+    def _settings(cfg):
+        """The stage's hyper-parameters (postprocess.py:13-110), read as the reference reads them."""
+        P = dict(
+            # simple post-processing
+            max_norm_energy=cfg.get('max_norm_energy', 0.2),
+            discard_image_boundary=cfg.get('discard_image_boundary', False),
+            min_boundary_obj_radius=cfg.get('min_boundary_obj_radius', 0),
+            min_obj_radius=cfg.get('min_object_radius', 0),
+            max_obj_radius=cfg.get('max_object_radius', np.inf),
+            max_eccentricity=cfg.get('max_eccentricity', 0.99),
+            max_boundary_eccentricity=cfg.get('max_boundary_eccentricity', np.inf),
+            # contrast-based post-processing
+            exterior_scale=cfg.get('exterior_scale', 5),
+            exterior_offset=cfg.get('exterior_offset', 5),
+            min_contrast=cfg.get('min_contrast', 1.35),
+            contrast_epsilon=cfg.get('contrast_epsilon', 1e-4),
+            # mask-based post-processing
+            mask_stdamp=cfg.get('mask_stdamp', 2),
+            mask_max_distance=cfg.get('mask_max_distance', 1),
+            mask_smoothness=cfg.get('mask_smoothness', 3),
+            fill_holes=cfg.get('fill_holes', True),
+            # autofluorescence glare removal
+            glare_detection_smoothness=cfg.get('glare_detection_smoothness', 3),
+            glare_detection_num_layers=cfg.get('glare_detection_num_layers', 5),
+            glare_detection_min_layer=cfg.get('glare_detection_min_layer', 0.5),
+            min_glare_radius=cfg.get('min_glare_radius', np.inf))
+        P['min_boundary_glare_radius'] = cfg.get('min_boundary_glare_radius', P['min_glare_radius'])
+        if P['max_boundary_eccentricity'] is None:
+            P['max_boundary_eccentricity'] = P['max_eccentricity']
+        return P
 
+    def _prepare(self, input_data, cfg):
+        """Settings, objects, background mask and the device images of one image."""
+        import torch
+        P = self._settings(cfg)
         g_raw = np.asarray(input_data['g_raw'], np.float64)
         solution = list(input_data['cover'].solution)
         # pixels allowed for the background estimate of the contrast (postprocess.py:152-155)
         background_mask = np.zeros(g_raw.shape, bool)
         for c in solution:
             c.fill_foreground(background_mask)
-        background_mask = _morph.binary_erosion(~background_mask, _morph.disk(exterior_offset))
+        background_mask = _morph.binary_erosion(~background_mask, _morph.disk(P['exterior_offset']))
 
         # (the reference's filter reads the loop variable of the loop above, postprocess.py:180: all objects or none)
         objects = [obj for obj in solution if (solution[-1].fg_fragment.any() if solution else False)]
         g_dev = torch.as_tensor(np.ascontiguousarray(g_raw)).cuda()
-        g_mask = gaussian_filter_gpu(g_dev, mask_smoothness)
-        recs, refined = process_objects_gpu(objects, g_dev, g_mask, background_mask, exterior_scale, exterior_offset, contrast_epsilon,
-                                            mask_max_distance, mask_stdamp)
-        need_glare = any((min_boundary_glare_radius if o.on_boundary else min_glare_radius) < math.sqrt(o.fg_fragment.sum() / math.pi) for o in objects)
-        g_glare = gaussian_filter_gpu(g_dev, glare_detection_smoothness).cpu().numpy() if need_glare else None
+        g_mask = gaussian_filter_gpu(g_dev, P['mask_smoothness'])
+        return P, objects, g_dev, g_mask, background_mask
+
+    def process(self, input_data, cfg, out, log_root_dir):
+        P, objects, g_dev, g_mask, background_mask = self._prepare(input_data, cfg)
+        recs, refined = process_objects_gpu(objects, g_dev, g_mask, background_mask, P['exterior_scale'], P['exterior_offset'],
+                                            P['contrast_epsilon'], P['mask_max_distance'], P['mask_stdamp'])
+        self.last_records = recs
+        return self._decide(P, objects, g_dev, recs, refined, get_output(out), log_root_dir)
+
+    def process_many(self, datas, cfg, out=None, log_root_dirs=None):
+        """The stage for a set of images, with the contract of ``GlobalEnergyMinimization.process_many`` (a list of pipeline data
+        dicts, one config for all or a list; returns the wall time): the Gaussians and background mask of every image as in
+        ``process``, the objects of all images in one launch (:func:`process_objects_gpu_multi`; images whose contrast and mask
+        settings differ go to launches of their own), then the decisions image by image.  Equal to ``process`` on every image;
+        ``last_records`` becomes the list of the images' records."""
+        t0 = time.time()
+        datas = list(datas)
+        cfgs = list(cfg) if isinstance(cfg, (list, tuple)) else [cfg] * len(datas)
+        cfgs = [c.get(self.cfgns, {}) for c in cfgs]
+        logs = list(log_root_dirs) if log_root_dirs is not None else [None] * len(datas)
+        out = get_output(out)
+        prepared = [self._prepare({inner: d[outer] for outer, inner in self.inputs.items()}, c) for d, c in zip(datas, cfgs)]
+        keys = ('exterior_scale', 'exterior_offset', 'contrast_epsilon', 'mask_max_distance', 'mask_stdamp')
+        groups = {}
+        for i, prep in enumerate(prepared):
+            groups.setdefault(tuple(prep[0][k] for k in keys), []).append(i)
+        per_object = [None] * len(datas)
+        for settings, members in groups.items():
+            res = process_objects_gpu_multi([(prepared[i][1], prepared[i][2], prepared[i][3], prepared[i][4]) for i in members], *settings)
+            for i, r in zip(members, res):
+                per_object[i] = r
+        self.last_records = [r[0] for r in per_object]
+        for data, prep, (recs, refined), log in zip(datas, prepared, per_object, logs):
+            P, objects, g_dev = prep[:3]
+            produced = self._decide(P, objects, g_dev, recs, refined, out, log)
+            for inner, outer in self.outputs.items():
+                data[outer] = produced[inner]
+        return time.time() - t0
+
+    def _decide(self, P, objects, g_dev, recs, refined, out, log_root_dir):
+        """The host part of one image (postprocess.py:175-243): glare test, hole filling, eccentricity, accept or discard."""
+        need_glare = any((P['min_boundary_glare_radius'] if o.on_boundary else P['min_glare_radius']) < math.sqrt(o.fg_fragment.sum() / math.pi) for o in objects)
+        g_glare = gaussian_filter_gpu(g_dev, P['glare_detection_smoothness']).cpu().numpy() if need_glare else None
 
         postprocessed_objects, log_entries = [], []
         for k, original in enumerate(objects):
             obj_radius = math.sqrt(original.fg_fragment.sum() / math.pi)
             is_glare = False
-            if (min_boundary_glare_radius if original.on_boundary else min_glare_radius) < obj_radius:
-                is_glare = _is_glare(original, g_glare, glare_detection_min_layer, glare_detection_num_layers)
+            if (P['min_boundary_glare_radius'] if original.on_boundary else P['min_glare_radius']) < obj_radius:
+                is_glare = _is_glare(original, g_glare, P['glare_detection_min_layer'], P['glare_detection_num_layers'])
             norm_energy = original.energy / original.cvxprog_region_size                    # postprocess.py:289-291 without the second distance transform
             contrast_response = float(recs['contrast'][k])
             if refined[k] is not None:                                                       # postprocess.py:316-337
                 fg_offset, fg_fragment = refined[k]
-                if fill_holes:
+                if P['fill_holes']:
                     fg_fragment = ndi.binary_fill_holes(fg_fragment)
-            elif fill_holes:
+            elif P['fill_holes']:
                 fg_offset, fg_fragment = original.fg_offset, ndi.binary_fill_holes(original.fg_fragment)
             else:
                 fg_offset, fg_fragment = None, None
@@ -227,27 +355,27 @@ class Postprocessing(Stage):
             if is_glare:
                 log_entries.append((obj, f'glare removed (radius: {obj_radius})'))
                 continue
-            if norm_energy > max_norm_energy:
+            if norm_energy > P['max_norm_energy']:
                 log_entries.append((obj, f'energy rate too high ({norm_energy})'))
                 continue
-            if contrast_response < min_contrast:
+            if contrast_response < P['min_contrast']:
                 log_entries.append((obj, f'contrast too low ({contrast_response})'))
                 continue
             if original.on_boundary:
-                if eccentricity > max_boundary_eccentricity:
+                if eccentricity > P['max_boundary_eccentricity']:
                     log_entries.append((obj, f'boundary object eccentricity too high ({eccentricity})'))
                     continue
-                if discard_image_boundary:
+                if P['discard_image_boundary']:
                     log_entries.append((obj, 'boundary object discarded'))
                     continue
-                if not (min_boundary_obj_radius <= obj_radius <= max_obj_radius):
+                if not (P['min_boundary_obj_radius'] <= obj_radius <= P['max_obj_radius']):
                     log_entries.append((obj, f'boundary object and/or too small/large (radius: {obj_radius})'))
                     continue
             else:
-                if eccentricity > max_eccentricity:
+                if eccentricity > P['max_eccentricity']:
                     log_entries.append((obj, f'eccentricity too high ({eccentricity})'))
                     continue
-                if not min_obj_radius <= obj_radius <= max_obj_radius:
+                if not P['min_obj_radius'] <= obj_radius <= P['max_obj_radius']:
                     log_entries.append((obj, f'object too small/large (radius: {obj_radius})'))
                     continue
             postprocessed_objects.append(obj)
@@ -259,7 +387,6 @@ class Postprocessing(Stage):
                     location = (c.fg_offset + np.divide(c.fg_fragment.shape, 2)).round().astype(int)
                     log_file.write(f'object at x={location[1]}, y={location[0]}: {comment}{os.linesep}')
         out.write(f'Remaining objects: {len(postprocessed_objects)} of {len(objects)}')
-        self.last_records = recs
         return {'postprocessed_objects': postprocessed_objects}
 
     def configure_ex(self, scale, radius, diameter):
