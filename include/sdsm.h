@@ -302,6 +302,87 @@ size_t sdsm_edt_exact_workspace_bytes_multi(const sdsm_set_image *images, int n_
 int sdsm_edt_exact_multi(const sdsm_set_image *images, int n_images, const uint8_t *d_target, double *d_out, void *d_ws, size_t ws_bytes,
                          void *stream);
 
+/* ---- label maps and overlays of a result (superdsm/render.py:137-451) --------------------------------------------------------------
+ * The kernel phases of render.rasterize_labels_gpu / render_result_over_image_gpu and their image-set forms; the definition they are
+ * tested against is the host code of superdsm_amd/render.py.  Objects are given as sdsm_post_objects takes them: d_boxes n x 4 int32
+ * (r0, c0, h, w, in the coordinates of the object's image), the h * w bits of the fragment row-major, LSB first in uint32 words at
+ * d_bits + d_bits_off[i].  A *_multi form takes the set as a HOST table of sdsm_set_image (1 .. SDSM_MAX_SET_IMAGES images, H, W <=
+ * 65535, H * W < 2^31) and the image of every object in d_obj_image (int32, may be NULL for one image); the pixel buffers are packed as
+ * the table says.  The single-image form is the set of that one image: the same kernels, the same bytes.  Only integer atomics whose
+ * result does not depend on the arrival order are used: a second launch gives the same bytes. */
+#define SDSM_RENDER_MAX_RADIUS 16
+/* render.py:380-384 (rasterize_objects): object i dilated (radius > 0) or eroded (radius < 0) by disk(|radius|), 1 <= |radius| <= 16,
+ * in the window of its box grown by |radius| and clipped to the image (dilation: outside the image is background; erosion: outside
+ * is foreground).  The window's bits go to d_new_bits + d_new_off[i] (in words, (window pixels + 31) / 32 words each), the number of
+ * set pixels to d_area[i]. */
+int sdsm_render_morph(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, int radius,
+                      const int64_t *d_new_off, uint32_t *d_new_bits, int32_t *d_area, void *stream);
+int sdsm_render_morph_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                            const int64_t *d_bits_off, const uint32_t *d_bits, int radius, const int64_t *d_new_off, uint32_t *d_new_bits,
+                            int32_t *d_area, void *stream);
+/* render.py:398-401 (rasterize_labels): d_inter[k] = |A n B| for the pair k of objects d_pairs[2 k], d_pairs[2 k + 1] of one image, an
+ * exact integer; the division by the smaller area and the merge bookkeeping stay on the host.  Serves any number of images. */
+int sdsm_render_overlaps(int n_pairs, const int32_t *d_pairs, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits,
+                         int32_t *d_inter, void *stream);
+/* render.py:425-431: d_obj_label[i] >= 1 is the label of the (merged) object that object i belongs to.  d_label (int32): the highest
+ * label covering a pixel (the definition assigns the labels in ascending order), 0 where two different labels meet and on the
+ * background; d_cover (uint8): 0 background, 1 one label, 2 several; d_target (uint8): d_label != 0, the input of sdsm_edt_exact.
+ * All three are cleared by the call; n may be 0. */
+int sdsm_render_paint(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits,
+                      const int32_t *d_obj_label, int32_t *d_label, uint8_t *d_cover, uint8_t *d_target, void *stream);
+int sdsm_render_paint_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                            const int64_t *d_bits_off, const uint32_t *d_bits, const int32_t *d_obj_label, int32_t *d_label,
+                            uint8_t *d_cover, uint8_t *d_target, void *stream);
+/* render.py:432-433: the pixels the flood can touch, per image: the pixels with d_cover == 2 (label 0) and the labelled pixels with such
+ * a 4-neighbour, each as (raster index in its image, label, d_dist there).  Image i writes at most capacity[i] entries (HOST array)
+ * behind those of the images before it, in no particular order; d_counts[i] is the exact number found. */
+typedef struct {
+    int32_t idx, label;
+    double dist;
+} sdsm_render_entry;
+int sdsm_render_compact(int H, int W, const int32_t *d_label, const uint8_t *d_cover, const double *d_dist, int64_t capacity,
+                        sdsm_render_entry *d_entries, int32_t *d_count, void *stream);
+int sdsm_render_compact_multi(const sdsm_set_image *images, int n_images, const int32_t *d_label, const uint8_t *d_cover, const double *d_dist,
+                              const int64_t *capacity, sdsm_render_entry *d_entries, int32_t *d_counts, void *stream);
+/* sdsm_flood_sparse (host, no device access): the priority flood of superdsm_amd/render.py:_watershed (what render.py:433 asks of
+ * skimage.segmentation.watershed) on the entries of one image, sorted by ascending idx: entries with label > 0 are seeds, pushed in
+ * raster order with ages 0, 1, 2, ...; the heap pops the smallest (dist, age, row, column); a popped pixel gives its label to its
+ * unlabelled neighbours in the set, visited up, down, left, right, which enter with the next ages.  out[k]: the label of entry k, 0
+ * where no seed reaches.  This is not the rule of sdsm_watershed (all markers age 0; up, left, right, down). */
+int sdsm_flood_sparse(int64_t n, const int32_t *idx, const int32_t *label, const double *dist, int H, int W, int32_t *out);
+/* d_label[d_pix[k]] = d_lab[k] for n entries (d_pix: int64 elements into the packed buffer, distinct): the flood's labels. */
+int sdsm_render_scatter(int64_t n, const int64_t *d_pix, const int32_t *d_lab, int32_t *d_label, void *stream);
+/* render.py:443-447, exactly coinciding objects: d_lost[l] (n_labels + 1 int32) = the pixels of label l's objects that have d_label 0,
+ * d_max[image] = the highest label in the image.  sdsm_render_fill: the pixels of the objects d_sel[0 .. n_sel) that have d_label 0 get
+ * new_label (1 .. 65535); *d_filled = their number (> 0 iff any; pixels shared by two selected objects may count twice). */
+int sdsm_render_lost(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, const int32_t *d_obj_label,
+                     int n_labels, int32_t *d_label, int32_t *d_lost, int32_t *d_max, void *stream);
+int sdsm_render_lost_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                           const int64_t *d_bits_off, const uint32_t *d_bits, const int32_t *d_obj_label, int n_labels, int32_t *d_label,
+                           int32_t *d_lost, int32_t *d_max, void *stream);
+int sdsm_render_fill(int H, int W, int n_sel, const int32_t *d_sel, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits,
+                     const int32_t *d_obj_label, int new_label, int32_t *d_label, int32_t *d_filled, void *stream);
+int sdsm_render_fill_multi(const sdsm_set_image *images, int n_images, int n_sel, const int32_t *d_sel, const int32_t *d_obj_image,
+                           const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, const int32_t *d_obj_label,
+                           int new_label, int32_t *d_label, int32_t *d_filled, void *stream);
+/* render.py:449: d_out[p] (uint16) = d_label[p], or (uint16) background_label (-65535 .. 0; -1 reads 65535) where it is 0, for the n
+ * elements of a packed buffer. */
+int sdsm_render_finish(int64_t n, const int32_t *d_label, int background_label, uint16_t *d_out, void *stream);
+/* The overlays (render.py:246-262 rasterize_regions, :265-287 render_regions_over_image, :291-365 render_result_over_image) in one
+ * pass over the image.  With mn / mx the minimum / maximum of d_labels (int32, >= 0) over the in-image pixels of disk(radius), 0 <=
+ * radius <= 16, around a pixel (a tile and its halo through LDS), a pixel is painted with color[0 .. 3) if
+ *   kind 0 (regions):          mn != mx;  and blended bg[c] * bg[3] + v * (1 - bg[3]) if bg != NULL and mn == mx == background_label
+ *   kind 1 (result, 'center'): mx > 0 and mn != mx
+ *   kind 2 (result, 'inner'):  label > 0 and mn != mx          (the caller passes twice the contour's radius)
+ *   kind 3 (rasterize_regions alone): nothing is painted; d_out holds ONE uint8 per pixel, bit 0 = mn != mx (border), bit 1 = bg !=
+ *           NULL and mn == mx == background_label (only bg's presence is read); d_base, channels and color are ignored (may be NULL)
+ * and keeps d_base (float64, channels = 1 or 3 per pixel) otherwise; d_out: 3 uint8 per pixel, 255 * v truncated (kind 0) or rounded
+ * half to even (kinds 1, 2) and clipped to 0 .. 255.  color and bg (4 doubles, or NULL) are HOST arrays. */
+int sdsm_render_overlay(int H, int W, const int32_t *d_labels, const double *d_base, int channels, int kind, int radius, const double *color,
+                        const double *bg, int background_label, uint8_t *d_out, void *stream);
+int sdsm_render_overlay_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const double *d_base, int channels,
+                              int kind, int radius, const double *color, const double *bg, int background_label, uint8_t *d_out, void *stream);
+
 /* ---- host-side combinatorial steps of the stage (no device access) -------------------------------------------------------------
  * Approximate min-weight set cover (superdsm/minsetcover.py:4-88: greedy + merge phase, retried with beta * gamma on up to max_iter
  * levels) and greedy max-weight set packing (superdsm/maxsetpack.py:8-24) over n objects whose footprints are bit sets of `words`

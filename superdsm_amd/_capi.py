@@ -39,6 +39,9 @@ assert DOH_PEAK_DTYPE.itemsize == 24
 DOH_PEAKS_HEADER_BYTES = 16
 DOH_MAX_SCALES = 32
 MAX_SET_IMAGES = 32          # SDSM_MAX_SET_IMAGES: images per call of a *_multi entry point
+RENDER_MAX_RADIUS = 16       # SDSM_RENDER_MAX_RADIUS: largest disk of the label-map and overlay kernels
+RENDER_ENTRY_DTYPE = np.dtype([('idx', 'i4'), ('label', 'i4'), ('dist', 'f8')])   # sdsm_render_entry
+assert RENDER_ENTRY_DTYPE.itemsize == 16
 
 
 class SetImage(C.Structure):
@@ -99,6 +102,22 @@ SYMBOLS = {
     'sdsm_c2f_markers_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, C.POINTER(C.c_double), _vp, _vp, _vp, _vp, _sz, _vp]),
     'sdsm_edt_exact_workspace_bytes_multi': (_sz, [C.POINTER(SetImage), _i32]),
     'sdsm_edt_exact_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, _vp, _sz, _vp]),
+    'sdsm_render_morph': (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    'sdsm_render_morph_multi': (_i32, [C.POINTER(SetImage), _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    'sdsm_render_overlaps': (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_render_paint': (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_render_paint_multi': (_i32, [C.POINTER(SetImage), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_render_compact': (_i32, [_i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    'sdsm_render_compact_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, _vp, C.POINTER(C.c_int64), _vp, _vp, _vp]),
+    'sdsm_flood_sparse': (_i32, [_i64, _vp, _vp, _vp, _i32, _i32, _vp]),
+    'sdsm_render_scatter': (_i32, [_i64, _vp, _vp, _vp, _vp]),
+    'sdsm_render_lost': (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    'sdsm_render_lost_multi': (_i32, [C.POINTER(SetImage), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    'sdsm_render_fill': (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    'sdsm_render_fill_multi': (_i32, [C.POINTER(SetImage), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    'sdsm_render_finish': (_i32, [_i64, _vp, _i32, _vp, _vp]),
+    'sdsm_render_overlay': (_i32, [_i32, _i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32, _vp, _vp]),
+    'sdsm_render_overlay_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32, _vp, _vp]),
     'sdsm_minsetcover': (_i32, [_i32, _i32, _vp, _vp, _f64, _i32, _i32, _f64, _vp, _vp]),
     'sdsm_minsetcover_multi': (_i32, [_i32, _vp, _vp, _vp, _vp, _f64, _i32, _i32, _f64, _vp, _vp]),
     'sdsm_maxsetpack': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp]),

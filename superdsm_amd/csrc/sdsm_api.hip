@@ -952,3 +952,178 @@ extern "C" int sdsm_post_objects_multi(const sdsm_post_image *images, int n_imag
                                         exterior_scale, exterior_offset, contrast_epsilon, max_distance, stdamp, d_out, (hipStream_t)stream);
     return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_post_objects_multi");
 }
+
+// ---- label maps and overlays (sdsm_render.hip) -----------------------------------------------------------------------------------
+extern "C" hipError_t sdsm_render_morph_impl(const sdsm_set_image *images, int n_images, int n, const int32_t *obj_image, const int32_t *boxes,
+                                             const int64_t *bits_off, const uint32_t *bits, int radius, const int64_t *new_off, uint32_t *new_bits,
+                                             int32_t *area, hipStream_t stream);
+extern "C" hipError_t sdsm_render_overlaps_impl(int n_pairs, const int32_t *pairs, const int32_t *boxes, const int64_t *bits_off, const uint32_t *bits,
+                                                int32_t *inter, hipStream_t stream);
+extern "C" hipError_t sdsm_render_paint_impl(const sdsm_set_image *images, int n_images, int n, const int32_t *obj_image, const int32_t *boxes,
+                                             const int64_t *bits_off, const uint32_t *bits, const int32_t *obj_label, int32_t *label, uint8_t *cover,
+                                             uint8_t *target, hipStream_t stream);
+extern "C" hipError_t sdsm_render_lost_impl(const sdsm_set_image *images, int n_images, int n, const int32_t *obj_image, const int32_t *boxes,
+                                            const int64_t *bits_off, const uint32_t *bits, const int32_t *obj_label, int32_t *label, int32_t *lost,
+                                            int n_labels, int32_t *vmax, hipStream_t stream);
+extern "C" hipError_t sdsm_render_fill_impl(const sdsm_set_image *images, int n_images, int n_sel, const int32_t *sel, const int32_t *obj_image,
+                                            const int32_t *boxes, const int64_t *bits_off, const uint32_t *bits, const int32_t *obj_label,
+                                            int32_t new_label, int32_t *label, int32_t *filled, hipStream_t stream);
+extern "C" hipError_t sdsm_render_compact_impl(const sdsm_set_image *images, int n_images, const int32_t *label, const uint8_t *cover, const double *dist,
+                                               const int64_t *capacity, void *entries, int32_t *counts, hipStream_t stream);
+extern "C" hipError_t sdsm_render_scatter_impl(int64_t n, const int64_t *pix, const int32_t *lab, int32_t *label, hipStream_t stream);
+extern "C" hipError_t sdsm_render_finish_impl(int64_t n, const int32_t *label, uint16_t bg, uint16_t *out, hipStream_t stream);
+extern "C" hipError_t sdsm_render_overlay_impl(const sdsm_set_image *images, int n_images, const int32_t *labels, const double *base, int channels,
+                                               int kind, int radius, const double *color, const double *bg, int has_bg, int background_label,
+                                               uint8_t *out, hipStream_t stream);
+
+// the table of a render call: as the EDT takes it, and every image below 2^31 pixels (pixel indices are int32)
+static bool render_table_ok(const sdsm_set_image *images, int n_images)
+{
+    if (!set_table_ok(images, n_images, true)) return false;
+    for (int i = 0; i < n_images; i++) if ((int64_t)images[i].H * images[i].W >= INT_MAX) return false;
+    return true;
+}
+#define RENDER_TABLE(name) \
+    if (!render_table_ok(images, n_images)) return fail(SDSM_ERR_ARGUMENT, name ": bad image table (1 .. 32 images, offset >= 0, 1 <= H, W <= 65535, H * W < 2^31)")
+#define RENDER_DONE(name) return e == hipSuccess ? SDSM_OK : hipfail(e, name)
+
+extern "C" int sdsm_render_morph_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                                       const int64_t *d_bits_off, const uint32_t *d_bits, int radius, const int64_t *d_new_off, uint32_t *d_new_bits,
+                                       int32_t *d_area, void *stream)
+{
+    RENDER_TABLE("sdsm_render_morph");
+    if (radius == 0 || radius > SDSM_RENDER_MAX_RADIUS || radius < -SDSM_RENDER_MAX_RADIUS)
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_render_morph: 1 <= |radius| <= 16 required");
+    if (n < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_morph: n < 0");
+    if (n == 0) return SDSM_OK;
+    if (!d_boxes || !d_bits_off || !d_bits || !d_new_off || !d_new_bits || !d_area || (n_images > 1 && !d_obj_image))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_render_morph: null argument");
+    hipError_t e = sdsm_render_morph_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, radius, d_new_off, d_new_bits, d_area, (hipStream_t)stream);
+    RENDER_DONE("sdsm_render_morph");
+}
+
+extern "C" int sdsm_render_morph(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, int radius,
+                                 const int64_t *d_new_off, uint32_t *d_new_bits, int32_t *d_area, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_render_morph_multi(&one, 1, n, nullptr, d_boxes, d_bits_off, d_bits, radius, d_new_off, d_new_bits, d_area, stream);
+}
+
+extern "C" int sdsm_render_overlaps(int n_pairs, const int32_t *d_pairs, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits,
+                                    int32_t *d_inter, void *stream)
+{
+    if (n_pairs < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_overlaps: n_pairs < 0");
+    if (n_pairs == 0) return SDSM_OK;
+    if (!d_pairs || !d_boxes || !d_bits_off || !d_bits || !d_inter) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_overlaps: null argument");
+    hipError_t e = sdsm_render_overlaps_impl(n_pairs, d_pairs, d_boxes, d_bits_off, d_bits, d_inter, (hipStream_t)stream);
+    RENDER_DONE("sdsm_render_overlaps");
+}
+
+extern "C" int sdsm_render_paint_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                                       const int64_t *d_bits_off, const uint32_t *d_bits, const int32_t *d_obj_label, int32_t *d_label,
+                                       uint8_t *d_cover, uint8_t *d_target, void *stream)
+{
+    RENDER_TABLE("sdsm_render_paint");
+    if (n < 0 || !d_label || !d_cover || !d_target) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_paint: bad argument");
+    if (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_obj_label || (n_images > 1 && !d_obj_image)))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_render_paint: null argument");
+    hipError_t e = sdsm_render_paint_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_obj_label, d_label, d_cover, d_target, (hipStream_t)stream);
+    RENDER_DONE("sdsm_render_paint");
+}
+
+extern "C" int sdsm_render_paint(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits,
+                                 const int32_t *d_obj_label, int32_t *d_label, uint8_t *d_cover, uint8_t *d_target, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_render_paint_multi(&one, 1, n, nullptr, d_boxes, d_bits_off, d_bits, d_obj_label, d_label, d_cover, d_target, stream);
+}
+
+extern "C" int sdsm_render_compact_multi(const sdsm_set_image *images, int n_images, const int32_t *d_label, const uint8_t *d_cover, const double *d_dist,
+                                         const int64_t *capacity, sdsm_render_entry *d_entries, int32_t *d_counts, void *stream)
+{
+    RENDER_TABLE("sdsm_render_compact");
+    if (!d_label || !d_cover || !d_dist || !capacity || !d_entries || !d_counts) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_compact: null argument");
+    for (int i = 0; i < n_images; i++) if (capacity[i] < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_compact: negative capacity");
+    hipError_t e = sdsm_render_compact_impl(images, n_images, d_label, d_cover, d_dist, capacity, d_entries, d_counts, (hipStream_t)stream);
+    RENDER_DONE("sdsm_render_compact");
+}
+
+extern "C" int sdsm_render_compact(int H, int W, const int32_t *d_label, const uint8_t *d_cover, const double *d_dist, int64_t capacity,
+                                   sdsm_render_entry *d_entries, int32_t *d_count, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_render_compact_multi(&one, 1, d_label, d_cover, d_dist, &capacity, d_entries, d_count, stream);
+}
+
+extern "C" int sdsm_render_scatter(int64_t n, const int64_t *d_pix, const int32_t *d_lab, int32_t *d_label, void *stream)
+{
+    if (n < 0 || n >= ((int64_t)INT_MAX - 1) * 256) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_scatter: bad count");
+    if (n == 0) return SDSM_OK;
+    if (!d_pix || !d_lab || !d_label) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_scatter: null argument");
+    hipError_t e = sdsm_render_scatter_impl(n, d_pix, d_lab, d_label, (hipStream_t)stream);
+    RENDER_DONE("sdsm_render_scatter");
+}
+
+extern "C" int sdsm_render_lost_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                                      const int64_t *d_bits_off, const uint32_t *d_bits, const int32_t *d_obj_label, int n_labels, int32_t *d_label,
+                                      int32_t *d_lost, int32_t *d_max, void *stream)
+{
+    RENDER_TABLE("sdsm_render_lost");
+    if (n < 1 || n_labels < 1 || !d_boxes || !d_bits_off || !d_bits || !d_obj_label || !d_label || !d_lost || !d_max || (n_images > 1 && !d_obj_image))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_render_lost: bad argument");
+    hipError_t e = sdsm_render_lost_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_obj_label, d_label, d_lost, n_labels, d_max, (hipStream_t)stream);
+    RENDER_DONE("sdsm_render_lost");
+}
+
+extern "C" int sdsm_render_lost(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, const int32_t *d_obj_label,
+                                int n_labels, int32_t *d_label, int32_t *d_lost, int32_t *d_max, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_render_lost_multi(&one, 1, n, nullptr, d_boxes, d_bits_off, d_bits, d_obj_label, n_labels, d_label, d_lost, d_max, stream);
+}
+
+extern "C" int sdsm_render_fill_multi(const sdsm_set_image *images, int n_images, int n_sel, const int32_t *d_sel, const int32_t *d_obj_image,
+                                      const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, const int32_t *d_obj_label,
+                                      int new_label, int32_t *d_label, int32_t *d_filled, void *stream)
+{
+    RENDER_TABLE("sdsm_render_fill");
+    if (n_sel < 1 || new_label < 1 || new_label > 65535 || !d_sel || !d_boxes || !d_bits_off || !d_bits || !d_obj_label || !d_label || !d_filled || (n_images > 1 && !d_obj_image))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_render_fill: bad argument (1 <= new_label <= 65535)");
+    hipError_t e = sdsm_render_fill_impl(images, n_images, n_sel, d_sel, d_obj_image, d_boxes, d_bits_off, d_bits, d_obj_label, new_label, d_label, d_filled, (hipStream_t)stream);
+    RENDER_DONE("sdsm_render_fill");
+}
+
+extern "C" int sdsm_render_fill(int H, int W, int n_sel, const int32_t *d_sel, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits,
+                                const int32_t *d_obj_label, int new_label, int32_t *d_label, int32_t *d_filled, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_render_fill_multi(&one, 1, n_sel, d_sel, nullptr, d_boxes, d_bits_off, d_bits, d_obj_label, new_label, d_label, d_filled, stream);
+}
+
+extern "C" int sdsm_render_finish(int64_t n, const int32_t *d_label, int background_label, uint16_t *d_out, void *stream)
+{
+    if (n < 1 || n >= ((int64_t)INT_MAX - 1) * 256 || !d_label || !d_out || background_label > 0 || background_label < -65535)
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_render_finish: bad argument (-65535 <= background_label <= 0)");
+    hipError_t e = sdsm_render_finish_impl(n, d_label, (uint16_t)background_label, d_out, (hipStream_t)stream);
+    RENDER_DONE("sdsm_render_finish");
+}
+
+extern "C" int sdsm_render_overlay_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const double *d_base, int channels,
+                                         int kind, int radius, const double *color, const double *bg, int background_label, uint8_t *d_out, void *stream)
+{
+    RENDER_TABLE("sdsm_render_overlay");
+    if (radius < 0 || radius > SDSM_RENDER_MAX_RADIUS) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_overlay: 0 <= radius <= 16 required");
+    if (kind < 0 || kind > 3 || !d_labels || !d_out || (kind != 3 && ((channels != 1 && channels != 3) || !color || !d_base)))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_render_overlay: bad argument (kind 0 .. 3, channels 1 or 3)");
+    static const double no_color[3] = {0, 0, 0};
+    if (!color) color = no_color;
+    hipError_t e = sdsm_render_overlay_impl(images, n_images, d_labels, d_base, channels, kind, radius, color, bg, bg != nullptr, background_label, d_out, (hipStream_t)stream);
+    RENDER_DONE("sdsm_render_overlay");
+}
+
+extern "C" int sdsm_render_overlay(int H, int W, const int32_t *d_labels, const double *d_base, int channels, int kind, int radius, const double *color,
+                                   const double *bg, int background_label, uint8_t *d_out, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_render_overlay_multi(&one, 1, d_labels, d_base, channels, kind, radius, color, bg, background_label, d_out, stream);
+}

@@ -226,3 +226,38 @@ extern "C" int sdsm_watershed(const double *image, const int32_t *markers, const
     }
     return SDSM_OK;
 }
+
+// The flood of rasterize_labels (superdsm/render.py:432-433 through superdsm_amd/render.py:_watershed) on the sparse set of pixels it
+// can touch: n entries in ascending raster index; label > 0: a marker pixel next to an overlap pixel (a seed), label == 0: an overlap
+// pixel.  The seeds enter the heap in raster order with ages 0, 1, 2, ...; the heap pops the smallest (distance, age, row, column); a
+// popped pixel labels its unlabelled neighbours up, down, left, right, which enter with the next ages.  NOT the rule of
+// sdsm_watershed above (all markers age 0; up, left, right, down).
+extern "C" int sdsm_flood_sparse(int64_t n, const int32_t *idx, const int32_t *label, const double *dist, int H, int W, int32_t *out)
+{
+    if (n < 0 || H < 1 || W < 1 || (int64_t)H * W >= INT32_MAX || (n > 0 && (!idx || !label || !dist || !out))) return SDSM_ERR_ARGUMENT;
+    for (int64_t k = 0; k < n; k++) {
+        if (idx[k] < 0 || idx[k] >= H * W || (k > 0 && idx[k] <= idx[k - 1]) || label[k] < 0) return SDSM_ERR_ARGUMENT;
+        out[k] = label[k];
+    }
+    typedef std::tuple<double, int64_t, int32_t, int32_t> Entry;     // distance, age, raster index (= row, column order), entry
+    std::priority_queue<Entry, std::vector<Entry>, std::greater<Entry>> heap;
+    int64_t age = 0;
+    for (int64_t k = 0; k < n; k++) if (label[k] > 0) heap.emplace(dist[k], age++, idx[k], (int32_t)k);
+    const int32_t *end = idx + n;
+    while (!heap.empty()) {
+        const int32_t p = std::get<2>(heap.top()), k = std::get<3>(heap.top());
+        heap.pop();
+        const int r = p / W, c = p - r * W;
+        const int32_t nb[4] = {r > 0 ? p - W : -1, r + 1 < H ? p + W : -1, c > 0 ? p - 1 : -1, c + 1 < W ? p + 1 : -1};
+        for (int32_t q : nb) {
+            if (q < 0) continue;
+            const int32_t *it = std::lower_bound(idx, end, q);
+            if (it == end || *it != q) continue;                     // not in the set: background, or a marker that nothing can change
+            const int64_t j = it - idx;
+            if (out[j] != 0) continue;
+            out[j] = out[k];
+            heap.emplace(dist[j], age++, q, (int32_t)j);
+        }
+    }
+    return SDSM_OK;
+}

@@ -77,29 +77,43 @@ def _refinement_radius(mask_max_distance, mask_stdamp):
     return int(mask_max_distance) if (mask_max_distance > 0 and mask_stdamp > 0) else 0
 
 
-def _pack_objects(objects, H, W, m):
-    """The per-object inputs of sdsm_post_objects: boxes, words of the bit-packed fragments and of the refined windows, the packed
-    fragments, areas."""
+def pack_fragments(objects):
+    """Boxes (n x 4 int32: r0, c0, h, w), word counts and the bit-packed fragments (row-major, LSB first, whole uint32 words) of a list
+    of objects, and their areas: the object format of sdsm_post_objects and of the label-map kernels (render.py)."""
     n = len(objects)
     boxes = np.zeros((n, 4), np.int32)
     words = np.zeros(n, np.int64)
-    new_words = np.zeros(n, np.int64)
     packed = []
     for k, obj in enumerate(objects):
         h, w = obj.fg_fragment.shape
-        r0, c0 = int(obj.fg_offset[0]), int(obj.fg_offset[1])
-        boxes[k] = (r0, c0, h, w)
+        boxes[k] = (int(obj.fg_offset[0]), int(obj.fg_offset[1]), h, w)
         bits = np.packbits(np.ascontiguousarray(obj.fg_fragment, bool).reshape(-1), bitorder='little')
         nw = (h * w + 31) // 32
         buf = np.zeros(nw * 4, np.uint8)
         buf[:bits.size] = bits
         packed.append(buf)
         words[k] = nw
-        nh = min(H, r0 + h + m) - max(0, r0 - m)
-        nwid = min(W, c0 + w + m) - max(0, c0 - m)
-        new_words[k] = (nh * nwid + 31) // 32
     areas = np.array([int(o.fg_fragment.sum()) for o in objects], np.int64)
-    return boxes, words, new_words, packed, areas
+    return boxes, words, packed, areas
+
+
+def grown_windows(boxes, H, W, m):
+    """The windows box +- m clipped to the image, n x 4 int64 (r0, c0, h, w); ``H`` / ``W``: scalars or one value per box."""
+    b = np.asarray(boxes, np.int64).reshape(-1, 4)
+    r0, c0 = np.maximum(0, b[:, 0] - m), np.maximum(0, b[:, 1] - m)
+    return np.stack([r0, c0, np.minimum(H, b[:, 0] + b[:, 2] + m) - r0, np.minimum(W, b[:, 1] + b[:, 3] + m) - c0], axis=1)
+
+
+def window_words(windows):
+    """Words of the bit-packed windows."""
+    return ((windows[:, 2] * windows[:, 3] + 31) // 32).astype(np.int64)
+
+
+def _pack_objects(objects, H, W, m):
+    """The per-object inputs of sdsm_post_objects: boxes, words of the bit-packed fragments and of the refined windows, the packed
+    fragments, areas."""
+    boxes, words, packed, areas = pack_fragments(objects)
+    return boxes, words, window_words(grown_windows(boxes, H, W, m)), packed, areas
 
 
 def _exclusive(counts):

@@ -14,6 +14,7 @@ import numpy as np
 import scipy.ndimage as ndi
 
 from . import _morph
+from .postprocess import _exclusive, grown_windows, pack_fragments, window_words
 
 
 def render_objects_foregrounds(shape, objects):
@@ -118,6 +119,572 @@ def rasterize_labels(data, objects='postprocessed_objects', merge_overlap_thresh
     #  value wraps -- background_label = -1 reads 65535 --, kept here)
     result[result == 0] = np.array(background_label).astype('uint16')
     return result
+
+
+# ---- label maps on the GPU (render.py:388-451 in kernel phases, sdsm_render.hip) ------------------------------------------------------
+def _check_radius(radius, what):
+    if float(radius) != int(radius) or abs(int(radius)) > 16:
+        raise NotImplementedError(f'{what} = {radius!r}: the GPU label maps and overlays take integer disk radii up to 16 only, see DESIGN.md "Limits"')
+    return int(radius)
+
+
+class _GpuSet:
+    """The device side of one set of up to ``_capi.MAX_SET_IMAGES`` images: the packed pixel buffers, the uploaded objects and one
+    method per kernel phase.  (The CPU tests replace this class by a host restatement to exercise the orchestration.)"""
+
+    def __init__(self, shapes):
+        import ctypes as C
+        import torch
+        from . import _capi
+        self.C, self.torch, self.capi, self.L = C, torch, _capi, _capi.lib()
+        self.shapes = [(int(h), int(w)) for h, w in shapes]
+        if not 1 <= len(self.shapes) <= _capi.MAX_SET_IMAGES:
+            raise ValueError(f'a set holds 1 .. {_capi.MAX_SET_IMAGES} images')
+        self.table = (_capi.SetImage * len(self.shapes))()
+        off = 0
+        for i, (h, w) in enumerate(self.shapes):
+            self.table[i].offset, self.table[i].H, self.table[i].W = off, h, w
+            off += (h * w + 63) // 64 * 64
+        self.offsets = np.array([t.offset for t in self.table], np.int64)
+        self.total = off
+        self.dev = torch.device('cuda', torch.cuda.current_device())
+        self.d_label = torch.empty(off, dtype=torch.int32, device=self.dev)
+        self.d_cover = torch.empty(off, dtype=torch.uint8, device=self.dev)
+        self.d_target = torch.empty(off, dtype=torch.uint8, device=self.dev)
+        self.n = 0
+
+    def _up(self, a):
+        return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+
+    def _p(self, t):
+        return self.C.c_void_p(t.data_ptr() if t is not None else None)
+
+    def _stream(self):
+        return self.C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
+
+    def load(self, obj_image, boxes, words, packed):
+        self.n = len(boxes)
+        self.obj_image, self.boxes = np.asarray(obj_image, np.int32), np.asarray(boxes, np.int32).reshape(-1, 4)
+        self.bits_off = _exclusive(words)
+        self.d_bits = self._up(np.concatenate(packed) if len(packed) else np.zeros(4, np.uint8))
+        self._objects()
+
+    def _objects(self):
+        self.d_obj_image, self.d_boxes, self.d_bits_off = self._up(self.obj_image), self._up(self.boxes), self._up(self.bits_off)
+
+    def morph(self, radius):
+        """Phase 1: every object dilated / eroded; the objects become their windows.  Returns (window boxes, areas)."""
+        H, W = (np.array([s[k] for s in self.shapes], np.int64)[self.obj_image] for k in (0, 1))
+        win = grown_windows(self.boxes, H, W, abs(radius))
+        new_words = window_words(win)
+        new_off = _exclusive(new_words)
+        d_new_off = self._up(new_off)
+        d_new = self.torch.empty(max(1, int(new_words.sum())) * 4, dtype=self.torch.uint8, device=self.dev)
+        d_area = self.torch.empty(max(1, self.n), dtype=self.torch.int32, device=self.dev)
+        self.capi.check(self.L.sdsm_render_morph_multi(self.table, len(self.shapes), self.n, self._p(self.d_obj_image), self._p(self.d_boxes), self._p(self.d_bits_off),
+                                                       self._p(self.d_bits), int(radius), self._p(d_new_off), self._p(d_new), self._p(d_area), self._stream()), 'sdsm_render_morph_multi')
+        areas = d_area.cpu().numpy()[:self.n].astype(np.int64)
+        self.boxes, self.bits_off, self.d_bits = win.astype(np.int32), new_off, d_new
+        self._objects()
+        return self.boxes, areas
+
+    def select(self, keep):
+        self.obj_image, self.boxes, self.bits_off = self.obj_image[keep], self.boxes[keep], self.bits_off[keep]
+        self.n = len(self.boxes)
+        self._objects()
+
+    def overlaps(self, pairs):
+        """Phase 2: |A n B| of every pair (global object indices)."""
+        pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
+        if len(pairs) == 0:
+            return np.zeros(0, np.int64)
+        d_pairs = self._up(pairs)
+        d_inter = self.torch.empty(len(pairs), dtype=self.torch.int32, device=self.dev)
+        self.capi.check(self.L.sdsm_render_overlaps(len(pairs), self._p(d_pairs), self._p(self.d_boxes), self._p(self.d_bits_off), self._p(self.d_bits), self._p(d_inter),
+                                                    self._stream()), 'sdsm_render_overlaps')
+        return d_inter.cpu().numpy().astype(np.int64)
+
+    def paint(self, obj_label):
+        """Phase 3."""
+        self.d_obj_label = self._up(np.asarray(obj_label, np.int32))
+        self.capi.check(self.L.sdsm_render_paint_multi(self.table, len(self.shapes), self.n, self._p(self.d_obj_image), self._p(self.d_boxes), self._p(self.d_bits_off),
+                                                       self._p(self.d_bits), self._p(self.d_obj_label), self._p(self.d_label), self._p(self.d_cover), self._p(self.d_target),
+                                                       self._stream()), 'sdsm_render_paint_multi')
+
+    def flood_inputs(self, capacity):
+        """Phases 4 and 5: the distance map and, per image, the entries of the flood sorted by raster index."""
+        n_im = len(self.shapes)
+        nbytes = self.L.sdsm_edt_exact_workspace_bytes_multi(self.table, n_im)
+        ws = self.torch.empty(max(1, nbytes), dtype=self.torch.uint8, device=self.dev)
+        d_dist = self.torch.empty(self.total, dtype=self.torch.float64, device=self.dev)
+        self.capi.check(self.L.sdsm_edt_exact_multi(self.table, n_im, self._p(self.d_target), self._p(d_dist), self._p(ws), nbytes, self._stream()), 'sdsm_edt_exact_multi')
+        cap = (self.C.c_int64 * n_im)(*[int(c) for c in capacity])
+        cap_off = _exclusive(np.asarray(capacity, np.int64))
+        d_entries = self.torch.empty(max(1, int(np.sum(capacity))) * 16, dtype=self.torch.uint8, device=self.dev)
+        d_counts = self.torch.empty(n_im, dtype=self.torch.int32, device=self.dev)
+        self.capi.check(self.L.sdsm_render_compact_multi(self.table, n_im, self._p(self.d_label), self._p(self.d_cover), self._p(d_dist), cap, self._p(d_entries),
+                                                         self._p(d_counts), self._stream()), 'sdsm_render_compact_multi')
+        counts = d_counts.cpu().numpy()
+        if (counts > np.asarray(capacity)).any():
+            raise self.capi.SdsmError('sdsm_render_compact_multi: more flood pixels than object pixels')
+        out = []
+        for i in range(n_im):
+            if counts[i] == 0:
+                out.append(np.zeros(0, self.capi.RENDER_ENTRY_DTYPE))
+                continue
+            e = d_entries[16 * int(cap_off[i]):16 * (int(cap_off[i]) + int(counts[i]))].cpu().numpy().view(self.capi.RENDER_ENTRY_DTYPE)
+            out.append(e[np.argsort(e['idx'], kind='stable')])
+        return out
+
+    def scatter(self, pix, lab):
+        if len(pix) == 0:
+            return
+        d_pix, d_lab = self._up(np.asarray(pix, np.int64)), self._up(np.asarray(lab, np.int32))
+        self.capi.check(self.L.sdsm_render_scatter(len(pix), self._p(d_pix), self._p(d_lab), self._p(self.d_label), self._stream()), 'sdsm_render_scatter')
+
+    def lost(self, obj_group, n_groups):
+        """Phase 6, counting: (pixels without a label per group 1 .. n_groups, highest label per image)."""
+        d_group = self._up(np.asarray(obj_group, np.int32))
+        d_lost = self.torch.empty(n_groups + 1, dtype=self.torch.int32, device=self.dev)
+        d_max = self.torch.empty(len(self.shapes), dtype=self.torch.int32, device=self.dev)
+        self.capi.check(self.L.sdsm_render_lost_multi(self.table, len(self.shapes), self.n, self._p(self.d_obj_image), self._p(self.d_boxes), self._p(self.d_bits_off),
+                                                      self._p(self.d_bits), self._p(d_group), n_groups, self._p(self.d_label), self._p(d_lost), self._p(d_max), self._stream()),
+                        'sdsm_render_lost_multi')
+        return d_lost.cpu().numpy(), d_max.cpu().numpy()
+
+    def fill(self, sel, new_label):
+        """Phase 6, filling: the unlabelled pixels of the objects ``sel`` get ``new_label``; returns whether there were any."""
+        d_sel = self._up(np.asarray(sel, np.int32))
+        d_filled = self.torch.empty(1, dtype=self.torch.int32, device=self.dev)
+        self.capi.check(self.L.sdsm_render_fill_multi(self.table, len(self.shapes), len(sel), self._p(d_sel), self._p(self.d_obj_image), self._p(self.d_boxes),
+                                                      self._p(self.d_bits_off), self._p(self.d_bits), self._p(self.d_obj_label), int(new_label), self._p(self.d_label),
+                                                      self._p(d_filled), self._stream()), 'sdsm_render_fill_multi')
+        return int(d_filled.cpu().numpy()[0]) > 0
+
+    def finish(self, background_label):
+        """Phase 7 and the download: the uint16 label map of every image."""
+        d_out = self.torch.empty(self.total, dtype=self.torch.int16, device=self.dev)
+        self.capi.check(self.L.sdsm_render_finish(self.total, self._p(self.d_label), int(background_label), self._p(d_out), self._stream()), 'sdsm_render_finish')
+        flat = d_out.cpu().numpy().view(np.uint16)
+        return [flat[o:o + h * w].reshape(h, w).copy() for o, (h, w) in zip(self.offsets, self.shapes)]
+
+    def region_flags(self, labels, radius, background_label):
+        """rasterize_regions for the set (kind 3 of the overlay kernel): (borders, background) per image."""
+        flat = np.zeros(self.total, np.int32)
+        for o, (h, w), l in zip(self.offsets, self.shapes, labels):
+            flat[o:o + h * w] = np.asarray(l).reshape(-1)
+        d_labels = self._up(flat)
+        d_out = self.torch.empty(self.total, dtype=self.torch.uint8, device=self.dev)
+        bgc = (self.C.c_double * 4)(0, 0, 0, 0) if background_label is not None else None
+        self.capi.check(self.L.sdsm_render_overlay_multi(self.table, len(self.shapes), self._p(d_labels), None, 1, 3, int(radius), None, bgc,
+                                                         int(background_label if background_label is not None else 0), self._p(d_out), self._stream()), 'sdsm_render_overlay_multi')
+        out = d_out.cpu().numpy()
+        flags = [out[o:o + h * w].reshape(h, w) for o, (h, w) in zip(self.offsets, self.shapes)]
+        return [((f & 1) != 0, (f & 2) != 0) for f in flags]
+
+    def overlay(self, labels, bases, kind, radius, color, bg, background_label):
+        """The overlay kernel for the set.  ``labels``: None (the label maps this set holds) or one integer array per image;
+        ``bases``: one float64 array per image, H x W or H x W x 3."""
+        n_im = len(self.shapes)
+        if labels is not None:
+            flat = np.zeros(self.total, np.int32)
+            for o, (h, w), l in zip(self.offsets, self.shapes, labels):
+                flat[o:o + h * w] = np.asarray(l).reshape(-1)
+            d_labels = self._up(flat)
+        else:
+            d_labels = self.d_label
+        ch = 3 if any(b.ndim == 3 for b in bases) else 1
+        flat = np.zeros(self.total * ch, np.float64)
+        for o, (h, w), b in zip(self.offsets, self.shapes, bases):
+            b = np.asarray(b, np.float64)
+            flat[o * ch:(o + h * w) * ch] = (b if b.ndim == 3 or ch == 1 else np.dstack([b] * 3)).reshape(-1)
+        d_base = self._up(flat)
+        d_out = self.torch.empty(self.total * 3, dtype=self.torch.uint8, device=self.dev)
+        col = (self.C.c_double * 3)(*[float(v) for v in color])
+        bgc = (self.C.c_double * 4)(*[float(v) for v in bg]) if bg is not None else None
+        self.capi.check(self.L.sdsm_render_overlay_multi(self.table, n_im, self._p(d_labels), self._p(d_base), ch, int(kind), int(radius), col, bgc,
+                                                         int(background_label if background_label is not None else 0), self._p(d_out), self._stream()), 'sdsm_render_overlay_multi')
+        out = d_out.cpu().numpy()
+        return [out[3 * o:3 * (o + h * w)].reshape(h, w, 3).copy() for o, (h, w) in zip(self.offsets, self.shapes)]
+
+
+def _candidate_pairs(boxes, all_pairs):
+    """The pairs (i1, i2 < i1) of one image in the order of render.py:398-399, restricted to those whose boxes intersect (any other pair
+    overlaps by 0, which exceeds no threshold >= 0)."""
+    b = np.asarray(boxes, np.int64).reshape(-1, 4)
+    r1, c1 = b[:, 0] + b[:, 2], b[:, 1] + b[:, 3]
+    pairs = []
+    for i1 in range(1, len(b)):
+        if all_pairs:
+            i2 = np.arange(i1)
+        else:
+            i2 = np.nonzero((b[:i1, 0] < r1[i1]) & (b[i1, 0] < r1[:i1]) & (b[:i1, 1] < c1[i1]) & (b[i1, 1] < c1[:i1]))[0]
+        if len(i2):
+            pairs.append(np.stack([np.full(len(i2), i1), i2], axis=1))
+    return np.concatenate(pairs) if pairs else np.zeros((0, 2), np.int64)
+
+
+def _merge_members(n, pairs, inter, areas, merge_overlap_threshold):
+    """The merge bookkeeping of render.py:397-418, as in :func:`rasterize_labels`: the member lists of the surviving labels, in
+    dictionary order."""
+    merge_list = []
+    for (i1, i2), ab in zip(pairs, inter):
+        overlap = ab / (0. + min(areas[i1], areas[i2]))
+        if overlap > merge_overlap_threshold:
+            merge_list.append((int(i1), int(i2)))
+    labels = list(range(1, 1 + n))
+    members = {label: [label - 1] for label in labels}
+    for merge_idx, (i1, i2) in enumerate(merge_list):
+        new_label = n + 1 + merge_idx
+        l1, l2 = labels[i1], labels[i2]
+        if l1 == l2:
+            continue
+        merged = members[l1] + members[l2]
+        for k in merged:
+            labels[k] = new_label
+        members[new_label] = merged
+        del members[l1], members[l2]
+    return list(members.values())
+
+
+def _labels_set(shapes, objects_per_image, merge_overlap_threshold, dilate, background_label, keep_set=False):
+    """rasterize_labels for one set of at most ``_capi.MAX_SET_IMAGES`` images: every phase one call for the whole set."""
+    S = _GpuSet(shapes)
+    packs = [pack_fragments(objs) for objs in objects_per_image]
+    obj_image = np.concatenate([np.full(len(pk[0]), i, np.int32) for i, pk in enumerate(packs)])
+    boxes = np.concatenate([pk[0] for pk in packs])
+    areas = np.concatenate([pk[3] for pk in packs])
+    Hs, Ws = (np.array([s[k] for s in S.shapes], np.int64)[obj_image] for k in (0, 1))
+    b = boxes.astype(np.int64)
+    if ((b[:, 0] < 0) | (b[:, 1] < 0) | (b[:, 2] < 0) | (b[:, 3] < 0) | (b[:, 0] + b[:, 2] > Hs) | (b[:, 1] + b[:, 3] > Ws)).any():
+        raise ValueError('an object reaches outside its image (fg_offset, fg_fragment.shape against g_raw.shape)')
+    S.load(obj_image, boxes, np.concatenate([pk[1] for pk in packs]), [b for pk in packs for b in pk[2]])
+    if dilate != 0 and len(boxes):                                       # phase 1 (render.py:380-384)
+        boxes, areas = S.morph(dilate)
+    keep = areas > 0                                                     # render.py:385
+    if not keep.all():
+        S.select(keep)
+        obj_image, boxes, areas = obj_image[keep], boxes[keep], areas[keep]
+    first = np.searchsorted(obj_image, np.arange(len(shapes) + 1))       # the objects of image i: first[i] .. first[i + 1]
+    pairs = [np.zeros((0, 2), np.int64)] * len(shapes)
+    if merge_overlap_threshold <= 1:                                     # phase 2 (render.py:397-403)
+        pairs = [_candidate_pairs(boxes[first[i]:first[i + 1]], merge_overlap_threshold < 0) for i in range(len(shapes))]
+    inter = S.overlaps(np.concatenate([p + first[i] for i, p in enumerate(pairs)])) if sum(len(p) for p in pairs) else np.zeros(0, np.int64)
+    obj_label, obj_group, groups, k0, g0 = np.zeros(len(boxes), np.int32), np.zeros(len(boxes), np.int32), [], 0, 0
+    for i in range(len(shapes)):
+        n_i = first[i + 1] - first[i]
+        members = _merge_members(n_i, pairs[i], inter[k0:k0 + len(pairs[i])], areas[first[i]:first[i + 1]], merge_overlap_threshold)
+        k0 += len(pairs[i])
+        if len(members) >= 2 ** 16:
+            raise ValueError(f'{len(members)} labels: a uint16 label map holds at most 65535')
+        for l, ks in enumerate(members, 1):
+            obj_label[first[i] + np.asarray(ks, np.int64)] = l
+            obj_group[first[i] + np.asarray(ks, np.int64)] = g0 + l
+            groups.append((i, first[i] + np.asarray(ks, np.int64)))
+        g0 += len(members)
+    S.paint(obj_label)                                                   # phase 3 (render.py:425-431)
+    if len(boxes):
+        capacity = [min(h * w, int(areas[first[i]:first[i + 1]].sum())) for i, (h, w) in enumerate(S.shapes)]
+        entries = S.flood_inputs(capacity)                               # phases 4, 5 (render.py:432-433)
+        pix, lab, unreached = [], [], False
+        for i, e in enumerate(entries):
+            if len(e) == 0 or not (e['label'] == 0).any():
+                continue
+            flooded = flood_sparse(e['idx'], e['label'], e['dist'], *S.shapes[i])
+            todo = e['label'] == 0
+            unreached |= bool((flooded[todo] == 0).any())
+            pix.append(S.offsets[i] + e['idx'][todo].astype(np.int64))
+            lab.append(flooded[todo])
+        if pix:
+            S.scatter(np.concatenate(pix), np.concatenate(lab))
+        if unreached:                                                    # phase 6 (render.py:443-447)
+            lost, vmax = S.lost(obj_group, len(groups))
+            vmax = [int(v) for v in vmax]
+            for g, (i, ks) in enumerate(groups, 1):
+                if lost[g] == 0:
+                    continue
+                if vmax[i] + 1 >= 2 ** 16:
+                    raise ValueError('more than 65535 labels: a uint16 label map cannot hold them')
+                if S.fill(ks, vmax[i] + 1):
+                    vmax[i] += 1
+    if keep_set:                                                         # the label map stays on the device (background 0) for an overlay
+        return None, S
+    return S.finish(background_label)                                    # phase 7 (render.py:449)
+
+
+def flood_sparse(idx, label, dist, H, W):
+    """``_watershed`` on the sparse set of pixels it can touch (native host code, sdsm_flood_sparse): entries sorted by raster index,
+    label > 0 for the marker pixels next to an unlabelled one, 0 for the unlabelled ones.  Returns the labels after the flood."""
+    import ctypes as C
+    from . import _capi
+    idx, label, dist = np.ascontiguousarray(idx, np.int32), np.ascontiguousarray(label, np.int32), np.ascontiguousarray(dist, np.float64)
+    out = np.zeros(len(idx), np.int32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    _capi.check(_capi.lib().sdsm_flood_sparse(len(idx), p(idx), p(label), p(dist), int(H), int(W), p(out)), 'sdsm_flood_sparse')
+    return out
+
+
+def _objects_of(data, objects):
+    return list(data[objects]) if isinstance(objects, str) else list(objects)
+
+
+def _labels_many(datas, objects, merge_overlap_threshold, dilate, background_label, keep_sets=False):
+    from . import _capi
+    assert background_label <= 0
+    if dilate != 0:
+        _check_radius(dilate, 'dilate')
+    datas = list(datas)
+    if isinstance(objects, str):
+        objs = [list(d[objects]) for d in datas]
+    else:
+        objs = [list(o) for o in objects]                                # one list of objects per image
+        if len(objs) != len(datas):
+            raise ValueError('objects: an output name or one list of objects per image')
+    results, sets = [], []
+    for lo in range(0, len(datas), _capi.MAX_SET_IMAGES):
+        part = slice(lo, lo + _capi.MAX_SET_IMAGES)
+        res = _labels_set([d['g_raw'].shape for d in datas[part]], objs[part], merge_overlap_threshold, int(dilate), int(background_label), keep_set=keep_sets)
+        if keep_sets:
+            sets.append(res[1])
+        else:
+            results += res
+    return (results, sets) if keep_sets else results
+
+
+def rasterize_labels_many(datas, objects='postprocessed_objects', merge_overlap_threshold=np.inf, dilate=0, background_label=0):
+    """:func:`rasterize_labels` for a list of pipeline data objects on the GPU: one launch per kernel phase for up to
+    ``_capi.MAX_SET_IMAGES`` images (larger lists are split).  ``objects``: an output name, or one list of objects per image.
+    Per image byte-equal to :func:`rasterize_labels` and to :func:`rasterize_labels_gpu`."""
+    return _labels_many(datas, objects, merge_overlap_threshold, dilate, background_label)
+
+
+def rasterize_labels_gpu(data, objects='postprocessed_objects', merge_overlap_threshold=np.inf, dilate=0, background_label=0):
+    """:func:`rasterize_labels` on the GPU (the same arguments, the same bytes): the set of this one image."""
+    return _labels_many([data], [_objects_of(data, objects)], merge_overlap_threshold, dilate, background_label)[0]
+
+
+# ---- overlays (render.py:137-365) -------------------------------------------------------------------------------------------------
+COLORMAP = {'r': [0], 'g': [1], 'b': [2], 'y': [0, 1], 't': [1, 2], 'w': [0, 1, 2]}
+
+
+def normalize_image(img, spread=1, ret_minmax=False):
+    """Contrast enhancement (render.py:137-166): intensities clipped to mean +- spread * std (within the image's range), then mapped to
+    [0, 1].  NumPy on the host: its statistics decide bytes of the overlays, so they are computed in NumPy's fixed order."""
+    img = np.asarray(img)
+    if not np.allclose(img.std(), 0):
+        minval, maxval = max([img.min(), img.mean() - spread * img.std()]), min([img.max(), img.mean() + spread * img.std()])
+        img = img.clip(minval, maxval)
+    else:
+        minval, maxval = 0, 1
+    img = img - img.min()
+    img /= img.max()
+    return (img, minval, maxval) if ret_minmax else img
+
+
+def _fetch_image(data, normalize_img=True):
+    img = data['g_raw']
+    return normalize_image(img) if normalize_img else img
+
+
+def _fetch_rgb_image(data, normalize_img=True, override_img=None):
+    """The RGB image under the contours, clipped to [0, 1] (render.py:174-187)."""
+    if override_img is not None:
+        img = override_img if override_img.ndim == 3 else np.dstack([override_img] * 3)
+    elif 'g_rgb' in data:
+        img = data['g_rgb']
+        if img.max() > 1:
+            img = img / 255
+    else:
+        img = _fetch_image(data, normalize_img)
+        img = np.dstack([img] * 3)
+    img = img.copy()
+    img[img < 0] = 0
+    img[img > 1] = 1
+    return img
+
+
+def rasterize_regions_host(regions, background_label=None, radius=3):
+    """(borders, background) of a label image, label by label (render.py:246-262): the border of a region is what a disk erosion takes
+    from it (the image border does not erode); ``background`` is the eroded region of ``background_label``."""
+    regions = np.asarray(regions)
+    borders, background = np.zeros(regions.shape, bool), np.zeros(regions.shape, bool)
+    for i in range(int(regions.max()) + 1):
+        region_mask = regions == i
+        interior = _morph.binary_erosion(region_mask, _morph.disk(radius))
+        borders |= region_mask & ~interior
+        if i == background_label:
+            background = interior.astype(bool)
+    return borders, background
+
+
+def _base_image(img):
+    assert img.ndim == 2 or (img.ndim == 3 and img.shape[2] in (1, 3)), f'image has wrong dimensions: {img.shape}'
+    img = np.asarray(img, np.float64)
+    return img if img.ndim == 2 or img.shape[2] == 3 else img[:, :, 0]
+
+
+def render_regions_over_image_host(img, regions, background_label=None, color=(0, 1, 0), bg=(0.6, 1, 0.6, 0.3), **kwargs):
+    """Host definition of :func:`render_regions_over_image` (render.py:265-287)."""
+    base = _base_image(img)
+    result = np.dstack([base] * 3) if base.ndim == 2 else base.copy()
+    borders, background = rasterize_regions_host(regions, background_label, **kwargs)
+    for i in range(3):
+        result[:, :, i][borders] = color[i]
+    for i in range(3):
+        result[background, i] = bg[i] * bg[3] + result[background, i] * (1 - bg[3])
+    return (255 * result).clip(0, 255).astype('uint8')
+
+
+def _regions_many(imgs, regions, background_label, color, bg, radius=3):
+    from . import _capi
+    radius = _check_radius(radius, 'radius')
+    if radius < 0:
+        raise ValueError('radius < 0')
+    out = []
+    for lo in range(0, len(imgs), _capi.MAX_SET_IMAGES):
+        part = slice(lo, lo + _capi.MAX_SET_IMAGES)
+        S = _GpuSet([np.asarray(r).shape for r in regions[part]])
+        out += S.overlay(regions[part], [_base_image(np.asarray(i)) for i in imgs[part]], 0, radius, color, bg if background_label is not None else None, background_label)
+    return out
+
+
+def rasterize_regions_many(regions, background_label=None, radius=3):
+    """:func:`rasterize_regions` for a list of label images, one launch per ``_capi.MAX_SET_IMAGES`` images."""
+    from . import _capi
+    radius = _check_radius(radius, 'radius')
+    if radius < 0:
+        raise ValueError('radius < 0')
+    regions, out = list(regions), []
+    for lo in range(0, len(regions), _capi.MAX_SET_IMAGES):
+        part = regions[lo:lo + _capi.MAX_SET_IMAGES]
+        out += _GpuSet([np.asarray(r).shape for r in part]).region_flags(part, radius, background_label)
+    return out
+
+
+def rasterize_regions(regions, background_label=None, radius=3):
+    """(borders, background) of a label image with labels >= 0 (render.py:246-262) on the GPU, in one pass: with mn / mx the smallest /
+    largest label over the in-image pixels of disk(radius), a pixel is border iff mn != mx, background iff mn == mx == background_label."""
+    return rasterize_regions_many([regions], background_label, radius)[0]
+
+
+def render_regions_over_image_many(imgs, regions, background_label=None, color=(0, 1, 0), bg=(0.6, 1, 0.6, 0.3), **kwargs):
+    """:func:`render_regions_over_image` for a list of images and their label images (one launch per ``_capi.MAX_SET_IMAGES``)."""
+    return _regions_many(list(imgs), list(regions), background_label, color, bg, **kwargs)
+
+
+def render_regions_over_image(img, regions, background_label=None, color=(0, 1, 0), bg=(0.6, 1, 0.6, 0.3), **kwargs):
+    """RGB uint8 image of the regions' borders over ``img`` (render.py:265-287), on the GPU; ``kwargs``: ``radius`` (default 3)."""
+    return _regions_many([img], [regions], background_label, color, bg, **kwargs)[0]
+
+
+def _atoms_base(data, normalize_img, override_img):
+    img = _fetch_image(data, normalize_img) if override_img is None else override_img
+    return img / img.max()
+
+
+def render_atoms_host(data, normalize_img=True, discarded_color=(0.3, 1, 0.3, 0.1), border_radius=2, border_color=(0, 1, 0), override_img=None):
+    """Host definition of :func:`render_atoms` (render.py:190-215), label by label."""
+    return render_regions_over_image_host(_atoms_base(data, normalize_img, override_img), data['atoms'], background_label=0, bg=discarded_color, radius=border_radius, color=border_color)
+
+
+def render_atoms_many(datas, normalize_img=True, discarded_color=(0.3, 1, 0.3, 0.1), border_radius=2, border_color=(0, 1, 0), override_imgs=None, _key='atoms'):
+    """:func:`render_atoms` for a list of pipeline data objects; ``override_imgs``: one image (or None) per data object."""
+    datas = list(datas)
+    over = list(override_imgs) if override_imgs is not None else [None] * len(datas)
+    return _regions_many([_atoms_base(d, normalize_img, o) for d, o in zip(datas, over)], [d[_key] for d in datas], 0, border_color, discarded_color, border_radius)
+
+
+def render_atoms(data, normalize_img=True, discarded_color=(0.3, 1, 0.3, 0.1), border_radius=2, border_color=(0, 1, 0), override_img=None):
+    """The atomic image regions over the image (render.py:190-215), on the GPU."""
+    return render_atoms_many([data], normalize_img, discarded_color, border_radius, border_color, [override_img])[0]
+
+
+def render_foreground_clusters_host(data, normalize_img=True, discarded_color=(0.3, 1, 0.3, 0.1), border_radius=2, border_color=(0, 1, 0), override_img=None):
+    """Host definition of :func:`render_foreground_clusters` (render.py:218-243), label by label."""
+    return render_regions_over_image_host(_atoms_base(data, normalize_img, override_img), data['clusters'], background_label=0, bg=discarded_color, radius=border_radius, color=border_color)
+
+
+def render_foreground_clusters_many(datas, normalize_img=True, discarded_color=(0.3, 1, 0.3, 0.1), border_radius=2, border_color=(0, 1, 0), override_imgs=None):
+    """:func:`render_foreground_clusters` for a list of pipeline data objects."""
+    return render_atoms_many(datas, normalize_img, discarded_color, border_radius, border_color, override_imgs, _key='clusters')
+
+
+def render_foreground_clusters(data, normalize_img=True, discarded_color=(0.3, 1, 0.3, 0.1), border_radius=2, border_color=(0, 1, 0), override_img=None):
+    """The regions of possibly clustered objects over the image (render.py:218-243), on the GPU."""
+    return render_foreground_clusters_many([data], normalize_img, discarded_color, border_radius, border_color, [override_img])[0]
+
+
+def _result_args(border_width, border_position, color):
+    assert border_width % 2 == 0
+    assert color in COLORMAP
+    if border_position == 'outer':
+        raise NotImplementedError("border_position = 'outer' has no one-pass form (it depends on the foreground of the other objects and a second dilation), see DESIGN.md \"Limits\"")
+    if border_position not in ('center', 'inner'):
+        raise ValueError(f'border_position = {border_position!r}')
+    radius = border_width // 2
+    return radius if border_position == 'center' else 2 * radius
+
+
+def _result_base(data, normalize_img, override_img, grey_ok=False):
+    """The image under the contours (render.py:352-353).  ``grey_ok``: a grey base stays one channel (its three channels would be
+    equal, the maximum too: the same values, a third of the upload)."""
+    if grey_ok and (override_img.ndim == 2 if override_img is not None else 'g_rgb' not in data):
+        img = (override_img if override_img is not None else _fetch_image(data, normalize_img)).copy()
+        img[img < 0] = 0
+        img[img > 1] = 1
+        return img / img.max()
+    im_seg = _fetch_rgb_image(data, normalize_img, override_img)
+    im_seg /= im_seg.max()
+    return im_seg
+
+
+def contour_mask_host(mask, radius, where):
+    """The contour of one object's mask (render.py:291-327, ContourPaint), 'center' or 'inner'."""
+    if where == 'center':
+        selem = _morph.disk(radius)
+        return np.logical_xor(_morph.binary_erosion(mask, selem), _morph.binary_dilation(mask, selem))
+    assert where == 'inner'
+    return np.logical_xor(mask, _morph.binary_erosion(mask, _morph.disk(2 * radius)))
+
+
+def render_result_over_image_host(data, objects='postprocessed_objects', merge_overlap_threshold=np.inf, normalize_img=True, border_width=6,
+                                  border_position='center', override_img=None, color='g'):
+    """Host definition of :func:`render_result_over_image` (render.py:330-365): one erosion / dilation per label."""
+    _result_args(border_width, border_position, color)
+    im_seg = _result_base(data, normalize_img, override_img)
+    seg_objects = rasterize_labels(data, objects, merge_overlap_threshold=merge_overlap_threshold)
+    for l in sorted(set(seg_objects.flatten().tolist()) - {0}):
+        seg_bnd = contour_mask_host(seg_objects == l, border_width // 2, border_position)
+        for i in range(3):
+            im_seg[seg_bnd, i] = (1 if i in COLORMAP[color] else 0)
+    return (255 * im_seg).round().clip(0, 255).astype('uint8')
+
+
+def render_result_over_image_many(datas, objects='postprocessed_objects', merge_overlap_threshold=np.inf, normalize_img=True, border_width=6,
+                                  border_position='center', override_imgs=None, color='g'):
+    """:func:`render_result_over_image` for a list of pipeline data objects: the label maps stay on the device between
+    :func:`rasterize_labels_many` and the overlay kernel."""
+    from . import _capi
+    radius = _result_args(border_width, border_position, color)
+    _check_radius(radius, 'border_width' if border_position == 'inner' else 'border_width // 2')
+    datas = list(datas)
+    over = list(override_imgs) if override_imgs is not None else [None] * len(datas)
+    _, sets = _labels_many(datas, objects, merge_overlap_threshold, 0, 0, keep_sets=True)
+    rgb = [1.0 if i in COLORMAP[color] else 0.0 for i in range(3)]
+    out = []
+    for k, S in enumerate(sets):
+        lo = k * _capi.MAX_SET_IMAGES
+        bases = [_result_base(d, normalize_img, o, grey_ok=True) for d, o in zip(datas[lo:lo + _capi.MAX_SET_IMAGES], over[lo:lo + _capi.MAX_SET_IMAGES])]
+        out += S.overlay(None, bases, 1 if border_position == 'center' else 2, radius, rgb, None, 0)
+    return out
+
+
+def render_result_over_image(data, objects='postprocessed_objects', merge_overlap_threshold=np.inf, normalize_img=True, border_width=6,
+                             border_position='center', override_img=None, color='g'):
+    """The contours of the segmentation result over the image (render.py:330-365), on the GPU: 'center' paints the pixels with
+    mx > 0 and mn != mx over disk(border_width // 2), 'inner' those with a label > 0 and mn != mx over disk(border_width)
+    (mn / mx: smallest / largest label in the disk); 'outer' is not supported."""
+    return render_result_over_image_many([data], [_objects_of(data, objects)], merge_overlap_threshold, normalize_img, border_width, border_position, [override_img], color)[0]
 
 
 # ---- regression metric (tests/regression/validate.py) -----------------------------------------------------------------
