@@ -27,12 +27,12 @@ def make_scene(workload='synthetic256', max_size=3, alpha_factor=None, layout_in
                 dsm_cfg=synth.dsm_config_for_scale(spec['scale'], af), scale=spec['scale'])
 
 
-def solve_scene_gpu(scene, footprints=None, want_xi=False):
+def solve_scene_gpu(scene, footprints=None, want_xi=False, mode=None):
     from . import engine
     import torch
     fps = scene['footprints'] if footprints is None else footprints
     img = engine.DeviceImage(scene['y'], None, scene['atoms'], scene['dsm_cfg']['background_margin'])
-    batch = engine.Batch(img, fps, scene['dsm_cfg'], want_xi=want_xi)
+    batch = engine.Batch(img, fps, scene['dsm_cfg'], want_xi=want_xi, mode=mode)
     batch.launch()
     torch.cuda.synchronize()
     recs = batch.records()

@@ -307,6 +307,34 @@ def gen_optimum(scene, tag, cfg, picks=None):
     save(f'optimum_{tag}', **out)
 
 
+GROUP_SCALE = 42.43     # AF_scale of the GOWT1 task: what superdsm_amd.testing.make_scene('gowt1_like') derives its dsm/* values from
+
+
+def gen_optimum_group():
+    """Tight optima in the regime that the kernels solve with a GROUP of workgroups (regions above 12 288 pixels), under the
+    hyper-parameters of the GOWT1-like workload: superdsm_amd.synth.dsm_config_for_scale(42.43, 0.0005), i.e. smooth_amount
+    int(0.2 scale) = 8, smooth_subsample = background_margin = int(0.4 scale) = 16 and alpha = scale^2 * 0.0005 = 0.9001...
+
+    Scene: three nuclei of nominal radius 80 on 330 x 380 pixels (y is all but incompressible: its 8 bytes per pixel decide the
+    size of the file), two of them single atoms, the third cut into three.  Picks, all tight (|g| < 1e-8):
+
+    * [1, 2]: a union of two atoms, 43 388 pixels, M = 170;
+    * [1, 2, 3, 4, 5]: the universe, 67 167 pixels, M = 263;
+    * [2]: 22 906 pixels, M = 88, a smaller group;
+    * [4]: 9 126 pixels, M = 40: the smallest group of throughput mode (a plan this small groups regions above 8192 pixels);
+    * [3] and [5]: 7 405 and 7 248 pixels, single workgroups under the same hyper-parameters (the control).
+
+    Hessian envelopes of the solver (setup kernel): 5 460, 10 559, 2 141, 745, 495 and 499 doubles.  None exceeds 11 000, so the
+    scene does NOT reach the group layout of class 2b (a grid step of 16 keeps 6 + M at 269 for 67 167 pixels); groups of that
+    layout are covered by tests/test_gpu_parity.py::test_groups_of_both_lds_layouts_give_the_bytes_of_single_workgroups.  The
+    deformation matters for the two largest picks (psi 9 724.5 -> 7 920.4 and 26 413.3 -> 16 935.7, |xi| up to 332 and 265); on the
+    other four the regulariser keeps |xi| below 1."""
+    scene = make_scene((330, 380), 3, 80, 54, sigma2=GROUP_SCALE)
+    cfg = dict(DSM_CFG, smooth_amount=8, smooth_subsample=16, background_margin=16, alpha=GROUP_SCALE ** 2 * 0.0005)
+    assert cfg == {k: v for k, v in synth.dsm_config_for_scale(GROUP_SCALE, 0.0005).items() if k != 'init'}
+    gen_optimum(scene, 'group_regime', cfg, picks=[[1, 2], [1, 2, 3, 4, 5], [2], [4], [3], [5]])
+
+
 # ----------------------------------------------------------------------------------------------
 # configuration (superdsm/automation.py:71-102), adjacency, set cover, generation logic
 # ----------------------------------------------------------------------------------------------
@@ -485,6 +513,8 @@ def main():
         # systems beyond the small solve classes (round 4): 6 + M in (128, 256], (256, 512], > 512, Hessian envelopes beyond LDS
         scene4 = make_scene((260, 300), 5, 40, 41, sigma2=20)
         gen_optimum(scene4, 'large_systems', dict(DSM_CFG, smooth_subsample=4), picks=[[9, 10], [5, 7], [3, 4, 5], [7, 8]])
+    if 'optimum' in what or 'optimum_group' in what:
+        gen_optimum_group()
     if 'config' in what: gen_config()
     if 'setcover' in what:
         scene3 = make_scene((160, 200), 14, 12, 33, sigma2=10)

@@ -5,6 +5,8 @@ import os
 import numpy as np
 import pytest
 
+from test_oracle_golden import OPTIMUM_TAGS, TIGHT_DEFORMABLE, reference_optimum_checks
+
 pytestmark = pytest.mark.gpu
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
@@ -29,6 +31,25 @@ def _golden_scene(tag):
     cfg = json.loads(str(d['cfg']))
     fps = [d[f'c{k}_fp'].tolist() for k in range(int(d['n_cases']))]
     return d, dict(cfg, init='elliptical'), fps
+
+
+def _tight(d, k):
+    return float(d[f'c{k}_gnorm_dsm']) < 1e-8 and float(d[f'c{k}_gnorm_ell']) < 1e-8
+
+
+def _modes(tag):
+    """`group_regime` is solved in throughput mode (0: groups for its regions above 8192 pixels), latency mode (1: groups of other
+    sizes, for every region above 3072 pixels) and without groups (2: the same regions through single workgroups) -- a failure that
+    shows in modes 0 / 1 only is the group's."""
+    return (0, 1, 2) if tag == 'group_regime' else (None,)
+
+
+def _group_members(batch):
+    import ctypes as C
+    from superdsm_amd import _capi
+    g = np.zeros(batch.n, np.int32)
+    _capi.check(_capi.lib().sdsm_plan_schedule(batch.plan, g.ctypes.data_as(C.c_void_p), None), 'sdsm_plan_schedule')
+    return g
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -59,7 +80,7 @@ def test_image_prepare_matches_oracle(gpu):
 # ---------------------------------------------------------------------------------------------------------
 # setup kernel: region crops, greedy grid, float32-exact G~ rows (dsm.py:137-237)
 # ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('tag', ['bbbc039_params', 'large_sigma', 'large_systems'])
+@pytest.mark.parametrize('tag', OPTIMUM_TAGS)
 def test_setup_matches_oracle_exactly(gpu, tag):
     from oracle import oracle
     from superdsm_amd import engine
@@ -70,6 +91,20 @@ def test_setup_matches_oracle_exactly(gpu, tag):
     batch.launch()
     gpu.cuda.synchronize()
     info = batch.inspect()
+    if tag == 'group_regime':
+        # the sample is what it claims: tight candidates of 40 000 .. 75 000 pixels solved by groups, one of them a union of two atoms,
+        # a smaller group, and tight candidates of the same scene that the plan's own schedule leaves to single workgroups (the control)
+        N = np.array([int(d[f'c{k}_N']) for k in range(len(fps))])
+        members = _group_members(batch)
+        assert (batch.records()['n_pixels'] == N).all() and all(_tight(d, k) and int(d[f'c{k}_M']) > 0 for k in range(len(fps)))
+        large = (N >= 40000) & (N <= 75000)
+        assert large.sum() >= 2 and (members[large] >= 2).all() and any(len(fps[k]) == 2 for k in np.flatnonzero(large))
+        assert ((members > 0) == (N > 8192)).all() and (N > 12288).sum() >= 3
+        control = members == 0
+        assert control.sum() >= 2 and (N[control] <= 8192).all()
+        env = np.array([st['env_size'] for st in batch.inspect_states()])
+        print('group_regime: N', N.tolist(), 'group members', members.tolist(), 'Hessian envelope', env.tolist())
+        assert (env <= 11000).all()                      # as the fixture's docstring says: all its groups have the LDS layout of class 2
     for k, fp in enumerate(fps):
         mask = oracle.region_mask(y, None, atoms, fp, cfg['background_margin'])
         np.testing.assert_array_equal(mask, unpack(d[f'c{k}_region'], y.shape))
@@ -137,38 +172,52 @@ def _paste(off, frag, shape):
     return out
 
 
-@pytest.mark.parametrize('tag', ['bbbc039_params', 'large_sigma', 'large_systems'])
+@pytest.mark.parametrize('tag', OPTIMUM_TAGS)
 def test_solve_reaches_reference_optima(gpu, tag):
+    """Energies, masks and boundary flags at the optima the reference's own Energy reaches; `group_regime` (regions of up to 67 167
+    pixels, sigma_G = 8, grid step 16) in the three scheduling modes, whose records must also be the same bytes."""
     from oracle import oracle
     from superdsm_amd import _capi, testing
     d, cfg, fps = _golden_scene(tag)
     scene = dict(y=d['y'], atoms=d['atoms'], dsm_cfg=cfg, footprints=fps)
-    res = testing.solve_scene_gpu(scene, want_xi=True)
-    recs, frags = res['records'], res['fragments']
     orecs, ofrags, oparams = oracle.compute_objects(d['y'], None, d['atoms'], fps, cfg, nthreads=0)
-    for k in range(len(fps)):
-        N, M = int(d[f'c{k}_N']), int(d[f'c{k}_M'])
-        assert (recs['n_pixels'][k], recs['n_deform'][k]) == (N, M)
-        psi_ref = float(d[f'c{k}_psi_dsm'])
-        tol = 1e-6 * N / 1000 + 1e-5 * abs(psi_ref)          # fp tolerance on energies
-        tight = float(d[f'c{k}_gnorm_dsm']) < 1e-8 and float(d[f'c{k}_gnorm_ell']) < 1e-8
-        # the energy the kernel reports is the reference's energy function at the kernel's own parameters
-        mask = oracle.region_mask(d['y'], None, d['atoms'], fps[k], cfg['background_margin'])
-        J = oracle.Energy(d['y'], mask, cfg['epsilon'], cfg['alpha'], cfg['smooth_amount'], cfg['gaussian_shape_multiplier'], cfg['smooth_subsample'])
-        xo = res['xi_offsets'][k]
-        p = np.concatenate([recs['theta'][k], res['xi'][xo:xo + M]])
-        assert abs(J(p) - recs['energy'][k]) <= 1e-9 * max(1.0, abs(recs['energy'][k])), (k, J(p), recs['energy'][k])
-        if tight:
-            assert recs['status'][k] == _capi.CAND_OPTIMAL
-            assert abs(recs['energy'][k] - psi_ref) <= tol, (k, recs['energy'][k], psi_ref)
-            assert abs(recs['energy'][k] - orecs['energy'][k]) <= tol
-            ref = _paste(d[f'c{k}_fg_offset'], unpack(d[f'c{k}_fg_fragment'], d[f'c{k}_fg_shape']), d['y'].shape)
-            got = _paste(*frags[k], d['y'].shape)
-            dice = 2 * (ref & got).sum() / max(1, ref.sum() + got.sum())
-            assert dice >= 0.999, (k, dice)
-            assert bool(recs['on_boundary'][k]) == bool(d[f'c{k}_on_boundary'])
-        else:
-            assert recs['energy'][k] <= psi_ref + tol          # near-separable: no finite minimiser
+    first = None
+    for mode in _modes(tag):
+        res = testing.solve_scene_gpu(scene, want_xi=True, mode=mode)
+        recs, frags = res['records'], res['fragments']
+        if tag == 'group_regime':
+            members = _group_members(res['batch'])
+            assert (members > 0).any() if mode != 2 else not members.any()
+        checked = 0
+        for k in range(len(fps)):
+            N, M = int(d[f'c{k}_N']), int(d[f'c{k}_M'])
+            assert (recs['n_pixels'][k], recs['n_deform'][k]) == (N, M)
+            psi_ref = float(d[f'c{k}_psi_dsm'])
+            tol = 1e-6 * N / 1000 + 1e-5 * abs(psi_ref)          # SURVEY.md 8c: fp tolerance on energies
+            tight = _tight(d, k)
+            # the energy the kernel reports is the reference's energy function at the kernel's own parameters
+            mask = oracle.region_mask(d['y'], None, d['atoms'], fps[k], cfg['background_margin'])
+            J = oracle.Energy(d['y'], mask, cfg['epsilon'], cfg['alpha'], cfg['smooth_amount'], cfg['gaussian_shape_multiplier'], cfg['smooth_subsample'])
+            xo = res['xi_offsets'][k]
+            p = np.concatenate([recs['theta'][k], res['xi'][xo:xo + M]])
+            assert abs(J(p) - recs['energy'][k]) <= 1e-9 * max(1.0, abs(recs['energy'][k])), (mode, k, J(p), recs['energy'][k])
+            if tight:
+                assert recs['status'][k] == _capi.CAND_OPTIMAL
+                ref = _paste(d[f'c{k}_fg_offset'], unpack(d[f'c{k}_fg_fragment'], d[f'c{k}_fg_shape']), d['y'].shape)
+                got = _paste(*frags[k], d['y'].shape)
+                dice = 2 * (ref & got).sum() / max(1, ref.sum() + got.sum())
+                print(f'{tag} mode {mode} cand {k} N={N} M={M}: |psi - psi_ref| / tol = {abs(recs["energy"][k] - psi_ref) / tol:.3e}, Dice = {dice:.6f}')
+                assert abs(recs['energy'][k] - psi_ref) <= tol, (mode, k, recs['energy'][k], psi_ref)
+                assert abs(recs['energy'][k] - orecs['energy'][k]) <= tol
+                assert dice >= 0.999, (mode, k, dice)
+                assert bool(recs['on_boundary'][k]) == bool(d[f'c{k}_on_boundary'])
+                checked += 1
+            else:
+                assert recs['energy'][k] <= psi_ref + tol          # near-separable: no finite minimiser
+        assert checked == TIGHT_DEFORMABLE[tag]                    # (every tight pick of the four fixtures has M > 0)
+        if first is None:
+            first = recs.tobytes(), res['xi'].tobytes()
+        assert (recs.tobytes(), res['xi'].tobytes()) == first, f'mode {mode}: other bytes than mode {_modes(tag)[0]}'
 
 
 def test_solve_matches_oracle_on_synthetic256(gpu):
@@ -765,39 +814,44 @@ def test_workgroup_group_elliptical_only_and_trivial_cases(gpu):
 # round 2: the fixtures of the reference's elliptical optimum / parameters, point evaluations, BASELINE configs[4],
 # forced protocol branches
 # ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('tag', ['bbbc039_params', 'large_sigma', 'large_systems'])
+@pytest.mark.parametrize('tag', OPTIMUM_TAGS)
 def test_elliptical_optimum_and_parameters_match_reference(gpu, tag):
     """`c{k}_psi_ell` (the reference's Energy of the 6-parameter model driven to its optimum: ALL of what the C2F operator
     returns), the moment initialisation's energy, and the DSM optimum's parameters theta / xi (`c{k}_x_dsm`)."""
     from superdsm_amd import testing
     d, cfg, fps = _golden_scene(tag)
     scene = dict(y=d['y'], atoms=d['atoms'], dsm_cfg=cfg, footprints=fps)
-    res = testing.solve_scene_gpu(scene, want_xi=True)
-    recs = res['records']
-    checked = 0
-    for k in range(len(fps)):
-        N, M = int(d[f'c{k}_N']), int(d[f'c{k}_M'])
-        psi_ell = float(d[f'c{k}_psi_ell'])
-        tol = 1e-6 * N / 1000 + 1e-5 * abs(psi_ell)
-        if float(d[f'c{k}_gnorm_ell']) < 1e-8:
-            assert abs(recs['energy_ell'][k] - psi_ell) <= tol, (k, recs['energy_ell'][k], psi_ell)
-        else:
-            assert recs['energy_ell'][k] <= psi_ell + tol                    # near-separable: no finite minimiser
-        if float(d[f'c{k}_gnorm_dsm']) < 1e-8 and float(d[f'c{k}_gnorm_ell']) < 1e-8:
-            x = d[f'c{k}_x_dsm']
-            xo = res['xi_offsets'][k]
-            th, xi = recs['theta'][k], res['xi'][xo:xo + M]
-            # the optimum is only determined to the solver's stopping accuracy (cond(Hessian) ~ 1e9 in these coordinates)
-            assert np.abs(th - x[:6]).max() <= 5e-3 * np.abs(x[:6]).max(), (k, th, x[:6])
-            if M:
-                # (systems of several hundred unknowns -- `large_systems` -- have flat directions: grid points that few pixels see, under a
-                # regulariser that is all but linear at |xi| ~ 1e3; the stopping rule lambda^2 / 2 <= 1e-7 + 1e-6 f leaves them undetermined to a
-                # few per cent of the scale while the energy is within 1e-6 relative -- the CPU oracle ends at the same xi as the GPU there)
-                loose = tag == 'large_systems'
-                assert np.abs(xi - x[6:]).max() <= (5e-2 if loose else 5e-3) * max(1.0, np.abs(x[6:]).max()), k
-                assert np.linalg.norm(xi - x[6:]) <= (5e-2 if loose else 5e-3) * max(1.0, np.linalg.norm(x[6:])), k
-            checked += 1
-    assert checked >= (4 if tag == 'large_systems' else 6)
+    for mode in _modes(tag):
+        res = testing.solve_scene_gpu(scene, want_xi=True, mode=mode)
+        recs = res['records']
+        checked = 0
+        for k in range(len(fps)):
+            N, M = int(d[f'c{k}_N']), int(d[f'c{k}_M'])
+            psi_ell = float(d[f'c{k}_psi_ell'])
+            tol = 1e-6 * N / 1000 + 1e-5 * abs(psi_ell)
+            if float(d[f'c{k}_gnorm_ell']) < 1e-8:
+                assert abs(recs['energy_ell'][k] - psi_ell) <= tol, (mode, k, recs['energy_ell'][k], psi_ell)
+            else:
+                assert recs['energy_ell'][k] <= psi_ell + tol                    # near-separable: no finite minimiser
+            if _tight(d, k):
+                x = d[f'c{k}_x_dsm']
+                xo = res['xi_offsets'][k]
+                th, xi = recs['theta'][k], res['xi'][xo:xo + M]
+                # the optimum is only determined to the solver's stopping accuracy (cond(Hessian) ~ 1e9 in these coordinates)
+                assert np.abs(th - x[:6]).max() <= 5e-3 * np.abs(x[:6]).max(), (mode, k, th, x[:6])
+                if M:
+                    # Systems of several hundred unknowns -- `large_systems` -- have flat directions: grid points that few pixels see, under a
+                    # regulariser that is all but linear at |xi| ~ 1e3; the stopping rule lambda^2 / 2 <= 1e-7 + 1e-6 f leaves them undetermined to
+                    # a few per cent of the scale while the energy is within 1e-6 relative, hence the raw 5e-2 there.  What makes that bound
+                    # safe is reference_optimum_checks below: the difference costs at most 2 tol in the metric of the reference's Hessian
+                    # (assertion 2), its part in the stiff eigen-directions stays at the 5e-3 of the other tags (3), and the surfaces agree
+                    # (5).  `group_regime` keeps the 5e-3 of the other tags: the CPU oracle's solver ends 4.7e-4 s from the reference there.
+                    loose = tag == 'large_systems'
+                    assert np.abs(xi - x[6:]).max() <= (5e-2 if loose else 5e-3) * max(1.0, np.abs(x[6:]).max()), (mode, k)
+                    assert np.linalg.norm(xi - x[6:]) <= (5e-2 if loose else 5e-3) * max(1.0, np.linalg.norm(x[6:])), (mode, k)
+                    reference_optimum_checks(tag, d, k, cfg, np.concatenate([th, xi]), label=f'{tag} mode {mode}')
+                checked += 1
+        assert checked == TIGHT_DEFORMABLE[tag]                                  # every tight pick (all of them have M > 0)
 
 
 def test_point_evaluations_match_reference_energy(gpu):
