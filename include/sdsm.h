@@ -383,6 +383,58 @@ int sdsm_render_overlay(int H, int W, const int32_t *d_labels, const double *d_b
 int sdsm_render_overlay_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const double *d_base, int channels,
                               int kind, int radius, const double *color, const double *bg, int background_label, uint8_t *d_out, void *stream);
 
+/* ---- colour maps and adjacency graphs (superdsm/render.py:13-134, :454-508) --------------------------------------------------------
+ * render_ymap, shuffle_labels / colorize_labels and draw_line / render_adjacencies; the definitions they are tested against are the
+ * *_host functions of superdsm_amd/render.py.  Conventions as above: pixel buffers packed as the HOST table of sdsm_set_image says, the
+ * single-image form is the set of that one image, integer atomics only (a second launch gives the same bytes).
+ *
+ * A colour map is a DEVICE table d_lut of (N + 3) x 4 float64, 1 <= N <= SDSM_RENDER_MAX_COLORS: the N colours, then the colours for
+ * values below, above and "bad" (NaN), as matplotlib keeps them; the fourth column is not read.  The lookup of x is matplotlib's
+ * Colormap.__call__ for float input: xa = x * N; xa == N reads N - 1; xa < 0 below; xa >= N above; NaN bad; else entry (int)xa. */
+#define SDSM_RENDER_MAX_COLORS 1024
+#define SDSM_RENDER_MAX_SEED_RADIUS 64
+/* render.py:462-473 (shuffle_labels) and :503 (labels.min(), labels.max()): with a permutation table (d_perm != NULL; image i owns
+ * d_perm[perm_off[i] .. perm_off[i + 1]), indexed by label - perm_min[i]; perm_off with n_images + 1 entries and perm_min are HOST
+ * arrays) a label reads its table entry, a label outside its table reads 0 (render.py:469); without one the labels stay.  d_range (2
+ * int32 per image, may be NULL) receives the minimum and maximum of the resulting labels, d_permuted (int32, packed as d_labels, may
+ * be NULL) the resulting labels. */
+int sdsm_render_label_range(int H, int W, const int32_t *d_labels, const int32_t *d_perm, int64_t perm_n, int perm_min, int32_t *d_range,
+                            int32_t *d_permuted, void *stream);
+int sdsm_render_label_range_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int32_t *d_perm,
+                                  const int64_t *perm_off, const int32_t *perm_min, int32_t *d_range, int32_t *d_permuted, void *stream);
+/* d_out: 3 float64 per pixel, the colour of
+ *   source 0 (render.py:127-134, render_ymap): d_src float64; x = (min(max(y, lo), hi) - sub) / div with (lo, hi, sub, div) = the four
+ *            doubles of image i in the HOST array clim, unfused, a NaN staying NaN.  d_flags[i] (int32, cleared by the call) gets bit
+ *            0 if the image holds a NaN: numpy's y.min() is NaN then and EVERY pixel of the definition is "bad", which is for the
+ *            caller to return.
+ *   source 1 (render.py:503-507, colorize_labels): d_src int32 labels, permuted as sdsm_render_label_range does; x = (double)(label -
+ *            min) / (double)(max - min) with (min, max) = d_range of the image (0 / 0 = NaN: "bad"); bg_color (3 HOST doubles) where
+ *            bg_color != NULL and the label equals bg_label. */
+int sdsm_render_colormap(int H, int W, int source, const void *d_src, const double *d_lut, int N, const double *clim, const int32_t *d_perm,
+                         int64_t perm_n, int perm_min, const int32_t *d_range, const double *bg_color, int bg_label, int32_t *d_flags,
+                         double *d_out, void *stream);
+int sdsm_render_colormap_multi(const sdsm_set_image *images, int n_images, int source, const void *d_src, const double *d_lut, int N,
+                               const double *clim, const int32_t *d_perm, const int64_t *perm_off, const int32_t *perm_min,
+                               const int32_t *d_range, const double *bg_color, int bg_label, int32_t *d_flags, double *d_out, void *stream);
+/* render.py:13-99 (draw_line, render_adjacencies).  d_prims: n_prims x 8 int32 (kind, index, image, r0, c0, r1, c1, 0); kind 0 is a
+ * seed at (r0, c0), kind 1 the line number `index` (0 .. 65534, the list order) from (r0, c0) to (r1, c1).  Seeds and end points lie
+ * INSIDE their image: the caller checks that.  Painted in the definition's order, whatever the order of d_prims:
+ *   1. every seed's rim, the pixels with ((r - r0) / rim_radius)^2 + ((c - c0) / rim_radius)^2 < 1 (float64, as written: what
+ *      skimage.draw.disk documents), colors[0 .. 3);
+ *   2. the lines by ascending index.  A line's pixels are those of skimage.draw.line (integer Bresenham: the longer axis drives,
+ *      columns on a tie; error term from 2 d_short - d_long; last pixel = the end point).  A pixel whose squared distance to the nearest
+ *      line pixel is <= core_d2 gets colors[6 .. 9), else if <= ring_d2 colors[9 .. 12) (the ring of a fractional thickness,
+ *      render.py:40-44; core_d2 = -1: no core); line_reach = floor(sqrt(ring_d2)) <= 16;
+ *   3. every seed's disk (disk_radius), colors[3 .. 6).
+ * Radii 0 .. SDSM_RENDER_MAX_SEED_RADIUS.  Unpainted pixels keep d_base (float64, channels = 1 or 3 per pixel).  d_out: 3 uint8 per
+ * pixel, 255 * v clipped to 0 .. 255 and truncated (render.py:99).  d_key (int32 per pixel, packed) is scratch, cleared by the call:
+ * the per-pixel integer maximum that makes the result independent of the arrival order.  colors: 12 HOST doubles. */
+int sdsm_render_graph(int H, int W, int n_prims, const int32_t *d_prims, double rim_radius, double disk_radius, int line_reach, int core_d2,
+                      int ring_d2, const double *colors, const double *d_base, int channels, int32_t *d_key, uint8_t *d_out, void *stream);
+int sdsm_render_graph_multi(const sdsm_set_image *images, int n_images, int n_prims, const int32_t *d_prims, double rim_radius,
+                            double disk_radius, int line_reach, int core_d2, int ring_d2, const double *colors, const double *d_base,
+                            int channels, int32_t *d_key, uint8_t *d_out, void *stream);
+
 /* ---- host-side combinatorial steps of the stage (no device access) -------------------------------------------------------------
  * Approximate min-weight set cover (superdsm/minsetcover.py:4-88: greedy + merge phase, retried with beta * gamma on up to max_iter
  * levels) and greedy max-weight set packing (superdsm/maxsetpack.py:8-24) over n objects whose footprints are bit sets of `words`

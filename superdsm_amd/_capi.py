@@ -40,6 +40,8 @@ DOH_PEAKS_HEADER_BYTES = 16
 DOH_MAX_SCALES = 32
 MAX_SET_IMAGES = 32          # SDSM_MAX_SET_IMAGES: images per call of a *_multi entry point
 RENDER_MAX_RADIUS = 16       # SDSM_RENDER_MAX_RADIUS: largest disk of the label-map and overlay kernels
+RENDER_MAX_COLORS = 1024     # SDSM_RENDER_MAX_COLORS: entries of a colour map of the colour-map kernel
+RENDER_MAX_SEED_RADIUS = 64  # SDSM_RENDER_MAX_SEED_RADIUS: largest seed disk (with its rim) of the graph kernel
 RENDER_ENTRY_DTYPE = np.dtype([('idx', 'i4'), ('label', 'i4'), ('dist', 'f8')])   # sdsm_render_entry
 assert RENDER_ENTRY_DTYPE.itemsize == 16
 
@@ -118,6 +120,13 @@ SYMBOLS = {
     'sdsm_render_finish': (_i32, [_i64, _vp, _i32, _vp, _vp]),
     'sdsm_render_overlay': (_i32, [_i32, _i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32, _vp, _vp]),
     'sdsm_render_overlay_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32, _vp, _vp]),
+    'sdsm_render_label_range': (_i32, [_i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    'sdsm_render_label_range_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, _vp, _vp]),
+    'sdsm_render_colormap': (_i32, [_i32, _i32, _i32, _vp, _vp, _i32, C.POINTER(C.c_double), _vp, _i64, _i32, _vp, C.POINTER(C.c_double), _i32, _vp, _vp, _vp]),
+    'sdsm_render_colormap_multi': (_i32, [C.POINTER(SetImage), _i32, _i32, _vp, _vp, _i32, C.POINTER(C.c_double), _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                          _vp, C.POINTER(C.c_double), _i32, _vp, _vp, _vp]),
+    'sdsm_render_graph': (_i32, [_i32, _i32, _i32, _vp, _f64, _f64, _i32, _i32, _i32, C.POINTER(C.c_double), _vp, _i32, _vp, _vp, _vp]),
+    'sdsm_render_graph_multi': (_i32, [C.POINTER(SetImage), _i32, _i32, _vp, _f64, _f64, _i32, _i32, _i32, C.POINTER(C.c_double), _vp, _i32, _vp, _vp, _vp]),
     'sdsm_minsetcover': (_i32, [_i32, _i32, _vp, _vp, _f64, _i32, _i32, _f64, _vp, _vp]),
     'sdsm_minsetcover_multi': (_i32, [_i32, _vp, _vp, _vp, _vp, _f64, _i32, _i32, _f64, _vp, _vp]),
     'sdsm_maxsetpack': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp]),

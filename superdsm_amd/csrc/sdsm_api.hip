@@ -1127,3 +1127,88 @@ extern "C" int sdsm_render_overlay(int H, int W, const int32_t *d_labels, const 
     const sdsm_set_image one = {0, H, W};
     return sdsm_render_overlay_multi(&one, 1, d_labels, d_base, channels, kind, radius, color, bg, background_label, d_out, stream);
 }
+
+// ---- colour maps and adjacency graphs (sdsm_render.hip) ----------------------------------------------------------------------------
+extern "C" hipError_t sdsm_render_label_range_impl(const sdsm_set_image *images, int n_images, const int32_t *labels, const int32_t *perm,
+                                                   const int64_t *perm_off, const int32_t *perm_min, int32_t *range, int32_t *permuted_out,
+                                                   hipStream_t stream);
+extern "C" hipError_t sdsm_render_colormap_impl(const sdsm_set_image *images, int n_images, int source, const void *src, const double *lut, int N,
+                                                const double *clim, const int32_t *perm, const int64_t *perm_off, const int32_t *perm_min,
+                                                const int32_t *range, int has_bg, int bg_label, const double *bg_color, int32_t *flags,
+                                                double *out, hipStream_t stream);
+extern "C" hipError_t sdsm_render_graph_impl(const sdsm_set_image *images, int n_images, int n_prims, const int32_t *prims, double rim_radius,
+                                             double disk_radius, int seed_reach, int line_reach, int core_d2, int ring_d2, const double *colors,
+                                             const double *base, int channels, int32_t *key, uint8_t *out, hipStream_t stream);
+
+static bool perm_tables_ok(int n_images, const int32_t *d_perm, const int64_t *perm_off, const int32_t *perm_min)
+{
+    if (!d_perm) return true;
+    if (!perm_off || !perm_min || perm_off[0] < 0) return false;
+    for (int i = 0; i < n_images; i++) if (perm_off[i + 1] < perm_off[i]) return false;
+    return true;
+}
+
+extern "C" int sdsm_render_label_range_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int32_t *d_perm,
+                                             const int64_t *perm_off, const int32_t *perm_min, int32_t *d_range, int32_t *d_permuted, void *stream)
+{
+    RENDER_TABLE("sdsm_render_label_range");
+    if (!d_labels || (!d_range && !d_permuted)) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_label_range: null argument");
+    if (!perm_tables_ok(n_images, d_perm, perm_off, perm_min)) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_label_range: bad permutation tables");
+    hipError_t e = sdsm_render_label_range_impl(images, n_images, d_labels, d_perm, perm_off, perm_min, d_range, d_permuted, (hipStream_t)stream);
+    RENDER_DONE("sdsm_render_label_range");
+}
+
+extern "C" int sdsm_render_label_range(int H, int W, const int32_t *d_labels, const int32_t *d_perm, int64_t perm_n, int perm_min, int32_t *d_range,
+                                       int32_t *d_permuted, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    const int64_t off[2] = {0, perm_n};
+    return sdsm_render_label_range_multi(&one, 1, d_labels, d_perm, off, &perm_min, d_range, d_permuted, stream);
+}
+
+extern "C" int sdsm_render_colormap_multi(const sdsm_set_image *images, int n_images, int source, const void *d_src, const double *d_lut, int N,
+                                          const double *clim, const int32_t *d_perm, const int64_t *perm_off, const int32_t *perm_min,
+                                          const int32_t *d_range, const double *bg_color, int bg_label, int32_t *d_flags, double *d_out, void *stream)
+{
+    RENDER_TABLE("sdsm_render_colormap");
+    if (N < 1 || N > SDSM_RENDER_MAX_COLORS) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_colormap: 1 <= N <= 1024 colours required");
+    if ((source != 0 && source != 1) || !d_src || !d_lut || !d_out || (source == 0 && (!clim || !d_flags)) || (source == 1 && !d_range))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_render_colormap: bad argument (source 0 needs clim and d_flags, source 1 d_range)");
+    if (source == 1 && !perm_tables_ok(n_images, d_perm, perm_off, perm_min)) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_colormap: bad permutation tables");
+    hipError_t e = sdsm_render_colormap_impl(images, n_images, source, d_src, d_lut, N, clim, source == 1 ? d_perm : nullptr, perm_off, perm_min, d_range,
+                                             bg_color != nullptr, bg_label, bg_color, d_flags, d_out, (hipStream_t)stream);
+    RENDER_DONE("sdsm_render_colormap");
+}
+
+extern "C" int sdsm_render_colormap(int H, int W, int source, const void *d_src, const double *d_lut, int N, const double *clim, const int32_t *d_perm,
+                                    int64_t perm_n, int perm_min, const int32_t *d_range, const double *bg_color, int bg_label, int32_t *d_flags,
+                                    double *d_out, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    const int64_t off[2] = {0, perm_n};
+    return sdsm_render_colormap_multi(&one, 1, source, d_src, d_lut, N, clim, d_perm, off, &perm_min, d_range, bg_color, bg_label, d_flags, d_out, stream);
+}
+
+extern "C" int sdsm_render_graph_multi(const sdsm_set_image *images, int n_images, int n_prims, const int32_t *d_prims, double rim_radius,
+                                       double disk_radius, int line_reach, int core_d2, int ring_d2, const double *colors, const double *d_base,
+                                       int channels, int32_t *d_key, uint8_t *d_out, void *stream)
+{
+    RENDER_TABLE("sdsm_render_graph");
+    if (!(rim_radius >= 0) || !(disk_radius >= 0) || rim_radius > SDSM_RENDER_MAX_SEED_RADIUS || disk_radius > SDSM_RENDER_MAX_SEED_RADIUS)
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_render_graph: 0 <= radius <= 64 required for the disks and their rims");
+    if (line_reach < 0 || line_reach > SDSM_RENDER_MAX_RADIUS || core_d2 < -1 || ring_d2 < core_d2 || (int64_t)ring_d2 >= (int64_t)(line_reach + 1) * (line_reach + 1))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_render_graph: bad line (0 <= line_reach <= 16, -1 <= core_d2 <= ring_d2 < (line_reach + 1)^2)");
+    if (n_prims < 0 || (n_prims > 0 && !d_prims) || !colors || !d_base || (channels != 1 && channels != 3) || !d_key || !d_out)
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_render_graph: bad argument (channels 1 or 3)");
+    const double reach = rim_radius > disk_radius ? rim_radius : disk_radius;
+    hipError_t e = sdsm_render_graph_impl(images, n_images, n_prims, d_prims, rim_radius, disk_radius, (int)ceil(reach), line_reach, core_d2, ring_d2, colors,
+                                          d_base, channels, d_key, d_out, (hipStream_t)stream);
+    RENDER_DONE("sdsm_render_graph");
+}
+
+extern "C" int sdsm_render_graph(int H, int W, int n_prims, const int32_t *d_prims, double rim_radius, double disk_radius, int line_reach, int core_d2,
+                                 int ring_d2, const double *colors, const double *d_base, int channels, int32_t *d_key, uint8_t *d_out, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_render_graph_multi(&one, 1, n_prims, d_prims, rim_radius, disk_radius, line_reach, core_d2, ring_d2, colors, d_base, channels, d_key, d_out, stream);
+}

@@ -9,6 +9,11 @@
 //                        render.py:449       k_finish: uint16 with the background label
 //   rasterize_regions, render_regions_over_image, render_result_over_image
 //                        render.py:246-365   k_overlay: disk minimum / maximum of the label image through LDS, fused with the painting
+//   render_ymap          render.py:123-134   k_colormap (source 0): clip, subtract, divide, colour-map lookup
+//   shuffle_labels, colorize_labels
+//                        render.py:462-508   k_label_range (minimum / maximum of the permuted labels), k_colormap (source 1), k_permute
+//   draw_line, render_adjacencies
+//                        render.py:13-99     k_graph_mark (one workgroup per seed or line), k_graph_paint
 //
 // Objects arrive as sdsm_post_objects takes them: a box (r0, c0, h, w) in the coordinates of their image and the h * w bits of the
 // fragment, row-major, LSB first in uint32 words.  Every atomic is an integer atomic (max, add, or) whose result does not depend on
@@ -18,6 +23,7 @@
 // sdsm_set_image table says; one launch per phase serves the whole set and runs the __device__ bodies of the single-image case, which
 // is a set of one image.
 #include "sdsm_common.h"
+#include <climits>
 
 #pragma clang fp contract(off)   // the blend of the discarded regions is numpy's a + b * c, unfused
 
@@ -279,6 +285,232 @@ __global__ __launch_bounds__(RTPB) void k_overlay(RSet S, OverlayArgs A)
     }
 }
 
+// ---- colour maps (render.py:102-134 render_ymap, :454-508 shuffle_labels / colorize_labels) ---------------------------------------
+// The lookup is matplotlib's Colormap.__call__ for float input (colors.py, _get_rgba_and_mask): xa = x * N; xa == N -> N - 1;
+// xa < 0 -> under (entry N); xa >= N -> over (N + 1); NaN -> bad (N + 2); otherwise the entry (int)xa, truncated.  -0.0 is not < 0
+// and reads entry 0; -inf / +inf are under / over.
+struct CmapArgs {
+    int32_t source;                              // 0: float64 values, 1: int32 labels
+    int32_t N;                                   // entries of the colour map; the table has N + 3 rows of 4 float64
+    int32_t has_bg, bg_label;
+    double bg_color[3];
+    double sub[SDSM_MAX_SET_IMAGES], div[SDSM_MAX_SET_IMAGES];   // source 0, per image: x = (clip(y, lo, hi) - sub) / div
+    double lo[SDSM_MAX_SET_IMAGES], hi[SDSM_MAX_SET_IMAGES];
+    int64_t perm_off[SDSM_MAX_SET_IMAGES + 1];   // source 1, per image: its permutation table is perm[perm_off[i] .. perm_off[i + 1])
+    int32_t perm_min[SDSM_MAX_SET_IMAGES];       //   indexed by label - perm_min[i]; a label outside the table reads 0 (render.py:469)
+    const double *lut;
+    const void *src;
+    const int32_t *perm;                         // null: the labels as they are
+    const int32_t *range;                        // source 1: minimum, maximum per image (k_label_range)
+    int32_t *flags;                              // source 0: bit 0 set per image that holds a NaN
+    double *out;                                 // 3 float64 per pixel
+};
+
+constexpr int CMAP_PIX = 2048;                   // pixels per workgroup: the table is loaded into LDS once for them
+
+__device__ __forceinline__ int32_t permuted(const int32_t *perm, int64_t off, int64_t n, int32_t lo, int32_t l)
+{
+    if (!perm) return l;
+    const int64_t k = (int64_t)l - lo;
+    return (k >= 0 && k < n) ? perm[off + k] : 0;
+}
+
+__global__ __launch_bounds__(RTPB) void k_label_range_init(int n, int32_t *range)
+{
+    const int i = blockIdx.x * RTPB + threadIdx.x;
+    if (i < n) { range[2 * i] = INT_MAX; range[2 * i + 1] = INT_MIN; }
+}
+
+__global__ __launch_bounds__(RTPB) void k_label_range(RSet S, CmapArgs A, int32_t *range)
+{
+    const int im = rset_find(S.start, S.n, blockIdx.x);
+    const int64_t px = (int64_t)S.H[im] * S.W[im];
+    const int64_t p0 = (int64_t)(blockIdx.x - S.start[im]) * CMAP_PIX;
+    const int32_t *lab = (const int32_t *)A.src + S.off[im];
+    const int64_t pn = A.perm_off[im + 1] - A.perm_off[im];
+    int32_t mn = INT_MAX, mx = INT_MIN;
+    for (int e = threadIdx.x; e < CMAP_PIX; e += RTPB) {
+        const int64_t p = p0 + e;
+        if (p >= px) break;
+        const int32_t l = permuted(A.perm, A.perm_off[im], pn, A.perm_min[im], lab[p]);
+        mn = l < mn ? l : mn; mx = l > mx ? l : mx;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const int32_t a = __shfl_down(mn, o), b = __shfl_down(mx, o);
+        mn = a < mn ? a : mn; mx = b > mx ? b : mx;
+    }
+    if ((threadIdx.x & 63) == 0 && mn <= mx) { atomicMin(range + 2 * im, mn); atomicMax(range + 2 * im + 1, mx); }
+}
+
+// shuffle_labels alone: out[p] = the permuted label
+__global__ __launch_bounds__(RTPB) void k_permute(RSet S, CmapArgs A, int32_t *out)
+{
+    const int im = rset_find(S.start, S.n, blockIdx.x);
+    const int64_t px = (int64_t)S.H[im] * S.W[im];
+    const int64_t p0 = (int64_t)(blockIdx.x - S.start[im]) * CMAP_PIX;
+    const int32_t *lab = (const int32_t *)A.src + S.off[im];
+    const int64_t pn = A.perm_off[im + 1] - A.perm_off[im];
+    for (int e = threadIdx.x; e < CMAP_PIX; e += RTPB) {
+        const int64_t p = p0 + e;
+        if (p >= px) break;
+        out[S.off[im] + p] = permuted(A.perm, A.perm_off[im], pn, A.perm_min[im], lab[p]);
+    }
+}
+
+// One thread per OUTPUT element (pixel, channel): consecutive lanes store consecutive float64, the three lanes of a pixel read the
+// same source element.  The table (3 of its 4 columns) sits in LDS.
+__global__ __launch_bounds__(RTPB) void k_colormap(RSet S, CmapArgs A)
+{
+    extern __shared__ double lut[];              // (N + 3) x 3
+    const int N = A.N;
+    for (int e = threadIdx.x; e < (N + 3) * 3; e += RTPB) lut[e] = A.lut[(e / 3) * 4 + e % 3];
+    __syncthreads();
+    const int im = rset_find(S.start, S.n, blockIdx.x);
+    const int64_t px = (int64_t)S.H[im] * S.W[im];
+    const int64_t p0 = (int64_t)(blockIdx.x - S.start[im]) * CMAP_PIX;
+    double *out = A.out + 3 * S.off[im];
+    const double lo = A.lo[im], hi = A.hi[im], sub = A.sub[im], div = A.div[im];
+    int32_t mn = 0, mx = 0;
+    const int64_t pn = A.perm_off[im + 1] - A.perm_off[im];
+    if (A.source == 1) { mn = A.range[2 * im]; mx = A.range[2 * im + 1]; }
+    const double span = (double)((int64_t)mx - mn);
+    bool nan_seen = false;
+    for (int e = threadIdx.x; e < 3 * CMAP_PIX; e += RTPB) {
+        const int64_t p = p0 + e / 3;
+        if (p >= px) break;
+        const int ch = e % 3;
+        double x;
+        bool back = false;
+        if (A.source == 0) {
+            double v = ((const double *)A.src)[S.off[im] + p];
+            nan_seen |= v != v;
+            v = v < lo ? lo : v;                 // numpy's clip: minimum(maximum(v, lo), hi), a NaN stays
+            v = v > hi ? hi : v;
+            x = (v - sub) / div;
+        } else {
+            const int32_t l = permuted(A.perm, A.perm_off[im], pn, A.perm_min[im], ((const int32_t *)A.src)[S.off[im] + p]);
+            back = A.has_bg && l == A.bg_label;
+            x = (double)((int64_t)l - mn) / span;    // 0 / 0 = NaN where the image holds one label: the "bad" colour
+        }
+        double xa = x * N;
+        if (xa == (double)N) xa = N - 1;
+        int idx;
+        if (xa != xa) idx = N + 2;
+        else if (xa < 0) idx = N;
+        else if (xa >= (double)N) idx = N + 1;
+        else idx = (int)xa;
+        out[3 * p + ch] = back ? A.bg_color[ch] : lut[3 * idx + ch];
+    }
+    if (nan_seen) atomicOr(A.flags + im, 1);
+}
+
+// ---- adjacency graphs (render.py:13-99 draw_line, render_adjacencies) ------------------------------------------------------------
+// Painting order of the definition: every rim, then the lines in list order, then every disk.  Pass 1 takes, per pixel, the integer
+// maximum of a key that grows in that order (KEY_RIM < line keys growing with the line's index < KEY_DISK); pass 2 paints from the
+// key.  The maximum does not depend on the arrival order.  A line's key carries in bit 0 whether the pixel lies in the line's core
+// (value 1) or in the ring of a fractional thickness (render.py:40-44: one value for the whole ring, computed on the host), so
+// pass 2 recomputes nothing: a line reaches a pixel once, through one candidate of its band.
+//
+// Line pixels (what skimage.draw.line documents): the longer axis drives (columns on a tie), one pixel per step i = 0 .. dl; the error
+// term starts at 2 ds - dl, gains 2 ds per step and, while >= 0 after a pixel, the minor coordinate steps and the term loses 2 dl.
+// As ds <= dl, the minor offset before pixel i is the smallest m with 2 ds i - dl - 2 dl m < 0: m_i = floor((2 ds i + dl) / (2 dl)),
+// which also gives m_dl = ds, the end point.  (dl = 0: the single pixel.)
+//
+// Thick line: pixels whose squared distance to the nearest line pixel is <= d2 (an integer the host derives from the definition's
+// sqrt(d2) < threshold).  With n = reach = floor(sqrt(d2)), the nearest line pixel of a pixel at driving coordinate k lies at a
+// step j with |j - k| <= n, and |m_j - m_clamp(k)| <= |j - clamp(k)| <= n, so the band minor = m_clamp(k) + [-2 n, 2 n] holds every
+// pixel the line can reach.  The m_j of a chunk of steps sit in LDS.
+constexpr int32_t KEY_RIM = 1, KEY_LINE = 1 << 20, KEY_DISK = 1 << 21;
+constexpr int GRAPH_REACH_MAX = 16;              // line thickness <= 33
+constexpr int GRAPH_CHUNK = 1024;                // driving steps per LDS chunk
+
+struct GraphArgs {
+    int32_t n_prims, seed_reach, line_reach, core_d2, ring_d2, channels;
+    double rim_radius, disk_radius;
+    double colors[12];                           // rim, disk, line core, line ring
+    const int32_t *prims;                        // 8 int32 each: kind (0 seed, 1 line), index, image, r0, c0, r1, c1, 0
+    const double *base;
+    int32_t *key;
+    uint8_t *out;
+};
+
+__global__ __launch_bounds__(RTPB) void k_graph_mark(RSet S, GraphArgs A)
+{
+    __shared__ int32_t minor[GRAPH_CHUNK + 2 * GRAPH_REACH_MAX];
+    const int32_t *P = A.prims + 8 * (int64_t)blockIdx.x;
+    const int kind = P[0], index = P[1] & 0xFFFF, im = P[2];
+    if (im < 0 || im >= S.n) return;
+    const int H = S.H[im], W = S.W[im];
+    int32_t *key = A.key + S.off[im];
+    const int r0 = P[3], c0 = P[4], r1 = P[5], c1 = P[6];
+    if (kind == 0) {                             // a seed: rim and disk, ((r - r0) / radius)^2 + ((c - c0) / radius)^2 < 1, as written
+        const int R = A.seed_reach, side = 2 * R + 1;
+        for (int e = threadIdx.x; e < side * side; e += RTPB) {
+            const int r = r0 - R + e / side, c = c0 - R + e % side;
+            if (r < 0 || c < 0 || r >= H || c >= W) continue;
+            const double dr = (double)(r - r0), dc = (double)(c - c0);
+            const double ar = dr / A.disk_radius, ac = dc / A.disk_radius, br = dr / A.rim_radius, bc = dc / A.rim_radius;
+            const bool in_disk = ar * ar + ac * ac < 1.0, in_rim = br * br + bc * bc < 1.0;
+            if (in_disk) atomicMax(key + (int64_t)r * W + c, KEY_DISK);
+            else if (in_rim) atomicMax(key + (int64_t)r * W + c, KEY_RIM);
+        }
+        return;
+    }
+    const int adr = r1 > r0 ? r1 - r0 : r0 - r1, adc = c1 > c0 ? c1 - c0 : c0 - c1;
+    const bool steep = adr > adc;
+    const int dl = steep ? adr : adc, ds = steep ? adc : adr;
+    const int sr = r1 - r0 > 0 ? 1 : -1, sc = c1 - c0 > 0 ? 1 : -1;
+    const int sl = steep ? sr : sc, ss = steep ? sc : sr;
+    const int l0 = steep ? r0 : c0, s0 = steep ? c0 : r0;
+    const int n = A.line_reach, width = 4 * n + 1;
+    for (int a = -n; a <= dl + n; a += GRAPH_CHUNK) {          // candidates with driving step k in [a, a + CHUNK)
+        const int j0 = a - n < 0 ? 0 : a - n;                  // the steps whose pixels they can reach: j0 .. j1
+        const int j1 = a + GRAPH_CHUNK - 1 + n > dl ? dl : a + GRAPH_CHUNK - 1 + n;
+        __syncthreads();
+        for (int j = j0 + threadIdx.x; j <= j1; j += RTPB)
+            minor[j - j0] = dl == 0 ? 0 : (int32_t)((2 * (int64_t)ds * j + dl) / (2 * (int64_t)dl));
+        __syncthreads();
+        const int k_end = a + GRAPH_CHUNK - 1 > dl + n ? dl + n : a + GRAPH_CHUNK - 1;
+        const int total = (k_end - a + 1) * width;
+        for (int e = threadIdx.x; e < total; e += RTPB) {
+            const int k = a + e / width;
+            const int kc = k < 0 ? 0 : (k > dl ? dl : k);
+            const int m = minor[kc - j0] + e % width - 2 * n;
+            const int lc = l0 + sl * k, mc = s0 + ss * m;
+            const int r = steep ? lc : mc, c = steep ? mc : lc;
+            if (r < 0 || c < 0 || r >= H || c >= W) continue;
+            const int ja = k - n < 0 ? 0 : k - n, jb = k + n > dl ? dl : k + n;
+            int best = INT_MAX;
+            for (int j = ja; j <= jb; j++) {
+                const int dj = j - k, dm = minor[j - j0] - m, d2 = dj * dj + dm * dm;
+                best = d2 < best ? d2 : best;
+            }
+            if (best <= A.ring_d2) atomicMax(key + (int64_t)r * W + c, KEY_LINE | (index << 1) | (best <= A.core_d2 ? 1 : 0));
+        }
+    }
+}
+
+__global__ __launch_bounds__(RTPB) void k_graph_paint(RSet S, GraphArgs A)
+{
+    const int im = rset_find(S.start, S.n, blockIdx.x);
+    const int64_t px = (int64_t)S.H[im] * S.W[im];
+    const int64_t p = (int64_t)(blockIdx.x - S.start[im]) * RTPB + threadIdx.x;
+    if (p >= px) return;
+    const int32_t k = A.key[S.off[im] + p];
+    const double *b = A.base + (S.off[im] + p) * A.channels;
+    uint8_t *o = A.out + (S.off[im] + p) * 3;
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {             // (selects on constant indices: the colours stay in scalar registers)
+        double v = b[A.channels == 3 ? ch : 0];
+        if (k >= KEY_DISK) v = A.colors[3 + ch];
+        else if (k >= KEY_LINE) v = (k & 1) ? A.colors[6 + ch] : A.colors[9 + ch];
+        else if (k >= KEY_RIM) v = A.colors[ch];
+        v = 255 * v;
+        v = v < 0 ? 0 : (v > 255 ? 255 : v);                               // render.py:99, truncation
+        o[ch] = (uint8_t)v;
+    }
+}
+
 RSet make_set(const sdsm_set_image *images, int n_images, int per_block /* pixels per workgroup, 0: none; -1: tiles */)
 {
     RSet S{};
@@ -405,5 +637,68 @@ extern "C" hipError_t sdsm_render_overlay_impl(const sdsm_set_image *images, int
     }
     A.labels = labels; A.base = base; A.out = out;
     hipLaunchKernelGGL(k_overlay, dim3(S.start[n_images]), dim3(RTPB), 0, stream, S, A);
+    return hipGetLastError();
+}
+
+static void cmap_tables(CmapArgs &A, int n_images, const int64_t *perm_off, const int32_t *perm_min)
+{
+    for (int i = 0; i < n_images; i++) {
+        A.perm_off[i] = perm_off ? perm_off[i] : 0; A.perm_min[i] = perm_min ? perm_min[i] : 0;
+    }
+    A.perm_off[n_images] = perm_off ? perm_off[n_images] : 0;
+}
+
+extern "C" hipError_t sdsm_render_label_range_impl(const sdsm_set_image *images, int n_images, const int32_t *labels, const int32_t *perm,
+                                                   const int64_t *perm_off, const int32_t *perm_min, int32_t *range, int32_t *permuted_out,
+                                                   hipStream_t stream)
+{
+    const RSet S = make_set(images, n_images, CMAP_PIX);
+    CmapArgs A{};
+    A.source = 1; A.src = labels; A.perm = perm;
+    cmap_tables(A, n_images, perm_off, perm_min);
+    if (range) {
+        hipLaunchKernelGGL(k_label_range_init, dim3(1), dim3(RTPB), 0, stream, n_images, range);
+        hipLaunchKernelGGL(k_label_range, dim3(S.start[n_images]), dim3(RTPB), 0, stream, S, A, range);
+    }
+    if (permuted_out) hipLaunchKernelGGL(k_permute, dim3(S.start[n_images]), dim3(RTPB), 0, stream, S, A, permuted_out);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t sdsm_render_colormap_impl(const sdsm_set_image *images, int n_images, int source, const void *src, const double *lut, int N,
+                                                const double *clim, const int32_t *perm, const int64_t *perm_off, const int32_t *perm_min,
+                                                const int32_t *range, int has_bg, int bg_label, const double *bg_color, int32_t *flags,
+                                                double *out, hipStream_t stream)
+{
+    const RSet S = make_set(images, n_images, CMAP_PIX);
+    CmapArgs A{};
+    A.source = source; A.N = N; A.has_bg = has_bg; A.bg_label = bg_label;
+    for (int k = 0; k < 3; k++) A.bg_color[k] = bg_color ? bg_color[k] : 0.0;
+    for (int i = 0; i < n_images && clim; i++) { A.lo[i] = clim[4 * i]; A.hi[i] = clim[4 * i + 1]; A.sub[i] = clim[4 * i + 2]; A.div[i] = clim[4 * i + 3]; }
+    cmap_tables(A, n_images, perm_off, perm_min);
+    A.lut = lut; A.src = src; A.perm = perm; A.range = range; A.flags = flags; A.out = out;
+    if (source == 0) {
+        hipError_t e = hipMemsetAsync(flags, 0, (size_t)n_images * sizeof(int32_t), stream);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_colormap, dim3(S.start[n_images]), dim3(RTPB), (size_t)(N + 3) * 3 * sizeof(double), stream, S, A);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t sdsm_render_graph_impl(const sdsm_set_image *images, int n_images, int n_prims, const int32_t *prims, double rim_radius,
+                                             double disk_radius, int seed_reach, int line_reach, int core_d2, int ring_d2, const double *colors,
+                                             const double *base, int channels, int32_t *key, uint8_t *out, hipStream_t stream)
+{
+    const RSet S = make_set(images, n_images, RTPB);
+    GraphArgs A{};
+    A.n_prims = n_prims; A.seed_reach = seed_reach; A.line_reach = line_reach; A.core_d2 = core_d2; A.ring_d2 = ring_d2; A.channels = channels;
+    A.rim_radius = rim_radius; A.disk_radius = disk_radius;
+    for (int k = 0; k < 12; k++) A.colors[k] = colors[k];
+    A.prims = prims; A.base = base; A.key = key; A.out = out;
+    for (int i = 0; i < n_images; i++) {
+        hipError_t e = hipMemsetAsync(key + images[i].offset, 0, (size_t)images[i].H * images[i].W * sizeof(int32_t), stream);
+        if (e != hipSuccess) return e;
+    }
+    if (n_prims > 0) hipLaunchKernelGGL(k_graph_mark, dim3(n_prims), dim3(RTPB), 0, stream, S, A);
+    hipLaunchKernelGGL(k_graph_paint, dim3(S.start[n_images]), dim3(RTPB), 0, stream, S, A);
     return hipGetLastError();
 }

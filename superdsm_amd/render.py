@@ -9,6 +9,7 @@ compared.  Host code (the reference's own is NumPy / scikit-image on the host to
 a priority flood with its documented semantics (4-connectivity, ties by insertion order)."""
 import csv
 import heapq
+import math
 
 import numpy as np
 import scipy.ndimage as ndi
@@ -685,6 +686,526 @@ def render_result_over_image(data, objects='postprocessed_objects', merge_overla
     mx > 0 and mn != mx over disk(border_width // 2), 'inner' those with a label > 0 and mn != mx over disk(border_width)
     (mn / mx: smallest / largest label in the disk); 'outer' is not supported."""
     return render_result_over_image_many([data], [_objects_of(data, objects)], merge_overlap_threshold, normalize_img, border_width, border_position, [override_img], color)[0]
+
+
+# ---- colour maps: y-maps and coloured labels (render.py:102-134, :454-508) -------------------------------------------------------
+class _PixelSet:
+    """The packed pixel layout of one set of up to ``_capi.MAX_SET_IMAGES`` images and the calls of the colour-map and graph kernels
+    (no label-map buffers: lighter than :class:`_GpuSet`)."""
+
+    def __init__(self, shapes):
+        import ctypes as C
+        import torch
+        from . import _capi
+        self.C, self.torch, self.capi, self.L = C, torch, _capi, _capi.lib()
+        self.shapes = [(int(h), int(w)) for h, w in shapes]
+        if not 1 <= len(self.shapes) <= _capi.MAX_SET_IMAGES:
+            raise ValueError(f'a set holds 1 .. {_capi.MAX_SET_IMAGES} images')
+        self.table = (_capi.SetImage * len(self.shapes))()
+        off = 0
+        for i, (h, w) in enumerate(self.shapes):
+            self.table[i].offset, self.table[i].H, self.table[i].W = off, h, w
+            off += (h * w + 63) // 64 * 64
+        self.offsets, self.total = np.array([t.offset for t in self.table], np.int64), off
+        self.dev = torch.device('cuda', torch.cuda.current_device())
+
+    _up, _p, _stream = _GpuSet._up, _GpuSet._p, _GpuSet._stream
+
+    def pack(self, arrays, dtype, channels=1):
+        flat = np.zeros(self.total * channels, dtype)
+        for o, (h, w), a in zip(self.offsets, self.shapes, arrays):
+            flat[o * channels:(o + h * w) * channels] = np.asarray(a).reshape(-1)
+        return self._up(flat)
+
+    def unpack(self, d, channels, shape_tail=()):
+        out = d.cpu().numpy()
+        return [out[channels * o:channels * (o + h * w)].reshape((h, w) + shape_tail).copy() for o, (h, w) in zip(self.offsets, self.shapes)]
+
+    def colormap_values(self, ys, clims, table):
+        """source 0 of the colour-map kernel: (pictures, NaN flag per image)."""
+        n_im = len(self.shapes)
+        d_src, d_lut = self.pack(ys, np.float64), self._up(table)
+        d_flags = self.torch.empty(n_im, dtype=self.torch.int32, device=self.dev)
+        d_out = self.torch.empty(self.total * 3, dtype=self.torch.float64, device=self.dev)
+        clim = (self.C.c_double * (4 * n_im))(*[float(v) for c in clims for v in c])
+        self.capi.check(self.L.sdsm_render_colormap_multi(self.table, n_im, 0, self._p(d_src), self._p(d_lut), len(table) - 3, clim, None, None, None, None, None, 0,
+                                                          self._p(d_flags), self._p(d_out), self._stream()), 'sdsm_render_colormap_multi')
+        return self.unpack(d_out, 3, (3,)), d_flags.cpu().numpy() != 0
+
+    def _perm(self, perms):
+        """The permutation tables of the set: (device table or None, host offsets, host minima)."""
+        n_im = len(self.shapes)
+        if perms is None:
+            return None, None, None
+        off = _exclusive(np.array([len(t) for _, t in perms] + [0], np.int64))
+        d_perm = self._up(np.concatenate([t for _, t in perms] + [np.zeros(1, np.int32)]).astype(np.int32))
+        return d_perm, (self.C.c_int64 * (n_im + 1))(*[int(v) for v in off]), (self.C.c_int32 * n_im)(*[int(lo) for lo, _ in perms])
+
+    def permute(self, labels, perms):
+        """shuffle_labels: the permuted labels (int32) per image."""
+        d_labels = self.pack(labels, np.int32)
+        d_perm, off, lo = self._perm(perms)
+        d_out = self.torch.empty(self.total, dtype=self.torch.int32, device=self.dev)
+        self.capi.check(self.L.sdsm_render_label_range_multi(self.table, len(self.shapes), self._p(d_labels), self._p(d_perm), off, lo, None, self._p(d_out), self._stream()),
+                        'sdsm_render_label_range_multi')
+        return self.unpack(d_out, 1)
+
+    def colormap_labels(self, labels, perms, table, bg_label, bg_color):
+        """source 1: the label range (integer atomics) and the colouring, without a round trip between them."""
+        n_im = len(self.shapes)
+        d_labels, d_lut = self.pack(labels, np.int32), self._up(table)
+        d_perm, off, lo = self._perm(perms)
+        d_range = self.torch.empty(2 * n_im, dtype=self.torch.int32, device=self.dev)
+        d_out = self.torch.empty(self.total * 3, dtype=self.torch.float64, device=self.dev)
+        self.capi.check(self.L.sdsm_render_label_range_multi(self.table, n_im, self._p(d_labels), self._p(d_perm), off, lo, self._p(d_range), None, self._stream()),
+                        'sdsm_render_label_range_multi')
+        bgc = (self.C.c_double * 3)(*[float(v) for v in bg_color]) if bg_label is not None else None
+        self.capi.check(self.L.sdsm_render_colormap_multi(self.table, n_im, 1, self._p(d_labels), self._p(d_lut), len(table) - 3, None, self._p(d_perm), off, lo,
+                                                          self._p(d_range), bgc, int(bg_label if bg_label is not None else 0), None, self._p(d_out), self._stream()),
+                        'sdsm_render_colormap_multi')
+        return self.unpack(d_out, 3, (3,))
+
+    def graph(self, prims, bases, rim_radius, disk_radius, reach, core_d2, ring_d2, colors):
+        n_im = len(self.shapes)
+        ch = 3 if any(b.ndim == 3 for b in bases) else 1
+        d_base = self.pack([b if b.ndim == 3 or ch == 1 else np.dstack([b] * 3) for b in bases], np.float64, ch)
+        d_prims = self._up(prims) if len(prims) else None
+        d_key = self.torch.empty(self.total, dtype=self.torch.int32, device=self.dev)
+        d_out = self.torch.empty(self.total * 3, dtype=self.torch.uint8, device=self.dev)
+        col = (self.C.c_double * 12)(*[float(v) for v in colors])
+        self.capi.check(self.L.sdsm_render_graph_multi(self.table, n_im, len(prims), self._p(d_prims), float(rim_radius), float(disk_radius), int(reach), int(core_d2),
+                                                       int(ring_d2), col, self._p(d_base), ch, self._p(d_key), self._p(d_out), self._stream()), 'sdsm_render_graph_multi')
+        return self.unpack(d_out, 3, (3,))
+
+
+def _in_sets(n):
+    from . import _capi
+    return [slice(lo, lo + _capi.MAX_SET_IMAGES) for lo in range(0, n, _capi.MAX_SET_IMAGES)]
+
+
+def colormap_table(cmap):
+    """The table the colour-map kernel takes: ``(N + 3) x 4`` float64, the ``N`` colours, then those for values below, above and
+    "bad".  ``cmap``: such a table, the name of a matplotlib colour map, or a matplotlib ``Colormap`` (matplotlib is imported for the
+    last two only)."""
+    if isinstance(cmap, (np.ndarray, list, tuple)):
+        table = np.ascontiguousarray(cmap, np.float64)
+    else:
+        if isinstance(cmap, str):
+            import matplotlib
+            cmap = matplotlib.colormaps[cmap]
+        if not cmap._isinit:
+            cmap._init()
+        table = np.ascontiguousarray(cmap._lut, np.float64)
+        assert (cmap._i_under, cmap._i_over, cmap._i_bad) == (cmap.N, cmap.N + 1, cmap.N + 2) and len(table) == cmap.N + 3
+    if table.ndim != 2 or table.shape[1] != 4 or table.shape[0] < 4:
+        raise ValueError('a colour-map table is (N + 3) x 4: the N colours, then under, over, bad')
+    return table
+
+
+def _check_table(table):
+    from . import _capi
+    if len(table) - 3 > _capi.RENDER_MAX_COLORS:
+        raise NotImplementedError(f'a colour map of {len(table) - 3} entries: the GPU colour maps take up to {_capi.RENDER_MAX_COLORS}, see DESIGN.md "Limits"')
+    return table
+
+
+def colormap_lookup_host(table, x):
+    """matplotlib's ``Colormap.__call__`` for float input on a table of :func:`colormap_table` (colors.py, _get_rgba_and_mask): scaled
+    by ``N``; exactly ``N`` reads entry ``N - 1``; negative values read "under" (-0.0 is not negative), values >= ``N`` "over", NaN
+    "bad"; everything else is truncated.  The arithmetic runs in the float type of ``x``, as there.  Returns ``x.shape + (4,)``."""
+    table = np.asarray(table, np.float64)
+    N = len(table) - 3
+    xa = np.array(x, copy=True)
+    if xa.dtype.kind != 'f':
+        raise TypeError('colormap_lookup_host takes floating-point values (matplotlib reads integers as indices)')
+    with np.errstate(invalid='ignore', over='ignore'):
+        xa *= N
+        xa[xa == N] = N - 1
+        under, over, bad = xa < 0, xa >= N, np.isnan(xa)
+        idx = xa.astype(int)
+    idx[under], idx[over], idx[bad] = N, N + 1, N + 2
+    return table.take(idx, axis=0, mode='clip')
+
+
+def _ymap_input(data, clim):
+    y = data if isinstance(data, np.ndarray) else data['y']
+    if clim is None:
+        clim = (-y.std(), +y.std())
+    return y, clim
+
+
+def render_ymap_host(data, clim=None, cmap='bwr'):
+    """Host definition of :func:`render_ymap` (render.py:102-134): a row ``(clim[0], ..., clim[0], clim[1])`` is put before ``y``, the
+    whole is clipped to ``clim``, its minimum subtracted, divided by its maximum and looked up; the row and the alpha channel go."""
+    y, clim = _ymap_input(data, clim)
+    z = np.full((1, y.shape[1]), clim[0])
+    z[0, -1] = clim[1]
+    y = np.concatenate((z, y), axis=0)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        y = y.clip(*clim)
+        y -= y.min()
+        y /= y.max()
+    return colormap_lookup_host(colormap_table(cmap), y)[1:, :, :3]
+
+
+def render_ymap_many(datas, clim=None, cmap='bwr'):
+    """:func:`render_ymap` for a list of data objects or ``y`` arrays (one launch per ``_capi.MAX_SET_IMAGES`` images); ``clim=None``
+    is each image's own ``(-y.std(), +y.std())``, NumPy's on the host: one number that decides bytes.
+
+    Without a NaN, and with ``clim[0] < clim[1]``, the clipped padded array has the minimum ``clim[0]`` and the maximum ``clim[1]``
+    exactly, so the kernel computes ``(clip(y) - clim[0]) / (clim[1] - clim[0])`` without a reduction.  In general the two numbers are
+    what the definition's arithmetic gives on the pair ``(clim[0], clim[1])`` alone: with ``clim[0] >= clim[1]`` the clip leaves
+    ``clim[1]`` everywhere, 0 / 0 follows and every pixel is "bad" (so is the ``y`` that is constant under ``clim=None``).  A NaN in
+    ``y`` makes ``y.min()`` NaN: the kernel flags it and every pixel of that picture is "bad"."""
+    table = _check_table(colormap_table(cmap))
+    ys, clims = [], []
+    for data in datas:
+        y, c = _ymap_input(data, clim)
+        if y.ndim != 2 or y.shape[1] < 2 or y.dtype != np.float64:
+            raise NotImplementedError('render_ymap on the GPU takes float64 H x W images with W >= 2 (the definition computes in the type of y; in one column the '
+                                      'padding row holds clim[1] alone), see DESIGN.md "Limits"')
+        lo, hi = float(c[0]), float(c[1])
+        with np.errstate(invalid='ignore'):
+            pair = np.array([lo, hi]).clip(lo, hi)
+            sub = pair.min()
+            pair -= sub
+        ys.append(y)
+        clims.append((lo, hi, sub, pair.max()))
+    out = []
+    for part in _in_sets(len(ys)):
+        pics, bad = _PixelSet([y.shape for y in ys[part]]).colormap_values(ys[part], clims[part], table)
+        out += [np.broadcast_to(table[-1, :3], p.shape).copy() if b else p for p, b in zip(pics, bad)]
+    return out
+
+
+def render_ymap(data, clim=None, cmap='bwr'):
+    """The offset image intensities ``y`` through a colour map (render.py:102-134), on the GPU: float64 ``H x W x 3``."""
+    return render_ymap_many([data], clim, cmap)[0]
+
+
+def _shuffle_map(labels, bg_label, seed):
+    """render.py:462-467: the present label values in the iteration order of their ``frozenset`` and their shuffle by NumPy's legacy
+    generator.  Both orders decide the result, so this is the reference's construction step by step."""
+    values0 = frozenset(labels.flatten())
+    if bg_label is not None:
+        values0 -= {bg_label}
+    values0 = list(values0)
+    if seed is not None:
+        np.random.seed(seed)
+    values1 = np.asarray(values0).copy()
+    np.random.shuffle(values1)
+    return values0, values1
+
+
+def shuffle_labels_host(labels, bg_label=None, seed=None):
+    """Host definition of :func:`shuffle_labels` (render.py:454-473), label by label.  As in the reference the result starts from
+    zeros: the pixels of ``bg_label`` read 0 afterwards (``bg_label`` itself only if it is 0)."""
+    labels = np.asarray(labels)
+    result = np.zeros_like(labels)
+    for l0, l1 in zip(*_shuffle_map(labels, bg_label, seed)):
+        result[labels == l0] = l1
+    return result
+
+
+def _int32_labels(labels, extra_zero=False):
+    """The labels as int32, refused where the reference's own arithmetic (``labels - labels.min()``, ``labels.max() - labels.min()`` in
+    the labels' dtype) would wrap or the values do not fit."""
+    labels = np.asarray(labels)
+    if labels.dtype.kind not in 'iu' or labels.ndim != 2:
+        raise TypeError('labels: a two-dimensional integer image')
+    if labels.dtype.kind == 'i' or labels.dtype.itemsize >= 4:
+        mn, mx = int(labels.min()), int(labels.max())
+        if extra_zero:
+            mn, mx = min(mn, 0), max(mx, 0)
+        if mn < -2 ** 31 or mx >= 2 ** 31 or (labels.dtype.kind == 'i' and mx - mn > np.iinfo(labels.dtype).max) or mx - mn >= 2 ** 31:
+            raise ValueError('labels: the values must fit int32 and their range the labels\' own dtype')
+    return labels.astype(np.int32)
+
+
+def _perm_table(labels, bg_label, seed):
+    """The shuffle as a lookup table: (lowest label of the table, int32 table indexed by label - lowest); labels that are not shuffled
+    (``bg_label``) read 0."""
+    values0, values1 = _shuffle_map(labels, bg_label, seed)
+    if len(values0) == 0:
+        return 0, np.zeros(1, np.int32)
+    v0 = np.asarray(values0).astype(np.int64)
+    lo, n = int(v0.min()), int(v0.max()) - int(v0.min()) + 1
+    if n > 2 ** 24:
+        raise NotImplementedError(f'labels spread over {n} values: the permutation table of the GPU form holds up to 2^24, see DESIGN.md "Limits"')
+    table = np.zeros(n, np.int32)
+    table[v0 - lo] = np.asarray(values1).astype(np.int64)
+    return lo, table
+
+
+def shuffle_labels_many(labels, bg_label=None, seed=None):
+    """:func:`shuffle_labels` for a list of label images.  The permutation of each image is built on the host exactly as the reference
+    does (:func:`_shuffle_map`; with a seed every image is shuffled from that seed, as separate calls would); the GPU applies it."""
+    labels = [np.asarray(l) for l in labels]
+    l32 = [_int32_labels(l, extra_zero=True) for l in labels]
+    perms = [_perm_table(l, bg_label, seed) for l in labels]
+    out = []
+    for part in _in_sets(len(labels)):
+        out += [r.astype(l.dtype) for r, l in zip(_PixelSet([l.shape for l in labels[part]]).permute(l32[part], perms[part]), labels[part])]
+    return out
+
+
+def shuffle_labels(labels, bg_label=None, seed=None):
+    """Randomly permutes the values of a label image (render.py:454-473); the lookup runs on the GPU."""
+    return shuffle_labels_many([labels], bg_label, seed)[0]
+
+
+def colorize_labels_host(labels, bg_label=0, cmap='gist_rainbow', bg_color=(0, 0, 0), shuffle=None):
+    """Host definition of :func:`colorize_labels` (render.py:476-508).  An image of one label divides 0 by 0: NaN, the "bad" colour,
+    everywhere but on the background."""
+    labels = np.asarray(labels)
+    if shuffle is not None:
+        labels = shuffle_labels_host(labels, bg_label=bg_label, seed=shuffle)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        img = colormap_lookup_host(colormap_table(cmap), (labels - labels.min()) / float(labels.max() - labels.min()))
+    img = img[:, :, :3]
+    if bg_label is not None:
+        img[labels == bg_label] = np.asarray(bg_color)[None, None, :]
+    return img
+
+
+def colorize_labels_many(labels, bg_label=0, cmap='gist_rainbow', bg_color=(0, 0, 0), shuffle=None):
+    """:func:`colorize_labels` for a list of label images (one launch per ``_capi.MAX_SET_IMAGES``): the permutation as a table lookup,
+    the minimum and maximum of the (shuffled) labels by integer atomics, ``(label - min) / float(max - min)`` in float64 and the
+    colour-map lookup per pixel."""
+    table = _check_table(colormap_table(cmap))
+    labels = [np.asarray(l) for l in labels]
+    l32 = [_int32_labels(l, extra_zero=shuffle is not None) for l in labels]
+    perms = [_perm_table(l, bg_label, shuffle) for l in labels] if shuffle is not None else None
+    out = []
+    for part in _in_sets(len(labels)):
+        out += _PixelSet([l.shape for l in labels[part]]).colormap_labels(l32[part], perms[part] if perms is not None else None, table, bg_label, bg_color)
+    return out
+
+
+def colorize_labels(labels, bg_label=0, cmap='gist_rainbow', bg_color=(0, 0, 0), shuffle=None):
+    """A colour picture of a label image (render.py:476-508), on the GPU: float64 ``H x W x 3``."""
+    return colorize_labels_many([labels], bg_label, cmap, bg_color, shuffle)[0]
+
+
+# ---- adjacency graphs (render.py:13-99) ---------------------------------------------------------------------------------------------
+# scikit-image is not a dependency: the two functions of skimage.draw that the reference calls are restated from their documented rules.
+def line_pixels_host(r0, c0, r1, c1):
+    """The pixels of ``skimage.draw.line(r0, c0, r1, c1)``: integer Bresenham.  The longer axis drives (the columns on a tie), one pixel
+    per step; the error term starts at ``2 * d_short - d_long``; after a pixel the minor coordinate steps while the term is >= 0; the
+    last pixel is the end point itself."""
+    r0, c0, r1, c1 = int(r0), int(c0), int(r1), int(c1)
+    dr, dc = abs(r1 - r0), abs(c1 - c0)
+    sr, sc = (1 if r1 - r0 > 0 else -1), (1 if c1 - c0 > 0 else -1)
+    steep = dr > dc
+    major, minor, d_long, d_short, s_major, s_minor = (r0, c0, dr, dc, sr, sc) if steep else (c0, r0, dc, dr, sc, sr)
+    rr, cc = np.zeros(d_long + 1, np.int64), np.zeros(d_long + 1, np.int64)
+    err = 2 * d_short - d_long
+    for i in range(d_long):
+        rr[i], cc[i] = (major, minor) if steep else (minor, major)
+        while err >= 0:
+            minor += s_minor
+            err -= 2 * d_long
+        major += s_major
+        err += 2 * d_short
+    rr[d_long], cc[d_long] = r1, c1
+    return rr, cc
+
+
+def disk_pixels_host(center, radius, shape):
+    """The pixels of ``skimage.draw.disk(center, radius, shape=shape)``: ``((r - r0) / radius) ** 2 + ((c - c0) / radius) ** 2 < 1`` in
+    float64, within the image."""
+    r = np.arange(shape[0], dtype=np.float64)[:, None]
+    c = np.arange(shape[1], dtype=np.float64)[None, :]
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.nonzero(((r - center[0]) / radius) ** 2 + ((c - center[1]) / radius) ** 2 < 1)
+
+
+def draw_line_host(p1, p2, thickness, shape):
+    """Host definition of ``draw_line`` (render.py:13-44): float64 mask of the straight line between two end points.  A thickness whose
+    threshold ``(thickness + 1) / 2`` is (close to) an integer gives the pixels nearer than the threshold to a line pixel (Euclidean
+    distance transform in the end points' box grown by the reach); any other thickness blends the two neighbouring odd ones."""
+    assert thickness >= 1
+    threshold = (thickness + 1) / 2
+    if np.allclose(threshold, round(threshold)):
+        p1, p2 = np.asarray(p1), np.asarray(p2)
+        n = math.ceil(threshold) - 1
+        box = np.array((np.minimum(p1, p2) - n, np.maximum(p1, p2) + n)).clip(0, np.subtract(shape, 1))
+        buf = np.zeros(1 + box[1] - box[0])
+        rr, cc = line_pixels_host(*(p1 - box[0]), *(p2 - box[0]))
+        buf[rr, cc] = 1
+        result = np.zeros(shape)
+        result[box[0, 0]:box[1, 0] + 1, box[0, 1]:box[1, 1] + 1] = ndi.distance_transform_edt(buf == 0) < threshold
+        return result
+    thickness1 = 2 * int((thickness + 1) // 2) - 1
+    thickness2 = thickness1 + 2
+    buf1, buf2 = draw_line_host(p1, p2, thickness1, shape), draw_line_host(p1, p2, thickness2, shape)
+    return (buf2 * (thickness - thickness1) / (thickness2 - thickness1) + buf1).clip(0, 1)
+
+
+def _graph_base(data, normalize_img, override_img):
+    """The image under the graph (render.py:77-83): float64, one channel where it is grey."""
+    if override_img is not None:
+        assert override_img.ndim == 3 and override_img.shape[2] >= 3
+        img = override_img[:, :, :3].copy()
+        if (img > 1).any():
+            img = img / 255
+        return img
+    img = _fetch_image(data, normalize_img)
+    return img / img.max()
+
+
+def _graph_lines(data, lines):
+    return list(data['adjacencies'].get_edge_lines()) if lines is None else list(lines)
+
+
+def render_adjacencies_host(data, normalize_img=True, edge_thickness=3, endpoint_radius=5, endpoint_edge_thickness=2, edge_color=(1, 0, 0),
+                            endpoint_color=(1, 0, 0), endpoint_edge_color=(0, 0, 0), override_img=None, lines=None):
+    """Host definition of :func:`render_adjacencies` (render.py:47-99).  The painting order is part of it: every seed's rim, the lines
+    in list order (a later line over an earlier one), every seed's disk."""
+    img = _graph_base(data, normalize_img, override_img)
+    if img.ndim == 2:
+        img = np.dstack([img] * 3)
+    shape = img.shape[:2]
+    for endpoint in data['seeds']:
+        mask = disk_pixels_host(endpoint, endpoint_radius + endpoint_edge_thickness, shape)
+        for i in range(3):
+            img[:, :, i][mask] = endpoint_edge_color[i]
+    for line in _graph_lines(data, lines):
+        buf = draw_line_host(line[0], line[1], edge_thickness, shape)
+        mask = buf > 0
+        for i in range(3):
+            img[:, :, i][mask] = buf[mask] * edge_color[i]
+    for endpoint in data['seeds']:
+        mask = disk_pixels_host(endpoint, endpoint_radius, shape)
+        for i in range(3):
+            img[:, :, i][mask] = endpoint_color[i]
+    return (255 * img).clip(0, 255).astype('uint8')
+
+
+def _d2_limit(threshold):
+    """The largest integer d2 with ``sqrt(d2) < threshold``, the test of the definition on the squared distances (integers) that the
+    distance transform takes the root of; -1 if there is none."""
+    d2 = np.arange((math.ceil(threshold) + 1) ** 2, dtype=np.float64)
+    ok = np.nonzero(np.sqrt(d2) < threshold)[0]
+    return int(ok.max()) if len(ok) else -1
+
+
+def _line_args(thickness, color):
+    """(reach, core_d2, ring_d2, core colour, ring colour) of the graph kernel for a line thickness (render.py:22-44, :91-94)."""
+    if not thickness >= 1:
+        raise ValueError('edge_thickness >= 1 required')
+    if not thickness <= 33:
+        raise NotImplementedError(f'edge_thickness = {thickness!r}: the GPU adjacency graphs take line thicknesses up to 33, see DESIGN.md "Limits"')
+    threshold = (thickness + 1) / 2
+    if np.allclose(threshold, round(threshold)):
+        core = ring = _d2_limit(threshold)
+        values = np.array([1., 1.])
+    else:
+        thickness1 = 2 * int((thickness + 1) // 2) - 1
+        thickness2 = thickness1 + 2
+        core, ring = _d2_limit((thickness1 + 1) / 2), _d2_limit((thickness2 + 1) / 2)
+        values = (np.array([1., 1.]) * (thickness - thickness1) / (thickness2 - thickness1) + np.array([1., 0.])).clip(0, 1)
+    return math.isqrt(ring), core, ring, [values[0] * c for c in color], [values[1] * c for c in color]
+
+
+def _graph_points(points, shape, what, image):
+    """``points`` (n x 2, or n x 2 x 2 for lines) as int32 after the checks the kernels do not make: integers inside the image."""
+    a = np.asarray(points)
+    if a.size == 0:
+        return np.zeros((0,) + ((2,) if what == 'seeds' else (2, 2)), np.int32)
+    if a.dtype.kind not in 'iu' and not (a.dtype.kind == 'f' and (a == np.floor(a)).all()):
+        raise ValueError(f'image {image}: {what} must have integer coordinates')
+    a = a.astype(np.int64).reshape((-1, 2) if what == 'seeds' else (-1, 2, 2))
+    if (a < 0).any() or (a[..., 0] >= shape[0]).any() or (a[..., 1] >= shape[1]).any():
+        raise ValueError(f'image {image}: {what} outside the image')
+    if len(a) > 65535:
+        raise ValueError(f'image {image}: {len(a)} {what}: at most 65535 per image')
+    return a.astype(np.int32)
+
+
+def render_adjacencies_many(datas, normalize_img=True, edge_thickness=3, endpoint_radius=5, endpoint_edge_thickness=2, edge_color=(1, 0, 0),
+                            endpoint_color=(1, 0, 0), endpoint_edge_color=(0, 0, 0), override_imgs=None, lines=None):
+    """:func:`render_adjacencies` for a list of pipeline data objects (one launch per ``_capi.MAX_SET_IMAGES`` images);
+    ``override_imgs`` / ``lines``: one image / one list of lines (or None) per data object."""
+    from . import _capi
+    datas = list(datas)
+    over = list(override_imgs) if override_imgs is not None else [None] * len(datas)
+    lines = list(lines) if lines is not None else [None] * len(datas)
+    rim, disk = endpoint_radius + endpoint_edge_thickness, endpoint_radius
+    for v, what in ((rim, 'endpoint_radius + endpoint_edge_thickness'), (disk, 'endpoint_radius')):
+        if not v >= 0:
+            raise ValueError(f'{what} = {v!r}: a radius >= 0')
+        if v > _capi.RENDER_MAX_SEED_RADIUS:
+            raise NotImplementedError(f'{what} = {v!r}: the GPU adjacency graphs take end points up to radius {_capi.RENDER_MAX_SEED_RADIUS} with their rim, see DESIGN.md "Limits"')
+    reach, core_d2, ring_d2, core_color, ring_color = _line_args(edge_thickness, edge_color)
+    colors = list(endpoint_edge_color) + list(endpoint_color) + core_color + ring_color
+    bases, prims = [], []
+    for k, (d, o, l) in enumerate(zip(datas, over, lines)):
+        base = _graph_base(d, normalize_img, o)
+        if base.dtype != np.float64:
+            raise NotImplementedError(f'image {k}: the image under the graph is {base.dtype} after its preparation; the GPU form paints float64 images, see DESIGN.md "Limits"')
+        seeds = _graph_points(d['seeds'], base.shape[:2], 'seeds', k)
+        ends = _graph_points(_graph_lines(d, l), base.shape[:2], 'lines', k)
+        p = np.zeros((len(seeds) + len(ends), 8), np.int32)
+        p[:len(seeds), 1], p[:len(seeds), 3:5] = np.arange(len(seeds)), seeds
+        p[len(seeds):, 0], p[len(seeds):, 1], p[len(seeds):, 3:7] = 1, np.arange(len(ends)), ends.reshape(-1, 4)
+        bases.append(base)
+        prims.append(p)
+    out = []
+    for part in _in_sets(len(datas)):
+        for j, p in enumerate(prims[part]):
+            p[:, 2] = j
+        out += _PixelSet([b.shape[:2] for b in bases[part]]).graph(np.concatenate(prims[part]), bases[part], rim, disk, reach, core_d2, ring_d2, colors)
+    return out
+
+
+def render_adjacencies(data, normalize_img=True, edge_thickness=3, endpoint_radius=5, endpoint_edge_thickness=2, edge_color=(1, 0, 0),
+                       endpoint_color=(1, 0, 0), endpoint_edge_color=(0, 0, 0), override_img=None, lines=None):
+    """The adjacency graph over the image (render.py:47-99), on the GPU.  ``lines``: the edges as ``((r, c), (r, c))`` pairs in painting
+    order; None takes ``data['adjacencies'].get_edge_lines()`` as it comes."""
+    return render_adjacencies_many([data], normalize_img, edge_thickness, endpoint_radius, endpoint_edge_thickness, edge_color, endpoint_color, endpoint_edge_color,
+                                   [override_img], [lines])[0]
+
+
+# ---- the pictures of the reference's export tool (export.py:97-126) ----------------------------------------------------------------
+EXPORT_DEFAULT_BORDER = {'seg': 8, 'fgc': 2, 'adj': 2, 'atm': 6}
+
+
+def _export_ymap_inputs(y, ymap):
+    """export.py:101-103: ``y`` clipped and squashed by a logistic curve, with the matching colour limits and the colour map's name."""
+    lo, hi, gain, name = (tf(v) for v, tf in zip(ymap.lstrip('/').split(':'), (float, float, float, str)))
+    squash = lambda v: np.exp(gain * v) / (1 + np.exp(gain * v)) - 0.5
+    return squash(y.clip(lo, hi)), squash(np.array((lo, hi))), name
+
+
+def export_views(datas, mode='seg', border=None, border_position='center', enhance=False, ymap='-0.8:+1:5:seismic', host=False):
+    """The pictures that the reference's ``export`` tool writes for ``mode`` in 'seg', 'fgc', 'adj', 'atm' (export.py:116-126), one per
+    pipeline data object, composed of the functions above on the GPU (``host=True``: of their ``*_host`` definitions, the same bytes).
+    ``border``, ``border_position``, ``enhance`` and ``ymap`` are that tool's options; it reads and writes no file."""
+    if mode not in EXPORT_DEFAULT_BORDER:
+        raise ValueError(f'Unknown mode: "{mode}"')
+    datas = list(datas)
+    width = EXPORT_DEFAULT_BORDER[mode] if border is None else border
+    each = lambda fn, **kw: [fn(d, **{k: (v[i] if k == 'override_img' else v) for k, v in kw.items()}) for i, d in enumerate(datas)]
+    if mode == 'seg':
+        kw = dict(border_width=width, border_position=border_position, normalize_img=enhance)
+        return each(render_result_over_image_host, **kw) if host else render_result_over_image_many(datas, **kw)
+    if mode == 'atm':
+        kw = dict(border_color=(0, 1, 0), border_radius=width // 2, normalize_img=enhance)
+        return each(render_atoms_host, **kw) if host else render_atoms_many(datas, **kw)
+    ymaps = []
+    spec = [_export_ymap_inputs(d['y'], ymap) for d in datas]
+    if host:
+        ymaps = [render_ymap_host(v, clim=c, cmap=name) for v, c, name in spec]
+    else:
+        for v, c, name in spec:                                          # (one colour limit per call; the tool's is the same for all)
+            ymaps.append(render_ymap(v, clim=c, cmap=name))
+    kw = dict(border_color=(0, 0, 0), border_radius=width // 2)
+    if mode == 'fgc':
+        return each(render_foreground_clusters_host, override_img=ymaps, **kw) if host else render_foreground_clusters_many(datas, override_imgs=ymaps, **kw)
+    atoms = each(render_atoms_host, override_img=ymaps, **kw) if host else render_atoms_many(datas, override_imgs=ymaps, **kw)
+    kw = dict(edge_color=(0, 1, 0), endpoint_color=(0, 1, 0))
+    return each(render_adjacencies_host, override_img=atoms, **kw) if host else render_adjacencies_many(datas, override_imgs=atoms, **kw)
 
 
 # ---- regression metric (tests/regression/validate.py) -----------------------------------------------------------------
