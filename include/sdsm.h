@@ -285,7 +285,7 @@ int sdsm_watershed(const double *image, const int32_t *markers, const uint8_t *m
  * in that buffer's element type).  Pixel indices stay local to their image, so only each image is bound by the single-image limits and
  * the set may hold more than 2^31 pixels.  The images must not overlap in an output buffer.  The table is read on the host; it
  * reaches the device with the launches, so the caller may free it when the call returns.  Per image, the results are byte-equal to
- * the single-image entry point.  The workspace sizes grow with the set (adding an image never shrinks them); 0 = bad table. */
+ * the single-image entry point, which is the set of one image {0, H, W}.  The workspace sizes grow with the set (adding an image never shrinks them); 0 = bad table. */
 #define SDSM_MAX_SET_IMAGES 32
 typedef struct {
     int64_t offset;         /* first element of the image in the packed buffers, >= 0 */

@@ -28,6 +28,7 @@ import scipy.ndimage as ndi
 from . import _capi, _morph
 from .atoms import AtomAdjacencyGraph
 from .image import Image
+from .imageset import SetLayout, in_sets
 from .objects import CvxprogError, Object
 from .output import get_output
 from .pipeline import Stage
@@ -385,16 +386,6 @@ def edt_exact_gpu(target):
     return out.cpu().numpy()
 
 
-def _set_layout(shapes):
-    """Packed layout of a set: the ``_capi.SetImage`` table and the total of elements (every image 256-element aligned)."""
-    table = (_capi.SetImage * len(shapes))()
-    total = 0
-    for k, (h, w) in enumerate(shapes):
-        table[k].offset, table[k].H, table[k].W = total, int(h), int(w)
-        total += (int(h) * int(w) + _CROP_ALIGN - 1) // _CROP_ALIGN * _CROP_ALIGN
-    return table, total
-
-
 def markers_and_edt_gpu_multi(ys, max_cluster_marker_irregularity):
     """:func:`cluster_markers_gpu` and then :func:`edt_exact_gpu` of the markers, for a set of images: one packed upload of all ``y``,
     ``sdsm_c2f_markers_multi`` and ``sdsm_edt_exact_multi`` over up to ``_capi.MAX_SET_IMAGES`` images per call, one download.
@@ -405,21 +396,17 @@ def markers_and_edt_gpu_multi(ys, max_cluster_marker_irregularity):
     ys = [np.asarray(y, np.float64) for y in ys]
     thrs = list(max_cluster_marker_irregularity) if np.ndim(max_cluster_marker_irregularity) else [max_cluster_marker_irregularity] * len(ys)
     results = []
-    for lo in range(0, len(ys), _capi.MAX_SET_IMAGES):
-        part = ys[lo:lo + _capi.MAX_SET_IMAGES]
-        table, total = _set_layout([y.shape for y in part])
-        y_all = np.zeros(total, np.float64)
-        for k, y in enumerate(part):
-            y_all[table[k].offset:table[k].offset + y.size] = y.ravel()
-        d_y = torch.from_numpy(y_all).cuda()
-        n = len(part)
+    for part in in_sets(len(ys)):
+        lay = SetLayout([y.shape for y in ys[part]], align=_CROP_ALIGN)
+        table, total, n = lay.table, lay.total, len(lay.shapes)
+        d_y = torch.from_numpy(lay.pack(ys[part], np.float64)).cuda()
         # one buffer for everything that comes back: distances (float64), markers (int32), y_mask (uint8), counts (int32)
         d_res = torch.empty(13 * total + 4 * n, dtype=torch.uint8, device=d_y.device)
         d_dist = d_res[:8 * total].view(torch.float64)
         d_markers = d_res[8 * total:12 * total].view(torch.int32)
         d_mask = d_res[12 * total:13 * total]
         d_count = d_res[13 * total:].view(torch.int32)
-        thr = (C.c_double * n)(*[float(t) for t in thrs[lo:lo + n]])
+        thr = (C.c_double * n)(*[float(t) for t in thrs[part]])
         m_bytes = L.sdsm_c2f_markers_workspace_bytes_multi(table, n)
         e_bytes = L.sdsm_edt_exact_workspace_bytes_multi(table, n)
         ws = torch.empty(max(m_bytes, e_bytes), dtype=torch.uint8, device=d_y.device)     # the EDT follows the markers on one stream
@@ -429,12 +416,9 @@ def markers_and_edt_gpu_multi(ys, max_cluster_marker_irregularity):
         d_target = (d_markers != 0).to(torch.uint8)
         _capi.check(L.sdsm_edt_exact_multi(table, n, p(d_target), p(d_dist), p(ws), e_bytes, _stream(torch)), 'sdsm_edt_exact_multi')
         res = d_res.cpu().numpy()
-        dist, markers = res[:8 * total].view(np.float64), res[8 * total:12 * total].view(np.int32)
-        mask, count = res[12 * total:13 * total], res[13 * total:].view(np.int32)
-        for k, y in enumerate(part):
-            o, sh = table[k].offset, y.shape
-            results.append((mask[o:o + y.size].reshape(sh).astype(bool), markers[o:o + y.size].reshape(sh).copy(), int(count[k]),
-                            dist[o:o + y.size].reshape(sh).copy()))
+        dist, markers = lay.unpack(res[:8 * total].view(np.float64)), lay.unpack(res[8 * total:12 * total].view(np.int32))
+        mask, count = lay.unpack(res[12 * total:13 * total]), res[13 * total:].view(np.int32)
+        results += [(mask[k].astype(bool), markers[k], int(count[k]), dist[k]) for k in range(n)]
     return results
 
 
@@ -444,20 +428,16 @@ def edt_exact_gpu_multi(targets):
     L = _capi.lib()
     targets = [np.asarray(t) != 0 for t in targets]
     out = []
-    for lo in range(0, len(targets), _capi.MAX_SET_IMAGES):
-        part = targets[lo:lo + _capi.MAX_SET_IMAGES]
-        table, total = _set_layout([t.shape for t in part])
-        t_all = np.zeros(total, np.uint8)
-        for k, t in enumerate(part):
-            t_all[table[k].offset:table[k].offset + t.size] = t.ravel()
-        d_t = torch.from_numpy(t_all).cuda()
-        d_out = torch.empty(total, dtype=torch.float64, device=d_t.device)
-        nbytes = L.sdsm_edt_exact_workspace_bytes_multi(table, len(part))
+    for part in in_sets(len(targets)):
+        lay = SetLayout([t.shape for t in targets[part]], align=_CROP_ALIGN)
+        table, n = lay.table, len(lay.shapes)
+        d_t = torch.from_numpy(lay.pack(targets[part], np.uint8)).cuda()
+        d_out = torch.empty(lay.total, dtype=torch.float64, device=d_t.device)
+        nbytes = L.sdsm_edt_exact_workspace_bytes_multi(table, n)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=d_t.device)
-        _capi.check(L.sdsm_edt_exact_multi(table, len(part), C.c_void_p(d_t.data_ptr()), C.c_void_p(d_out.data_ptr()), C.c_void_p(ws.data_ptr()),
+        _capi.check(L.sdsm_edt_exact_multi(table, n, C.c_void_p(d_t.data_ptr()), C.c_void_p(d_out.data_ptr()), C.c_void_p(ws.data_ptr()),
                                            nbytes, _stream(torch)), 'sdsm_edt_exact_multi')
-        res = d_out.cpu().numpy()
-        out += [res[table[k].offset:table[k].offset + t.size].reshape(t.shape).copy() for k, t in enumerate(part)]
+        out += lay.unpack(d_out.cpu().numpy())
     return out
 
 

@@ -748,29 +748,9 @@ extern "C" int64_t sdsm_unpack_fragments(const sdsm_record *records, const int32
     return pos;
 }
 
-// ---- post-processing, per-object work ----------------------------------------------------------------------------------------
-extern "C" hipError_t sdsm_launch_post(const double *g, const double *gs, const uint8_t *bg, int H, int W, int n, const int32_t *boxes,
-                                       const int64_t *bits_off, const uint32_t *bits, const int64_t *new_off, uint32_t *new_bits,
-                                       uint32_t *boundary_pool, const int64_t *bpool_off, double exterior_scale, double exterior_offset,
-                                       double contrast_epsilon, double inv_gstd, int max_distance, double stdamp, sdsm_post_record *out, hipStream_t stream);
+// ---- post-processing: the smoothed images (the per-object work, sdsm_post_objects, is with the image sets below) -------------------
 extern "C" hipError_t sdsm_gaussian_filter_impl(const double *d_in, int H, int W, double sigma, double *d_out, void *d_ws, hipStream_t stream);
 extern "C" size_t sdsm_gaussian_workspace_bytes(int H, int W, double sigma);
-
-extern "C" int sdsm_post_objects(const double *d_g, const double *d_gs, const uint8_t *d_bg, int H, int W, int n, const int32_t *d_boxes,
-                                 const int64_t *d_bits_off, const uint32_t *d_bits, const int64_t *d_new_off, uint32_t *d_new_bits,
-                                 uint32_t *d_boundary_pool, const int64_t *d_bpool_off, double exterior_scale, double exterior_offset,
-                                 double contrast_epsilon, double inv_gstd, int max_distance, double stdamp, sdsm_post_record *d_out, void *stream)
-{
-    if (n < 0 || H < 1 || W < 1 || H > 65535 || W > 65535) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_objects: bad shape");
-    if (n == 0) return SDSM_OK;
-    if (!d_g || !d_gs || !d_bg || !d_boxes || !d_bits_off || !d_bits || !d_out) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_objects: null argument");
-    if (!(exterior_scale > 0) || !(exterior_offset >= 0) || max_distance < 0 || max_distance > 16) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_objects: exterior_scale > 0, exterior_offset >= 0, 0 <= max_distance <= 16 required");
-    if (max_distance > 0 && stdamp > 0 && (!d_new_off || !d_new_bits)) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_objects: refinement needs the output mask buffers");
-    if ((d_boundary_pool == nullptr) != (d_bpool_off == nullptr)) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_objects: boundary pool and its offsets go together");
-    hipError_t e = sdsm_launch_post(d_g, d_gs, d_bg, H, W, n, d_boxes, d_bits_off, d_bits, d_new_off, d_new_bits, d_boundary_pool, d_bpool_off,
-                                    exterior_scale, exterior_offset, contrast_epsilon, inv_gstd, max_distance, stdamp, d_out, (hipStream_t)stream);
-    return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_post_objects");
-}
 
 extern "C" int sdsm_gaussian_filter(const double *d_in, int H, int W, double sigma, double *d_out, void *d_ws, size_t ws_bytes, void *stream)
 {
@@ -840,41 +820,7 @@ extern "C" int sdsm_doh_peaks(const double *d_cube, int H, int W, int n_scales, 
     return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_doh_peaks");
 }
 
-extern "C" size_t sdsm_c2f_markers_workspace_bytes_impl(int H, int W);
-extern "C" hipError_t sdsm_c2f_markers_impl(const double *d_y, int H, int W, double thr, uint8_t *d_y_mask, int32_t *d_markers,
-                                            int32_t *d_count, void *d_ws, hipStream_t stream);
-extern "C" size_t sdsm_edt_exact_workspace_bytes_impl(int H, int W);
-extern "C" hipError_t sdsm_edt_exact_impl(const uint8_t *d_target, int H, int W, double *d_out, void *d_ws, hipStream_t stream);
-
-extern "C" size_t sdsm_c2f_markers_workspace_bytes(int H, int W)
-{
-    return H < 1 || W < 1 ? 0 : sdsm_c2f_markers_workspace_bytes_impl(H, W);
-}
-
-extern "C" int sdsm_c2f_markers(const double *d_y, int H, int W, double max_irregularity, uint8_t *d_y_mask, int32_t *d_markers, int32_t *d_count,
-                                void *d_ws, size_t ws_bytes, void *stream)
-{
-    if (!d_y || !d_y_mask || !d_markers || !d_count || !d_ws || H < 1 || W < 1 || (int64_t)H * W >= INT_MAX)
-        return fail(SDSM_ERR_ARGUMENT, "sdsm_c2f_markers: bad argument");
-    if (ws_bytes < sdsm_c2f_markers_workspace_bytes(H, W)) return fail(SDSM_ERR_WORKSPACE, "sdsm_c2f_markers: workspace too small");
-    hipError_t e = sdsm_c2f_markers_impl(d_y, H, W, max_irregularity, d_y_mask, d_markers, d_count, d_ws, (hipStream_t)stream);
-    return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_c2f_markers");
-}
-
-extern "C" size_t sdsm_edt_exact_workspace_bytes(int H, int W)
-{
-    return H < 1 || W < 1 ? 0 : sdsm_edt_exact_workspace_bytes_impl(H, W);
-}
-
-extern "C" int sdsm_edt_exact(const uint8_t *d_target, int H, int W, double *d_out, void *d_ws, size_t ws_bytes, void *stream)
-{
-    if (!d_target || !d_out || !d_ws || H < 1 || W < 1 || H > 65535 || W > 65535) return fail(SDSM_ERR_ARGUMENT, "sdsm_edt_exact: bad argument");
-    if (ws_bytes < sdsm_edt_exact_workspace_bytes(H, W)) return fail(SDSM_ERR_WORKSPACE, "sdsm_edt_exact: workspace too small");
-    hipError_t e = sdsm_edt_exact_impl(d_target, H, W, d_out, d_ws, (hipStream_t)stream);
-    return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_edt_exact");
-}
-
-// ---- image sets ----------------------------------------------------------------------------------------------------------------
+// ---- image sets: C2F markers, exact EDT, per-object post-processing (a single image is the set of one) -------------------------------
 extern "C" size_t sdsm_c2f_markers_workspace_bytes_multi_impl(const sdsm_set_image *images, int n_images);
 extern "C" hipError_t sdsm_c2f_markers_multi_impl(const sdsm_set_image *images, int n_images, const double *d_y, const double *thr,
                                                   uint8_t *d_y_mask, int32_t *d_markers, int32_t *d_count, void *d_ws, hipStream_t stream);
@@ -886,47 +832,82 @@ extern "C" hipError_t sdsm_launch_post_set(const sdsm_post_image *images, int n_
                                            const int64_t *bpool_off, double exterior_scale, double exterior_offset, double contrast_epsilon,
                                            int max_distance, double stdamp, sdsm_post_record *out, hipStream_t stream);
 
-// a set table every image of which the single-image entry point takes: 1 .. SDSM_MAX_SET_IMAGES images, offsets >= 0, H, W >= 1, and
-// H * W < 2^31 (markers) or H, W <= 65535 (EDT)
-static bool set_table_ok(const sdsm_set_image *images, int n_images, bool edt)
+// The table of a set: 1 .. SDSM_MAX_SET_IMAGES images, offsets >= 0, H, W >= 1, and the limits of the kernels that take it.
+enum { SET_PIXELS = 1,      // H * W < 2^31: pixel indices are int32
+       SET_SIDES = 2 };     // H, W <= 65535: coordinates packed into 16 bits, squared distances in int64
+static int64_t set_offset(const sdsm_set_image &im) { return im.offset; }
+static int64_t set_offset(const sdsm_post_image &) { return 0; }      // (its images are not packed: device pointers)
+template <class Image> static bool set_table_ok(const Image *images, int n_images, int limits)
 {
     if (!images || n_images < 1 || n_images > SDSM_MAX_SET_IMAGES) return false;
     for (int i = 0; i < n_images; i++) {
-        const sdsm_set_image &im = images[i];
-        if (im.offset < 0 || im.H < 1 || im.W < 1) return false;
-        if (edt ? (im.H > 65535 || im.W > 65535) : (int64_t)im.H * im.W >= INT_MAX) return false;
+        const Image &im = images[i];
+        if (set_offset(im) < 0 || im.H < 1 || im.W < 1) return false;
+        if ((limits & SET_PIXELS) && (int64_t)im.H * im.W >= INT_MAX) return false;
+        if ((limits & SET_SIDES) && (im.H > 65535 || im.W > 65535)) return false;
     }
     return true;
 }
+#define SET_TABLE(name, limits) \
+    if (!set_table_ok(images, n_images, limits)) \
+        return fail(SDSM_ERR_ARGUMENT, std::string(name ": bad image table (1 .. 32 images, offset >= 0, 1 <= H, W") + \
+                                       ((limits) & SET_SIDES ? " <= 65535" : "") + ((limits) & SET_PIXELS ? ", H * W < 2^31)" : ")"))
+#define SET_DONE(name) return e == hipSuccess ? SDSM_OK : hipfail(e, name)
 
 extern "C" size_t sdsm_c2f_markers_workspace_bytes_multi(const sdsm_set_image *images, int n_images)
 {
-    return set_table_ok(images, n_images, false) ? sdsm_c2f_markers_workspace_bytes_multi_impl(images, n_images) : 0;
+    return set_table_ok(images, n_images, SET_PIXELS) ? sdsm_c2f_markers_workspace_bytes_multi_impl(images, n_images) : 0;
 }
 
 extern "C" int sdsm_c2f_markers_multi(const sdsm_set_image *images, int n_images, const double *d_y, const double *max_irregularity,
                                       uint8_t *d_y_mask, int32_t *d_markers, int32_t *d_count, void *d_ws, size_t ws_bytes, void *stream)
 {
-    if (!set_table_ok(images, n_images, false)) return fail(SDSM_ERR_ARGUMENT, "sdsm_c2f_markers_multi: bad image table (1 .. 32 images, offset >= 0, 1 <= H, W, H * W < 2^31)");
+    SET_TABLE("sdsm_c2f_markers_multi", SET_PIXELS);
     if (!d_y || !max_irregularity || !d_y_mask || !d_markers || !d_count || !d_ws) return fail(SDSM_ERR_ARGUMENT, "sdsm_c2f_markers_multi: null argument");
-    if (ws_bytes < sdsm_c2f_markers_workspace_bytes_multi(images, n_images)) return fail(SDSM_ERR_WORKSPACE, "sdsm_c2f_markers_multi: workspace too small");
+    if (ws_bytes < sdsm_c2f_markers_workspace_bytes_multi_impl(images, n_images)) return fail(SDSM_ERR_WORKSPACE, "sdsm_c2f_markers_multi: workspace too small");
     hipError_t e = sdsm_c2f_markers_multi_impl(images, n_images, d_y, max_irregularity, d_y_mask, d_markers, d_count, d_ws, (hipStream_t)stream);
-    return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_c2f_markers_multi");
+    SET_DONE("sdsm_c2f_markers_multi");
+}
+
+// (the single-image queries answer for every H, W >= 1, also where the call itself refuses the shape)
+extern "C" size_t sdsm_c2f_markers_workspace_bytes(int H, int W)
+{
+    const sdsm_set_image one = {0, H, W};
+    return H < 1 || W < 1 ? 0 : sdsm_c2f_markers_workspace_bytes_multi_impl(&one, 1);
+}
+
+extern "C" int sdsm_c2f_markers(const double *d_y, int H, int W, double max_irregularity, uint8_t *d_y_mask, int32_t *d_markers, int32_t *d_count,
+                                void *d_ws, size_t ws_bytes, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_c2f_markers_multi(&one, 1, d_y, &max_irregularity, d_y_mask, d_markers, d_count, d_ws, ws_bytes, stream);
 }
 
 extern "C" size_t sdsm_edt_exact_workspace_bytes_multi(const sdsm_set_image *images, int n_images)
 {
-    return set_table_ok(images, n_images, true) ? sdsm_edt_exact_workspace_bytes_multi_impl(images, n_images) : 0;
+    return set_table_ok(images, n_images, SET_SIDES) ? sdsm_edt_exact_workspace_bytes_multi_impl(images, n_images) : 0;
 }
 
 extern "C" int sdsm_edt_exact_multi(const sdsm_set_image *images, int n_images, const uint8_t *d_target, double *d_out, void *d_ws, size_t ws_bytes,
                                     void *stream)
 {
-    if (!set_table_ok(images, n_images, true)) return fail(SDSM_ERR_ARGUMENT, "sdsm_edt_exact_multi: bad image table (1 .. 32 images, offset >= 0, 1 <= H, W <= 65535)");
+    SET_TABLE("sdsm_edt_exact_multi", SET_SIDES);
     if (!d_target || !d_out || !d_ws) return fail(SDSM_ERR_ARGUMENT, "sdsm_edt_exact_multi: null argument");
-    if (ws_bytes < sdsm_edt_exact_workspace_bytes_multi(images, n_images)) return fail(SDSM_ERR_WORKSPACE, "sdsm_edt_exact_multi: workspace too small");
+    if (ws_bytes < sdsm_edt_exact_workspace_bytes_multi_impl(images, n_images)) return fail(SDSM_ERR_WORKSPACE, "sdsm_edt_exact_multi: workspace too small");
     hipError_t e = sdsm_edt_exact_multi_impl(images, n_images, d_target, d_out, d_ws, (hipStream_t)stream);
-    return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_edt_exact_multi");
+    SET_DONE("sdsm_edt_exact_multi");
+}
+
+extern "C" size_t sdsm_edt_exact_workspace_bytes(int H, int W)
+{
+    const sdsm_set_image one = {0, H, W};
+    return H < 1 || W < 1 ? 0 : sdsm_edt_exact_workspace_bytes_multi_impl(&one, 1);
+}
+
+extern "C" int sdsm_edt_exact(const uint8_t *d_target, int H, int W, double *d_out, void *d_ws, size_t ws_bytes, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_edt_exact_multi(&one, 1, d_target, d_out, d_ws, ws_bytes, stream);
 }
 
 extern "C" int sdsm_post_objects_multi(const sdsm_post_image *images, int n_images, const int32_t *d_boxes, const int64_t *d_bits_off,
@@ -934,11 +915,11 @@ extern "C" int sdsm_post_objects_multi(const sdsm_post_image *images, int n_imag
                                        const int64_t *d_bpool_off, double exterior_scale, double exterior_offset, double contrast_epsilon,
                                        int max_distance, double stdamp, sdsm_post_record *d_out, void *stream)
 {
-    if (!images || n_images < 1 || n_images > SDSM_MAX_SET_IMAGES) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_objects_multi: 1 .. 32 images per call");
+    SET_TABLE("sdsm_post_objects_multi", SET_SIDES);
     int64_t n = 0;
     for (int j = 0; j < n_images; j++) {
         const sdsm_post_image &im = images[j];
-        if (im.n_objects < 0 || im.H < 1 || im.W < 1 || im.H > 65535 || im.W > 65535) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_objects_multi: bad image (shape or object count)");
+        if (im.n_objects < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_objects_multi: negative object count");
         if (im.n_objects > 0 && (!im.d_g || !im.d_gs || !im.d_bg)) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_objects_multi: null image input");
         n += im.n_objects;
     }
@@ -950,7 +931,17 @@ extern "C" int sdsm_post_objects_multi(const sdsm_post_image *images, int n_imag
     if ((d_boundary_pool == nullptr) != (d_bpool_off == nullptr)) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_objects_multi: boundary pool and its offsets go together");
     hipError_t e = sdsm_launch_post_set(images, n_images, d_boxes, d_bits_off, d_bits, d_new_off, d_new_bits, d_boundary_pool, d_bpool_off,
                                         exterior_scale, exterior_offset, contrast_epsilon, max_distance, stdamp, d_out, (hipStream_t)stream);
-    return e == hipSuccess ? SDSM_OK : hipfail(e, "sdsm_post_objects_multi");
+    SET_DONE("sdsm_post_objects_multi");
+}
+
+extern "C" int sdsm_post_objects(const double *d_g, const double *d_gs, const uint8_t *d_bg, int H, int W, int n, const int32_t *d_boxes,
+                                 const int64_t *d_bits_off, const uint32_t *d_bits, const int64_t *d_new_off, uint32_t *d_new_bits,
+                                 uint32_t *d_boundary_pool, const int64_t *d_bpool_off, double exterior_scale, double exterior_offset,
+                                 double contrast_epsilon, double inv_gstd, int max_distance, double stdamp, sdsm_post_record *d_out, void *stream)
+{
+    const sdsm_post_image one = {d_g, d_gs, d_bg, H, W, inv_gstd, n, 0};
+    return sdsm_post_objects_multi(&one, 1, d_boxes, d_bits_off, d_bits, d_new_off, d_new_bits, d_boundary_pool, d_bpool_off, exterior_scale,
+                                   exterior_offset, contrast_epsilon, max_distance, stdamp, d_out, stream);
 }
 
 // ---- label maps and overlays (sdsm_render.hip) -----------------------------------------------------------------------------------
@@ -976,22 +967,11 @@ extern "C" hipError_t sdsm_render_overlay_impl(const sdsm_set_image *images, int
                                                int kind, int radius, const double *color, const double *bg, int has_bg, int background_label,
                                                uint8_t *out, hipStream_t stream);
 
-// the table of a render call: as the EDT takes it, and every image below 2^31 pixels (pixel indices are int32)
-static bool render_table_ok(const sdsm_set_image *images, int n_images)
-{
-    if (!set_table_ok(images, n_images, true)) return false;
-    for (int i = 0; i < n_images; i++) if ((int64_t)images[i].H * images[i].W >= INT_MAX) return false;
-    return true;
-}
-#define RENDER_TABLE(name) \
-    if (!render_table_ok(images, n_images)) return fail(SDSM_ERR_ARGUMENT, name ": bad image table (1 .. 32 images, offset >= 0, 1 <= H, W <= 65535, H * W < 2^31)")
-#define RENDER_DONE(name) return e == hipSuccess ? SDSM_OK : hipfail(e, name)
-
 extern "C" int sdsm_render_morph_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
                                        const int64_t *d_bits_off, const uint32_t *d_bits, int radius, const int64_t *d_new_off, uint32_t *d_new_bits,
                                        int32_t *d_area, void *stream)
 {
-    RENDER_TABLE("sdsm_render_morph");
+    SET_TABLE("sdsm_render_morph", SET_SIDES | SET_PIXELS);
     if (radius == 0 || radius > SDSM_RENDER_MAX_RADIUS || radius < -SDSM_RENDER_MAX_RADIUS)
         return fail(SDSM_ERR_ARGUMENT, "sdsm_render_morph: 1 <= |radius| <= 16 required");
     if (n < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_morph: n < 0");
@@ -999,7 +979,7 @@ extern "C" int sdsm_render_morph_multi(const sdsm_set_image *images, int n_image
     if (!d_boxes || !d_bits_off || !d_bits || !d_new_off || !d_new_bits || !d_area || (n_images > 1 && !d_obj_image))
         return fail(SDSM_ERR_ARGUMENT, "sdsm_render_morph: null argument");
     hipError_t e = sdsm_render_morph_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, radius, d_new_off, d_new_bits, d_area, (hipStream_t)stream);
-    RENDER_DONE("sdsm_render_morph");
+    SET_DONE("sdsm_render_morph");
 }
 
 extern "C" int sdsm_render_morph(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, int radius,
@@ -1016,19 +996,19 @@ extern "C" int sdsm_render_overlaps(int n_pairs, const int32_t *d_pairs, const i
     if (n_pairs == 0) return SDSM_OK;
     if (!d_pairs || !d_boxes || !d_bits_off || !d_bits || !d_inter) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_overlaps: null argument");
     hipError_t e = sdsm_render_overlaps_impl(n_pairs, d_pairs, d_boxes, d_bits_off, d_bits, d_inter, (hipStream_t)stream);
-    RENDER_DONE("sdsm_render_overlaps");
+    SET_DONE("sdsm_render_overlaps");
 }
 
 extern "C" int sdsm_render_paint_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
                                        const int64_t *d_bits_off, const uint32_t *d_bits, const int32_t *d_obj_label, int32_t *d_label,
                                        uint8_t *d_cover, uint8_t *d_target, void *stream)
 {
-    RENDER_TABLE("sdsm_render_paint");
+    SET_TABLE("sdsm_render_paint", SET_SIDES | SET_PIXELS);
     if (n < 0 || !d_label || !d_cover || !d_target) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_paint: bad argument");
     if (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_obj_label || (n_images > 1 && !d_obj_image)))
         return fail(SDSM_ERR_ARGUMENT, "sdsm_render_paint: null argument");
     hipError_t e = sdsm_render_paint_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_obj_label, d_label, d_cover, d_target, (hipStream_t)stream);
-    RENDER_DONE("sdsm_render_paint");
+    SET_DONE("sdsm_render_paint");
 }
 
 extern "C" int sdsm_render_paint(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits,
@@ -1041,11 +1021,11 @@ extern "C" int sdsm_render_paint(int H, int W, int n, const int32_t *d_boxes, co
 extern "C" int sdsm_render_compact_multi(const sdsm_set_image *images, int n_images, const int32_t *d_label, const uint8_t *d_cover, const double *d_dist,
                                          const int64_t *capacity, sdsm_render_entry *d_entries, int32_t *d_counts, void *stream)
 {
-    RENDER_TABLE("sdsm_render_compact");
+    SET_TABLE("sdsm_render_compact", SET_SIDES | SET_PIXELS);
     if (!d_label || !d_cover || !d_dist || !capacity || !d_entries || !d_counts) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_compact: null argument");
     for (int i = 0; i < n_images; i++) if (capacity[i] < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_compact: negative capacity");
     hipError_t e = sdsm_render_compact_impl(images, n_images, d_label, d_cover, d_dist, capacity, d_entries, d_counts, (hipStream_t)stream);
-    RENDER_DONE("sdsm_render_compact");
+    SET_DONE("sdsm_render_compact");
 }
 
 extern "C" int sdsm_render_compact(int H, int W, const int32_t *d_label, const uint8_t *d_cover, const double *d_dist, int64_t capacity,
@@ -1061,18 +1041,18 @@ extern "C" int sdsm_render_scatter(int64_t n, const int64_t *d_pix, const int32_
     if (n == 0) return SDSM_OK;
     if (!d_pix || !d_lab || !d_label) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_scatter: null argument");
     hipError_t e = sdsm_render_scatter_impl(n, d_pix, d_lab, d_label, (hipStream_t)stream);
-    RENDER_DONE("sdsm_render_scatter");
+    SET_DONE("sdsm_render_scatter");
 }
 
 extern "C" int sdsm_render_lost_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
                                       const int64_t *d_bits_off, const uint32_t *d_bits, const int32_t *d_obj_label, int n_labels, int32_t *d_label,
                                       int32_t *d_lost, int32_t *d_max, void *stream)
 {
-    RENDER_TABLE("sdsm_render_lost");
+    SET_TABLE("sdsm_render_lost", SET_SIDES | SET_PIXELS);
     if (n < 1 || n_labels < 1 || !d_boxes || !d_bits_off || !d_bits || !d_obj_label || !d_label || !d_lost || !d_max || (n_images > 1 && !d_obj_image))
         return fail(SDSM_ERR_ARGUMENT, "sdsm_render_lost: bad argument");
     hipError_t e = sdsm_render_lost_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_obj_label, d_label, d_lost, n_labels, d_max, (hipStream_t)stream);
-    RENDER_DONE("sdsm_render_lost");
+    SET_DONE("sdsm_render_lost");
 }
 
 extern "C" int sdsm_render_lost(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, const int32_t *d_obj_label,
@@ -1086,11 +1066,11 @@ extern "C" int sdsm_render_fill_multi(const sdsm_set_image *images, int n_images
                                       const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, const int32_t *d_obj_label,
                                       int new_label, int32_t *d_label, int32_t *d_filled, void *stream)
 {
-    RENDER_TABLE("sdsm_render_fill");
+    SET_TABLE("sdsm_render_fill", SET_SIDES | SET_PIXELS);
     if (n_sel < 1 || new_label < 1 || new_label > 65535 || !d_sel || !d_boxes || !d_bits_off || !d_bits || !d_obj_label || !d_label || !d_filled || (n_images > 1 && !d_obj_image))
         return fail(SDSM_ERR_ARGUMENT, "sdsm_render_fill: bad argument (1 <= new_label <= 65535)");
     hipError_t e = sdsm_render_fill_impl(images, n_images, n_sel, d_sel, d_obj_image, d_boxes, d_bits_off, d_bits, d_obj_label, new_label, d_label, d_filled, (hipStream_t)stream);
-    RENDER_DONE("sdsm_render_fill");
+    SET_DONE("sdsm_render_fill");
 }
 
 extern "C" int sdsm_render_fill(int H, int W, int n_sel, const int32_t *d_sel, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits,
@@ -1105,20 +1085,20 @@ extern "C" int sdsm_render_finish(int64_t n, const int32_t *d_label, int backgro
     if (n < 1 || n >= ((int64_t)INT_MAX - 1) * 256 || !d_label || !d_out || background_label > 0 || background_label < -65535)
         return fail(SDSM_ERR_ARGUMENT, "sdsm_render_finish: bad argument (-65535 <= background_label <= 0)");
     hipError_t e = sdsm_render_finish_impl(n, d_label, (uint16_t)background_label, d_out, (hipStream_t)stream);
-    RENDER_DONE("sdsm_render_finish");
+    SET_DONE("sdsm_render_finish");
 }
 
 extern "C" int sdsm_render_overlay_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const double *d_base, int channels,
                                          int kind, int radius, const double *color, const double *bg, int background_label, uint8_t *d_out, void *stream)
 {
-    RENDER_TABLE("sdsm_render_overlay");
+    SET_TABLE("sdsm_render_overlay", SET_SIDES | SET_PIXELS);
     if (radius < 0 || radius > SDSM_RENDER_MAX_RADIUS) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_overlay: 0 <= radius <= 16 required");
     if (kind < 0 || kind > 3 || !d_labels || !d_out || (kind != 3 && ((channels != 1 && channels != 3) || !color || !d_base)))
         return fail(SDSM_ERR_ARGUMENT, "sdsm_render_overlay: bad argument (kind 0 .. 3, channels 1 or 3)");
     static const double no_color[3] = {0, 0, 0};
     if (!color) color = no_color;
     hipError_t e = sdsm_render_overlay_impl(images, n_images, d_labels, d_base, channels, kind, radius, color, bg, bg != nullptr, background_label, d_out, (hipStream_t)stream);
-    RENDER_DONE("sdsm_render_overlay");
+    SET_DONE("sdsm_render_overlay");
 }
 
 extern "C" int sdsm_render_overlay(int H, int W, const int32_t *d_labels, const double *d_base, int channels, int kind, int radius, const double *color,
@@ -1151,11 +1131,11 @@ static bool perm_tables_ok(int n_images, const int32_t *d_perm, const int64_t *p
 extern "C" int sdsm_render_label_range_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int32_t *d_perm,
                                              const int64_t *perm_off, const int32_t *perm_min, int32_t *d_range, int32_t *d_permuted, void *stream)
 {
-    RENDER_TABLE("sdsm_render_label_range");
+    SET_TABLE("sdsm_render_label_range", SET_SIDES | SET_PIXELS);
     if (!d_labels || (!d_range && !d_permuted)) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_label_range: null argument");
     if (!perm_tables_ok(n_images, d_perm, perm_off, perm_min)) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_label_range: bad permutation tables");
     hipError_t e = sdsm_render_label_range_impl(images, n_images, d_labels, d_perm, perm_off, perm_min, d_range, d_permuted, (hipStream_t)stream);
-    RENDER_DONE("sdsm_render_label_range");
+    SET_DONE("sdsm_render_label_range");
 }
 
 extern "C" int sdsm_render_label_range(int H, int W, const int32_t *d_labels, const int32_t *d_perm, int64_t perm_n, int perm_min, int32_t *d_range,
@@ -1170,14 +1150,14 @@ extern "C" int sdsm_render_colormap_multi(const sdsm_set_image *images, int n_im
                                           const double *clim, const int32_t *d_perm, const int64_t *perm_off, const int32_t *perm_min,
                                           const int32_t *d_range, const double *bg_color, int bg_label, int32_t *d_flags, double *d_out, void *stream)
 {
-    RENDER_TABLE("sdsm_render_colormap");
+    SET_TABLE("sdsm_render_colormap", SET_SIDES | SET_PIXELS);
     if (N < 1 || N > SDSM_RENDER_MAX_COLORS) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_colormap: 1 <= N <= 1024 colours required");
     if ((source != 0 && source != 1) || !d_src || !d_lut || !d_out || (source == 0 && (!clim || !d_flags)) || (source == 1 && !d_range))
         return fail(SDSM_ERR_ARGUMENT, "sdsm_render_colormap: bad argument (source 0 needs clim and d_flags, source 1 d_range)");
     if (source == 1 && !perm_tables_ok(n_images, d_perm, perm_off, perm_min)) return fail(SDSM_ERR_ARGUMENT, "sdsm_render_colormap: bad permutation tables");
     hipError_t e = sdsm_render_colormap_impl(images, n_images, source, d_src, d_lut, N, clim, source == 1 ? d_perm : nullptr, perm_off, perm_min, d_range,
                                              bg_color != nullptr, bg_label, bg_color, d_flags, d_out, (hipStream_t)stream);
-    RENDER_DONE("sdsm_render_colormap");
+    SET_DONE("sdsm_render_colormap");
 }
 
 extern "C" int sdsm_render_colormap(int H, int W, int source, const void *d_src, const double *d_lut, int N, const double *clim, const int32_t *d_perm,
@@ -1193,7 +1173,7 @@ extern "C" int sdsm_render_graph_multi(const sdsm_set_image *images, int n_image
                                        double disk_radius, int line_reach, int core_d2, int ring_d2, const double *colors, const double *d_base,
                                        int channels, int32_t *d_key, uint8_t *d_out, void *stream)
 {
-    RENDER_TABLE("sdsm_render_graph");
+    SET_TABLE("sdsm_render_graph", SET_SIDES | SET_PIXELS);
     if (!(rim_radius >= 0) || !(disk_radius >= 0) || rim_radius > SDSM_RENDER_MAX_SEED_RADIUS || disk_radius > SDSM_RENDER_MAX_SEED_RADIUS)
         return fail(SDSM_ERR_ARGUMENT, "sdsm_render_graph: 0 <= radius <= 64 required for the disks and their rims");
     if (line_reach < 0 || line_reach > SDSM_RENDER_MAX_RADIUS || core_d2 < -1 || ring_d2 < core_d2 || (int64_t)ring_d2 >= (int64_t)(line_reach + 1) * (line_reach + 1))
@@ -1203,7 +1183,7 @@ extern "C" int sdsm_render_graph_multi(const sdsm_set_image *images, int n_image
     const double reach = rim_radius > disk_radius ? rim_radius : disk_radius;
     hipError_t e = sdsm_render_graph_impl(images, n_images, n_prims, d_prims, rim_radius, disk_radius, (int)ceil(reach), line_reach, core_d2, ring_d2, colors,
                                           d_base, channels, d_key, d_out, (hipStream_t)stream);
-    RENDER_DONE("sdsm_render_graph");
+    SET_DONE("sdsm_render_graph");
 }
 
 extern "C" int sdsm_render_graph(int H, int W, int n_prims, const int32_t *d_prims, double rim_radius, double disk_radius, int line_reach, int core_d2,

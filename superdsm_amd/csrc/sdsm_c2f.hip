@@ -8,13 +8,14 @@
 // if it lost a race, so parents only decrease and the root of a component is its minimum raster index whatever order the races
 // resolve in.  Labels are the ranks of the roots in raster order (a prefix scan), which is the numbering ndi.label gives.
 //
-// Image sets (the *_multi entry points): every phase is one launch for the whole set.  A workgroup (pixel blocks, scan chunks) or a
-// thread (EDT columns and rows) finds its image in the prefix table of the launch, by binary search; the per-pixel work is the same
-// __device__ code the single-image kernels run, on pointers offset to the image, with pixel indices local to it.
+// Every phase is one launch for a whole set of images (the *_multi entry points; a single image is the set of one, sdsm_api.hip).  A
+// workgroup (pixel blocks, scan chunks) or a thread (EDT columns and rows) finds its image in the prefix table of the launch, by binary
+// search, and runs the __device__ body of its phase on pointers offset to the image, with pixel indices local to it.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
 #include "../../include/sdsm.h"
+#include "sdsm_set.h"
 
 namespace {
 
@@ -59,22 +60,12 @@ __device__ __forceinline__ void markers_init(const double *y, int n, int p, int3
     if (threadIdx.x == 0 && c) atomicAdd(n_bg, c);
 }
 
-__global__ void k_markers_init(const double *y, int n, int32_t *parent, int32_t *area, int32_t *bd, int32_t *n_bg)
-{
-    markers_init(y, n, blockIdx.x * TPB + threadIdx.x, parent, area, bd, n_bg);
-}
-
 __device__ __forceinline__ void markers_union(int H, int W, int p, int32_t *parent)
 {
     if (p >= H * W || parent[p] < 0) return;
     const int r = p / W, c = p - r * W;
     if (c > 0 && parent[p - 1] >= 0) unite(parent, p, p - 1);
     if (r > 0 && parent[p - W] >= 0) unite(parent, p, p - W);
-}
-
-__global__ void k_markers_union(int H, int W, int32_t *parent)
-{
-    markers_union(H, W, blockIdx.x * TPB + threadIdx.x, parent);
 }
 
 // after all unions: every pixel points at its root; area and boundary counts go to the root
@@ -89,11 +80,6 @@ __device__ __forceinline__ void markers_count(int H, int W, int p, int32_t *pare
     atomicAdd(&area[root], 1);
     if (boundary) atomicAdd(&bd[root], 1);
     parent[p] = root;                                 // safe: a root keeps parent == itself, others only move to their root
-}
-
-__global__ void k_markers_count(int H, int W, int32_t *parent, int32_t *area, int32_t *bd)
-{
-    markers_count(H, W, blockIdx.x * TPB + threadIdx.x, parent, area, bd);
 }
 
 __device__ inline bool regular_root(const int32_t *parent, const int32_t *area, const int32_t *bd, int p, double thr)
@@ -138,11 +124,6 @@ __device__ __forceinline__ void markers_chunk_count(int n, int chunk_index, cons
     if (threadIdx.x == 0) chunk[chunk_index] = total;
 }
 
-__global__ void k_markers_chunk_count(int n, const int32_t *parent, const int32_t *area, const int32_t *bd, double thr, int32_t *chunk)
-{
-    markers_chunk_count(n, blockIdx.x, parent, area, bd, thr, chunk);
-}
-
 // one block: exclusive scan of the chunk counts in place; the number of markers to d_count
 __device__ __forceinline__ void markers_scan_chunks(int n_chunks, int32_t *chunk, const int32_t *n_bg, int32_t *d_count)
 {
@@ -163,11 +144,6 @@ __device__ __forceinline__ void markers_scan_chunks(int n_chunks, int32_t *chunk
     if (threadIdx.x == 0) *d_count = *n_bg > 0 ? carry : 0;
 }
 
-__global__ void k_markers_scan_chunks(int n_chunks, int32_t *chunk, const int32_t *n_bg, int32_t *d_count)
-{
-    markers_scan_chunks(n_chunks, chunk, n_bg, d_count);
-}
-
 __device__ __forceinline__ void markers_rank(int n, int chunk_index, const int32_t *parent, const int32_t *area, const int32_t *bd, double thr,
                                              const int32_t *chunk, int32_t *lab)
 {
@@ -178,12 +154,6 @@ __device__ __forceinline__ void markers_rank(int n, int chunk_index, const int32
         const int p = base + k;
         if (p < n && parent[p] == p) lab[p] = regular_root(parent, area, bd, p, thr) ? next++ : 0;
     }
-}
-
-__global__ void k_markers_rank(int n, const int32_t *parent, const int32_t *area, const int32_t *bd, double thr, const int32_t *chunk,
-                               int32_t *lab)
-{
-    markers_rank(n, blockIdx.x, parent, area, bd, thr, chunk, lab);
 }
 
 __device__ __forceinline__ void markers_label(int n, int p, const int32_t *parent, const int32_t *lab, const int32_t *n_bg, double thr,
@@ -199,12 +169,6 @@ __device__ __forceinline__ void markers_label(int n, int p, const int32_t *paren
     const int l = lab[root];
     y_mask[p] = l > 0;
     markers[p] = *n_bg > 0 ? l : 0;
-}
-
-__global__ void k_markers_label(int n, const int32_t *parent, const int32_t *lab, const int32_t *n_bg, double thr, uint8_t *y_mask,
-                                int32_t *markers)
-{
-    markers_label(n, blockIdx.x * TPB + threadIdx.x, parent, lab, n_bg, thr, y_mask, markers);
 }
 
 // ---- exact EDT -------------------------------------------------------------------------------------------------------------------
@@ -224,13 +188,6 @@ __device__ __forceinline__ void edt_col(const uint8_t *target, int H, int W, int
         if (target[p]) last = r;
         if (last >= 0 && last - r < g[p]) g[p] = last - r;
     }
-}
-
-__global__ void k_edt_cols(const uint8_t *target, int H, int W, int32_t *g)
-{
-    const int c = blockIdx.x * TPB + threadIdx.x;
-    if (c >= W) return;
-    edt_col(target, H, W, c, g);
 }
 
 // lower envelope of the parabolas (c - q)^2 + g(q)^2 of one row (Felzenszwalb & Huttenlocher), with the breakpoints compared as
@@ -275,16 +232,9 @@ __device__ __forceinline__ void edt_row(const int32_t *g, int W, int r, int32_t 
     }
 }
 
-__global__ void k_edt_rows(const int32_t *g, int H, int W, int32_t *v_ws, double *out)
-{
-    const int r = blockIdx.x * TPB + threadIdx.x;
-    if (r >= H) return;
-    edt_row(g, W, r, v_ws, out);
-}
-
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// ---- image sets --------------------------------------------------------------------------------------------------------------------
+// ---- the kernels: one launch per phase and set ------------------------------------------------------------------------------------
 
 // what the kernels of a set launch know about its images (a kernel argument, < 2 KB)
 struct SetTable {
@@ -297,18 +247,6 @@ struct SetTable {
     int32_t start2[SDSM_MAX_SET_IMAGES + 1];     // prefix of the image's scan chunks (markers) or rows (EDT)
     double thr[SDSM_MAX_SET_IMAGES];
 };
-
-// the image of item x of a flattened grid: the last i with start[i] <= x
-__device__ __forceinline__ int set_find(const int32_t *start, int n, int x)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (start[mid] <= x) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
 
 __global__ void k_set_markers_init(SetTable T, const double *y, int32_t *parent, int32_t *area, int32_t *bd, int32_t *n_bg)
 {
@@ -401,54 +339,6 @@ SetLayout set_layout(const sdsm_set_image *im, int n, const double *thr, bool ed
 }
 
 }  // namespace
-
-extern "C" size_t sdsm_c2f_markers_workspace_bytes_impl(int H, int W)
-{
-    const size_t n = (size_t)H * W;
-    const size_t n_chunks = (n + CHUNK - 1) / CHUNK;
-    return 4 * align256(n * 4) + align256(n_chunks * 4) + 256;
-}
-
-extern "C" hipError_t sdsm_c2f_markers_impl(const double *d_y, int H, int W, double thr, uint8_t *d_y_mask, int32_t *d_markers,
-                                            int32_t *d_count, void *d_ws, hipStream_t stream)
-{
-    const int n = H * W;
-    const int n_chunks = (n + CHUNK - 1) / CHUNK;
-    char *ws = (char *)d_ws;
-    int32_t *parent = (int32_t *)ws; ws += align256((size_t)n * 4);
-    int32_t *area = (int32_t *)ws; ws += align256((size_t)n * 4);
-    int32_t *bd = (int32_t *)ws; ws += align256((size_t)n * 4);
-    int32_t *lab = (int32_t *)ws; ws += align256((size_t)n * 4);
-    int32_t *chunk = (int32_t *)ws; ws += align256((size_t)n_chunks * 4);
-    int32_t *n_bg = (int32_t *)ws;
-    hipError_t e = hipMemsetAsync(n_bg, 0, sizeof(int32_t), stream);
-    if (e != hipSuccess) return e;
-    const int blocks = (n + TPB - 1) / TPB;
-    hipLaunchKernelGGL(k_markers_init, dim3(blocks), dim3(TPB), 0, stream, d_y, n, parent, area, bd, n_bg);
-    hipLaunchKernelGGL(k_markers_union, dim3(blocks), dim3(TPB), 0, stream, H, W, parent);
-    hipLaunchKernelGGL(k_markers_count, dim3(blocks), dim3(TPB), 0, stream, H, W, parent, area, bd);
-    hipLaunchKernelGGL(k_markers_chunk_count, dim3(n_chunks), dim3(TPB), 0, stream, n, parent, area, bd, thr, chunk);
-    hipLaunchKernelGGL(k_markers_scan_chunks, dim3(1), dim3(TPB), 0, stream, n_chunks, chunk, n_bg, d_count);
-    hipLaunchKernelGGL(k_markers_rank, dim3(n_chunks), dim3(TPB), 0, stream, n, parent, area, bd, thr, chunk, lab);
-    hipLaunchKernelGGL(k_markers_label, dim3(blocks), dim3(TPB), 0, stream, n, parent, lab, n_bg, thr, d_y_mask, d_markers);
-    return hipGetLastError();
-}
-
-extern "C" size_t sdsm_edt_exact_workspace_bytes_impl(int H, int W)
-{
-    return 2 * align256((size_t)H * W * 4);
-}
-
-extern "C" hipError_t sdsm_edt_exact_impl(const uint8_t *d_target, int H, int W, double *d_out, void *d_ws, hipStream_t stream)
-{
-    int32_t *g = (int32_t *)d_ws;
-    int32_t *v = (int32_t *)((char *)d_ws + align256((size_t)H * W * 4));
-    hipLaunchKernelGGL(k_edt_cols, dim3((W + TPB - 1) / TPB), dim3(TPB), 0, stream, d_target, H, W, g);
-    hipLaunchKernelGGL(k_edt_rows, dim3((H + TPB - 1) / TPB), dim3(TPB), 0, stream, g, H, W, v, d_out);
-    return hipGetLastError();
-}
-
-// ---- image sets --------------------------------------------------------------------------------------------------------------------
 
 extern "C" size_t sdsm_c2f_markers_workspace_bytes_multi_impl(const sdsm_set_image *images, int n_images)
 {

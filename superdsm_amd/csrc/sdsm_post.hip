@@ -1,5 +1,5 @@
-// Per-object work of the post-processing stage, one workgroup per object, one launch per image
-// (sdsm_k_post) or per set of images (sdsm_k_post_set: the image of an object comes from the launch's table).
+// Per-object work of the post-processing stage, one workgroup per object, one launch per set of images
+// (sdsm_k_post_set: the image of an object comes from the launch's table; a single image is the set of one).
 //
 // Reference behaviour restated here (never its code):
 //   contrast response           superdsm/postprocess.py:254-266  (_compute_contrast)
@@ -11,6 +11,7 @@
 //   scipy.ndimage.distance_transform_edt returns; the nearest mask pixel of an outside pixel is a boundary pixel of the mask, so
 //   the minimum runs over the boundary list (LDS) only.
 #include "sdsm_common.h"
+#include "sdsm_set.h"
 
 namespace {
 
@@ -43,7 +44,7 @@ __device__ __forceinline__ bool frag_bit(const uint32_t *bits, int h, int w, int
 
 }  // namespace
 
-// object i of P (one workgroup): the body of sdsm_k_post and of sdsm_k_post_set
+// object i of P (one workgroup): the body of sdsm_k_post_set
 __device__ __forceinline__ void post_object(const PostParams &P, int i)
 {
     __shared__ uint32_t bnd[POST_MAX_BOUNDARY];
@@ -176,11 +177,6 @@ __device__ __forceinline__ void post_object(const PostParams &P, int i)
     if (tid == 0) P.out[i] = rec;
 }
 
-__global__ __launch_bounds__(POST_WG) void sdsm_k_post(PostParams P)
-{
-    post_object(P, blockIdx.x);
-}
-
 namespace {
 
 // the objects of a set of images: the shared parameters and per-object arrays in P, the per-image inputs in the table
@@ -195,14 +191,7 @@ struct PostSetParams {
 
 __global__ __launch_bounds__(POST_WG) void sdsm_k_post_set(PostSetParams S)
 {
-    // the image of this object: the last j with first[j] <= blockIdx.x (images without objects are passed over)
-    int lo = 0, hi = S.n_images - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (S.first[mid] <= (int)blockIdx.x) lo = mid;
-        else hi = mid - 1;
-    }
-    const sdsm_post_image &im = S.im[lo];
+    const sdsm_post_image &im = S.im[set_find(S.first, S.n_images, blockIdx.x)];
     PostParams P = S.P;
     P.H = im.H; P.W = im.W; P.n = im.n_objects; P.inv_gstd = im.inv_gstd;
     P.g = im.d_g; P.gs = im.d_gs; P.bg = im.d_bg;
@@ -229,20 +218,5 @@ extern "C" hipError_t sdsm_launch_post_set(const sdsm_post_image *images, int n_
     P.boxes = boxes; P.bits_off = bits_off; P.bits = bits; P.new_off = new_off; P.new_bits = new_bits;
     P.boundary_pool = boundary_pool; P.bpool_off = bpool_off; P.out = out;
     hipLaunchKernelGGL(sdsm_k_post_set, dim3(n), dim3(POST_WG), 0, stream, S);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t sdsm_launch_post(const double *g, const double *gs, const uint8_t *bg, int H, int W, int n, const int32_t *boxes,
-                                       const int64_t *bits_off, const uint32_t *bits, const int64_t *new_off, uint32_t *new_bits,
-                                       uint32_t *boundary_pool, const int64_t *bpool_off, double exterior_scale, double exterior_offset,
-                                       double contrast_epsilon, double inv_gstd, int max_distance, double stdamp, sdsm_post_record *out, hipStream_t stream)
-{
-    if (n <= 0) return hipSuccess;
-    PostParams P{};
-    P.H = H; P.W = W; P.n = n; P.max_distance = max_distance;
-    P.exterior_scale = exterior_scale; P.exterior_offset = exterior_offset; P.contrast_epsilon = contrast_epsilon; P.inv_gstd = inv_gstd; P.stdamp = stdamp;
-    P.g = g; P.gs = gs; P.bg = bg; P.boxes = boxes; P.bits_off = bits_off; P.bits = bits; P.new_off = new_off; P.new_bits = new_bits;
-    P.boundary_pool = boundary_pool; P.bpool_off = bpool_off; P.out = out;
-    hipLaunchKernelGGL(sdsm_k_post, dim3(n), dim3(POST_WG), 0, stream, P);
     return hipGetLastError();
 }

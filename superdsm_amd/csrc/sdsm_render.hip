@@ -23,6 +23,7 @@
 // sdsm_set_image table says; one launch per phase serves the whole set and runs the __device__ bodies of the single-image case, which
 // is a set of one image.
 #include "sdsm_common.h"
+#include "sdsm_set.h"
 #include <climits>
 
 #pragma clang fp contract(off)   // the blend of the discarded regions is numpy's a + b * c, unfused
@@ -56,17 +57,6 @@ __device__ __forceinline__ bool rbit(const uint32_t *bits, int h, int w, int r, 
     if (r < 0 || c < 0 || r >= h || c >= w) return false;
     const int b = r * w + c;
     return (bits[b >> 5] >> (b & 31)) & 1u;
-}
-
-__device__ __forceinline__ int rset_find(const int32_t *start, int n, int x)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (start[mid] <= x) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
 }
 
 // sum of an int over the workgroup (LDS integer atomic: order-independent)
@@ -186,7 +176,7 @@ __global__ __launch_bounds__(RTPB) void k_paint(RSet S, RObjects O, PaintArgs A)
 // ---- phase 5: the sparse set of the flood (render._watershed) --------------------------------------------------------------------
 __global__ __launch_bounds__(RTPB) void k_compact(RSet S, const int32_t *label_, const uint8_t *cover_, const double *dist_, Entry *entries, int32_t *counts)
 {
-    const int im = rset_find(S.start, S.n, blockIdx.x);
+    const int im = set_find(S.start, S.n, blockIdx.x);
     const int H = S.H[im], W = S.W[im];
     const int64_t n = (int64_t)H * W, p = (int64_t)(blockIdx.x - S.start[im]) * RTPB + threadIdx.x;
     if (p >= n) return;
@@ -241,7 +231,7 @@ struct OverlayArgs {
 __global__ __launch_bounds__(RTPB) void k_overlay(RSet S, OverlayArgs A)
 {
     __shared__ int32_t tile[PITCH_MAX * PITCH_MAX];
-    const int im = rset_find(S.start, S.n, blockIdx.x);
+    const int im = set_find(S.start, S.n, blockIdx.x);
     const int H = S.H[im], W = S.W[im];
     const int tiles_x = (W + TILE - 1) / TILE;
     const int t = blockIdx.x - S.start[im];
@@ -323,7 +313,7 @@ __global__ __launch_bounds__(RTPB) void k_label_range_init(int n, int32_t *range
 
 __global__ __launch_bounds__(RTPB) void k_label_range(RSet S, CmapArgs A, int32_t *range)
 {
-    const int im = rset_find(S.start, S.n, blockIdx.x);
+    const int im = set_find(S.start, S.n, blockIdx.x);
     const int64_t px = (int64_t)S.H[im] * S.W[im];
     const int64_t p0 = (int64_t)(blockIdx.x - S.start[im]) * CMAP_PIX;
     const int32_t *lab = (const int32_t *)A.src + S.off[im];
@@ -345,7 +335,7 @@ __global__ __launch_bounds__(RTPB) void k_label_range(RSet S, CmapArgs A, int32_
 // shuffle_labels alone: out[p] = the permuted label
 __global__ __launch_bounds__(RTPB) void k_permute(RSet S, CmapArgs A, int32_t *out)
 {
-    const int im = rset_find(S.start, S.n, blockIdx.x);
+    const int im = set_find(S.start, S.n, blockIdx.x);
     const int64_t px = (int64_t)S.H[im] * S.W[im];
     const int64_t p0 = (int64_t)(blockIdx.x - S.start[im]) * CMAP_PIX;
     const int32_t *lab = (const int32_t *)A.src + S.off[im];
@@ -365,7 +355,7 @@ __global__ __launch_bounds__(RTPB) void k_colormap(RSet S, CmapArgs A)
     const int N = A.N;
     for (int e = threadIdx.x; e < (N + 3) * 3; e += RTPB) lut[e] = A.lut[(e / 3) * 4 + e % 3];
     __syncthreads();
-    const int im = rset_find(S.start, S.n, blockIdx.x);
+    const int im = set_find(S.start, S.n, blockIdx.x);
     const int64_t px = (int64_t)S.H[im] * S.W[im];
     const int64_t p0 = (int64_t)(blockIdx.x - S.start[im]) * CMAP_PIX;
     double *out = A.out + 3 * S.off[im];
@@ -492,7 +482,7 @@ __global__ __launch_bounds__(RTPB) void k_graph_mark(RSet S, GraphArgs A)
 
 __global__ __launch_bounds__(RTPB) void k_graph_paint(RSet S, GraphArgs A)
 {
-    const int im = rset_find(S.start, S.n, blockIdx.x);
+    const int im = set_find(S.start, S.n, blockIdx.x);
     const int64_t px = (int64_t)S.H[im] * S.W[im];
     const int64_t p = (int64_t)(blockIdx.x - S.start[im]) * RTPB + threadIdx.x;
     if (p >= px) return;

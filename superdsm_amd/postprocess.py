@@ -15,6 +15,7 @@ import numpy as np
 import scipy.ndimage as ndi
 
 from . import _capi, _morph
+from .imageset import in_sets
 from .objects import BaseObject
 from .output import get_output
 from .pipeline import Stage
@@ -146,54 +147,23 @@ def _inv_gstd(g):
 
 def process_objects_gpu(objects, g, g_mask_processing, background_mask, exterior_scale, exterior_offset, contrast_epsilon,
                         mask_max_distance, mask_stdamp, device=None):
-    """Contrast response and refined mask (before hole filling) of every object: one launch (sdsm_post_objects).
-    ``g`` / ``g_mask_processing``: float64 device tensors; ``background_mask``: bool array or uint8 device tensor.
-    Returns (records POST_RECORD_DTYPE, list of (offset, fragment) or None where the device did not refine)."""
-    import ctypes as C
-    import torch
-    L = _capi.lib()
-    dev = g.device
-    H, W = (int(v) for v in g.shape)
-    n = len(objects)
-    if n == 0:
-        return np.zeros(0, _capi.POST_RECORD_DTYPE), []
-    m = _refinement_radius(mask_max_distance, mask_stdamp)
-    boxes, words, new_words, packed, areas = _pack_objects(objects, H, W, m)
-    bits_off, new_off = _exclusive(words), _exclusive(new_words)
-    # objects with a very long mask boundary keep their boundary list in global memory (4 B per boundary pixel <= mask pixels)
-    need_pool = areas > 12288
-    bpool_off = np.where(need_pool, np.concatenate([[0], np.cumsum(np.where(need_pool, areas, 0))[:-1]]), -1).astype(np.int64)
-    to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    d_boxes, d_bits_off, d_new_off, d_bpool_off = to_dev(boxes), to_dev(bits_off), to_dev(new_off), to_dev(bpool_off)
-    d_bits = to_dev(np.concatenate(packed))
-    d_new = torch.zeros(max(1, int(new_words.sum())) * 4, dtype=torch.uint8, device=dev)
-    d_pool = torch.empty(max(1, int(np.where(need_pool, areas, 0).sum())) * 4, dtype=torch.uint8, device=dev)
-    d_out = torch.zeros(n * 64, dtype=torch.uint8, device=dev)
-    bg = background_mask if torch.is_tensor(background_mask) else to_dev(np.asarray(background_mask, np.uint8))
-    p = lambda t: C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        _capi.check(L.sdsm_post_objects(p(g), p(g_mask_processing), p(bg), H, W, n, p(d_boxes), p(d_bits_off), p(d_bits), p(d_new_off), p(d_new),
-                                        p(d_pool), p(d_bpool_off), float(exterior_scale), float(exterior_offset), float(contrast_epsilon),
-                                        _inv_gstd(g), m, float(mask_stdamp), p(d_out), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                    'sdsm_post_objects')
-        recs = d_out.cpu().numpy().view(_capi.POST_RECORD_DTYPE).copy()
-        new_bits = d_new.cpu().numpy() if m > 0 else None
-    if (recs['status'] == 1).any():
-        raise _capi.SdsmError('sdsm_post_objects: boundary list overflow')
-    return recs, _unpack_refined(recs, boxes, new_bits, new_off, new_words, H, W, m)
+    """Contrast response and refined mask (before hole filling) of every object of one image: the set of this image
+    (:func:`process_objects_gpu_multi`).  ``g`` / ``g_mask_processing``: float64 device tensors; ``background_mask``: bool array or uint8
+    device tensor.  Returns (records POST_RECORD_DTYPE, list of (offset, fragment) or None where the device did not refine)."""
+    return process_objects_gpu_multi([(objects, g, g_mask_processing, background_mask)], exterior_scale, exterior_offset, contrast_epsilon,
+                                     mask_max_distance, mask_stdamp)[0]
 
 
 def process_objects_gpu_multi(images, exterior_scale, exterior_offset, contrast_epsilon, mask_max_distance, mask_stdamp):
-    """:func:`process_objects_gpu` for the objects of a set of images, ``images`` = ``(objects, g, g_mask_processing,
+    """Contrast response and refined mask of the objects of a set of images, ``images`` = ``(objects, g, g_mask_processing,
     background_mask)`` per image (one device for all): one sdsm_post_objects_multi launch per ``_capi.MAX_SET_IMAGES`` images.
-    Returns ``(records, refined)`` per image, equal to :func:`process_objects_gpu` on that image."""
+    Returns ``(records, refined)`` per image, what the image gives as a set of its own."""
     import ctypes as C
     import torch
     L = _capi.lib()
     m = _refinement_radius(mask_max_distance, mask_stdamp)
     results = []
-    for lo in range(0, len(images), _capi.MAX_SET_IMAGES):
-        part = images[lo:lo + _capi.MAX_SET_IMAGES]
+    for part in (images[sl] for sl in in_sets(len(images))):
         dev = part[0][1].device
         to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         table = (_capi.PostImage * len(part))()

@@ -15,6 +15,7 @@ import numpy as np
 import scipy.ndimage as ndi
 
 from . import _morph
+from .imageset import SetLayout, in_sets
 from .postprocess import _exclusive, grown_windows, pack_fragments, window_words
 
 
@@ -79,26 +80,10 @@ def rasterize_labels(data, objects='postprocessed_objects', merge_overlap_thresh
     assert background_label <= 0
     objects = list(rasterize_objects(data, objects, dilate))
 
-    merge_list = []
-    if merge_overlap_threshold <= 1:
-        for i1 in range(len(objects)):
-            for i2 in range(i1):
-                overlap = np.logical_and(objects[i1], objects[i2]).sum() / (0. + min(objects[i1].sum(), objects[i2].sum()))
-                if overlap > merge_overlap_threshold:
-                    merge_list.append((i1, i2))
-    labels = list(range(1, 1 + len(objects)))
-    members = {label: [label - 1] for label in labels}
-    for merge_idx, (i1, i2) in enumerate(merge_list):
-        new_label = len(objects) + 1 + merge_idx
-        l1, l2 = labels[i1], labels[i2]
-        if l1 == l2:
-            continue                                         # already merged (transitivity)
-        merged = members[l1] + members[l2]
-        for k in merged:
-            labels[k] = new_label
-        members[new_label] = merged
-        del members[l1], members[l2]
-    objects = [np.sum([objects[k] for k in ks], axis=0) > 0 for ks in members.values()]
+    pairs = [(i1, i2) for i1 in range(len(objects)) for i2 in range(i1)] if merge_overlap_threshold <= 1 else []
+    inter = [np.logical_and(objects[i1], objects[i2]).sum() for i1, i2 in pairs]
+    members = _merge_members(len(objects), pairs, inter, [obj.sum() for obj in objects], merge_overlap_threshold)
+    objects = [np.sum([objects[k] for k in ks], axis=0) > 0 for ks in members]
 
     result = np.zeros(data['g_raw'].shape, 'uint16')
     if len(objects) > 0:
@@ -129,30 +114,18 @@ def _check_radius(radius, what):
     return int(radius)
 
 
-class _GpuSet:
-    """The device side of one set of up to ``_capi.MAX_SET_IMAGES`` images: the packed pixel buffers, the uploaded objects and one
-    method per kernel phase.  (The CPU tests replace this class by a host restatement to exercise the orchestration.)"""
+class _DeviceSet:
+    """One set of up to ``_capi.MAX_SET_IMAGES`` images on the current device: its packed layout (:class:`SetLayout`) and what every
+    call of a ``*_multi`` entry point needs."""
 
     def __init__(self, shapes):
         import ctypes as C
         import torch
         from . import _capi
         self.C, self.torch, self.capi, self.L = C, torch, _capi, _capi.lib()
-        self.shapes = [(int(h), int(w)) for h, w in shapes]
-        if not 1 <= len(self.shapes) <= _capi.MAX_SET_IMAGES:
-            raise ValueError(f'a set holds 1 .. {_capi.MAX_SET_IMAGES} images')
-        self.table = (_capi.SetImage * len(self.shapes))()
-        off = 0
-        for i, (h, w) in enumerate(self.shapes):
-            self.table[i].offset, self.table[i].H, self.table[i].W = off, h, w
-            off += (h * w + 63) // 64 * 64
-        self.offsets = np.array([t.offset for t in self.table], np.int64)
-        self.total = off
+        self.layout = SetLayout(shapes)
+        self.shapes, self.table, self.offsets, self.total = self.layout.shapes, self.layout.table, self.layout.offsets, self.layout.total
         self.dev = torch.device('cuda', torch.cuda.current_device())
-        self.d_label = torch.empty(off, dtype=torch.int32, device=self.dev)
-        self.d_cover = torch.empty(off, dtype=torch.uint8, device=self.dev)
-        self.d_target = torch.empty(off, dtype=torch.uint8, device=self.dev)
-        self.n = 0
 
     def _up(self, a):
         return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
@@ -162,6 +135,29 @@ class _GpuSet:
 
     def _stream(self):
         return self.C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
+
+    def pack(self, arrays, dtype, channels=1):
+        return self._up(self.layout.pack(arrays, dtype, channels))
+
+    def unpack(self, d, channels=1, tail=()):
+        return self.layout.unpack(d.cpu().numpy(), channels, tail)
+
+    def pack_bases(self, bases):
+        """The images under an overlay, H x W or H x W x 3 each: (packed float64 buffer, channels); grey ones are tripled if any has colour."""
+        ch = 3 if any(b.ndim == 3 for b in bases) else 1
+        return self.pack([b if b.ndim == 3 or ch == 1 else np.dstack([b] * 3) for b in bases], np.float64, ch), ch
+
+
+class _GpuSet(_DeviceSet):
+    """The device side of the label maps of one set: the packed pixel buffers, the uploaded objects and one method per kernel phase.
+    (The CPU tests replace this class by a host restatement to exercise the orchestration.)"""
+
+    def __init__(self, shapes):
+        super().__init__(shapes)
+        self.d_label = self.torch.empty(self.total, dtype=self.torch.int32, device=self.dev)
+        self.d_cover = self.torch.empty(self.total, dtype=self.torch.uint8, device=self.dev)
+        self.d_target = self.torch.empty(self.total, dtype=self.torch.uint8, device=self.dev)
+        self.n = 0
 
     def load(self, obj_image, boxes, words, packed):
         self.n = len(boxes)
@@ -266,47 +262,29 @@ class _GpuSet:
         """Phase 7 and the download: the uint16 label map of every image."""
         d_out = self.torch.empty(self.total, dtype=self.torch.int16, device=self.dev)
         self.capi.check(self.L.sdsm_render_finish(self.total, self._p(self.d_label), int(background_label), self._p(d_out), self._stream()), 'sdsm_render_finish')
-        flat = d_out.cpu().numpy().view(np.uint16)
-        return [flat[o:o + h * w].reshape(h, w).copy() for o, (h, w) in zip(self.offsets, self.shapes)]
+        return [a.view(np.uint16) for a in self.unpack(d_out)]
 
     def region_flags(self, labels, radius, background_label):
         """rasterize_regions for the set (kind 3 of the overlay kernel): (borders, background) per image."""
-        flat = np.zeros(self.total, np.int32)
-        for o, (h, w), l in zip(self.offsets, self.shapes, labels):
-            flat[o:o + h * w] = np.asarray(l).reshape(-1)
-        d_labels = self._up(flat)
+        d_labels = self.pack(labels, np.int32)
         d_out = self.torch.empty(self.total, dtype=self.torch.uint8, device=self.dev)
         bgc = (self.C.c_double * 4)(0, 0, 0, 0) if background_label is not None else None
         self.capi.check(self.L.sdsm_render_overlay_multi(self.table, len(self.shapes), self._p(d_labels), None, 1, 3, int(radius), None, bgc,
                                                          int(background_label if background_label is not None else 0), self._p(d_out), self._stream()), 'sdsm_render_overlay_multi')
-        out = d_out.cpu().numpy()
-        flags = [out[o:o + h * w].reshape(h, w) for o, (h, w) in zip(self.offsets, self.shapes)]
-        return [((f & 1) != 0, (f & 2) != 0) for f in flags]
+        return [((f & 1) != 0, (f & 2) != 0) for f in self.unpack(d_out)]
 
     def overlay(self, labels, bases, kind, radius, color, bg, background_label):
         """The overlay kernel for the set.  ``labels``: None (the label maps this set holds) or one integer array per image;
         ``bases``: one float64 array per image, H x W or H x W x 3."""
         n_im = len(self.shapes)
-        if labels is not None:
-            flat = np.zeros(self.total, np.int32)
-            for o, (h, w), l in zip(self.offsets, self.shapes, labels):
-                flat[o:o + h * w] = np.asarray(l).reshape(-1)
-            d_labels = self._up(flat)
-        else:
-            d_labels = self.d_label
-        ch = 3 if any(b.ndim == 3 for b in bases) else 1
-        flat = np.zeros(self.total * ch, np.float64)
-        for o, (h, w), b in zip(self.offsets, self.shapes, bases):
-            b = np.asarray(b, np.float64)
-            flat[o * ch:(o + h * w) * ch] = (b if b.ndim == 3 or ch == 1 else np.dstack([b] * 3)).reshape(-1)
-        d_base = self._up(flat)
+        d_labels = self.pack(labels, np.int32) if labels is not None else self.d_label
+        d_base, ch = self.pack_bases(bases)
         d_out = self.torch.empty(self.total * 3, dtype=self.torch.uint8, device=self.dev)
         col = (self.C.c_double * 3)(*[float(v) for v in color])
         bgc = (self.C.c_double * 4)(*[float(v) for v in bg]) if bg is not None else None
         self.capi.check(self.L.sdsm_render_overlay_multi(self.table, n_im, self._p(d_labels), self._p(d_base), ch, int(kind), int(radius), col, bgc,
                                                          int(background_label if background_label is not None else 0), self._p(d_out), self._stream()), 'sdsm_render_overlay_multi')
-        out = d_out.cpu().numpy()
-        return [out[3 * o:3 * (o + h * w)].reshape(h, w, 3).copy() for o, (h, w) in zip(self.offsets, self.shapes)]
+        return self.unpack(d_out, 3, (3,))
 
 
 def _candidate_pairs(boxes, all_pairs):
@@ -430,7 +408,6 @@ def _objects_of(data, objects):
 
 
 def _labels_many(datas, objects, merge_overlap_threshold, dilate, background_label, keep_sets=False):
-    from . import _capi
     assert background_label <= 0
     if dilate != 0:
         _check_radius(dilate, 'dilate')
@@ -442,8 +419,7 @@ def _labels_many(datas, objects, merge_overlap_threshold, dilate, background_lab
         if len(objs) != len(datas):
             raise ValueError('objects: an output name or one list of objects per image')
     results, sets = [], []
-    for lo in range(0, len(datas), _capi.MAX_SET_IMAGES):
-        part = slice(lo, lo + _capi.MAX_SET_IMAGES)
+    for part in in_sets(len(datas)):
         res = _labels_set([d['g_raw'].shape for d in datas[part]], objs[part], merge_overlap_threshold, int(dilate), int(background_label), keep_set=keep_sets)
         if keep_sets:
             sets.append(res[1])
@@ -537,13 +513,11 @@ def render_regions_over_image_host(img, regions, background_label=None, color=(0
 
 
 def _regions_many(imgs, regions, background_label, color, bg, radius=3):
-    from . import _capi
     radius = _check_radius(radius, 'radius')
     if radius < 0:
         raise ValueError('radius < 0')
     out = []
-    for lo in range(0, len(imgs), _capi.MAX_SET_IMAGES):
-        part = slice(lo, lo + _capi.MAX_SET_IMAGES)
+    for part in in_sets(len(imgs)):
         S = _GpuSet([np.asarray(r).shape for r in regions[part]])
         out += S.overlay(regions[part], [_base_image(np.asarray(i)) for i in imgs[part]], 0, radius, color, bg if background_label is not None else None, background_label)
     return out
@@ -551,14 +525,12 @@ def _regions_many(imgs, regions, background_label, color, bg, radius=3):
 
 def rasterize_regions_many(regions, background_label=None, radius=3):
     """:func:`rasterize_regions` for a list of label images, one launch per ``_capi.MAX_SET_IMAGES`` images."""
-    from . import _capi
     radius = _check_radius(radius, 'radius')
     if radius < 0:
         raise ValueError('radius < 0')
     regions, out = list(regions), []
-    for lo in range(0, len(regions), _capi.MAX_SET_IMAGES):
-        part = regions[lo:lo + _capi.MAX_SET_IMAGES]
-        out += _GpuSet([np.asarray(r).shape for r in part]).region_flags(part, radius, background_label)
+    for part in in_sets(len(regions)):
+        out += _GpuSet([np.asarray(r).shape for r in regions[part]]).region_flags(regions[part], radius, background_label)
     return out
 
 
@@ -665,7 +637,6 @@ def render_result_over_image_many(datas, objects='postprocessed_objects', merge_
                                   border_position='center', override_imgs=None, color='g'):
     """:func:`render_result_over_image` for a list of pipeline data objects: the label maps stay on the device between
     :func:`rasterize_labels_many` and the overlay kernel."""
-    from . import _capi
     radius = _result_args(border_width, border_position, color)
     _check_radius(radius, 'border_width' if border_position == 'inner' else 'border_width // 2')
     datas = list(datas)
@@ -673,9 +644,8 @@ def render_result_over_image_many(datas, objects='postprocessed_objects', merge_
     _, sets = _labels_many(datas, objects, merge_overlap_threshold, 0, 0, keep_sets=True)
     rgb = [1.0 if i in COLORMAP[color] else 0.0 for i in range(3)]
     out = []
-    for k, S in enumerate(sets):
-        lo = k * _capi.MAX_SET_IMAGES
-        bases = [_result_base(d, normalize_img, o, grey_ok=True) for d, o in zip(datas[lo:lo + _capi.MAX_SET_IMAGES], over[lo:lo + _capi.MAX_SET_IMAGES])]
+    for part, S in zip(in_sets(len(datas)), sets):
+        bases = [_result_base(d, normalize_img, o, grey_ok=True) for d, o in zip(datas[part], over[part])]
         out += S.overlay(None, bases, 1 if border_position == 'center' else 2, radius, rgb, None, 0)
     return out
 
@@ -689,37 +659,8 @@ def render_result_over_image(data, objects='postprocessed_objects', merge_overla
 
 
 # ---- colour maps: y-maps and coloured labels (render.py:102-134, :454-508) -------------------------------------------------------
-class _PixelSet:
-    """The packed pixel layout of one set of up to ``_capi.MAX_SET_IMAGES`` images and the calls of the colour-map and graph kernels
-    (no label-map buffers: lighter than :class:`_GpuSet`)."""
-
-    def __init__(self, shapes):
-        import ctypes as C
-        import torch
-        from . import _capi
-        self.C, self.torch, self.capi, self.L = C, torch, _capi, _capi.lib()
-        self.shapes = [(int(h), int(w)) for h, w in shapes]
-        if not 1 <= len(self.shapes) <= _capi.MAX_SET_IMAGES:
-            raise ValueError(f'a set holds 1 .. {_capi.MAX_SET_IMAGES} images')
-        self.table = (_capi.SetImage * len(self.shapes))()
-        off = 0
-        for i, (h, w) in enumerate(self.shapes):
-            self.table[i].offset, self.table[i].H, self.table[i].W = off, h, w
-            off += (h * w + 63) // 64 * 64
-        self.offsets, self.total = np.array([t.offset for t in self.table], np.int64), off
-        self.dev = torch.device('cuda', torch.cuda.current_device())
-
-    _up, _p, _stream = _GpuSet._up, _GpuSet._p, _GpuSet._stream
-
-    def pack(self, arrays, dtype, channels=1):
-        flat = np.zeros(self.total * channels, dtype)
-        for o, (h, w), a in zip(self.offsets, self.shapes, arrays):
-            flat[o * channels:(o + h * w) * channels] = np.asarray(a).reshape(-1)
-        return self._up(flat)
-
-    def unpack(self, d, channels, shape_tail=()):
-        out = d.cpu().numpy()
-        return [out[channels * o:channels * (o + h * w)].reshape((h, w) + shape_tail).copy() for o, (h, w) in zip(self.offsets, self.shapes)]
+class _PixelSet(_DeviceSet):
+    """The calls of the colour-map and graph kernels for one set (no label-map buffers: lighter than :class:`_GpuSet`)."""
 
     def colormap_values(self, ys, clims, table):
         """source 0 of the colour-map kernel: (pictures, NaN flag per image)."""
@@ -767,8 +708,7 @@ class _PixelSet:
 
     def graph(self, prims, bases, rim_radius, disk_radius, reach, core_d2, ring_d2, colors):
         n_im = len(self.shapes)
-        ch = 3 if any(b.ndim == 3 for b in bases) else 1
-        d_base = self.pack([b if b.ndim == 3 or ch == 1 else np.dstack([b] * 3) for b in bases], np.float64, ch)
+        d_base, ch = self.pack_bases(bases)
         d_prims = self._up(prims) if len(prims) else None
         d_key = self.torch.empty(self.total, dtype=self.torch.int32, device=self.dev)
         d_out = self.torch.empty(self.total * 3, dtype=self.torch.uint8, device=self.dev)
@@ -776,11 +716,6 @@ class _PixelSet:
         self.capi.check(self.L.sdsm_render_graph_multi(self.table, n_im, len(prims), self._p(d_prims), float(rim_radius), float(disk_radius), int(reach), int(core_d2),
                                                        int(ring_d2), col, self._p(d_base), ch, self._p(d_key), self._p(d_out), self._stream()), 'sdsm_render_graph_multi')
         return self.unpack(d_out, 3, (3,))
-
-
-def _in_sets(n):
-    from . import _capi
-    return [slice(lo, lo + _capi.MAX_SET_IMAGES) for lo in range(0, n, _capi.MAX_SET_IMAGES)]
 
 
 def colormap_table(cmap):
@@ -872,7 +807,7 @@ def render_ymap_many(datas, clim=None, cmap='bwr'):
         ys.append(y)
         clims.append((lo, hi, sub, pair.max()))
     out = []
-    for part in _in_sets(len(ys)):
+    for part in in_sets(len(ys)):
         pics, bad = _PixelSet([y.shape for y in ys[part]]).colormap_values(ys[part], clims[part], table)
         out += [np.broadcast_to(table[-1, :3], p.shape).copy() if b else p for p, b in zip(pics, bad)]
     return out
@@ -944,7 +879,7 @@ def shuffle_labels_many(labels, bg_label=None, seed=None):
     l32 = [_int32_labels(l, extra_zero=True) for l in labels]
     perms = [_perm_table(l, bg_label, seed) for l in labels]
     out = []
-    for part in _in_sets(len(labels)):
+    for part in in_sets(len(labels)):
         out += [r.astype(l.dtype) for r, l in zip(_PixelSet([l.shape for l in labels[part]]).permute(l32[part], perms[part]), labels[part])]
     return out
 
@@ -977,7 +912,7 @@ def colorize_labels_many(labels, bg_label=0, cmap='gist_rainbow', bg_color=(0, 0
     l32 = [_int32_labels(l, extra_zero=shuffle is not None) for l in labels]
     perms = [_perm_table(l, bg_label, shuffle) for l in labels] if shuffle is not None else None
     out = []
-    for part in _in_sets(len(labels)):
+    for part in in_sets(len(labels)):
         out += _PixelSet([l.shape for l in labels[part]]).colormap_labels(l32[part], perms[part] if perms is not None else None, table, bg_label, bg_color)
     return out
 
@@ -1152,7 +1087,7 @@ def render_adjacencies_many(datas, normalize_img=True, edge_thickness=3, endpoin
         bases.append(base)
         prims.append(p)
     out = []
-    for part in _in_sets(len(datas)):
+    for part in in_sets(len(datas)):
         for j, p in enumerate(prims[part]):
             p[:, 2] = j
         out += _PixelSet([b.shape[:2] for b in bases[part]]).graph(np.concatenate(prims[part]), bases[part], rim, disk, reach, core_d2, ring_d2, colors)

@@ -155,6 +155,30 @@ def test_post_objects_multi_equals_single(gpu, settings):
     assert len(got[2][0]) == 0 and got[3][0]['area'][0] > 12288
 
 
+def test_post_objects_of_one_image_and_of_none(gpu):
+    """The single-image function is the set of one image: equal to that image's part of a larger set (with an image without objects
+    before it), and an image without objects gives empty records whatever stands beside it."""
+    from superdsm_amd import _capi, postprocess
+    settings = (5, 5, 1e-4, 1, 2)
+    items = []
+    for g, objs, bg in _post_images():
+        g_dev = gpu.as_tensor(g).cuda()
+        items.append((objs, g_dev, postprocess.gaussian_filter_gpu(g_dev, 3), bg))
+    assert len(items[2][0]) == 0 and len(items[3][0]) == 1
+    want = postprocess.process_objects_gpu_multi(items, *settings)
+    for k in (0, 3):
+        recs, refined = postprocess.process_objects_gpu(*items[k], *settings)
+        (recs1, refined1), = postprocess.process_objects_gpu_multi([items[k]], *settings)
+        assert recs.dtype == _capi.POST_RECORD_DTYPE and recs.tobytes() == recs1.tobytes() == want[k][0].tobytes() and len(recs) == len(items[k][0])
+        for a, b, c in zip(refined, refined1, want[k][1]):
+            assert np.array_equal(a[0], b[0]) and np.array_equal(a[0], c[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[1], c[1])
+    recs, refined = postprocess.process_objects_gpu(*items[2], *settings)
+    assert recs.dtype == _capi.POST_RECORD_DTYPE and len(recs) == 0 and refined == []
+    assert postprocess.process_objects_gpu_multi([], *settings) == []
+    both = postprocess.process_objects_gpu_multi([items[2], items[2]], *settings)
+    assert [(len(r), f) for r, f in both] == [(0, []), (0, [])]
+
+
 def _dsm_cfg():
     from superdsm_amd import synth
     return synth.dsm_config_for_scale(10, 0.00033)
