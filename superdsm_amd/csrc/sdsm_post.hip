@@ -57,7 +57,7 @@ __device__ __forceinline__ void post_object(const PostParams &P, int i)
     __syncthreads();
 
     // ---- A. interior statistics and the boundary list ------------------------------------------------------------------------
-    double s_g = 0, s_gs = 0, s_gs2 = 0;
+    double s_g = 0, s_gs = 0;
     int cnt = 0;
     uint32_t *blist = bnd;
     const bool use_pool = P.boundary_pool != nullptr && P.bpool_off[i] >= 0;
@@ -67,22 +67,22 @@ __device__ __forceinline__ void post_object(const PostParams &P, int i)
         if (!frag_bit(bits, h, w, r, c)) continue;
         const size_t p = (size_t)(r0 + r) * P.W + (c0 + c);
         const double gv = P.g[p], sv = P.gs[p];
-        s_g += gv; s_gs += sv; s_gs2 += sv * sv; cnt++;
+        s_g += gv; s_gs += sv; cnt++;
         if (!(frag_bit(bits, h, w, r - 1, c) && frag_bit(bits, h, w, r + 1, c) && frag_bit(bits, h, w, r, c - 1) && frag_bit(bits, h, w, r, c + 1))) {
             const int k = atomicAdd(&nb_sh, 1);
             if (use_pool || k < POST_MAX_BOUNDARY) blist[k] = ((uint32_t)(r0 + r) << 16) | (uint32_t)(c0 + c);
         }
     }
-    double v4[4] = {s_g, s_gs, s_gs2, (double)cnt};
+    double v3[3] = {s_g, s_gs, (double)cnt};
 #pragma unroll
-    for (int k = 0; k < 4; k++) v4[k] = wave_sum(v4[k]);
+    for (int k = 0; k < 3; k++) v3[k] = wave_sum(v3[k]);
     __syncthreads();
-    if ((tid & 63) == 0) for (int k = 0; k < 4; k++) red[(tid >> 6) * 8 + k] = v4[k];
+    if ((tid & 63) == 0) for (int k = 0; k < 3; k++) red[(tid >> 6) * 8 + k] = v3[k];
     __syncthreads();
-    double tot[4] = {0, 0, 0, 0};
-    for (int wv = 0; wv < POST_WG / 64; wv++) for (int k = 0; k < 4; k++) tot[k] += red[wv * 8 + k];
+    double tot[3] = {0, 0, 0};
+    for (int wv = 0; wv < POST_WG / 64; wv++) for (int k = 0; k < 3; k++) tot[k] += red[wv * 8 + k];
     const int nb = nb_sh;
-    const double area = tot[3];
+    const double area = tot[2];
     sdsm_post_record rec = {};
     rec.area = (int32_t)area;
     if (!use_pool && nb > POST_MAX_BOUNDARY) {           // the host did not reserve a global list for this object
@@ -92,8 +92,22 @@ __device__ __forceinline__ void post_object(const PostParams &P, int i)
     if (area == 0) { if (tid == 0) { rec.status = 2; P.out[i] = rec; } return; }
     const double interior_mean = (tot[0] / area) * P.inv_gstd;
     const double fg_mean = tot[1] / area;
-    double var = tot[2] / area - fg_mean * fg_mean;       // population variance (numpy std)
-    var = var < 0 ? 0 : var;
+    // population variance (numpy std) in a second pass over the fragment, with the mean known: sum(sv^2) / area - mean^2 loses
+    // every digit of the deviation that lies below eps * mean^2 (an image with a large constant level)
+    double s_d2 = 0;
+    for (int e = tid; e < h * w; e += POST_WG) {
+        const int r = e / w, c = e - r * w;
+        if (!frag_bit(bits, h, w, r, c)) continue;
+        const double d = P.gs[(size_t)(r0 + r) * P.W + (c0 + c)] - fg_mean;
+        s_d2 += d * d;
+    }
+    s_d2 = wave_sum(s_d2);
+    __syncthreads();
+    if ((tid & 63) == 0) red[(tid >> 6) * 8] = s_d2;
+    __syncthreads();
+    double var = 0;
+    for (int wv = 0; wv < POST_WG / 64; wv++) var += red[wv * 8];
+    var /= area;
     const double fg_amp = sqrt(var) * P.stdamp;
     __syncthreads();
 

@@ -141,8 +141,12 @@ def _unpack_refined(recs, boxes, new_bits, new_off, new_words, H, W, m):
 
 
 def _inv_gstd(g):
-    gstd = float(g.std(unbiased=False).item())               # a constant image: 1 / 0 = inf, the contrast comes out NaN and nothing is discarded, as in the reference (postprocess.py:254-266)
-    return (1.0 / gstd) if gstd > 0 else float('inf')
+    """1 / g.std() in two passes, as NumPy's (postprocess.py:255): an error of the mean enters the variance squared only, so the
+    normaliser keeps its digits on an image that is not normalised (torch's one-pass std loses mean / std of them).  A constant image
+    whose deviations all round to 0 gives inf: the contrast comes out NaN and nothing is discarded (postprocess.py:254-266)."""
+    d = g - g.mean()
+    gstd = float(d.mul_(d).mean().sqrt())
+    return 1.0 / gstd if gstd > 0 else float('inf')
 
 
 def process_objects_gpu(objects, g, g_mask_processing, background_mask, exterior_scale, exterior_offset, contrast_epsilon,
@@ -159,18 +163,24 @@ def process_objects_gpu_multi(images, exterior_scale, exterior_offset, contrast_
     background_mask)`` per image (one device for all): one sdsm_post_objects_multi launch per ``_capi.MAX_SET_IMAGES`` images.
     Returns ``(records, refined)`` per image, what the image gives as a set of its own."""
     import ctypes as C
+    m = _refinement_radius(mask_max_distance, mask_stdamp)
+    all_packs = []
+    for objects, g, *_ in images:                            # the kernel reads the image at every pixel of a box: refuse before anything is uploaded
+        pk = _pack_objects(objects, *g.shape, m)
+        b = pk[0].astype(np.int64)
+        if ((b[:, :2] < 0) | (b[:, 2:] <= 0) | (b[:, :2] + b[:, 2:] > tuple(g.shape))).any():
+            raise ValueError('an object reaches outside its image or has an empty box (fg_offset, fg_fragment.shape against g.shape)')
+        all_packs.append(pk)
     import torch
     L = _capi.lib()
-    m = _refinement_radius(mask_max_distance, mask_stdamp)
     results = []
-    for part in (images[sl] for sl in in_sets(len(images))):
+    for part, packs in ((images[sl], all_packs[sl]) for sl in in_sets(len(images))):
         dev = part[0][1].device
         to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         table = (_capi.PostImage * len(part))()
-        packs, keep = [], []
+        keep = []
         for j, (objects, g, gs, bg) in enumerate(part):
             H, W = (int(v) for v in g.shape)
-            packs.append(_pack_objects(objects, H, W, m))
             bg = bg if torch.is_tensor(bg) else to_dev(np.asarray(bg, np.uint8))
             keep.append(bg)
             table[j].d_g, table[j].d_gs, table[j].d_bg = g.data_ptr(), gs.data_ptr(), bg.data_ptr()
