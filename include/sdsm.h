@@ -193,7 +193,7 @@ typedef struct {
  * d_bg: background_mask uint8 (postprocess.py:152-155).  Objects: d_boxes n*4 int32 (r0, c0, h, w of each fragment), fragments
  * bit-packed (row-major, LSB first in uint32 words) at d_bits + d_bits_off[i] (in words).  Outputs: d_out n records; the refined
  * masks over the windows box +- max_distance (clamped to the image), bit-packed at d_new_bits + d_new_off[i] (only written when
- * max_distance > 0 and stdamp > 0; hole filling stays on the host).  d_boundary_pool / d_bpool_off (may be NULL): global
+ * max_distance > 0 and stdamp > 0; holes are filled by sdsm_post_fill_holes, over these windows).  d_boundary_pool / d_bpool_off (may be NULL): global
  * boundary lists for objects whose mask boundary exceeds 12288 pixels (d_bpool_off[i] < 0: none).  inv_gstd = 1 / g.std(). */
 int sdsm_post_objects(const double *d_g, const double *d_gs, const uint8_t *d_bg, int H, int W, int n, const int32_t *d_boxes,
                       const int64_t *d_bits_off, const uint32_t *d_bits, const int64_t *d_new_off, uint32_t *d_new_bits,
@@ -217,6 +217,42 @@ int sdsm_post_objects_multi(const sdsm_post_image *images, int n_images, const i
                             const uint32_t *d_bits, const int64_t *d_new_off, uint32_t *d_new_bits, uint32_t *d_boundary_pool,
                             const int64_t *d_bpool_off, double exterior_scale, double exterior_offset, double contrast_epsilon,
                             int max_distance, double stdamp, sdsm_post_record *d_out, void *stream);
+/* ---- post-processing, the exact bit problems: background mask, hole filling, glare test ------------------------------------------
+ * All three compute what SciPy computes on the host, bit for bit (superdsm/postprocess.py:152-155, :269-286, :336).  Objects and
+ * windows are bit-packed as sdsm_post_objects takes them (row-major, LSB first, whole uint32 words per object). */
+#define SDSM_POST_MAX_BG_RADIUS 32
+#define SDSM_POST_MAX_GLARE_LAYERS 32
+/* One image of sdsm_post_background_multi.  d_work: 5*H*W bytes of scratch, int32-aligned: H*W int32 of paint, then H*W uint8 of row
+   distances (contents ignored and destroyed). */
+typedef struct {
+    uint8_t *d_bg;          /* out: background_mask, H*W uint8 (0 / 1) */
+    int32_t *d_work;
+    int32_t H, W;           /* 1 .. 65535, H * W < 2^31 */
+    int32_t n_objects;      /* >= 0 */
+    int32_t reserved;
+} sdsm_post_bg_image;
+/* background_mask of every image of a set: the complement of the objects' boxes painted in their order (an object assigns its whole
+ * box, so the last one decides where boxes overlap), eroded by disk(radius) with the outside of the image as background.  The objects
+ * of image 0 come first in d_boxes / d_bits_off (n_objects of them), then those of image 1, and so on; parts of a box outside its
+ * image are ignored.  0 <= radius <= SDSM_POST_MAX_BG_RADIUS; radius 0 gives the plain complement. */
+int sdsm_post_background_multi(const sdsm_post_bg_image *images, int n_images, const int32_t *d_boxes, const int64_t *d_bits_off,
+                               const uint32_t *d_bits, int radius, void *stream);
+/* scipy.ndimage.binary_fill_holes (default structure: 4-connected background) of n bit-packed windows, one workgroup each: window i
+ * has d_dims[2i] x d_dims[2i+1] pixels at word d_off[i] of d_in and of d_out (d_out may be d_in).  A window of more than 4096 words
+ * of whole-word rows (h * ceil(w / 32)) is flooded in global memory and needs 2 * h * ceil(w / 32) words at d_ws + d_ws_off[i]
+ * (d_ws_off[i] < 0, or d_ws NULL: none); d_status[i] = 0 filled, 1 workspace missing (the window is not written). */
+int sdsm_post_fill_holes(int n, const int32_t *d_dims, const int64_t *d_off, const uint32_t *d_in, uint32_t *d_out, uint32_t *d_ws,
+                         const int64_t *d_ws_off, int32_t *d_status, void *stream);
+/* The glare test of the objects of a set (one workgroup per object; table and object order as for sdsm_post_objects_multi, of which
+ * only d_g -- here the smoothed glare image --, H, W and n_objects are read).  Per object: the fragment eroded by disk(2) with its
+ * border as foreground; max and min of d_g over it; for each of the num_layers proportions h_props (HOST doubles) the layer
+ * eroded & (d_g > (max - min) * prop + min), the threshold in two rounded operations.  d_out[2i] = pixels of the eroded mask,
+ * d_out[2i+1] = bit l set iff layer l has more than one 4-connected component (all clear when a masked value is NaN).  d_out[2i] =
+ * -1: the fragment exceeds 4096 words of whole-word rows and has no 3 * h * ceil(w / 32) words at d_ws + d_ws_off[i]; -2: its box is
+ * empty or reaches outside its image.  1 <= num_layers <= SDSM_POST_MAX_GLARE_LAYERS. */
+int sdsm_post_glare_multi(const sdsm_post_image *images, int n_images, const int32_t *d_boxes, const int64_t *d_bits_off,
+                          const uint32_t *d_bits, const double *h_props, int num_layers, uint32_t *d_ws, const int64_t *d_ws_off,
+                          int32_t *d_out, void *stream);
 /* Separable Gaussian filter with SciPy's defaults (mode 'reflect', truncate 4): the smoothing of postprocess.py:165-166 and the
  * building block of sdsm_preprocess. */
 size_t sdsm_gaussian_workspace_bytes(int H, int W, double sigma);

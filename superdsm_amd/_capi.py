@@ -56,6 +56,15 @@ class PostImage(C.Structure):
     _fields_ = [('d_g', C.c_void_p), ('d_gs', C.c_void_p), ('d_bg', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32),
                 ('inv_gstd', C.c_double), ('n_objects', C.c_int32), ('reserved', C.c_int32)]
 
+class PostBgImage(C.Structure):
+    """sdsm_post_bg_image: the per-image buffers of sdsm_post_background_multi."""
+    _fields_ = [('d_bg', C.c_void_p), ('d_work', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32), ('n_objects', C.c_int32), ('reserved', C.c_int32)]
+
+
+POST_MAX_BG_RADIUS = 32          # SDSM_POST_MAX_BG_RADIUS
+POST_MAX_GLARE_LAYERS = 32       # SDSM_POST_MAX_GLARE_LAYERS
+POST_FLOOD_WORDS = 4096          # POST_FLOOD_WORDS of sdsm_post.hip: whole-word rows of a window flooded in LDS
+
 # every entry point of include/sdsm.h: name -> (restype, argtypes)
 _vp, _i32, _f64, _sz, _i64 = C.c_void_p, C.c_int, C.c_double, C.c_size_t, C.c_int64
 SYMBOLS = {
@@ -86,6 +95,9 @@ SYMBOLS = {
     'sdsm_plan_set_latency_mode': (_i32, [_vp, _i32]),
     'sdsm_post_objects': (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _f64, _i32, _f64, _vp, _vp]),
     'sdsm_post_objects_multi': (_i32, [C.POINTER(PostImage), _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _i32, _f64, _vp, _vp]),
+    'sdsm_post_background_multi': (_i32, [C.POINTER(PostBgImage), _i32, _vp, _vp, _vp, _i32, _vp]),
+    'sdsm_post_fill_holes': (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_post_glare_multi': (_i32, [C.POINTER(PostImage), _i32, _vp, _vp, _vp, C.POINTER(C.c_double), _i32, _vp, _vp, _vp, _vp]),
     'sdsm_gaussian_workspace_bytes': (_sz, [_i32, _i32, _f64]),
     'sdsm_gaussian_filter': (_i32, [_vp, _i32, _i32, _f64, _vp, _vp, _sz, _vp]),
     'sdsm_separable_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32]),

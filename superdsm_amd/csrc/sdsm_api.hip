@@ -831,12 +831,20 @@ extern "C" hipError_t sdsm_launch_post_set(const sdsm_post_image *images, int n_
                                            const uint32_t *bits, const int64_t *new_off, uint32_t *new_bits, uint32_t *boundary_pool,
                                            const int64_t *bpool_off, double exterior_scale, double exterior_offset, double contrast_epsilon,
                                            int max_distance, double stdamp, sdsm_post_record *out, hipStream_t stream);
+extern "C" hipError_t sdsm_launch_post_background(const sdsm_post_bg_image *images, int n_images, const int32_t *boxes, const int64_t *bits_off,
+                                                  const uint32_t *bits, int radius, hipStream_t stream);
+extern "C" hipError_t sdsm_launch_post_fill(int n, const int32_t *dims, const int64_t *off, const uint32_t *in, uint32_t *out, uint32_t *ws,
+                                            const int64_t *ws_off, int32_t *status, hipStream_t stream);
+extern "C" hipError_t sdsm_launch_post_glare(const sdsm_post_image *images, int n_images, const int32_t *boxes, const int64_t *bits_off,
+                                             const uint32_t *bits, const double *props, int num_layers, uint32_t *ws, const int64_t *ws_off,
+                                             int32_t *out, hipStream_t stream);
 
 // The table of a set: 1 .. SDSM_MAX_SET_IMAGES images, offsets >= 0, H, W >= 1, and the limits of the kernels that take it.
 enum { SET_PIXELS = 1,      // H * W < 2^31: pixel indices are int32
        SET_SIDES = 2 };     // H, W <= 65535: coordinates packed into 16 bits, squared distances in int64
 static int64_t set_offset(const sdsm_set_image &im) { return im.offset; }
 static int64_t set_offset(const sdsm_post_image &) { return 0; }      // (its images are not packed: device pointers)
+static int64_t set_offset(const sdsm_post_bg_image &) { return 0; }
 template <class Image> static bool set_table_ok(const Image *images, int n_images, int limits)
 {
     if (!images || n_images < 1 || n_images > SDSM_MAX_SET_IMAGES) return false;
@@ -1191,4 +1199,55 @@ extern "C" int sdsm_render_graph(int H, int W, int n_prims, const int32_t *d_pri
 {
     const sdsm_set_image one = {0, H, W};
     return sdsm_render_graph_multi(&one, 1, n_prims, d_prims, rim_radius, disk_radius, line_reach, core_d2, ring_d2, colors, d_base, channels, d_key, d_out, stream);
+}
+
+extern "C" int sdsm_post_background_multi(const sdsm_post_bg_image *images, int n_images, const int32_t *d_boxes, const int64_t *d_bits_off,
+                                          const uint32_t *d_bits, int radius, void *stream)
+{
+    SET_TABLE("sdsm_post_background_multi", SET_SIDES | SET_PIXELS);
+    if (radius < 0 || radius > SDSM_POST_MAX_BG_RADIUS) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_background_multi: 0 <= radius <= 32 required");
+    int64_t n = 0, tiles = 0;
+    for (int j = 0; j < n_images; j++) {
+        const sdsm_post_bg_image &im = images[j];
+        if (im.n_objects < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_background_multi: negative object count");
+        if (!im.d_bg || !im.d_work) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_background_multi: null image buffer");
+        n += im.n_objects;
+        tiles += ((int64_t)im.H * im.W + 255) / 256;
+    }
+    if (n >= (1 << 30) || tiles >= INT_MAX) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_background_multi: more than 2^30 - 1 objects or 2^39 pixels");
+    if (n > 0 && (!d_boxes || !d_bits_off || !d_bits)) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_background_multi: null argument");
+    hipError_t e = sdsm_launch_post_background(images, n_images, d_boxes, d_bits_off, d_bits, radius, (hipStream_t)stream);
+    SET_DONE("sdsm_post_background_multi");
+}
+
+extern "C" int sdsm_post_fill_holes(int n, const int32_t *d_dims, const int64_t *d_off, const uint32_t *d_in, uint32_t *d_out, uint32_t *d_ws,
+                                    const int64_t *d_ws_off, int32_t *d_status, void *stream)
+{
+    if (n < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_fill_holes: negative window count");
+    if (n == 0) return SDSM_OK;
+    if (!d_dims || !d_off || !d_in || !d_out || !d_status) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_fill_holes: null argument");
+    if ((d_ws == nullptr) != (d_ws_off == nullptr)) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_fill_holes: workspace and its offsets go together");
+    hipError_t e = sdsm_launch_post_fill(n, d_dims, d_off, d_in, d_out, d_ws, d_ws_off, d_status, (hipStream_t)stream);
+    SET_DONE("sdsm_post_fill_holes");
+}
+
+extern "C" int sdsm_post_glare_multi(const sdsm_post_image *images, int n_images, const int32_t *d_boxes, const int64_t *d_bits_off,
+                                     const uint32_t *d_bits, const double *h_props, int num_layers, uint32_t *d_ws, const int64_t *d_ws_off,
+                                     int32_t *d_out, void *stream)
+{
+    SET_TABLE("sdsm_post_glare_multi", SET_SIDES);
+    if (num_layers < 1 || num_layers > SDSM_POST_MAX_GLARE_LAYERS || !h_props) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_glare_multi: 1 <= num_layers <= 32 proportions required");
+    int64_t n = 0;
+    for (int j = 0; j < n_images; j++) {
+        const sdsm_post_image &im = images[j];
+        if (im.n_objects < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_glare_multi: negative object count");
+        if (im.n_objects > 0 && !im.d_g) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_glare_multi: null image input");
+        n += im.n_objects;
+    }
+    if (n >= INT_MAX) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_glare_multi: more than 2^31 - 1 objects");
+    if (n == 0) return SDSM_OK;
+    if (!d_boxes || !d_bits_off || !d_bits || !d_out) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_glare_multi: null argument");
+    if ((d_ws == nullptr) != (d_ws_off == nullptr)) return fail(SDSM_ERR_ARGUMENT, "sdsm_post_glare_multi: workspace and its offsets go together");
+    hipError_t e = sdsm_launch_post_glare(images, n_images, d_boxes, d_bits_off, d_bits, h_props, num_layers, d_ws, d_ws_off, d_out, (hipStream_t)stream);
+    SET_DONE("sdsm_post_glare_multi");
 }

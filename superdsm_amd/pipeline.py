@@ -227,7 +227,8 @@ def create_pipeline(stages):
 def create_default_pipeline(extra_stages=()):
     """Preprocessing -> DSM_Config -> [extra stages, e.g. a region-analysis stage producing ``atoms`` and
     ``adjacencies``] -> GlobalEnergyMinimization.  The reference's C2F region analysis and post-processing stages
-    stay on the host and are not part of this package."""
+    are part of this package too (``c2freganal.C2F_RegionAnalysis``, ``postprocess.Postprocessing``, both with their per-image work
+    on the GPU): ``create_reference_pipeline`` chains all five."""
     from .dsmcfg import DSM_Config
     from .globalenergymin import GlobalEnergyMinimization
     from .preprocess import Preprocessing

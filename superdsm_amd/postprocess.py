@@ -5,8 +5,12 @@ Same stage name, inputs (``cover, y_img, atoms, g_raw, dsm_cfg``), output (``pos
 Euclidean distance transforms of the WHOLE image (contrast, postprocess.py:254-266; the region of the normalised energy,
 :289-291).  Here the per-object work of an image is ONE batch of the HIP engine (sdsm_post_objects: contrast response and
 mask refinement on a window around each object; the two smoothed images by the separable Gaussian kernels); the normalised
-energy needs no recomputation (``Object.cvxprog_region_size``).  What stays on the host, on the small fragments: hole
-filling, the glare test, the eccentricity and the accept / discard decisions.  There is no CPU path for the batch."""
+energy needs no recomputation (``Object.cvxprog_region_size``).  The exact bit problems around that batch run on the device too,
+each one launch per set of images: the background mask (sdsm_post_background_multi; integer ``exterior_offset`` up to 32, any
+other value keeps the SciPy erosion), hole filling (sdsm_post_fill_holes; for a set over the refined windows while they are still
+on the device) and the glare test on the smoothed image where it was computed (sdsm_post_glare_multi).  What stays on
+the host: the eccentricity and the accept / discard decisions.  There is no CPU path for the batch; ``_is_glare`` is kept as the
+host definition the device is tested against."""
 import math
 import os
 import time
@@ -149,6 +153,211 @@ def _inv_gstd(g):
     return 1.0 / gstd if gstd > 0 else float('inf')
 
 
+def _check_boxes(boxes, shape):
+    b = np.asarray(boxes, np.int64).reshape(-1, 4)
+    if ((b[:, :2] < 0) | (b[:, 2:] <= 0) | (b[:, :2] + b[:, 2:] > tuple(int(v) for v in shape))).any():
+        raise ValueError('an object reaches outside its image or has an empty box (fg_offset, fg_fragment.shape against g.shape)')
+
+
+def background_radius(exterior_offset):
+    """The disk radius of the device route of the background mask, or None where ``exterior_offset`` keeps the host route (not an
+    integer in 0 .. ``_capi.POST_MAX_BG_RADIUS``)."""
+    try:
+        r = int(exterior_offset)
+    except (TypeError, ValueError, OverflowError):
+        return None
+    return r if r == exterior_offset and 0 <= r <= _capi.POST_MAX_BG_RADIUS else None
+
+
+def background_mask_gpu_multi(images, exterior_offset, device=None):
+    """``background_mask`` (postprocess.py:152-155) of a set of images, ``images`` = ``(objects, shape)`` per image: the objects painted
+    in their order (``fill_foreground`` assigns the whole box), the complement eroded by ``disk(exterior_offset)`` with the image border
+    not eroding.  One sdsm_post_background_multi launch per ``_capi.MAX_SET_IMAGES`` images; returns one uint8 H x W device tensor per
+    image, equal to the SciPy erosion bit for bit."""
+    import ctypes as C
+    r = background_radius(exterior_offset)
+    if r is None:
+        raise NotImplementedError(f'exterior_offset = {exterior_offset!r}: the GPU background mask takes integer radii 0 .. {_capi.POST_MAX_BG_RADIUS} only, see DESIGN.md "Limits"')
+    packs = []
+    for objects, shape in images:                            # refuse before anything is uploaded
+        if len(shape) != 2 or min(shape) < 1:
+            raise ValueError(f'image shape {tuple(shape)!r}')
+        pk = pack_fragments(objects)
+        _check_boxes(pk[0], shape)
+        packs.append(pk)
+    import torch
+    L = _capi.lib()
+    dev = torch.device('cuda' if device is None else device)
+    to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    out = []
+    for part, pks in ((images[sl], packs[sl]) for sl in in_sets(len(images))):
+        table = (_capi.PostBgImage * len(part))()
+        work = []
+        for j, (objects, shape) in enumerate(part):
+            H, W = (int(v) for v in shape)
+            bg, wk = torch.empty((H, W), dtype=torch.uint8, device=dev), torch.empty(H * W + (H * W + 3) // 4, dtype=torch.int32, device=dev)
+            out.append(bg)
+            work.append(wk)
+            table[j].d_bg, table[j].d_work, table[j].H, table[j].W, table[j].n_objects = bg.data_ptr(), wk.data_ptr(), H, W, len(objects)
+        n = sum(len(o) for o, _ in part)
+        boxes = np.concatenate([pk[0] for pk in pks]) if n else np.zeros((1, 4), np.int32)
+        bits_off = _exclusive(np.concatenate([pk[1] for pk in pks])) if n else np.zeros(1, np.int64)
+        d_boxes, d_bits_off = to_dev(boxes), to_dev(bits_off)
+        d_bits = to_dev(np.concatenate([b for pk in pks for b in pk[2]])) if n else torch.zeros(4, dtype=torch.uint8, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        with torch.cuda.device(dev):
+            _capi.check(L.sdsm_post_background_multi(table, len(part), p(d_boxes), p(d_bits_off), p(d_bits), r, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                        'sdsm_post_background_multi')         # (the work images and the uploads go back to the allocator in stream order)
+    return out
+
+
+def background_mask_gpu(objects, shape, exterior_offset, device=None):
+    """``background_mask`` of one image on the device: the set of this image (:func:`background_mask_gpu_multi`)."""
+    return background_mask_gpu_multi([(objects, shape)], exterior_offset, device)[0]
+
+
+def pack_windows(windows):
+    """Bit-packed windows as sdsm_post_fill_holes takes them: ``(dims, offsets, bits)`` = n x 2 int32 (h, w), the first uint32 word of
+    each window, and the bits (row-major, LSB first, continuous over the rows, whole words per window) as uint8."""
+    dims = np.zeros((len(windows), 2), np.int32)
+    packed = []
+    for k, win in enumerate(windows):
+        win = np.asarray(win)
+        if win.ndim != 2 or win.size == 0:
+            raise ValueError(f'window {k}: a non-empty 2-d mask is required, not shape {win.shape}')
+        dims[k] = win.shape
+        bits = np.packbits(np.ascontiguousarray(win, bool).reshape(-1), bitorder='little')
+        buf = np.zeros((win.size + 31) // 32 * 4, np.uint8)
+        buf[:bits.size] = bits
+        packed.append(buf)
+    words = (dims[:, 0].astype(np.int64) * dims[:, 1] + 31) // 32
+    return dims, _exclusive(words), (np.concatenate(packed) if packed else np.zeros(0, np.uint8))
+
+
+def unpack_windows(bits, offsets, dims):
+    """The bool windows of a buffer packed as :func:`pack_windows` packs it."""
+    out = []
+    for off, (h, w) in zip(offsets, dims):
+        h, w = int(h), int(w)
+        out.append(np.unpackbits(bits[4 * int(off):4 * (int(off) + (h * w + 31) // 32)], bitorder='little')[:h * w].reshape(h, w).astype(bool))
+    return out
+
+
+def flood_workspace(dims, planes):
+    """Offsets (in words, -1: the window is flooded in LDS) and total words of the global-memory workspace of windows of ``dims``
+    (n x 2: h, w) whose whole-word rows exceed ``_capi.POST_FLOOD_WORDS``, ``planes`` bit planes each."""
+    d = np.asarray(dims, np.int64).reshape(-1, 2)
+    words = d[:, 0] * ((d[:, 1] + 31) // 32)
+    need = np.where(words > _capi.POST_FLOOD_WORDS, planes * words, 0)
+    return np.where(need > 0, _exclusive(need), -1).astype(np.int64), int(need.sum())
+
+
+def _fill_holes_device(d_bits, dims, offsets, in_place=False):
+    """sdsm_post_fill_holes on the current stream over windows already on the device (``d_bits``: uint8 tensor); returns the filled
+    windows as a device tensor of the same layout, and the per-window status for :func:`_fill_status` once the caller has downloaded."""
+    import ctypes as C
+    import torch
+    L = _capi.lib()
+    dev = d_bits.device
+    to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    n = len(dims)
+    ws_off, ws_words = flood_workspace(dims, 2)
+    d_out = d_bits if in_place else torch.empty_like(d_bits)
+    d_dims, d_off, d_status = to_dev(np.asarray(dims, np.int32)), to_dev(np.asarray(offsets, np.int64)), torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+    d_ws, d_ws_off = (torch.empty(ws_words, dtype=torch.int32, device=dev), to_dev(ws_off)) if ws_words else (None, None)
+    p = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
+    with torch.cuda.device(dev):
+        _capi.check(L.sdsm_post_fill_holes(n, p(d_dims), p(d_off), p(d_bits), p(d_out), p(d_ws), p(d_ws_off), p(d_status),
+                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'sdsm_post_fill_holes')
+    return d_out, d_status[:n]
+
+
+def _fill_status(d_status):
+    """Refuses the windows of a sdsm_post_fill_holes launch if one of them was not flooded; read after the launch's results, so that
+    the host waits for the stream once."""
+    if d_status.cpu().numpy().any():
+        raise _capi.SdsmError('sdsm_post_fill_holes: a window had no workspace')
+
+
+def fill_holes_gpu(windows, device=None):
+    """``scipy.ndimage.binary_fill_holes`` (default structure) of every 2-d mask of ``windows`` in one sdsm_post_fill_holes launch; returns
+    the filled bool arrays."""
+    dims, offsets, bits = pack_windows(windows)
+    if not len(windows):
+        return []
+    import torch
+    d_bits = torch.from_numpy(bits).to(torch.device('cuda' if device is None else device))
+    d_out, d_status = _fill_holes_device(d_bits, dims, offsets, in_place=True)
+    filled = d_out.cpu().numpy()
+    _fill_status(d_status)
+    return unpack_windows(filled, offsets, dims)
+
+
+def glare_proportions(min_layer, num_layers):
+    """The layer proportions of the glare test (postprocess.py:283), refused beyond what the device takes before anything runs."""
+    num_layers = int(num_layers)
+    if num_layers > _capi.POST_MAX_GLARE_LAYERS:
+        raise NotImplementedError(f'glare_detection_num_layers = {num_layers}: the GPU glare test takes up to {_capi.POST_MAX_GLARE_LAYERS} layers, see DESIGN.md "Limits"')
+    if num_layers < 1:
+        raise ValueError('the glare test needs at least one layer')
+    return np.ascontiguousarray(np.linspace(min_layer, 1, num_layers, endpoint=False), np.float64)
+
+
+def glare_flags_gpu_multi(images, min_layer=0.5, num_layers=5):
+    """The device part of the glare test (``_is_glare``) for the objects of a set of images, ``images`` = ``(objects, g_smooth)`` per image
+    (``g_smooth``: float64 H x W device tensor, one device for all): one sdsm_post_glare_multi launch per ``_capi.MAX_SET_IMAGES`` images.
+    Returns per image an n x 2 int32 array: the pixels of the fragment eroded by ``disk(2)`` and the bit mask of the layers with more than
+    one component; :func:`glare_decision` turns a row into what ``_is_glare`` returns."""
+    import ctypes as C
+    props = glare_proportions(min_layer, num_layers)
+    packs = []
+    for objects, g in images:
+        pk = pack_fragments(objects)
+        _check_boxes(pk[0], g.shape)
+        packs.append(pk)
+    import torch
+    L = _capi.lib()
+    results = []
+    for part, pks in ((images[sl], packs[sl]) for sl in in_sets(len(images))):
+        n = sum(len(o) for o, _ in part)
+        if n == 0:
+            results += [np.zeros((0, 2), np.int32) for _ in part]
+            continue
+        dev = part[0][1].device
+        to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        table = (_capi.PostImage * len(part))()
+        for j, (objects, g) in enumerate(part):
+            if g.dtype != torch.float64 or not g.is_contiguous():
+                raise ValueError('the smoothed image must be a contiguous float64 tensor')
+            table[j].d_g, table[j].H, table[j].W, table[j].n_objects = g.data_ptr(), int(g.shape[0]), int(g.shape[1]), len(objects)
+        boxes = np.concatenate([pk[0] for pk in pks])
+        ws_off, ws_words = flood_workspace(boxes[:, 2:], 3)
+        d_boxes, d_bits_off = to_dev(boxes), to_dev(_exclusive(np.concatenate([pk[1] for pk in pks])))
+        d_bits = to_dev(np.concatenate([b for pk in pks for b in pk[2]]))
+        d_ws, d_ws_off = (torch.empty(ws_words, dtype=torch.int32, device=dev), to_dev(ws_off)) if ws_words else (None, None)
+        d_out = torch.zeros((n, 2), dtype=torch.int32, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
+        with torch.cuda.device(dev):
+            _capi.check(L.sdsm_post_glare_multi(table, len(part), p(d_boxes), p(d_bits_off), p(d_bits), props.ctypes.data_as(C.POINTER(C.c_double)), len(props),
+                                                p(d_ws), p(d_ws_off), p(d_out), C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'sdsm_post_glare_multi')
+            flags = d_out.cpu().numpy()
+        if (flags[:, 0] < 0).any():
+            raise _capi.SdsmError('sdsm_post_glare_multi: an object had no workspace or an invalid box')
+        first = 0
+        for objects, _ in part:
+            results.append(flags[first:first + len(objects)].copy())
+            first += len(objects)
+    return results
+
+
+def glare_decision(flags):
+    """What ``_is_glare`` returns for one row of :func:`glare_flags_gpu_multi`: the first layer with more than one component ends its
+    loop with False; an empty eroded mask fails as the maximum of an empty array does."""
+    if int(flags[0]) == 0:
+        raise ValueError('zero-size array to reduction operation maximum which has no identity')
+    return int(flags[1]) == 0
+
+
 def process_objects_gpu(objects, g, g_mask_processing, background_mask, exterior_scale, exterior_offset, contrast_epsilon,
                         mask_max_distance, mask_stdamp, device=None):
     """Contrast response and refined mask (before hole filling) of every object of one image: the set of this image
@@ -162,6 +371,18 @@ def process_objects_gpu_multi(images, exterior_scale, exterior_offset, contrast_
     """Contrast response and refined mask of the objects of a set of images, ``images`` = ``(objects, g, g_mask_processing,
     background_mask)`` per image (one device for all): one sdsm_post_objects_multi launch per ``_capi.MAX_SET_IMAGES`` images.
     Returns ``(records, refined)`` per image, what the image gives as a set of its own."""
+    return _process_objects(images, exterior_scale, exterior_offset, contrast_epsilon, mask_max_distance, mask_stdamp, None)
+
+
+def _process_objects(images, exterior_scale, exterior_offset, contrast_epsilon, mask_max_distance, mask_stdamp, fill_holes):
+    """:func:`process_objects_gpu_multi` (``fill_holes`` None), or the masks the stage decides on (postprocess.py:316-337; ``fill_holes``
+    True / False): with hole filling, sdsm_post_fill_holes runs on the stream behind the refinement over the refined windows, and only
+    the filled windows are downloaded; where nothing is refined it fills the original fragments.
+
+    Filling the window equals filling the cropped fragment: a background component that does not touch the mask's bounding box is
+    enclosed by mask pixels, all inside the box, so it cannot reach the window's margin either; and every background pixel outside the
+    box is connected to the margin.  The bounding box of the filled mask is that of the unfilled one: the box in the record stays
+    valid."""
     import ctypes as C
     m = _refinement_radius(mask_max_distance, mask_stdamp)
     all_packs = []
@@ -206,8 +427,17 @@ def process_objects_gpu_multi(images, exterior_scale, exterior_offset, contrast_
                                                   p(d_bpool_off), float(exterior_scale), float(exterior_offset), float(contrast_epsilon), m,
                                                   float(mask_stdamp), p(d_out), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
                         'sdsm_post_objects_multi')
+            d_filled = d_fill_status = None
+            if fill_holes and m > 0:
+                wins = np.concatenate([grown_windows(pk[0], *(int(v) for v in g.shape), m) for (_, g, *_), pk in zip(part, packs) if len(pk[0])])
+                _, d_fill_status = _fill_holes_device(d_new, wins[:, 2:], new_off, in_place=True)
+            elif fill_holes:
+                d_filled, d_fill_status = _fill_holes_device(d_bits, boxes[:, 2:], bits_off)
             recs = d_out.cpu().numpy().view(_capi.POST_RECORD_DTYPE).copy()
             new_bits = d_new.cpu().numpy() if m > 0 else None
+            filled_bits = d_filled.cpu().numpy() if d_filled is not None else None
+            if d_fill_status is not None:
+                _fill_status(d_fill_status)
         if (recs['status'] == 1).any():
             raise _capi.SdsmError('sdsm_post_objects_multi: boundary list overflow')
         first = 0
@@ -217,6 +447,8 @@ def process_objects_gpu_multi(images, exterior_scale, exterior_offset, contrast_
             r = recs[k].copy()
             # the refined windows of this image, offsets relative to its first word
             refined = _unpack_refined(r, pk[0], new_bits, new_off[k], new_words[k], H, W, m) if len(objects) else []
+            if filled_bits is not None:                      # nothing refined: the original fragments, filled
+                refined = [(o.fg_offset, f) for o, f in zip(objects, unpack_windows(filled_bits, bits_off[k], pk[0][:, 2:]))]
             results.append((r, refined))
             first += len(objects)
     return results
@@ -262,82 +494,128 @@ class Postprocessing(Stage):
             P['max_boundary_eccentricity'] = P['max_eccentricity']
         return P
 
-    def _prepare(self, input_data, cfg):
-        """Settings, objects, background mask and the device images of one image."""
+    def _prepare_host(self, input_data, cfg):
+        """Settings, cover, objects and the device images of one image."""
         import torch
         P = self._settings(cfg)
         g_raw = np.asarray(input_data['g_raw'], np.float64)
         solution = list(input_data['cover'].solution)
-        # pixels allowed for the background estimate of the contrast (postprocess.py:152-155)
-        background_mask = np.zeros(g_raw.shape, bool)
-        for c in solution:
-            c.fill_foreground(background_mask)
-        background_mask = _morph.binary_erosion(~background_mask, _morph.disk(P['exterior_offset']))
-
         # (the reference's filter reads the loop variable of the loop above, postprocess.py:180: all objects or none)
         objects = [obj for obj in solution if (solution[-1].fg_fragment.any() if solution else False)]
         g_dev = torch.as_tensor(np.ascontiguousarray(g_raw)).cuda()
         g_mask = gaussian_filter_gpu(g_dev, P['mask_smoothness'])
+        # the mask is built where the image is: a caller that stands host arrays in for the device images (the CPU pipeline of the
+        # regression-metric test does, through process_objects_gpu and gaussian_filter_gpu) gets the host mask it always got
+        offset = P['exterior_offset'] if torch.is_tensor(g_dev) else None
+        return P, solution, objects, g_dev, g_mask, (solution, g_raw.shape, P['exterior_offset'], offset)
+
+    @staticmethod
+    def _background_masks(items):
+        """The pixels allowed for the background estimate of the contrast (postprocess.py:152-155) of ``items`` = ``(solution, shape,
+        exterior_offset, device_offset)`` per image: one launch per offset the device takes (:func:`background_mask_gpu_multi`), the
+        SciPy erosion of the whole image for any other offset (``device_offset`` None: the image is not on a device)."""
+        masks, groups = [None] * len(items), {}
+        for i, (solution, shape, offset, device_offset) in enumerate(items):
+            if background_radius(device_offset) is not None:
+                groups.setdefault(background_radius(device_offset), []).append(i)
+                continue
+            background_mask = np.zeros(shape, bool)
+            for c in solution:
+                c.fill_foreground(background_mask)
+            masks[i] = _morph.binary_erosion(~background_mask, _morph.disk(offset))
+        for r, members in groups.items():
+            for i, bg in zip(members, background_mask_gpu_multi([items[i][:2] for i in members], r)):
+                masks[i] = bg
+        return masks
+
+    def _prepare(self, input_data, cfg):
+        """Settings, objects, background mask and the device images of one image."""
+        P, solution, objects, g_dev, g_mask, item = self._prepare_host(input_data, cfg)
+        background_mask, = self._background_masks([item])
         return P, objects, g_dev, g_mask, background_mask
+
+    @staticmethod
+    def _glare(items):
+        """The glare test (postprocess.py:188-190) of ``items`` = ``(P, objects, g_dev)`` per image: per image a dict object index ->
+        is_glare of the objects whose radius exceeds their glare radius.  The smoothed image stays on the device; one launch
+        (:func:`glare_flags_gpu_multi`) per setting of the layers."""
+        tested, groups = [], {}
+        for i, (P, objects, g_dev) in enumerate(items):
+            need = [k for k, o in enumerate(objects)
+                    if (P['min_boundary_glare_radius'] if o.on_boundary else P['min_glare_radius']) < math.sqrt(o.fg_fragment.sum() / math.pi)]
+            tested.append(dict.fromkeys(need, True))
+            if need and P['glare_detection_num_layers'] >= 1:            # (without layers the reference's loop is empty: glare)
+                glare_proportions(P['glare_detection_min_layer'], P['glare_detection_num_layers'])
+                groups.setdefault((P['glare_detection_min_layer'], P['glare_detection_num_layers']), []).append(i)
+        for (min_layer, num_layers), members in groups.items():
+            images = [([items[i][1][k] for k in tested[i]], gaussian_filter_gpu(items[i][2], items[i][0]['glare_detection_smoothness'])) for i in members]
+            for i, flags in zip(members, glare_flags_gpu_multi(images, min_layer, num_layers)):
+                for k, row in zip(list(tested[i]), flags):
+                    tested[i][k] = glare_decision(row)
+        return tested
+
+    @staticmethod
+    def _filled(objects, refined):
+        """The masks of postprocess.py:336-337 from those before hole filling: the refined mask of every object, or its own where
+        nothing was refined, holes filled in one launch (:func:`fill_holes_gpu`)."""
+        pairs = [(o.fg_offset, o.fg_fragment) if r is None else r for o, r in zip(objects, refined)]
+        return [(off, frag) for (off, _), frag in zip(pairs, fill_holes_gpu([frag for _, frag in pairs]))]
 
     def process(self, input_data, cfg, out, log_root_dir):
         P, objects, g_dev, g_mask, background_mask = self._prepare(input_data, cfg)
+        # one image goes through the public batch call, whose masks are those before hole filling, and fills their fragments in a launch
+        # of their own (0.4 ms per BBBC039-like image over filling the resident windows, DESIGN.md section 8); the set (process_many)
+        # fills the refined windows while they are still on the device
         recs, refined = process_objects_gpu(objects, g_dev, g_mask, background_mask, P['exterior_scale'], P['exterior_offset'],
                                             P['contrast_epsilon'], P['mask_max_distance'], P['mask_stdamp'])
         self.last_records = recs
-        return self._decide(P, objects, g_dev, recs, refined, get_output(out), log_root_dir)
+        masks = self._filled(objects, refined) if P['fill_holes'] else list(refined)
+        glare, = self._glare([(P, objects, g_dev)])
+        return self._decide(P, objects, recs, masks, glare, get_output(out), log_root_dir)
 
     def process_many(self, datas, cfg, out=None, log_root_dirs=None):
         """The stage for a set of images, with the contract of ``GlobalEnergyMinimization.process_many`` (a list of pipeline data
-        dicts, one config for all or a list; returns the wall time): the Gaussians and background mask of every image as in
-        ``process``, the objects of all images in one launch (:func:`process_objects_gpu_multi`; images whose contrast and mask
-        settings differ go to launches of their own), then the decisions image by image.  Equal to ``process`` on every image;
-        ``last_records`` becomes the list of the images' records."""
+        dicts, one config for all or a list; returns the wall time): the Gaussians of every image as in ``process``, then the background
+        masks, the objects (:func:`process_objects_gpu_multi` with the hole filling behind it) and the glare test of all images, each in
+        one launch (images whose settings for a step differ go to launches of their own), then the decisions image by image.  Equal to
+        ``process`` on every image; ``last_records`` becomes the list of the images' records."""
         t0 = time.time()
         datas = list(datas)
         cfgs = list(cfg) if isinstance(cfg, (list, tuple)) else [cfg] * len(datas)
         cfgs = [c.get(self.cfgns, {}) for c in cfgs]
         logs = list(log_root_dirs) if log_root_dirs is not None else [None] * len(datas)
         out = get_output(out)
-        prepared = [self._prepare({inner: d[outer] for outer, inner in self.inputs.items()}, c) for d, c in zip(datas, cfgs)]
+        hosts = [self._prepare_host({inner: d[outer] for outer, inner in self.inputs.items()}, c) for d, c in zip(datas, cfgs)]
+        masks = self._background_masks([h[5] for h in hosts])
+        prepared = [(P, objects, g_dev, g_mask, bg) for (P, _, objects, g_dev, g_mask, _), bg in zip(hosts, masks)]
         keys = ('exterior_scale', 'exterior_offset', 'contrast_epsilon', 'mask_max_distance', 'mask_stdamp')
         groups = {}
         for i, prep in enumerate(prepared):
-            groups.setdefault(tuple(prep[0][k] for k in keys), []).append(i)
+            groups.setdefault(tuple(prep[0][k] for k in keys) + (bool(prep[0]['fill_holes']),), []).append(i)
         per_object = [None] * len(datas)
         for settings, members in groups.items():
-            res = process_objects_gpu_multi([(prepared[i][1], prepared[i][2], prepared[i][3], prepared[i][4]) for i in members], *settings)
+            res = _process_objects([(prepared[i][1], prepared[i][2], prepared[i][3], prepared[i][4]) for i in members], *settings)
             for i, r in zip(members, res):
                 per_object[i] = r
         self.last_records = [r[0] for r in per_object]
-        for data, prep, (recs, refined), log in zip(datas, prepared, per_object, logs):
-            P, objects, g_dev = prep[:3]
-            produced = self._decide(P, objects, g_dev, recs, refined, out, log)
+        glares = self._glare([prep[:3] for prep in prepared])
+        for data, prep, (recs, final), glare, log in zip(datas, prepared, per_object, glares, logs):
+            produced = self._decide(prep[0], prep[1], recs, final, glare, out, log)
             for inner, outer in self.outputs.items():
                 data[outer] = produced[inner]
         return time.time() - t0
 
-    def _decide(self, P, objects, g_dev, recs, refined, out, log_root_dir):
-        """The host part of one image (postprocess.py:175-243): glare test, hole filling, eccentricity, accept or discard."""
-        need_glare = any((P['min_boundary_glare_radius'] if o.on_boundary else P['min_glare_radius']) < math.sqrt(o.fg_fragment.sum() / math.pi) for o in objects)
-        g_glare = gaussian_filter_gpu(g_dev, P['glare_detection_smoothness']).cpu().numpy() if need_glare else None
-
+    def _decide(self, P, objects, recs, masks, glare, out, log_root_dir):
+        """The host part of one image (postprocess.py:175-243): eccentricity, accept or discard.  ``masks``: the final mask (offset,
+        fragment) of every object, holes filled where the settings say so, or None where the object keeps its own; ``glare``: object index
+        -> is_glare of the tested objects."""
         postprocessed_objects, log_entries = [], []
         for k, original in enumerate(objects):
             obj_radius = math.sqrt(original.fg_fragment.sum() / math.pi)
-            is_glare = False
-            if (P['min_boundary_glare_radius'] if original.on_boundary else P['min_glare_radius']) < obj_radius:
-                is_glare = _is_glare(original, g_glare, P['glare_detection_min_layer'], P['glare_detection_num_layers'])
+            is_glare = glare.get(k, False)
             norm_energy = original.energy / original.cvxprog_region_size                    # postprocess.py:289-291 without the second distance transform
             contrast_response = float(recs['contrast'][k])
-            if refined[k] is not None:                                                       # postprocess.py:316-337
-                fg_offset, fg_fragment = refined[k]
-                if P['fill_holes']:
-                    fg_fragment = ndi.binary_fill_holes(fg_fragment)
-            elif P['fill_holes']:
-                fg_offset, fg_fragment = original.fg_offset, ndi.binary_fill_holes(original.fg_fragment)
-            else:
-                fg_offset, fg_fragment = None, None
+            fg_offset, fg_fragment = masks[k] if masks[k] is not None else (None, None)     # postprocess.py:316-337
             eccentricity = _compute_eccentricity(original.fg_fragment)
 
             obj = PostprocessedObject(original)

@@ -279,3 +279,213 @@ def post_reference(g, gs, bg, off, frag, exterior_scale, exterior_offset, contra
             out['margin'] = float(min(np.abs(v - (mean - amp)).min(), np.abs(v - (mean + amp)).min())) if v.size else np.inf
             out['band'] = float(4 * (n_in if n_in > 1 else 0) * _EPS * (abs(mean) + amp))     # one pixel: its mean is the pixel, exactly
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the cases of the exact post-processing steps (tests/test_post_steps_gpu.py and tests/test_post_steps_cpu.py): hole filling, the
+# background mask, the glare test.  NumPy only; the CPU file checks what the cases claim about themselves.
+# ---------------------------------------------------------------------------------------------------------
+FILL_WIDTHS = (31, 32, 33, 64, 65)
+FILL_LDS_WORDS = 4096            # POST_FLOOD_WORDS of sdsm_post.hip: h * ceil(w / 32) beyond it floods in global memory
+
+
+def fill_ring(h=9, w=9, wall=2):
+    a = _rect(h, w)
+    a[wall:h - wall, wall:w - wall] = False
+    return a
+
+
+def fill_spiral(n=63):
+    """Walls with a background corridor of one pixel that winds from the border pixel (1, 0) to the centre: ONE background component,
+    whose pixels are up to n^2 / 2 steps from the border."""
+    a = _rect(n, n)
+    r, c, dr, dc = 1, 0, 0, 1
+    a[r, c] = False
+    while True:
+        moved = False
+        while 0 < r + dr < n - 1 and 0 < c + dc < n - 1 and a[r + 2 * dr, c + 2 * dc] if (0 <= r + 2 * dr < n and 0 <= c + 2 * dc < n) else False:
+            r, c = r + dr, c + dc
+            a[r, c] = False
+            moved = True
+        if not moved:
+            break
+        dr, dc = dc, -dr
+    return a
+
+
+def fill_cases():
+    """``name -> window`` of the hole-filling test."""
+    rng = np.random.default_rng(77)
+    C = {'1x1 set': _rect(1, 1), '1x1 clear': ~_rect(1, 1), '1x40': rng.random((1, 40)) < 0.5, '40x1': rng.random((40, 1)) < 0.5}
+    for w in FILL_WIDTHS:                                   # rows straddle words (odd heights), the last word is partial
+        a = rng.random((7 + 2 * (w % 3), w)) < 0.62
+        a[0, 0] = a[-1, -1] = True
+        C[f'random {a.shape[0]}x{w}'] = a
+        b = _rect(9, w)
+        b[2:7, 2:w - 2] = False
+        b[4, 4:w - 4] = True
+        C[f'frame {w}'] = b
+    C['ring'] = fill_ring()
+    opened = fill_ring()
+    opened[4, 7:] = False
+    C['ring open to the border'] = opened
+    diag = np.zeros((9, 9), bool)                           # the wall's only gap is diagonal: closed for a 4-connected background
+    diag[1:8, 1:8] = fill_ring(7, 7, 1)
+    diag[1, 1] = False
+    C['ring with a diagonal gap'] = diag
+    nested = fill_ring(21, 37, 2)
+    nested[6:15, 8:29] = fill_ring(9, 21, 2)
+    C['nested rings'] = np.pad(nested, 1)
+    C['checkerboard'] = (np.add.outer(np.arange(33), np.arange(35)) % 2).astype(bool)
+    C['all ones'] = _rect(13, 70)
+    C['all zeros'] = ~_rect(13, 70)
+    C['spiral 63'] = fill_spiral(63)
+    comb = post_comb(16, 66)
+    comb[-1, :] = True                                      # a frame around the teeth would close them: the gaps stay open to the right
+    C['comb'] = comb
+    closed = np.pad(post_comb(16, 66), 1, constant_values=True)
+    C['comb in a frame'] = closed
+    big = rng.random((2049, 33)) < 0.7                     # 2049 * 2 words: just above the LDS cut-over
+    big[0], big[-1], big[:, 0], big[:, -1] = True, True, True, True
+    C['above the cut-over'] = big
+    edge = rng.random((2048, 33)) < 0.7                    # 4096 words: the last window flooded in LDS
+    C['at the cut-over'] = edge
+    return C
+
+
+def fill_embedded(frag, pads):
+    """``frag`` in a larger clear window, ``pads`` = (top, bottom, left, right)."""
+    return np.pad(np.asarray(frag, bool), ((pads[0], pads[1]), (pads[2], pads[3])))
+
+
+FILL_PADS = ((0, 0, 0, 0), (1, 0, 0, 0), (0, 3, 0, 0), (0, 0, 2, 0), (0, 0, 0, 1), (1, 1, 1, 1), (3, 0, 5, 31), (2, 7, 32, 1))
+
+
+def bg_cases():
+    """``name -> (shape, [(offset, fragment), ...])`` of the background-mask test (every case runs at every radius)."""
+    rng = np.random.default_rng(78)
+    H, W = 45, 83                                           # a width that is no multiple of 64
+    corners = [((0, 0), _rect(3, 4)), ((0, W - 5), _rect(6, 5)), ((H - 4, 0), _rect(4, 2)), ((H - 3, W - 3), _rect(3, 3))]
+    edges = [((0, 30), _ellipse(5, 9)), ((H - 6, 40), _ellipse(6, 7)), ((20, 0), _ellipse(9, 4)), ((15, W - 3), _rect(8, 3))]
+    overlap = [((10, 10), _ellipse(14, 18)), ((15, 20), _rect(12, 12)), ((12, 14), rng.random((10, 20)) < 0.5), ((30, 60), _ellipse(9, 9))]
+    return {
+        'no objects': ((37, 53), []),
+        '1x1': ((1, 1), []),
+        '1x1 covered': ((1, 1), [((0, 0), _rect(1, 1))]),
+        'corners': ((H, W), corners),
+        'edges': ((H, W), edges),
+        'corners and edges': ((H, W), corners + edges),
+        'overlapping': ((50, 90), overlap),                  # a later box overwrites an earlier one, also with clear bits
+        'whole image': ((37, 53), [((0, 0), _rect(37, 53))]),
+        'one pixel': ((70, 130), [((35, 64), _rect(1, 1))]),
+        '1x200': ((1, 200), [((0, 60), _rect(1, 5)), ((0, 199), _rect(1, 1))]),
+        '200x1': ((200, 1), [((100, 0), _rect(3, 1))]),
+    }
+
+
+BG_RADII = (0, 1, 5, 16, 32)
+BG_SET = ('corners and edges', 'no objects', 'overlapping')       # three images of different shapes, the one in the middle empty
+
+
+def _peaks(shape, centres, sigma, heights=None):
+    rr, cc = np.mgrid[:shape[0], :shape[1]]
+    heights = heights or [1.0] * len(centres)
+    return sum(hh * np.exp(-((rr - y) ** 2 + (cc - x) ** 2) / (2.0 * sigma * sigma)) for (y, x), hh in zip(centres, heights))
+
+
+def glare_cases():
+    """``name -> dict(g, offset, fragment, expect)`` of the glare test; ``expect``: what the case is built to give at min_layer 0.5
+    with 5 layers (True / False / 'empty' for the ValueError of an empty eroded mask), checked against the oracle on the CPU."""
+    C = {}
+    shape, off = (60, 90), (7, 11)
+    frag = _ellipse(41, 70)
+    add = lambda name, g, expect, fragment=frag, offset=off: C.__setitem__(name, dict(g=np.ascontiguousarray(g, np.float64), offset=offset, fragment=fragment, expect=expect))
+    add('one peak', _peaks(shape, [(27, 45)], 12), True)
+    add('two peaks', _peaks(shape, [(27, 28), (27, 64)], 7), False)
+    # the saddle between the peaks lies at 0.88 of the top: only the layer at 0.9 (of 0.5, 0.6, .. 0.9) separates them; the floor of 0 comes
+    # from the rest of the mask
+    add('two peaks, highest layer only', _peaks(shape, [(27, 38), (27, 53)], 6), False)
+    g = np.zeros(shape)
+    g[20:25, 30:35] = 1.0
+    g[25:30, 35:40] = 1.0                                   # two plateaus that touch at a corner only
+    add('diagonal contact', g, False)
+    add('border on all sides', _peaks((30, 40), [(15, 20)], 6), True, _rect(30, 40), (0, 0))
+    add('constant', np.full(shape, 0.25), True)
+    g = _peaks(shape, [(27, 45)], 12)
+    g[27, 45] = np.nan
+    add('nan inside the mask', g, True)
+    add('empty erosion', _peaks(shape, [(27, 45)], 12), 'empty', np.pad(_rect(4, 30), 1), (10, 10))
+    wide = _rect(3, 40)
+    wide[1, 5] = False
+    add('thin', _peaks(shape, [(27, 45)], 12), 'empty', np.pad(wide, 2), (20, 20))
+    return C
+
+
+def glare_tie_search(limit=200000, seed=5):
+    """A triple (max, min, prop) of doubles for which (max - min) * prop + min differs between two rounded operations and one fused
+    multiply-add, found with exact rational arithmetic; returns (max, min, prop, twice_rounded, fused) or None."""
+    from fractions import Fraction
+    rng = np.random.default_rng(seed)
+    for prop in np.linspace(0.5, 1, 5, endpoint=False)[1:]:
+        for _ in range(limit // 4):
+            mx, mn = float(rng.random()), float(rng.random()) * 0.5
+            if mx <= mn:
+                continue
+            d = mx - mn
+            if Fraction(mx) - Fraction(mn) != Fraction(d):
+                continue                                    # keep the subtraction exact, so that only the multiply-add is in question
+            twice = float(np.float64(d) * np.float64(prop) + np.float64(mn))
+            exact = Fraction(d) * Fraction(float(prop)) + Fraction(mn)
+            fused = _round_fraction(exact)
+            if fused != twice:
+                return mx, mn, float(prop), twice, fused
+    return None
+
+
+def _round_fraction(q):
+    """The double nearest to the rational q (ties to even): float(Fraction) divides two integers, which Python rounds correctly."""
+    return q.numerator / q.denominator
+
+
+def glare_tie_case():
+    """The tie case: a mask whose eroded pixels hold max, min and one pixel exactly AT the twice-rounded threshold of the layer ``prop``
+    (so the pixel is not above it and the layer stays one component), which a fused threshold -- smaller here -- would put above it as a
+    second component.  The test runs ONE layer at ``min_layer`` = prop (np.linspace starts at it exactly): at the lower layers the pixel
+    is a second component either way.  Returns None when the search finds no triple whose fused threshold is the smaller one."""
+    for seed in range(5, 40):
+        t = glare_tie_search(seed=seed)
+        if t is not None and t[4] < t[3]:
+            break
+    else:
+        return None
+    mx, mn, prop, twice, fused = t
+    g = np.full((20, 40), mn)
+    g[8:12, 8:12] = mx                                      # the top plateau: one component of every layer
+    g[10, 30] = twice                                       # at the threshold of layer `prop`: above it only if the threshold is fused
+    return dict(g=g, offset=(2, 2), fragment=_rect(16, 36), max=mx, min=mn, prop=prop, twice=twice, fused=fused, min_layer=prop, num_layers=1)
+
+
+def post_steps_stage_images():
+    """Five images for the stage-level test of the device steps and their ``postprocess`` settings: the first without hole filling and
+    with the default (infinite) glare radius; the second with hole filling and a finite ``min_glare_radius``; the third shares the
+    second's settings, so one launch refines and fills the windows of two images (offsets past the first image's); the last two share
+    ``mask_stdamp = 0``: nothing is refined and the original fragments are filled.  Objects with holes, one glare-like object with two
+    peaks, contrasts on both sides of ``min_contrast``."""
+    ring = _ellipse(21, 25)
+    ring[8:13, 9:16] = False
+    a = _image((60, 80), 51, [((5, 8), ring, 'holes'), ((30, 40), _ellipse(18, 30), ''), ((0, 60), _ellipse(12, 20), 'corner')])
+    two = _ellipse(23, 41)
+    two[10:13, 18:23] = False
+    b = _image((64, 72), 52, [((6, 6), _ellipse(20, 20), ''), ((34, 20), two, 'two peaks, hole'), ((3, 40), ring, 'holes')])
+    dots = _ellipse(27, 33)
+    dots[6:9, 10:13] = dots[15:20, 17:19] = False
+    c = _image((50, 97), 53, [((20, 60), dots, 'two holes'), ((2, 3), _ellipse(15, 22), ''), ((25, 10), ring, 'holes'), ((0, 70), _rect(9, 27), 'edge')])
+    d = _image((45, 66), 54, [((4, 30), dots, 'two holes'), ((20, 2), _ellipse(19, 23), '')])
+    e = _image((70, 41), 55, [((1, 1), _ellipse(14, 14), ''), ((40, 8), ring, 'holes'), ((18, 5), dots, 'two holes')])
+    for im in (a, b, c, d, e):
+        for k, o in enumerate(im['objects']):
+            h, w = o.fg_fragment.shape
+            im['g'][o.fg_offset[0]:o.fg_offset[0] + h, o.fg_offset[1]:o.fg_offset[1] + w][o.fg_fragment] += (0.6, 0.0, 0.3)[k % 3]
+    b['g'] += 0.8 * _peaks((64, 72), [(45, 28), (45, 52)], 4)      # object 1 of the second image: two bright spots
+    shared, unrefined = dict(min_contrast=1.2, min_glare_radius=6.0, exterior_offset=3), dict(min_contrast=1.2, mask_stdamp=0)
+    return [a, b, c, d, e], [dict(exterior_scale=2.5, min_contrast=1.2, fill_holes=False), shared, dict(shared), unrefined, dict(unrefined)]
