@@ -528,6 +528,12 @@ int sdsm_batch_eval(const sdsm_plan *plan, void *d_workspace, size_t workspace_b
 int sdsm_enable_kernel_timing(int enable);
 double sdsm_last_solve_kernel_ms(void);
 double sdsm_last_setup_kernel_ms(void);
+/* Solver diagnostics of the production build, process-wide, taken by every following launch: bit 0 = a second full evaluation at an
+ * unchanged iterate repeats the pass over the pixels instead of taking the sums the first one kept.  Results do not depend on it (the
+ * tests compare).  An unknown bit: SDSM_ERR_ARGUMENT.  sdsm_batch_solver_counters synchronises the device and reads the event
+ * counters of the plan's last launch on this workspace (0 before any): out[0] full evaluations served from kept sums, out[1 .. 3] 0. */
+int sdsm_set_solver_diagnostics(int flags);
+int sdsm_batch_solver_counters(const sdsm_plan *plan, void *d_workspace, int64_t out[4]);
 /* Diagnostic builds only (-DSDSM_PROFILE): device buffer receiving 8 int64 cycle counters per candidate
  * (phase A, phase B, reductions, factor+solve, line search, total, elliptical total, reserved). */
 int sdsm_set_debug_buffer(void *d_buf);

@@ -152,6 +152,8 @@ SYMBOLS = {
     'sdsm_enable_kernel_timing': (_i32, [_i32]),
     'sdsm_last_solve_kernel_ms': (_f64, []),
     'sdsm_last_setup_kernel_ms': (_f64, []),
+    'sdsm_set_solver_diagnostics': (_i32, [_i32]),
+    'sdsm_batch_solver_counters': (_i32, [_vp, _vp, _vp]),
     'sdsm_set_debug_buffer': (_i32, [_vp]),
     'sdsm_set_group_timeout_us': (_i32, [_f64]),
     'sdsm_side_queues_distinct': (_i32, []),

@@ -1,6 +1,7 @@
 // Host side of the C ABI (include/sdsm.h): planning, workspace layout, launches.  No device allocation
 // happens here: every device buffer is provided by the caller.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -518,6 +519,7 @@ extern "C" int sdsm_batch_upload(const sdsm_plan *p, void *d_ws, size_t ws_bytes
     if (!p->fp_labels.empty() && (e = hipMemcpyAsync(b + p->off_fp, p->fp_labels.data(), 4 * p->fp_labels.size(), hipMemcpyHostToDevice, s)) != hipSuccess) return hipfail(e, "upload footprints");
     if ((e = hipMemcpyAsync(b + p->off_order, p->order.data(), 4 * p->order.size(), hipMemcpyHostToDevice, s)) != hipSuccess) return hipfail(e, "upload order");
     if ((e = hipMemcpyAsync(b + p->off_psf, p->psf.data(), 4 * p->psf.size(), hipMemcpyHostToDevice, s)) != hipSuccess) return hipfail(e, "upload psf");
+    if ((e = hipMemsetAsync(b + p->off_ticket, 0, 256, s)) != hipSuccess) return hipfail(e, "hipMemsetAsync");   // (the event counters read 0 before the first launch)
     p->uploaded_gen = p->layout_gen; p->uploaded_ws = d_ws;
     return SDSM_OK;
 }
@@ -563,6 +565,7 @@ extern "C" int sdsm_set_debug_buffer(void *d_buf) { g_prof = (long long *)d_buf;
 #ifndef SDSM_HESS_THR
 #define SDSM_HESS_THR 0.1f    // same constant as the oracle's ORC_HESS_THR
 #endif
+static std::atomic<int> g_solver_diag{0};      // sdsm_set_solver_diagnostics (process-wide)
 // Kernel arguments of a plan laid out in the caller's workspace.
 static BatchParams make_params(const sdsm_plan *p, void *d_ws)
 {
@@ -571,7 +574,7 @@ static BatchParams make_params(const sdsm_plan *p, void *d_ws)
     P.n = p->n; P.n_total = p->n; P.latency = p->mode == 1; P.n_images = (int)p->images.size();
     for (size_t i = 0; i < p->images.size(); i++) { P.img[i].H = p->images[i].H; P.img[i].W = p->images[i].W; }   // device pointers: filled by the launch
     P.k = p->k; P.R = p->R; P.subsample = p->cfg.smooth_subsample; P.zcap = p->zcap; P.zcap_run = p->zcap_run; P.zshift = p->zshift; P.no_deform = p->no_deform; P.no_trivial_rule = p->cfg.flags & 1;
-    P.init_elliptical = p->cfg.init_elliptical; P.max_iters = p->cfg.max_iters; P.k1_pixmax = p->wide_pixels; P.boost_pixels = p->boost_pixels; P.rows_mcap = p->rows_mcap; P.pad2 = 0;
+    P.init_elliptical = p->cfg.init_elliptical; P.max_iters = p->cfg.max_iters; P.k1_pixmax = p->wide_pixels; P.boost_pixels = p->boost_pixels; P.rows_mcap = p->rows_mcap; P.pad2 = g_solver_diag.load(std::memory_order_relaxed);
     P.scale = p->cfg.scale; P.epsilon = p->cfg.epsilon; P.alpha = p->cfg.alpha; P.reg_unit = p->cfg.alpha * std::sqrt(p->cfg.epsilon);
     P.cand = (const CandDesc *)(b + p->off_cand); P.state = (CandState *)(b + p->off_state);
     P.fp_labels = (const int32_t *)(b + p->off_fp); P.order = (const int32_t *)(b + p->off_order);
@@ -613,6 +616,25 @@ static double elapsed(int a, int b)
     return ms;
 }
 extern "C" double sdsm_last_setup_kernel_ms(void) { return elapsed(0, 1); }
+
+extern "C" int sdsm_set_solver_diagnostics(int flags)
+{
+    if (flags & ~1) return fail(SDSM_ERR_ARGUMENT, "sdsm_set_solver_diagnostics: unknown flag bit (1: recompute at unchanged iterates)");
+    g_solver_diag.store(flags, std::memory_order_relaxed);
+    return SDSM_OK;
+}
+
+extern "C" int sdsm_batch_solver_counters(const sdsm_plan *p, void *d_ws, int64_t out[4])
+{
+    if (!p || !d_ws || !out) return fail(SDSM_ERR_ARGUMENT, "sdsm_batch_solver_counters: null argument");
+    if (p->uploaded_ws != d_ws) return fail(SDSM_ERR_ARGUMENT, "sdsm_batch_solver_counters: not the workspace of the plan's upload (sdsm_batch_upload)");
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (p->n == 0) return SDSM_OK;
+    hipError_t e;
+    if ((e = hipDeviceSynchronize()) != hipSuccess) return hipfail(e, "hipDeviceSynchronize");
+    if ((e = hipMemcpy(out, (const uint8_t *)d_ws + p->off_ticket + 64 + 4 * SDSM_SOLVER_COUNTERS, 8, hipMemcpyDeviceToHost)) != hipSuccess) return hipfail(e, "hipMemcpy");
+    return SDSM_OK;
+}
 extern "C" double sdsm_last_solve_kernel_ms(void) { return elapsed(1, 2); }
 
 extern "C" int sdsm_batch_launch_multi(const sdsm_plan *p, const double *const *d_y, const int32_t *const *d_atoms, const uint8_t *const *d_valid,

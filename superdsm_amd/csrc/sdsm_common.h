@@ -140,7 +140,7 @@ struct BatchParams {
     double reg_unit;                   // alpha * sqrt(epsilon): the regulariser's value per grid point at xi = 0 (dsm.py:325-326), computed on the host
     float hess_thr;                    // Hessian ignores row entries < hess_thr * row maximum (solver approximation)
     int32_t boost_pixels;              // throughput mode: regions with more pixels run their passes over the pixels at a raised issue priority (the long chains of a launch; layout_plan)
-    int32_t rows_mcap, pad2;           // largest bound on M among the regions whose rows sdsm_k_setup_rows builds (sizes its LDS tables)
+    int32_t rows_mcap, pad2;           // largest bound on M among the regions whose rows sdsm_k_setup_rows builds (sizes its LDS tables); pad2: solver diagnostics (sdsm_set_solver_diagnostics)
     const CandDesc *cand;
     CandState *state;
     const int32_t *fp_labels;
@@ -175,6 +175,7 @@ struct BatchParams {
     double *wide_pool;                 // sync words and all-reduce buffers of the workgroup groups (CandDesc.wide_off)
     int32_t *wide_ticket;              // [0] / [1] (the groups of class-2 / class-2b layout): next entry of the group launch list (members are claimed in the order in which workgroups START, see sdsm_solve.hip)
     long long wide_timeout;            // ticks of the 100 MHz wall clock a group member waits for its partners before the group is given up
+#define SDSM_SOLVER_COUNTERS 32        // cls_count + 32 (int32 words; byte 192 of the zeroed block): 64-bit event counters of the launch (sdsm_batch_solver_counters)
     int32_t *cls_count;                // [l]: next entry of launch list l that a resident workgroup of a class beyond 1 takes (sdsm_k_solve; zeroed before every launch)
     double *hglob;                     // Hessian pool of the global-memory class (envelope too large for LDS), CandDesc.hglob_off
     long long *prof;                   // diagnostic build only (-DSDSM_PROFILE): 16 cycle counters per candidate (solve kernel)

@@ -84,7 +84,7 @@ struct Lay {
     static constexpr int W = NMAX + 2;             // vectors are indexed up to n (right-hand-side row) inclusive
     static constexpr int LT = 0, B0 = 2 * SDSM_LOGTAB_N;   // the table of log_w (the same address in every class), then the vectors
     static constexpr int X = B0, G = B0 + W, D = B0 + 2 * W, XT = B0 + 3 * W, SC = B0 + 4 * W, YROW = B0 + 5 * W, TMP = B0 + 6 * W;
-    static constexpr int RED = B0 + 7 * W, FLAG = RED + NWAVES * 32, MS = FLAG + 2, IB = MS + 42 * NSLOT;   // MS: fixed-point moment accumulators, 21 sums x 2 words x NSLOT lane slots
+    static constexpr int RED = B0 + 7 * W, FLAG = RED + NWAVES * 32, KEPT = FLAG + 2, MS = KEPT + 4, IB = MS + 42 * NSLOT;   // KEPT: KeptState; MS: fixed-point moment accumulators, 21 sums x 2 words x NSLOT lane slots
     static constexpr int NPANEL = NMAX / SDSM_PANEL + 2;
     static constexpr int IB_DOUBLES = (2 * W + NPANEL + 1) / 2;      // int arrays: rb[W], fst[W], rend[NPANEL]
     static constexpr int HP = IB + IB_DOUBLES;
@@ -189,7 +189,7 @@ template <class F>
 __device__ __forceinline__ double wave_canon_sum(int cnt, F &&f)
 {
     double s = 0;
-    for (int j = (int)(threadIdx.x & 63); j < cnt; j += 64) s += f(j);
+    for (int j = opaque_tid() & 63; j < cnt; j += 64) s += f(j);   // (opaque: the lane's addresses are formed here, not kept from the top of the kernel)
     return wave_sum(s);
 }
 
@@ -777,8 +777,27 @@ __device__ __forceinline__ double fx_get(double raw, double unit) { return (doub
 // Full evaluation: psi, gradient and (approximate) Hessian at L::X.  M = 0: the elliptical model (the entries of the runs are
 // not touched).
 // ---------------------------------------------------------------------------------------------------------
+// The pixel sums of the last full evaluation, kept for a second evaluation at the same point (newton: EV_RETRY, EV_CHECK): the
+// envelope and the gradient as they are BEFORE the regulariser is added, in the unused tail of the envelope area (Hp[env_size ..]:
+// env_size entries, then g[0 .. n)), the pixel part of psi and the fixed-point scales the sums were taken at.  Only where the tail
+// holds them (never in the global-memory class); otherwise the second evaluation is a second pass, as it always was.
+template <class L> __device__ __forceinline__ double *Hp_tail(const Cand &c) { return SD + L::HP + c.env_size; }
+// (In LDS, not in registers: it is written once per evaluation by one lane and read at the rare second evaluation; the solver's
+// uniform state already overflows the scalar registers.)  diag, counters: the launch's diagnostics, put there once per workgroup (sdsm_k_solve).
+struct KeptState {
+    double psi_pix; int fxh_hi, fxg_hi;
+    unsigned long long *counters;       // BatchParams.cls_count + SDSM_SOLVER_COUNTERS: [0] evaluations served from the kept sums
+    int diag, pad;                      // BatchParams.pad2 (sdsm_set_solver_diagnostics): bit 0 recompute at unchanged iterates
+};
+static_assert(sizeof(KeptState) == 32, "L::KEPT holds four doubles");
+#define KEPT (reinterpret_cast<KeptState *>(SD + L::KEPT))
+template <class L> __device__ __forceinline__ bool sums_kept(const Cand &c, int M)
+{
+    if constexpr (L::GLOBAL_H) return false; else return M > 0 && 2 * c.env_size + 6 + M <= L::EMAX;
+}
+
 template <class L>
-__device__ __forceinline__ double eval_full(const Cand &c, int M, double reg_mu, double psi_bound PROF_PARAM)
+__device__ __forceinline__ double eval_full(const Cand &c, int M, double reg_mu, double psi_bound, bool same_point PROF_PARAM)
 {
     long long pt = PROF_NOW();
     const int tid = opaque_tid();
@@ -791,6 +810,21 @@ __device__ __forceinline__ double eval_full(const Cand &c, int M, double reg_mu,
     const int *rbp = RBP;
     unsigned long long *msl = reinterpret_cast<unsigned long long *>(SD + L::MS);
     const int esz = M > 0 ? c.env_size : 21;
+    double tot[1];
+    // A second evaluation at the point of the last one (newton: EV_RETRY, EV_CHECK): the pixel sums depend on x and, through the fixed-point
+    // scales, on the exponent of psi_bound, on nothing else.  The same scales: the kept sums ARE this pass's, bit for bit.
+    bool again = false;
+    if (same_point && sums_kept<L>(c, M)) again = uni((int)(fxh_hi == KEPT->fxh_hi && fxg_hi == KEPT->fxg_hi && !(KEPT->diag & 1))) != 0;
+    if (again) {
+#ifdef SDSM_PROFILE
+        prof_acc[1]++;
+#endif
+        const double *kh = Hp_tail<L>(c), *kg = kh + c.env_size;
+        for (int e = tid; e < c.env_size; e += L::WGS) Hp[e] = kh[e];
+        for (int i = tid; i < n; i += L::WGS) g[i] = kg[i];
+        tot[0] = KEPT->psi_pix;
+        if (tid == 0 && c.wg == 0) atomicAdd(KEPT->counters, 1ull);
+    } else {                                             // (the pass and its reductions: not indented)
     for (int e = tid; e < esz; e += L::WGS) Hp[e] = 0;
     for (int i = tid; i < n; i += L::WGS) g[i] = 0;
     for (int e = tid; e < 42 * NSLOT; e += L::WGS) msl[e] = 0;
@@ -800,7 +834,6 @@ __device__ __forceinline__ double eval_full(const Cand &c, int M, double reg_mu,
     for (int b = 0; b < 6; b++) rbt[b] = M > 0 ? __builtin_amdgcn_readfirstlane(rbp[M + b]) : 0;
     double *ms = reinterpret_cast<double *>(msl + (tid & (NSLOT - 1)));     // this lane's slot: moment m at ms[2 (m - 1) NSLOT] (high word) and ms[(2 (m - 1) + 1) NSLOT]
     const bool hfast = c.hzmax <= HZREG;
-    double tot[1];
     run_pass<L, 1>(c, tot, [&](int p, bool active, double (&pv)[1]) {
         RunPix rp;
         const int pl = load_pos(c, p, active);
@@ -950,24 +983,31 @@ __device__ __forceinline__ double eval_full(const Cand &c, int M, double reg_mu,
     }
     __syncthreads();
     if (c.wG > 1) wide_finish<L, 1>(c, tot, Hp, M > 0 ? c.env_size : 0, g + 6, M, reinterpret_cast<double *>(mraw), 42);
+    const bool keep = sums_kept<L>(c, M);
+    double *kh = Hp_tail<L>(c), *kg = kh + c.env_size;    // (only written if keep)
     {
         const double uh = fx_unit(fxh_hi), ug = fx_unit(fxg_hi);
         if (M > 0) {
-            for (int e = tid; e < c.env_size; e += L::WGS) Hp[e] = fx_get(Hp[e], uh);
-            for (int i = 6 + tid; i < n; i += L::WGS) g[i] = fx_get(g[i], ug);
+            for (int e = tid; e < c.env_size; e += L::WGS) { const double v = fx_get(Hp[e], uh); Hp[e] = v; if (keep) kh[e] = v; }
+            for (int i = 6 + tid; i < n; i += L::WGS) { const double v = fx_get(g[i], ug); g[i] = v; if (keep) kg[i] = v; }
         }
         if (tid < 21) tot22[1 + tid] = fx_get2(reinterpret_cast<double *>(mraw)[2 * tid], reinterpret_cast<double *>(mraw)[2 * tid + 1], tid < 6 ? ug : uh);
     }
     __syncthreads();
-    if (tid < 6) g[tid] = moment_grad(tot22, tid);
+    if (tid < 6) { const double v = moment_grad(tot22, tid); g[tid] = v; if (keep) kg[tid] = v; }
     if (tid < 21) {
         if (M == 0) Hp[tid] = moment_hess(tot22, tid);           // packed lower triangle of a 6x6 matrix = the same enumeration order
         else {
             int a = 0;
             while ((a + 1) * (a + 2) / 2 <= tid) a++;
-            Hp[rbp[M + a] + M + (tid - a * (a + 1) / 2)] = moment_hess(tot22, tid);   // theta-theta block: columns M .. M + a of row M + a
+            const int e = rbp[M + a] + M + (tid - a * (a + 1) / 2);
+            const double v = moment_hess(tot22, tid);             // theta-theta block: columns M .. M + a of row M + a
+            Hp[e] = v;
+            if (keep) kh[e] = v;
         }
     }
+    if (keep && tid == 0) { KEPT->psi_pix = tot[0]; KEPT->fxh_hi = fxh_hi; KEPT->fxg_hi = fxg_hi; }
+    }                                                    // !again
     double psi = tot[0];
     __syncthreads();
     if (M > 0) psi += add_regulariser<L>(c, M, reg_mu);
@@ -1458,7 +1498,9 @@ __device__ __forceinline__ int newton(const Cand &c, int M, int max_iters, doubl
     double psi = NAN, f = NAN, lam2 = 0;                     // f, lam2 describe x (kept across a speculative evaluation)
     double bound = uni(psi_start_bound);                     // an upper bound of psi at the point of the next evaluation (fx_exponents); infinity: none
     for (;;) {
-        const double pe = eval_full<L>(c, M, why == EV_SPEC ? mu_spec : mu, bound PROF_ARG);
+        // (EV_RETRY, EV_CHECK: at the point of the last evaluation -- both follow a factor_solve of the Hessian of exactly that evaluation;
+        // a rejected speculative step goes on to the line search and a new iterate -- eval_full takes the sums it kept there)
+        const double pe = eval_full<L>(c, M, why == EV_SPEC ? mu_spec : mu, bound, why == EV_RETRY || why == EV_CHECK PROF_ARG);
         (*ev_full)++;
         long long pt = PROF_NOW();
         bool line = false;
@@ -1877,6 +1919,7 @@ __global__ __launch_bounds__(WGSIZE, WPE) void sdsm_k_solve(BatchParams P, int h
     // picks an instruction, the pixel passes of the other candidates of the compute unit fill the gaps (+2 % on the 8-image launch).
     __builtin_amdgcn_s_setprio(2);
     const int tid = threadIdx.x;
+    if (tid == 0) { KEPT->diag = P.pad2; KEPT->counters = reinterpret_cast<unsigned long long *>(P.cls_count + SDSM_SOLVER_COUNTERS); }   // once per workgroup (a barrier follows)
     load_log_table(tid);
     if constexpr (!WIDE) {                                   // (one call site of the solver per kernel: the groups take entry `ticket`, everybody else pops)
         // Class 1 too (round 4): with one workgroup per candidate the hardware deals workgroup b to compute-unit die b mod 8 IN ORDER -- a die whose
@@ -1969,7 +2012,7 @@ __global__ __launch_bounds__(WGSIZE) void sdsm_k_eval(BatchParams P, int nprev, 
     long long prof_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
     const double psi_value = eval_value<L>(c, L::X, M);
-    const double psi_full = eval_full<L>(c, M, 0.0, psi_value PROF_ARG);
+    const double psi_full = eval_full<L>(c, M, 0.0, psi_value, false PROF_ARG);
     __syncthreads();
     if (tid == 0) {
         double Rm[6][6];                                   // theta_local = Rm theta_global (reparam is linear in theta)

@@ -257,6 +257,14 @@ class Batch:
             torch.cuda.current_stream().synchronize()
         return cur[0].numpy()[:need[0]].view(_capi.RECORD_DTYPE)[:self.n], cur[1].numpy()[:need[1]]
 
+    def solver_counters(self):
+        """Event counters of the last launch (sdsm_batch_solver_counters; synchronises): full evaluations served from the sums kept
+        at an unchanged iterate."""
+        out = np.zeros(4, np.int64)
+        with torch.cuda.device(self.image.device):
+            _capi.check(_capi.lib().sdsm_batch_solver_counters(self.plan, _ptr(self.ws), out.ctypes.data_as(C.c_void_p)), 'sdsm_batch_solver_counters')
+        return dict(evals_reused=int(out[0]))
+
     def records(self):
         return self.records_dev.cpu().numpy().view(_capi.RECORD_DTYPE)[:self.n].copy()
 

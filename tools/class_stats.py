@@ -38,9 +38,10 @@ for nm, m in (('K1', k1 & ~grp), ('K1b', k1b & ~grp), ('K2', k2 & ~grp), ('K2b',
         print(nm, 'cands', m.sum(), 'sum ms %.1f' % tot[m].sum(), 'median ms %.2f' % np.median(tot[m]), 'max ms %.2f' % tot[m].max(), 'M median', int(np.median(recs['n_deform'][m])), 'M max', int(recs['n_deform'][m].max()),
               'env median', int(np.median(env[m])), 'env max', env[m].max(), 'N median', int(np.median(N[m])), 'N max', int(N[m].max()))
 print('env percentiles', np.percentile(env, [50, 75, 90, 95, 99, 100]).astype(int), 'n percentiles', np.percentile(n, [50, 75, 90, 95, 99, 100]).astype(int))
-print('slowest candidates (ms, N, M, env, evals full/value, phases A / factor / line search):')
+print('full evaluations served from kept sums (slot 1): %d of %d of the candidates with M > 0' % (int(p[:, 1].sum()), int(recs['evals_full'][recs['n_deform'] > 0].sum())))
+print('slowest candidates (ms, N, M, env, evals full (served from kept sums)/value, phases A / factor / line search):')
 for k in np.argsort(-tot)[:12]:
-    print('  %.2f  N=%d M=%d env=%d evals=%d/%d  A=%.2f fac=%.2f ls=%.2f' % (tot[k], N[k], recs['n_deform'][k], env[k], recs['evals_full'][k], recs['evals_value'][k], p[k, 0] / 2.4e6, p[k, 3] / 2.4e6, p[k, 4] / 2.4e6))
+    print('  %.2f  N=%d M=%d env=%d evals=%d (%d)/%d  A=%.2f fac=%.2f ls=%.2f' % (tot[k], N[k], recs['n_deform'][k], env[k], recs['evals_full'][k], int(p[k, 1]), recs['evals_value'][k], p[k, 0] / 2.4e6, p[k, 3] / 2.4e6, p[k, 4] / 2.4e6))
 print('factor_solve parts of the slowest candidates, ms: head | diag block, trailing update, barrier wait, write-back (panel loop, thread 0) | after loop | norm + back substitution')
 for k in np.argsort(-tot)[:6]:
     print('  N=%d M=%d: %.2f | %.2f %.2f %.2f %.2f | %.2f | %.2f   (factorisations: %d)' % (N[k], recs['n_deform'][k], p[k, 13] / 2.4e6, p[k, 8] / 2.4e6, p[k, 9] / 2.4e6, p[k, 10] / 2.4e6, p[k, 11] / 2.4e6,
