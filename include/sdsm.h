@@ -471,6 +471,53 @@ int sdsm_render_graph_multi(const sdsm_set_image *images, int n_images, int n_pr
                             double disk_radius, int line_reach, int core_d2, int ring_d2, const double *colors, const double *d_base,
                             int channels, int32_t *d_key, uint8_t *d_out, void *stream);
 
+/* ---- per-object measurement tables (no reference counterpart beyond tests/regression/validate.py:31-36 and the eccentricity of
+ * superdsm/postprocess.py:340-344) ---------------------------------------------------------------------------------------------------
+ * One record per object or per label: the exact integer sums from which superdsm_amd/measure.py derives counts, sizes, positions,
+ * shapes and intensities on the host; the definitions the kernels are tested against are its *_host functions.  Conventions as
+ * for the label maps: objects as sdsm_post_objects takes them, sets as a HOST table of sdsm_set_image (1 .. SDSM_MAX_SET_IMAGES images,
+ * H, W <= 65535, H * W < 2^31), pixel buffers packed as the table says, the single-image form is the set of that one image.  Every sum
+ * over pixels is an integer sum and every atomic an integer add / min / max / or: the bytes do not depend on the order, the launch or
+ * the set size, and a second launch gives the same bytes.
+ *
+ * Ranges: r, c <= 65534 and area < 2^31, so sum_rr < 2^63 and nothing wraps.
+ * Intensities (d_g, float64, optional): per image, e is the smallest exponent with (max finite |g|) < 2^e, clamped to -960 .. 1024, 0 for
+ * an image without a non-zero finite pixel.  A finite pixel adds q = rint(ldexp(g, 62 - e)) as a signed 64-bit integer: its bits
+ * 0 .. 31 to gsum_lo, the arithmetic shift q >> 32 to gsum_hi; the sum is (gsum_hi * 2^32 + gsum_lo) * 2^(e - 62), exact up to half a
+ * quantum 2^(e - 62) per pixel.  A non-finite pixel sets flag bit 1 and adds nothing.  A first kernel leaves each image's max finite
+ * |g| in d_gmax_abs (n_images float64) and the measuring kernels take e from there; d_scale_exp (n_images int32, may be NULL) receives
+ * e.  Without d_g both may be NULL, the intensity fields are those of an object without a finite pixel and e is 0.  112 bytes. */
+typedef struct {
+    int64_t area;                       /* pixels */
+    int64_t sum_r, sum_c;               /* sums of the row / column indices, image coordinates */
+    uint64_t sum_rr, sum_rc, sum_cc;    /* sums of r * r, r * c, c * c */
+    int32_t r0, c0, r1, c1;             /* bounding box of the pixels, end exclusive; all 0 when area == 0 */
+    int32_t flags;                      /* bit 0: the box touches the image border; bit 1: a non-finite intensity inside */
+    int32_t scale_exp;                  /* e of the record's image */
+    int64_t n_finite;                   /* pixels with a finite intensity */
+    uint64_t gsum_lo;                   /* low limb of the intensity sum */
+    int64_t gsum_hi;                    /* high limb of the intensity sum */
+    double gmin, gmax;                  /* over the finite pixels (-0.0 reads +0.0); +inf / -inf when there are none */
+} sdsm_measure_record;
+/* One record per object (one workgroup each, no global atomics): d_out[i] for object i of d_boxes / d_bits_off (n of them; d_obj_image
+ * int32, NULL for one image).  Objects may overlap.  The bits of a fragment's last word past h * w are ignored; a fragment without a set
+ * bit, and an object whose box is empty or leaves its image, give the zero record (all integers 0 but scale_exp; gmin, gmax +inf, -inf). */
+int sdsm_measure_objects(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, const double *d_g,
+                         double *d_gmax_abs, int32_t *d_scale_exp, sdsm_measure_record *d_out, void *stream);
+int sdsm_measure_objects_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                               const int64_t *d_bits_off, const uint32_t *d_bits, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp,
+                               sdsm_measure_record *d_out, void *stream);
+/* One record per label of a label map (d_labels int32, packed): image i owns the records rec_off[i] + label of d_out for the labels
+ * 0 .. n_labels[i] - 1 (rec_off, n_labels: HOST arrays; 1 <= n_labels <= SDSM_MEASURE_MAX_LABELS; the ranges must not overlap).  The
+ * call clears them; an absent label keeps the zero record.  A label outside 0 .. n_labels[i] - 1 is counted in d_bad[i] (int32 per
+ * image, cleared by the call) and skipped. */
+#define SDSM_MEASURE_MAX_LABELS 65536
+int sdsm_measure_labels(int H, int W, const int32_t *d_labels, int n_labels, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp,
+                        sdsm_measure_record *d_out, int32_t *d_bad, void *stream);
+int sdsm_measure_labels_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int64_t *rec_off,
+                              const int32_t *n_labels, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp,
+                              sdsm_measure_record *d_out, int32_t *d_bad, void *stream);
+
 /* ---- host-side combinatorial steps of the stage (no device access) -------------------------------------------------------------
  * Approximate min-weight set cover (superdsm/minsetcover.py:4-88: greedy + merge phase, retried with beta * gamma on up to max_iter
  * levels) and greedy max-weight set packing (superdsm/maxsetpack.py:8-24) over n objects whose footprints are bit sets of `words`

@@ -44,6 +44,20 @@ RENDER_MAX_COLORS = 1024     # SDSM_RENDER_MAX_COLORS: entries of a colour map o
 RENDER_MAX_SEED_RADIUS = 64  # SDSM_RENDER_MAX_SEED_RADIUS: largest seed disk (with its rim) of the graph kernel
 RENDER_ENTRY_DTYPE = np.dtype([('idx', 'i4'), ('label', 'i4'), ('dist', 'f8')])   # sdsm_render_entry
 assert RENDER_ENTRY_DTYPE.itemsize == 16
+MEASURE_MAX_LABELS = 65536   # SDSM_MEASURE_MAX_LABELS: labels 0 .. 65535 per image of the label form of the measurement tables
+_MEASURE_FIELDS = [('area', 'i8'), ('sum_r', 'i8'), ('sum_c', 'i8'), ('sum_rr', 'u8'), ('sum_rc', 'u8'), ('sum_cc', 'u8'),
+                   ('r0', 'i4'), ('c0', 'i4'), ('r1', 'i4'), ('c1', 'i4'), ('flags', 'i4'), ('scale_exp', 'i4'),
+                   ('n_finite', 'i8'), ('gsum_lo', 'u8'), ('gsum_hi', 'i8'), ('gmin', 'f8'), ('gmax', 'f8')]
+MEASURE_RECORD_DTYPE = np.dtype(_MEASURE_FIELDS)                                   # sdsm_measure_record
+assert MEASURE_RECORD_DTYPE.itemsize == 112
+
+
+class MeasureRecord(C.Structure):
+    """sdsm_measure_record: the exact integer sums of one object or label."""
+    _fields_ = [(name, {'i8': C.c_int64, 'u8': C.c_uint64, 'i4': C.c_int32, 'f8': C.c_double}[kind]) for name, kind in _MEASURE_FIELDS]
+
+
+assert C.sizeof(MeasureRecord) == 112 and all(getattr(MeasureRecord, n).offset == MEASURE_RECORD_DTYPE.fields[n][1] for n, _ in _MEASURE_FIELDS)
 
 
 class SetImage(C.Structure):
@@ -139,6 +153,10 @@ SYMBOLS = {
                                           _vp, C.POINTER(C.c_double), _i32, _vp, _vp, _vp]),
     'sdsm_render_graph': (_i32, [_i32, _i32, _i32, _vp, _f64, _f64, _i32, _i32, _i32, C.POINTER(C.c_double), _vp, _i32, _vp, _vp, _vp]),
     'sdsm_render_graph_multi': (_i32, [C.POINTER(SetImage), _i32, _i32, _vp, _f64, _f64, _i32, _i32, _i32, C.POINTER(C.c_double), _vp, _i32, _vp, _vp, _vp]),
+    'sdsm_measure_objects': (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_measure_objects_multi': (_i32, [C.POINTER(SetImage), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_measure_labels': (_i32, [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_measure_labels_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp, _vp]),
     'sdsm_minsetcover': (_i32, [_i32, _i32, _vp, _vp, _f64, _i32, _i32, _f64, _vp, _vp]),
     'sdsm_minsetcover_multi': (_i32, [_i32, _vp, _vp, _vp, _vp, _f64, _i32, _i32, _f64, _vp, _vp]),
     'sdsm_maxsetpack': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp]),

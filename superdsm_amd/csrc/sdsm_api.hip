@@ -1223,6 +1223,61 @@ extern "C" int sdsm_render_graph(int H, int W, int n_prims, const int32_t *d_pri
     return sdsm_render_graph_multi(&one, 1, n_prims, d_prims, rim_radius, disk_radius, line_reach, core_d2, ring_d2, colors, d_base, channels, d_key, d_out, stream);
 }
 
+// ---- per-object measurement tables (sdsm_measure.hip) ------------------------------------------------------------------------------
+extern "C" hipError_t sdsm_measure_objects_impl(const sdsm_set_image *images, int n_images, int n, const int32_t *obj_image, const int32_t *boxes,
+                                                const int64_t *bits_off, const uint32_t *bits, const double *d_g, double *d_gmax_abs,
+                                                int32_t *d_scale_exp, sdsm_measure_record *out, hipStream_t stream);
+extern "C" hipError_t sdsm_measure_labels_impl(const sdsm_set_image *images, int n_images, const int32_t *labels, const int64_t *rec_off,
+                                               const int32_t *n_labels, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp,
+                                               sdsm_measure_record *out, int32_t *bad, hipStream_t stream);
+
+extern "C" int sdsm_measure_objects_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                                          const int64_t *d_bits_off, const uint32_t *d_bits, const double *d_g, double *d_gmax_abs,
+                                          int32_t *d_scale_exp, sdsm_measure_record *d_out, void *stream)
+{
+    SET_TABLE("sdsm_measure_objects", SET_SIDES | SET_PIXELS);
+    if (n < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_measure_objects: n < 0");
+    if (d_g && !d_gmax_abs) return fail(SDSM_ERR_ARGUMENT, "sdsm_measure_objects: intensities need d_gmax_abs");
+    if (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_out || (n_images > 1 && !d_obj_image)))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_measure_objects: null argument");
+    hipError_t e = sdsm_measure_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_g, d_gmax_abs, d_scale_exp, d_out,
+                                             (hipStream_t)stream);
+    SET_DONE("sdsm_measure_objects");
+}
+
+extern "C" int sdsm_measure_objects(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, const double *d_g,
+                                    double *d_gmax_abs, int32_t *d_scale_exp, sdsm_measure_record *d_out, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_measure_objects_multi(&one, 1, n, nullptr, d_boxes, d_bits_off, d_bits, d_g, d_gmax_abs, d_scale_exp, d_out, stream);
+}
+
+extern "C" int sdsm_measure_labels_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int64_t *rec_off,
+                                         const int32_t *n_labels, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp,
+                                         sdsm_measure_record *d_out, int32_t *d_bad, void *stream)
+{
+    SET_TABLE("sdsm_measure_labels", SET_SIDES | SET_PIXELS);
+    if (!d_labels || !rec_off || !n_labels || !d_out || !d_bad) return fail(SDSM_ERR_ARGUMENT, "sdsm_measure_labels: null argument");
+    if (d_g && !d_gmax_abs) return fail(SDSM_ERR_ARGUMENT, "sdsm_measure_labels: intensities need d_gmax_abs");
+    for (int i = 0; i < n_images; i++) {
+        if (n_labels[i] < 1 || n_labels[i] > SDSM_MEASURE_MAX_LABELS || rec_off[i] < 0)
+            return fail(SDSM_ERR_ARGUMENT, "sdsm_measure_labels: 1 <= n_labels <= 65536 and rec_off >= 0 required");
+        for (int j = 0; j < i; j++)
+            if (rec_off[i] < rec_off[j] + n_labels[j] && rec_off[j] < rec_off[i] + n_labels[i])
+                return fail(SDSM_ERR_ARGUMENT, "sdsm_measure_labels: the records of two images overlap");
+    }
+    hipError_t e = sdsm_measure_labels_impl(images, n_images, d_labels, rec_off, n_labels, d_g, d_gmax_abs, d_scale_exp, d_out, d_bad, (hipStream_t)stream);
+    SET_DONE("sdsm_measure_labels");
+}
+
+extern "C" int sdsm_measure_labels(int H, int W, const int32_t *d_labels, int n_labels, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp,
+                                   sdsm_measure_record *d_out, int32_t *d_bad, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    const int64_t off = 0;
+    return sdsm_measure_labels_multi(&one, 1, d_labels, &off, &n_labels, d_g, d_gmax_abs, d_scale_exp, d_out, d_bad, stream);
+}
+
 extern "C" int sdsm_post_background_multi(const sdsm_post_bg_image *images, int n_images, const int32_t *d_boxes, const int64_t *d_bits_off,
                                           const uint32_t *d_bits, int radius, void *stream)
 {

@@ -1,0 +1,420 @@
+// Per-object measurement tables on the GPU: one sdsm_measure_record per object (bit-packed fragments) or per label (label maps),
+// for one image or a set of images.  No reference counterpart beyond a test helper (tests/regression/validate.py:31-36: area and
+// centre of mass per label) and one regionprops(...).eccentricity call (superdsm/postprocess.py:340-344); the definition every kernel
+// is tested against is the host code of superdsm_amd/measure.py.
+//
+//   k_absmax            max finite |g| per image (integer atomic on the bits of a non-negative double), from which the measuring
+//                       kernels take the exponent e of the image's intensity quantum 2^(e - 62) without a host round trip
+//   k_measure_objects   one workgroup per object: the set bits of the fragment by ctz, 64-bit sums in registers, one reduction of the
+//                       workgroup through LDS, no global atomics
+//   k_measure_labels    one workgroup per band of LBAND consecutive pixels (raster order) of one image: a thread owns segments of LSEG
+//                       pixels and keeps the sums of its current label in registers while the label does not change; on a change
+//                       it flushes into an LDS table keyed by label (open addressing, claimed by compare-and-swap, 64-bit LDS adds);
+//                       the occupied slots go to the global records by 64-bit integer atomics at the end of the band.  A label
+//                       without a free slot goes straight to the global atomics.
+//   k_labels_init / k_labels_finish   the identities of the atomics before, the record's final form after
+//
+// Every sum over pixels is an integer sum and every atomic an integer add / min / max / or, so the bytes do not depend on the order,
+// the launch or the set size.  Intensities enter as q = rint(ldexp(g, 62 - e)) in two limbs (bits 0-31, and q >> 32).
+#include "sdsm_common.h"
+#include "sdsm_set.h"
+#include <climits>
+
+namespace {
+
+constexpr int MTPB = 256;
+constexpr int ABS_PIX = 2048;                    // k_absmax: pixels per workgroup
+constexpr int LSEG = 16;                         // k_measure_labels: consecutive pixels of a thread's segment (64 B of labels)
+constexpr int LBAND = 16384;                     //   pixels of a band: 4 segments per thread
+constexpr int LSLOTS = 256;                      //   slots of the LDS table (28 KB: 5 workgroups per compute unit)
+constexpr int LPROBES = 16;                      //   slots tried before a label goes to the global atomics
+constexpr int FIN_RECS = MTPB;                   // k_labels_init / k_labels_finish: records per workgroup
+
+typedef unsigned long long u64;
+typedef long long i64;
+
+struct MSet {                                    // the images of a launch
+    int32_t n;
+    int32_t H[SDSM_MAX_SET_IMAGES], W[SDSM_MAX_SET_IMAGES];
+    int64_t off[SDSM_MAX_SET_IMAGES];            // first pixel of the image in the packed buffers
+    int64_t rec_off[SDSM_MAX_SET_IMAGES];        // labels: first record of the image
+    int32_t n_labels[SDSM_MAX_SET_IMAGES];
+    int32_t start[SDSM_MAX_SET_IMAGES + 1];      // flattened grid: first workgroup of the image
+};
+
+// the sums of a set of pixels, and how two of them combine
+struct Acc {
+    i64 area, sum_r, sum_c, n_finite, ghi;
+    u64 sum_rr, sum_rc, sum_cc, glo, kmin, kmax;     // kmin / kmax: monotone keys of gmin / gmax
+    int32_t r0, c0, r1, c1, flags;
+};
+
+__device__ __forceinline__ void acc_clear(Acc &a)
+{
+    a.area = a.sum_r = a.sum_c = a.n_finite = a.ghi = 0;
+    a.sum_rr = a.sum_rc = a.sum_cc = a.glo = 0;
+    a.kmin = ~0ull; a.kmax = 0;
+    a.r0 = a.c0 = INT_MAX; a.r1 = a.c1 = 0; a.flags = 0;
+}
+
+// the monotone 64-bit key of a double: a < b iff key(a) < key(b); -0.0 is made +0.0 first
+__device__ __forceinline__ u64 dkey(double v)
+{
+    if (v == 0.0) v = 0.0;
+    const u64 b = (u64)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | (1ull << 63));
+}
+
+__device__ __forceinline__ double dkey_inv(u64 k)
+{
+    return __longlong_as_double((i64)((k >> 63) ? (k & ~(1ull << 63)) : ~k));
+}
+
+// e of an image from the bits of its max finite |g|: the smallest e with max < 2^e, clamped to -960 .. 1024; 0 without a non-zero pixel
+__device__ __forceinline__ int scale_exp(u64 maxbits)
+{
+    if (maxbits == 0) return 0;
+    const int E = (int)(maxbits >> 52);
+    const int e = E == 0 ? -960 : E - 1022;
+    return e < -960 ? -960 : e;
+}
+
+__device__ __forceinline__ void acc_pixel(Acc &a, int r, int c)
+{
+    a.area++;
+    a.sum_r += r; a.sum_c += c;
+    a.sum_rr += (u64)((uint32_t)r * (uint32_t)r);           // r, c <= 65534: the products fit 32 bits
+    a.sum_rc += (u64)((uint32_t)r * (uint32_t)c);
+    a.sum_cc += (u64)((uint32_t)c * (uint32_t)c);
+    a.r0 = r < a.r0 ? r : a.r0; a.r1 = r + 1 > a.r1 ? r + 1 : a.r1;
+    a.c0 = c < a.c0 ? c : a.c0; a.c1 = c + 1 > a.c1 ? c + 1 : a.c1;
+}
+
+__device__ __forceinline__ void acc_intensity(Acc &a, double g, int shift)
+{
+    const u64 b = (u64)__double_as_longlong(g);
+    if (((b >> 52) & 0x7ff) == 0x7ff) { a.flags |= 2; return; }     // inf / NaN: counted by the flag, adds nothing
+    const i64 q = (i64)rint(ldexp(g, shift));                        // |q| <= 2^62
+    a.n_finite++;
+    a.glo += (u64)(uint32_t)q;
+    a.ghi += q >> 32;
+    const u64 k = dkey(g);
+    a.kmin = k < a.kmin ? k : a.kmin; a.kmax = k > a.kmax ? k : a.kmax;
+}
+
+__device__ __forceinline__ void acc_merge(Acc &a, const Acc &b)
+{
+    a.area += b.area; a.sum_r += b.sum_r; a.sum_c += b.sum_c; a.n_finite += b.n_finite; a.ghi += b.ghi;
+    a.sum_rr += b.sum_rr; a.sum_rc += b.sum_rc; a.sum_cc += b.sum_cc; a.glo += b.glo;
+    a.kmin = b.kmin < a.kmin ? b.kmin : a.kmin; a.kmax = b.kmax > a.kmax ? b.kmax : a.kmax;
+    a.r0 = b.r0 < a.r0 ? b.r0 : a.r0; a.c0 = b.c0 < a.c0 ? b.c0 : a.c0;
+    a.r1 = b.r1 > a.r1 ? b.r1 : a.r1; a.c1 = b.c1 > a.c1 ? b.c1 : a.c1;
+    a.flags |= b.flags;
+}
+
+__device__ __forceinline__ Acc acc_shfl_down(const Acc &a, int o)
+{
+    Acc b;
+    b.area = __shfl_down(a.area, o); b.sum_r = __shfl_down(a.sum_r, o); b.sum_c = __shfl_down(a.sum_c, o);
+    b.n_finite = __shfl_down(a.n_finite, o); b.ghi = __shfl_down(a.ghi, o);
+    b.sum_rr = __shfl_down(a.sum_rr, o); b.sum_rc = __shfl_down(a.sum_rc, o); b.sum_cc = __shfl_down(a.sum_cc, o);
+    b.glo = __shfl_down(a.glo, o); b.kmin = __shfl_down(a.kmin, o); b.kmax = __shfl_down(a.kmax, o);
+    b.r0 = __shfl_down(a.r0, o); b.c0 = __shfl_down(a.c0, o); b.r1 = __shfl_down(a.r1, o); b.c1 = __shfl_down(a.c1, o);
+    b.flags = __shfl_down(a.flags, o);
+    return b;
+}
+
+// the record of a set of pixels of an H x W image (area == 0: the zero record)
+__device__ __forceinline__ void write_record(sdsm_measure_record *out, const Acc &a, int H, int W, int e)
+{
+    sdsm_measure_record R;
+    const bool any = a.area > 0;
+    R.area = a.area; R.sum_r = a.sum_r; R.sum_c = a.sum_c;
+    R.sum_rr = a.sum_rr; R.sum_rc = a.sum_rc; R.sum_cc = a.sum_cc;
+    R.r0 = any ? a.r0 : 0; R.c0 = any ? a.c0 : 0; R.r1 = any ? a.r1 : 0; R.c1 = any ? a.c1 : 0;
+    R.flags = any ? ((a.flags & 2) | ((a.r0 == 0 || a.c0 == 0 || a.r1 == H || a.c1 == W) ? 1 : 0)) : 0;
+    R.scale_exp = e;
+    R.n_finite = a.n_finite; R.gsum_lo = a.glo; R.gsum_hi = a.ghi;
+    R.gmin = a.n_finite > 0 ? dkey_inv(a.kmin) : __longlong_as_double(0x7ff0000000000000ll);
+    R.gmax = a.n_finite > 0 ? dkey_inv(a.kmax) : __longlong_as_double((i64)0xfff0000000000000ull);
+    *out = R;
+}
+
+// ---- max finite |g| per image ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MTPB) void k_absmax(MSet S, const double *g_, u64 *maxbits)
+{
+    const int im = set_find(S.start, S.n, blockIdx.x);
+    const int64_t px = (int64_t)S.H[im] * S.W[im];
+    const int64_t p0 = (int64_t)(blockIdx.x - S.start[im]) * ABS_PIX;
+    const double *g = g_ + S.off[im];
+    u64 m = 0;
+    for (int e = threadIdx.x; e < ABS_PIX; e += MTPB) {
+        const int64_t p = p0 + e;
+        if (p >= px) break;
+        const u64 b = (u64)__double_as_longlong(g[p]) & ~(1ull << 63);
+        if ((b >> 52) != 0x7ff && b > m) m = b;
+    }
+    for (int o = 32; o > 0; o >>= 1) { const u64 t = __shfl_down(m, o); m = t > m ? t : m; }
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(maxbits + im, m);
+}
+
+__global__ __launch_bounds__(MTPB) void k_scale_exp(int n, const u64 *maxbits, int32_t *out)
+{
+    const int i = blockIdx.x * MTPB + threadIdx.x;
+    if (i < n) out[i] = maxbits ? scale_exp(maxbits[i]) : 0;
+}
+
+// ---- objects: one workgroup per fragment ----------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MTPB) void k_measure_objects(MSet S, const int32_t *obj_image, const int32_t *boxes, const int64_t *bits_off,
+                                                          const uint32_t *bits_, const double *g_, const u64 *maxbits, sdsm_measure_record *out)
+{
+    __shared__ Acc part[MTPB / 64];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const int im = obj_image ? obj_image[i] : 0;
+    Acc a;
+    acc_clear(a);
+    if (im < 0 || im >= S.n) {                   // (the caller checks this; nothing of another image is read)
+        if (tid == 0) write_record(out + i, a, 0, 0, 0);
+        return;
+    }
+    const int H = S.H[im], W = S.W[im];
+    const int r0 = boxes[4 * i], c0 = boxes[4 * i + 1], h = boxes[4 * i + 2], w = boxes[4 * i + 3];
+    const int e = g_ ? scale_exp(maxbits[im]) : 0;
+    const bool inside = r0 >= 0 && c0 >= 0 && h >= 1 && w >= 1 && h <= H && w <= W && r0 <= H - h && c0 <= W - w;
+    if (inside) {                                // a box that leaves its image gives the zero record: no pixel outside is read
+        const uint32_t *bits = bits_ + bits_off[i];
+        const double *g = g_ ? g_ + S.off[im] : nullptr;
+        const uint32_t n_bits = (uint32_t)h * (uint32_t)w, n_words = (n_bits + 31) >> 5;
+        for (uint32_t k = tid; k < n_words; k += MTPB) {
+            uint32_t word = bits[k];
+            if (k == n_words - 1 && (n_bits & 31)) word &= (1u << (n_bits & 31)) - 1;       // the bits past h * w are not the object's
+            while (word) {
+                const uint32_t b = (k << 5) + (uint32_t)__builtin_ctz(word);
+                word &= word - 1;
+                const int r = r0 + (int)(b / (uint32_t)w), c = c0 + (int)(b % (uint32_t)w);
+                acc_pixel(a, r, c);
+                if (g) acc_intensity(a, g[(int64_t)r * W + c], 62 - e);
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) acc_merge(a, acc_shfl_down(a, o));
+    if ((tid & 63) == 0) part[tid >> 6] = a;
+    __syncthreads();
+    if (tid == 0) {
+        for (int k = 1; k < MTPB / 64; k++) acc_merge(a, part[k]);
+        write_record(out + i, a, H, W, e);
+    }
+}
+
+// ---- labels ------------------------------------------------------------------------------------------------------------------------
+// While the atomics run, a record holds their identities and partial results: r0 / c0 INT_MAX, gmin / gmax as keys; k_labels_finish
+// gives it its final form.
+__global__ __launch_bounds__(MTPB) void k_labels_init(MSet S, sdsm_measure_record *recs, int32_t *bad)
+{
+    const int im = set_find(S.start, S.n, blockIdx.x);
+    const int l = (blockIdx.x - S.start[im]) * FIN_RECS + threadIdx.x;
+    if (blockIdx.x == 0 && threadIdx.x < S.n) bad[threadIdx.x] = 0;
+    if (l >= S.n_labels[im]) return;
+    sdsm_measure_record R;
+    R.area = R.sum_r = R.sum_c = 0; R.sum_rr = R.sum_rc = R.sum_cc = 0;
+    R.r0 = R.c0 = INT_MAX; R.r1 = R.c1 = 0; R.flags = 0; R.scale_exp = 0;
+    R.n_finite = 0; R.gsum_lo = 0; R.gsum_hi = 0;
+    R.gmin = __longlong_as_double(-1ll); R.gmax = __longlong_as_double(0ll);      // keys: ~0 and 0
+    recs[S.rec_off[im] + l] = R;
+}
+
+__global__ __launch_bounds__(MTPB) void k_labels_finish(MSet S, sdsm_measure_record *recs, const u64 *maxbits)
+{
+    const int im = set_find(S.start, S.n, blockIdx.x);
+    const int l = (blockIdx.x - S.start[im]) * FIN_RECS + threadIdx.x;
+    if (l >= S.n_labels[im]) return;
+    sdsm_measure_record *R = recs + S.rec_off[im] + l;
+    Acc a;
+    a.area = R->area; a.sum_r = R->sum_r; a.sum_c = R->sum_c; a.n_finite = R->n_finite; a.ghi = R->gsum_hi;
+    a.sum_rr = R->sum_rr; a.sum_rc = R->sum_rc; a.sum_cc = R->sum_cc; a.glo = R->gsum_lo;
+    a.kmin = (u64)__double_as_longlong(R->gmin); a.kmax = (u64)__double_as_longlong(R->gmax);
+    a.r0 = R->r0; a.c0 = R->c0; a.r1 = R->r1; a.c1 = R->c1; a.flags = R->flags;
+    write_record(R, a, S.H[im], S.W[im], maxbits ? scale_exp(maxbits[im]) : 0);
+}
+
+// the sums of one label into its global record, by integer atomics (zero terms are left out)
+__device__ __forceinline__ void emit_global(sdsm_measure_record *R, const Acc &a)
+{
+    atomicAdd((u64 *)&R->area, (u64)a.area);
+    atomicAdd((u64 *)&R->sum_r, (u64)a.sum_r);
+    atomicAdd((u64 *)&R->sum_c, (u64)a.sum_c);
+    atomicAdd((u64 *)&R->sum_rr, a.sum_rr);
+    atomicAdd((u64 *)&R->sum_rc, a.sum_rc);
+    atomicAdd((u64 *)&R->sum_cc, a.sum_cc);
+    atomicMin(&R->r0, a.r0); atomicMin(&R->c0, a.c0);
+    atomicMax(&R->r1, a.r1); atomicMax(&R->c1, a.c1);
+    if (a.flags) atomicOr(&R->flags, a.flags);
+    if (a.n_finite) {
+        atomicAdd((u64 *)&R->n_finite, (u64)a.n_finite);
+        atomicAdd((u64 *)&R->gsum_lo, a.glo);
+        atomicAdd((u64 *)&R->gsum_hi, (u64)a.ghi);
+        atomicMin((u64 *)&R->gmin, a.kmin);
+        atomicMax((u64 *)&R->gmax, a.kmax);
+    }
+}
+
+struct LTable {                                  // the per-workgroup table, one array per field: a slot is one index
+    int32_t key[LSLOTS];                         // -1: free
+    u64 area[LSLOTS], sum_r[LSLOTS], sum_c[LSLOTS], sum_rr[LSLOTS], sum_rc[LSLOTS], sum_cc[LSLOTS];
+    u64 n_finite[LSLOTS], glo[LSLOTS], ghi[LSLOTS], kmin[LSLOTS], kmax[LSLOTS];
+    int32_t r0[LSLOTS], c0[LSLOTS], r1[LSLOTS], c1[LSLOTS], flags[LSLOTS];
+};
+
+__device__ __forceinline__ void flush_label(LTable &T, int32_t label, const Acc &a, sdsm_measure_record *recs)
+{
+    uint32_t s = ((uint32_t)label * 2654435761u) >> 24;              // 8 bits = LSLOTS
+    for (int k = 0; k < LPROBES; k++, s = (s + 1) & (LSLOTS - 1)) {
+        const int32_t old = atomicCAS(&T.key[s], -1, label);
+        if (old != -1 && old != label) continue;
+        atomicAdd(&T.area[s], (u64)a.area);
+        atomicAdd(&T.sum_r[s], (u64)a.sum_r);
+        atomicAdd(&T.sum_c[s], (u64)a.sum_c);
+        atomicAdd(&T.sum_rr[s], a.sum_rr);
+        atomicAdd(&T.sum_rc[s], a.sum_rc);
+        atomicAdd(&T.sum_cc[s], a.sum_cc);
+        atomicMin(&T.r0[s], a.r0); atomicMin(&T.c0[s], a.c0);
+        atomicMax(&T.r1[s], a.r1); atomicMax(&T.c1[s], a.c1);
+        if (a.flags) atomicOr(&T.flags[s], a.flags);
+        if (a.n_finite) {
+            atomicAdd(&T.n_finite[s], (u64)a.n_finite);
+            atomicAdd(&T.glo[s], a.glo);
+            atomicAdd(&T.ghi[s], (u64)a.ghi);
+            atomicMin(&T.kmin[s], a.kmin);
+            atomicMax(&T.kmax[s], a.kmax);
+        }
+        return;
+    }
+    emit_global(recs + label, a);                // no slot: correct and slow
+}
+
+__global__ __launch_bounds__(MTPB) void k_measure_labels(MSet S, const int32_t *labels_, const double *g_, const u64 *maxbits,
+                                                         sdsm_measure_record *recs_, int32_t *bad)
+{
+    __shared__ LTable T;
+    static_assert(LSLOTS == 256 && LBAND % (LSEG * MTPB) == 0, "hash width and band size");
+    const int im = set_find(S.start, S.n, blockIdx.x), tid = threadIdx.x;
+    const int W = S.W[im], n_labels = S.n_labels[im];
+    const int64_t px = (int64_t)S.H[im] * W;
+    const int64_t p0 = (int64_t)(blockIdx.x - S.start[im]) * LBAND;
+    const int32_t *lab = labels_ + S.off[im];
+    const double *g = g_ ? g_ + S.off[im] : nullptr;
+    sdsm_measure_record *recs = recs_ + S.rec_off[im];
+    const int shift = 62 - (g ? scale_exp(maxbits[im]) : 0);
+    for (int s = tid; s < LSLOTS; s += MTPB) {
+        T.key[s] = -1;
+        T.area[s] = T.sum_r[s] = T.sum_c[s] = T.sum_rr[s] = T.sum_rc[s] = T.sum_cc[s] = 0;
+        T.n_finite[s] = T.glo[s] = T.ghi[s] = 0; T.kmin[s] = ~0ull; T.kmax[s] = 0;
+        T.r0[s] = T.c0[s] = INT_MAX; T.r1[s] = T.c1[s] = 0; T.flags[s] = 0;
+    }
+    __syncthreads();
+    Acc a;
+    acc_clear(a);
+    int32_t cur = -1;                            // the label whose sums the registers hold; -1: none
+    int n_bad = 0;
+    for (int it = 0; it < LBAND / (LSEG * MTPB); it++) {
+        const int64_t q0 = p0 + ((int64_t)it * MTPB + tid) * LSEG;
+        if (q0 >= px) break;
+        const int n = px - q0 < LSEG ? (int)(px - q0) : LSEG;
+        const bool vec = n == LSEG && (((uintptr_t)(lab + q0)) & 15) == 0;       // 16-byte loads where the segment is whole and aligned
+        int r = (int)(q0 / W), c = (int)(q0 % W);
+        int4 t = make_int4(0, 0, 0, 0);
+#pragma unroll 1
+        for (int k = 0; k < n; k++) {            // (one flush site: the loop stays rolled)
+            if ((k & 3) == 0) {
+                if (vec) t = *(const int4 *)(lab + q0 + k);
+                else { t.x = lab[q0 + k]; t.y = k + 1 < n ? lab[q0 + k + 1] : 0; t.z = k + 2 < n ? lab[q0 + k + 2] : 0; t.w = k + 3 < n ? lab[q0 + k + 3] : 0; }
+            }
+            const int32_t l = (k & 3) == 0 ? t.x : (k & 3) == 1 ? t.y : (k & 3) == 2 ? t.z : t.w;
+            if (l != cur) {
+                if (cur >= 0) flush_label(T, cur, a, recs);
+                acc_clear(a);
+                cur = (l >= 0 && l < n_labels) ? l : -1;
+            }
+            if (cur >= 0) {
+                acc_pixel(a, r, c);
+                if (g) acc_intensity(a, g[q0 + k], shift);
+            } else {
+                n_bad++;
+            }
+            if (++c == W) { c = 0; r++; }
+        }
+    }
+    if (cur >= 0) flush_label(T, cur, a, recs);
+    if (n_bad) atomicAdd(bad + im, n_bad);
+    __syncthreads();
+    for (int s = tid; s < LSLOTS; s += MTPB) {
+        const int32_t label = T.key[s];
+        if (label < 0) continue;
+        Acc t;
+        t.area = (i64)T.area[s]; t.sum_r = (i64)T.sum_r[s]; t.sum_c = (i64)T.sum_c[s]; t.n_finite = (i64)T.n_finite[s]; t.ghi = (i64)T.ghi[s];
+        t.sum_rr = T.sum_rr[s]; t.sum_rc = T.sum_rc[s]; t.sum_cc = T.sum_cc[s]; t.glo = T.glo[s]; t.kmin = T.kmin[s]; t.kmax = T.kmax[s];
+        t.r0 = T.r0[s]; t.c0 = T.c0[s]; t.r1 = T.r1[s]; t.c1 = T.c1[s]; t.flags = T.flags[s];
+        emit_global(recs + label, t);
+    }
+}
+
+MSet make_mset(const sdsm_set_image *images, int n_images)
+{
+    MSet S{};
+    S.n = n_images;
+    for (int i = 0; i < n_images; i++) { S.H[i] = images[i].H; S.W[i] = images[i].W; S.off[i] = images[i].offset; }
+    return S;
+}
+
+void grid_pixels(MSet &S, int per_block)
+{
+    for (int i = 0; i < S.n; i++) S.start[i + 1] = S.start[i] + (int32_t)(((int64_t)S.H[i] * S.W[i] + per_block - 1) / per_block);
+}
+
+void grid_records(MSet &S)
+{
+    for (int i = 0; i < S.n; i++) S.start[i + 1] = S.start[i] + (S.n_labels[i] + FIN_RECS - 1) / FIN_RECS;
+}
+
+// max finite |g| per image into d_gmax_abs (the bits of a non-negative double are ordered as integers) and e into d_scale_exp
+hipError_t launch_scale(MSet S, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp, hipStream_t stream)
+{
+    if (d_g) {
+        hipError_t e = hipMemsetAsync(d_gmax_abs, 0, (size_t)S.n * sizeof(double), stream);
+        if (e != hipSuccess) return e;
+        grid_pixels(S, ABS_PIX);
+        hipLaunchKernelGGL(k_absmax, dim3(S.start[S.n]), dim3(MTPB), 0, stream, S, d_g, (u64 *)d_gmax_abs);
+    }
+    if (d_scale_exp) hipLaunchKernelGGL(k_scale_exp, dim3(1), dim3(MTPB), 0, stream, S.n, d_g ? (const u64 *)d_gmax_abs : nullptr, d_scale_exp);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" hipError_t sdsm_measure_objects_impl(const sdsm_set_image *images, int n_images, int n, const int32_t *obj_image, const int32_t *boxes,
+                                                const int64_t *bits_off, const uint32_t *bits, const double *d_g, double *d_gmax_abs,
+                                                int32_t *d_scale_exp, sdsm_measure_record *out, hipStream_t stream)
+{
+    MSet S = make_mset(images, n_images);
+    hipError_t e = launch_scale(S, d_g, d_gmax_abs, d_scale_exp, stream);
+    if (e != hipSuccess || n == 0) return e;
+    hipLaunchKernelGGL(k_measure_objects, dim3(n), dim3(MTPB), 0, stream, S, obj_image, boxes, bits_off, bits, d_g, (const u64 *)d_gmax_abs, out);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t sdsm_measure_labels_impl(const sdsm_set_image *images, int n_images, const int32_t *labels, const int64_t *rec_off,
+                                               const int32_t *n_labels, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp,
+                                               sdsm_measure_record *out, int32_t *bad, hipStream_t stream)
+{
+    MSet S = make_mset(images, n_images);
+    for (int i = 0; i < n_images; i++) { S.rec_off[i] = rec_off[i]; S.n_labels[i] = n_labels[i]; }
+    hipError_t e = launch_scale(S, d_g, d_gmax_abs, d_scale_exp, stream);
+    if (e != hipSuccess) return e;
+    MSet R = S;
+    grid_records(R);
+    hipLaunchKernelGGL(k_labels_init, dim3(R.start[n_images]), dim3(MTPB), 0, stream, R, out, bad);
+    grid_pixels(S, LBAND);
+    hipLaunchKernelGGL(k_measure_labels, dim3(S.start[n_images]), dim3(MTPB), 0, stream, S, labels, d_g, (const u64 *)d_gmax_abs, out, bad);
+    hipLaunchKernelGGL(k_labels_finish, dim3(R.start[n_images]), dim3(MTPB), 0, stream, R, out, d_g ? (const u64 *)d_gmax_abs : nullptr);
+    return hipGetLastError();
+}
