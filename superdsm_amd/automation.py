@@ -323,15 +323,10 @@ def _expand(cfg, key, factor, default_user_factor, type=None, min=None, max=None
 
 def create_config(pipeline, base_cfg, img=None):
     """Scale-dependent hyper-parameters from ``AF_scale`` or, if that is not set, from the estimated scale of ``img``
-    (automation.py:80-102)."""
-    cfg = base_cfg.copy()
-    scale = cfg.get('AF_scale', None)
-    if scale is None:
-        if img is None:
-            raise ValueError('AF_scale is not set and there is no image to estimate the scale from')
-        scale = _estimate_scale(img, num_radii=10, thresholds=[0.01])[0]
-    _configure(pipeline, cfg, scale)
-    return cfg, scale
+    (automation.py:80-102): the set of this one image (:func:`create_configs`)."""
+    if img is None and base_cfg.copy().get('AF_scale', None) is None:
+        raise ValueError('AF_scale is not set and there is no image to estimate the scale from')
+    return create_configs(pipeline, base_cfg, [img])[0]
 
 
 def _configure(pipeline, cfg, scale):
@@ -342,15 +337,15 @@ def _configure(pipeline, cfg, scale):
 
 
 def create_configs(pipeline, base_cfg, images):
-    """:func:`create_config` for every image of a set: ``(cfg, scale)`` per image.  Without ``AF_scale``, :func:`estimate_scales`
-    estimates the scales of all images in one call."""
+    """The config sequence of automation.py:80-102 for every image of a set: ``(cfg, scale)`` per image.  Without ``AF_scale``,
+    :func:`estimate_scales` estimates the scales of all images in one call."""
     images = list(images)
     scale = base_cfg.copy().get('AF_scale', None)
     scales = [scale] * len(images) if scale is not None else [s[0] for s in estimate_scales(images, num_radii=10, thresholds=[0.01])]
     result = []
     for scale in scales:
         cfg = base_cfg.copy()
-        cfg.get('AF_scale', None)                       # (as create_config: the key is there afterwards, None if it was unset)
+        cfg.get('AF_scale', None)                       # (as the reference's get: the key is there afterwards, None if it was unset)
         _configure(pipeline, cfg, scale)
         result.append((cfg, scale))
     return result

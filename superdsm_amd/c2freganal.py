@@ -5,10 +5,12 @@ Two implementations of one stage live here:
 
 * the definition: a plain, sequential restatement of the reference's ``process`` and ``_process_cluster_impl`` on NumPy / SciPy
   (:func:`region_analysis_host`), which takes the normalised-energy function as a parameter;
-* the GPU path of the stage (:func:`region_analysis_gpu`): the cluster markers and the exact EDT in HIP (``sdsm_c2f_markers``,
-  ``sdsm_edt_exact``), the marker flood in native host code (``sdsm_watershed``), and the split loops of all clusters in lock step:
-  every cluster advances until it needs energies, the requests of all clusters form one round, solved by ``engine.Batch`` plans of
-  at most 16 cluster crops each, all queued on one stream.
+* the GPU path of the stage, for a set of images (:func:`region_analysis_gpu_multi`; :func:`region_analysis_gpu` is the set of one
+  image): the cluster markers and the exact EDT of all images in HIP (``sdsm_c2f_markers_multi``, ``sdsm_edt_exact_multi``), then
+  :func:`region_analysis_lockstep`: the marker flood in native host code (``sdsm_watershed``) and the split loops of all clusters
+  of all images in lock step.  Every cluster advances until it needs energies, the requests of all clusters form one round, solved
+  by ``engine.Batch`` plans of at most 16 cluster crops each, all queued on one stream.  The driver takes the flood and the solver
+  of the rounds as parameters, so it runs without a GPU as well.
 
 Both drive the same split loop (:func:`_split_cluster`, a generator that yields its energy requests).  The conventions the
 restatement fixes where the reference leaves them to scikit-image or to chance are listed in DESIGN.md (row f5): the heap flood of
@@ -388,7 +390,7 @@ def edt_exact_gpu(target):
 
 def markers_and_edt_gpu_multi(ys, max_cluster_marker_irregularity):
     """:func:`cluster_markers_gpu` and then :func:`edt_exact_gpu` of the markers, for a set of images: one packed upload of all ``y``,
-    ``sdsm_c2f_markers_multi`` and ``sdsm_edt_exact_multi`` over up to ``_capi.MAX_SET_IMAGES`` images per call, one download.
+    ``sdsm_c2f_markers_multi`` and ``sdsm_edt_exact_multi`` over up to ``_capi.MAX_SET_IMAGES`` images per call, one download per kind of result.
     ``max_cluster_marker_irregularity``: one threshold for all or one per image.  Returns ``(y_mask, cluster_markers, count,
     distances)`` per image, equal to the single-image functions."""
     torch = _device()
@@ -415,9 +417,11 @@ def markers_and_edt_gpu_multi(ys, max_cluster_marker_irregularity):
                     'sdsm_c2f_markers_multi')
         d_target = (d_markers != 0).to(torch.uint8)
         _capi.check(L.sdsm_edt_exact_multi(table, n, p(d_target), p(d_dist), p(ws), e_bytes, _stream(torch)), 'sdsm_edt_exact_multi')
-        res = d_res.cpu().numpy()
-        dist, markers = lay.unpack(res[:8 * total].view(np.float64)), lay.unpack(res[8 * total:12 * total].view(np.int32))
-        mask, count = lay.unpack(res[12 * total:13 * total]), res[13 * total:].view(np.int32)
+        # one download per kind of result, as the calls for a single image make them: the 13 bytes per pixel in one piece pass the
+        # size (4 MiB) from which the runtime pins the host buffer in place already for one 520 x 696 image, and releasing such a
+        # buffer stalls the queues for 20 - 30 ms in the energy round that follows
+        dist, markers = lay.unpack(d_dist.cpu().numpy()), lay.unpack(d_markers.cpu().numpy())
+        mask, count = lay.unpack(d_mask.cpu().numpy()), d_count.cpu().numpy()
         results += [(mask[k].astype(bool), markers[k], int(count[k]), dist[k]) for k in range(n)]
     return results
 
@@ -561,58 +565,6 @@ class EnergyRounds:
         return results
 
 
-def region_analysis_gpu(y, dsm_cfg, **params):
-    """The stage's GPU path; returns ``(outputs, stats)`` with the wall clock of every phase and the log of the energy rounds."""
-    torch = _device()
-    params = _params(**params)
-    dsm_cfg = dict(dsm_cfg)
-    dsm_cfg['smooth_amount'] = np.inf
-    y = np.asarray(y, np.float64)
-    stats = {}
-    t_all = t0 = time.perf_counter()
-    y_mask, cluster_markers, d_markers, _ = cluster_markers_gpu(y, params['max_cluster_marker_irregularity'])
-    t1 = time.perf_counter()
-    distances = edt_exact_gpu(d_markers)
-    t2 = time.perf_counter()
-    clusters = watershed_native(distances, cluster_markers)
-    t3 = time.perf_counter()
-    stats.update(markers_s=t1 - t0, edt_s=t2 - t1, flood_s=t3 - t2)
-
-    yi = Image.create_from_array(y, normalize=False)
-    rounds = EnergyRounds(dsm_cfg)
-    boxes = ndi.find_objects(clusters)
-    labels = [label for label in range(1, len(boxes) + 1) if boxes[label - 1] is not None]
-    done, pending = {}, {}
-    host_s = 0.0
-    th = time.perf_counter()
-    for label in labels:
-        cluster, masked_cluster = _cluster_regions(yi, y_mask, clusters, label, boxes[label - 1])
-        steps = _split_cluster(label, cluster, masked_cluster, params, watershed_native)
-        try:
-            pending[label] = (cluster, masked_cluster, steps, next(steps))
-        except StopIteration as stop:
-            done[label] = (cluster, *stop.value)
-    host_s += time.perf_counter() - th
-    while pending:
-        order = sorted(pending)
-        requests = [(pending[k][0].model, pending[k][1].mask, pending[k][3][0], pending[k][3][1]) for k in order]
-        results = rounds.solve(requests)
-        th = time.perf_counter()
-        for k, res in zip(order, results):
-            cluster, masked_cluster, steps, _ = pending.pop(k)
-            try:
-                pending[k] = (cluster, masked_cluster, steps, steps.send(res))
-            except StopIteration as stop:
-                done[k] = (cluster, *stop.value)
-        host_s += time.perf_counter() - th
-    ta = time.perf_counter()
-    out = _assemble(y, y_mask, clusters, [done[k] for k in labels])
-    t_end = time.perf_counter()
-    stats.update(host_split_s=host_s, assemble_s=t_end - ta, rounds=rounds.log, launches=rounds.launches,
-                 energy_s=sum(r['seconds'] for r in rounds.log), clusters=len(labels), total_s=t_end - t_all)
-    return out, stats
-
-
 def _same_config(a, b):
     try:
         return bool(a == b)
@@ -620,17 +572,19 @@ def _same_config(a, b):
         return False
 
 
-def region_analysis_gpu_multi(ys, dsm_cfgs, params):
-    """:func:`region_analysis_gpu` for a set of images: the markers and EDT of all images in one pass
-    (:func:`markers_and_edt_gpu_multi`), the flood per image, then the split loops of ALL clusters of ALL images in lock step, keyed
-    ``(image, label)``: every round's requests go through one ``EnergyRounds.solve`` per distinct energy configuration (one for a set
-    with one configuration).  A candidate's record does not depend on the plan it is solved in, so every image's
-    outputs equal :func:`region_analysis_gpu` on that image alone, and the set takes as many rounds as its image with the most.
+def region_analysis_lockstep(ys, dsm_cfgs, params, marked, flood=watershed_native, new_rounds=EnergyRounds):
+    """The host part of the stage for a set of images, after the device phase: ``marked`` holds ``(y_mask, cluster_markers, count,
+    distances)`` per image (:func:`markers_and_edt_gpu_multi`).  The flood per image, then the split loops of ALL clusters of ALL
+    images in lock step, keyed ``(image, label)`` and taken in that order: every cluster advances until it needs energies, and every
+    round's requests go through one ``solve`` per distinct energy configuration (one for a set with one configuration).
+    ``new_rounds(dsm_cfg)`` makes the object that answers them, once per distinct configuration; of it only ``solve(requests)``,
+    ``log`` and ``launches`` are read (:class:`EnergyRounds`).  A candidate's record does not depend on the plan it is solved in
+    (DESIGN.md section 4), so every image's outputs are those of the image alone, and the set takes as many rounds as its image with
+    the most.
 
     ``dsm_cfgs`` / ``params``: one per image.  An image whose split fails (``C2FError``, ``CvxprogError``) leaves the set; the others
-    finish.  Returns ``(outputs, stats, set_stats, errors)``: per image its outputs (None where it failed), its phase timings (set-wide
-    phases shared evenly) and its error (or None)."""
-    _device()
+    finish.  Returns ``(outputs, stats, set_stats, errors)``: per image its outputs (None where it failed), its phase timings (the
+    energy rounds shared evenly) and its error (or None)."""
     t_all = time.perf_counter()
     n = len(ys)
     params = [_params(**p) for p in params]
@@ -638,10 +592,7 @@ def region_analysis_gpu_multi(ys, dsm_cfgs, params):
     ys = [np.asarray(y, np.float64) for y in ys]
     stats = [dict(rounds=[], host_split_s=0.0) for _ in range(n)]
     errors = [None] * n
-    t0 = time.perf_counter()
-    marked = markers_and_edt_gpu_multi(ys, [p['max_cluster_marker_irregularity'] for p in params])
-    markers_edt_s = time.perf_counter() - t0
-    groups = []                                         # (energy configuration, EnergyRounds, images)
+    groups = []                                         # (energy configuration, rounds object, images)
     for i, c in enumerate(dsm_cfgs):
         key = _energy_config(c)
         for g in groups:
@@ -649,12 +600,12 @@ def region_analysis_gpu_multi(ys, dsm_cfgs, params):
                 g[2].append(i)
                 break
         else:
-            groups.append((key, EnergyRounds(c), [i]))
+            groups.append((key, new_rounds(c), [i]))
     flood_s = 0.0
     clusters, labels, images = [None] * n, [None] * n, [None] * n
     for i, (y, (y_mask, cluster_markers, _, distances)) in enumerate(zip(ys, marked)):
         tf = time.perf_counter()
-        clusters[i] = watershed_native(distances, cluster_markers)
+        clusters[i] = flood(distances, cluster_markers)
         stats[i]['flood_s'] = time.perf_counter() - tf
         flood_s += stats[i]['flood_s']
         images[i] = Image.create_from_array(y, normalize=False)
@@ -673,7 +624,7 @@ def region_analysis_gpu_multi(ys, dsm_cfgs, params):
         labels[i] = [label for label in range(1, len(boxes) + 1) if boxes[label - 1] is not None]
         for label in labels[i]:
             cluster, masked_cluster = _cluster_regions(images[i], marked[i][0], clusters[i], label, boxes[label - 1])
-            steps = _split_cluster(label, cluster, masked_cluster, params[i], watershed_native)
+            steps = _split_cluster(label, cluster, masked_cluster, params[i], flood)
             try:
                 pending[i, label] = (cluster, masked_cluster, steps, next(steps))
             except StopIteration as stop:
@@ -720,12 +671,42 @@ def region_analysis_gpu_multi(ys, dsm_cfgs, params):
         stats[i].update(assemble_s=time.perf_counter() - ta, clusters=len(labels[i]))
         assemble_s += stats[i]['assemble_s']
     logs = [r for _, rounds, _ in groups for r in rounds.log]
-    set_stats = dict(images=n, markers_edt_s=markers_edt_s, flood_s=flood_s, host_split_s=host_s, assemble_s=assemble_s, n_rounds=n_rounds,
-                     rounds=logs, launches=sum(rounds.launches for _, rounds, _ in groups), energy_s=sum(r['seconds'] for r in logs),
+    set_stats = dict(images=n, flood_s=flood_s, host_split_s=host_s, assemble_s=assemble_s, n_rounds=n_rounds, rounds=logs,
+                     launches=sum(rounds.launches for _, rounds, _ in groups), energy_s=sum(r['seconds'] for r in logs),
                      total_s=time.perf_counter() - t_all)
     for st in stats:
-        st.update(markers_edt_s=markers_edt_s / max(n, 1), energy_s=set_stats['energy_s'] / max(n, 1))
+        st['energy_s'] = set_stats['energy_s'] / max(n, 1)
     return outputs, stats, set_stats, errors
+
+
+def region_analysis_gpu_multi(ys, dsm_cfgs, params):
+    """The stage's GPU path for a set of images: the markers and EDT of all images in one pass (:func:`markers_and_edt_gpu_multi`),
+    then :func:`region_analysis_lockstep` with the native flood and :class:`EnergyRounds`.  Returns what it returns, with the wall
+    clock of the device phase (``markers_edt_s``, per image an even share) added to the stats."""
+    t0 = time.perf_counter()
+    ys = [np.asarray(y, np.float64) for y in ys]
+    params = [_params(**p) for p in params]
+    marked = markers_and_edt_gpu_multi(ys, [p['max_cluster_marker_irregularity'] for p in params])
+    markers_edt_s = time.perf_counter() - t0
+    outputs, stats, set_stats, errors = region_analysis_lockstep(ys, dsm_cfgs, params, marked)
+    set_stats.update(markers_edt_s=markers_edt_s, total_s=time.perf_counter() - t0)
+    for st in stats:
+        st['markers_edt_s'] = markers_edt_s / max(len(ys), 1)
+    return outputs, stats, set_stats, errors
+
+
+def _set_of_one(outputs, stats, set_stats, errors):
+    """What a set of one image returned, as the call for a single image returns it: ``(outputs, stats)``, the image's stats updated
+    with the set's (``rounds`` is then the log of the energy rounds); the image's own exception is raised if it failed."""
+    if errors[0] is not None:
+        raise errors[0]
+    return outputs[0], dict(stats[0], **set_stats)
+
+
+def region_analysis_gpu(y, dsm_cfg, **params):
+    """The stage's GPU path for one image, the set of this image (:func:`region_analysis_gpu_multi`); returns ``(outputs, stats)``
+    with the wall clock of every phase and the log of the energy rounds."""
+    return _set_of_one(*region_analysis_gpu_multi([y], [dsm_cfg], [params]))
 
 
 class C2F_RegionAnalysis(Stage):
@@ -733,7 +714,8 @@ class C2F_RegionAnalysis(Stage):
     ``adjacencies``, ``seeds`` and ``clusters``.  Hyper-parameters (``c2f-region-analysis/...``) and defaults as in the reference:
     ``seed_connectivity`` (8), ``min_atom_radius`` (15, or ``AF_min_atom_radius`` x radius with a default factor of 0.33),
     ``max_atom_norm_energy`` (0.05), ``min_norm_energy_improvement`` (0.1), ``max_cluster_marker_irregularity`` (0.2).  Runs
-    :func:`region_analysis_gpu`; the phase timings and the energy rounds of the last image are kept in ``last_stats``."""
+    :func:`region_analysis_gpu_multi`, for ``process`` on the set of its one image; the phase timings and the energy rounds of the
+    last call are kept in ``last_stats``."""
 
     ENABLED_BY_DEFAULT = True
 

@@ -87,34 +87,13 @@ class Pipeline:
         data['g_raw'] = normalize_image(g_raw)
         return data
 
-    def process_image(self, g_raw, cfg, first_stage=None, last_stage=None, data=None, out=None, log_root_dir=None):
-        cfg = cfg.copy()
-        if log_root_dir is not None:
-            os.makedirs(log_root_dir, exist_ok=True)
-        if first_stage == self.stages[0].name and data is None:
-            first_stage = None
+    def _stage_range(self, first_stage, last_stage):
+        """``first_stage`` with its ``+`` suffix resolved (the stage after the named one) and the stages that run from it (None: from
+        the pipeline's first) up to and including ``last_stage`` (None: to the end); no stages if the range is inverted."""
         if first_stage is not None and first_stage.endswith('+'):
             first_stage = self.stages[1 + self.find(first_stage[:-1])].name
         if first_stage is not None and last_stage is not None and self.find(first_stage) > self.find(last_stage):
-            return data, cfg, {}
-        out = get_output(out)
-        running = first_stage is None
-        if running:
-            data = self.init(g_raw, cfg)
-        else:
-            assert data is not None, 'data argument must be provided if first_stage is used'
-        timings = {}
-        for stage in self.stages:
-            if not running and stage.name == first_stage:
-                running = True
-            if running:
-                timings[stage.name] = stage(data, cfg, out=out, log_root_dir=log_root_dir)
-            if stage.name == last_stage:
-                running = False
-        return data, cfg, timings
-
-    def _selected_stages(self, first_stage, last_stage):
-        """The stages ``process_image`` runs for ``first_stage`` (None or a stage name) and ``last_stage``."""
+            return first_stage, []
         running, selected = first_stage is None, []
         for stage in self.stages:
             if not running and stage.name == first_stage:
@@ -123,7 +102,26 @@ class Pipeline:
                 selected.append(stage)
             if stage.name == last_stage:
                 running = False
-        return selected
+        return first_stage, selected
+
+    def _from_scratch(self, first_stage, data):
+        """Whether an image starts with ``init``: no first stage, or the pipeline's first stage and no data to go on from."""
+        return first_stage is None or (first_stage == self.stages[0].name and data is None)
+
+    def process_image(self, g_raw, cfg, first_stage=None, last_stage=None, data=None, out=None, log_root_dir=None):
+        cfg = cfg.copy()
+        if log_root_dir is not None:
+            os.makedirs(log_root_dir, exist_ok=True)
+        first_stage, stages = self._stage_range(first_stage, last_stage)
+        if not stages:
+            return data, cfg, {}
+        out = get_output(out)
+        if self._from_scratch(first_stage, data):
+            data = self.init(g_raw, cfg)
+        else:
+            assert data is not None, 'data argument must be provided if first_stage is used'
+        timings = {stage.name: stage(data, cfg, out=out, log_root_dir=log_root_dir) for stage in stages}
+        return data, cfg, timings
 
     def process_images(self, g_raws, cfg, first_stage=None, last_stage=None, datas=None, out=None, log_root_dirs=None):
         """``process_image`` for a set of images: returns one ``(data, cfg, timings)`` per image, equal to what ``process_image``
@@ -149,21 +147,18 @@ class Pipeline:
         for log in logs:
             if log is not None:
                 os.makedirs(log, exist_ok=True)
-        # per image, as in process_image: the first stage without data starts from scratch
-        fresh = [first_stage is None or (first_stage == self.stages[0].name and data is None) for data in datas]
-        if first_stage is not None and first_stage.endswith('+'):
-            first_stage = self.stages[1 + self.find(first_stage[:-1])].name
-        if first_stage is not None and last_stage is not None and self.find(first_stage) > self.find(last_stage):
+        first_stage, stages = self._stage_range(first_stage, last_stage)
+        if not stages:
             return [(data, c, {}) for data, c in zip(datas, cfgs)]
         out = get_output(out)
         for i in range(n):
-            if fresh[i]:
+            if self._from_scratch(first_stage, datas[i]):
                 datas[i] = self.init(g_raws[i], cfgs[i])
             else:
                 assert datas[i] is not None, 'data argument must be provided if first_stage is used'
         timings = [{} for _ in range(n)]
         errors = {}
-        for stage in self._selected_stages(first_stage, last_stage):
+        for stage in stages:
             live = [i for i in range(n) if i not in errors]
             if hasattr(stage, 'process_many'):
                 enabled = []

@@ -7,7 +7,7 @@ Euclidean distance transforms of the WHOLE image (contrast, postprocess.py:254-2
 mask refinement on a window around each object; the two smoothed images by the separable Gaussian kernels); the normalised
 energy needs no recomputation (``Object.cvxprog_region_size``).  The exact bit problems around that batch run on the device too,
 each one launch per set of images: the background mask (sdsm_post_background_multi; integer ``exterior_offset`` up to 32, any
-other value keeps the SciPy erosion), hole filling (sdsm_post_fill_holes; for a set over the refined windows while they are still
+other value keeps the SciPy erosion), hole filling (sdsm_post_fill_holes; in the stage over the refined windows while they are still
 on the device) and the glare test on the smoothed image where it was computed (sdsm_post_glare_multi).  What stays on
 the host: the eccentricity and the accept / discard decisions.  There is no CPU path for the batch; ``_is_glare`` is kept as the
 host definition the device is tested against."""
@@ -388,9 +388,7 @@ def _process_objects(images, exterior_scale, exterior_offset, contrast_epsilon, 
     all_packs = []
     for objects, g, *_ in images:                            # the kernel reads the image at every pixel of a box: refuse before anything is uploaded
         pk = _pack_objects(objects, *g.shape, m)
-        b = pk[0].astype(np.int64)
-        if ((b[:, :2] < 0) | (b[:, 2:] <= 0) | (b[:, :2] + b[:, 2:] > tuple(g.shape))).any():
-            raise ValueError('an object reaches outside its image or has an empty box (fg_offset, fg_fragment.shape against g.shape)')
+        _check_boxes(pk[0], g.shape)
         all_packs.append(pk)
     import torch
     L = _capi.lib()
@@ -505,7 +503,7 @@ class Postprocessing(Stage):
         g_dev = torch.as_tensor(np.ascontiguousarray(g_raw)).cuda()
         g_mask = gaussian_filter_gpu(g_dev, P['mask_smoothness'])
         # the mask is built where the image is: a caller that stands host arrays in for the device images (the CPU pipeline of the
-        # regression-metric test does, through process_objects_gpu and gaussian_filter_gpu) gets the host mask it always got
+        # regression-metric test does, through _process_objects and gaussian_filter_gpu) gets the host mask it always got
         offset = P['exterior_offset'] if torch.is_tensor(g_dev) else None
         return P, solution, objects, g_dev, g_mask, (solution, g_raw.shape, P['exterior_offset'], offset)
 
@@ -528,12 +526,6 @@ class Postprocessing(Stage):
                 masks[i] = bg
         return masks
 
-    def _prepare(self, input_data, cfg):
-        """Settings, objects, background mask and the device images of one image."""
-        P, solution, objects, g_dev, g_mask, item = self._prepare_host(input_data, cfg)
-        background_mask, = self._background_masks([item])
-        return P, objects, g_dev, g_mask, background_mask
-
     @staticmethod
     def _glare(items):
         """The glare test (postprocess.py:188-190) of ``items`` = ``(P, objects, g_dev)`` per image: per image a dict object index ->
@@ -554,55 +546,48 @@ class Postprocessing(Stage):
                     tested[i][k] = glare_decision(row)
         return tested
 
-    @staticmethod
-    def _filled(objects, refined):
-        """The masks of postprocess.py:336-337 from those before hole filling: the refined mask of every object, or its own where
-        nothing was refined, holes filled in one launch (:func:`fill_holes_gpu`)."""
-        pairs = [(o.fg_offset, o.fg_fragment) if r is None else r for o, r in zip(objects, refined)]
-        return [(off, frag) for (off, _), frag in zip(pairs, fill_holes_gpu([frag for _, frag in pairs]))]
-
-    def process(self, input_data, cfg, out, log_root_dir):
-        P, objects, g_dev, g_mask, background_mask = self._prepare(input_data, cfg)
-        # one image goes through the public batch call, whose masks are those before hole filling, and fills their fragments in a launch
-        # of their own (0.4 ms per BBBC039-like image over filling the resident windows, DESIGN.md section 8); the set (process_many)
-        # fills the refined windows while they are still on the device
-        recs, refined = process_objects_gpu(objects, g_dev, g_mask, background_mask, P['exterior_scale'], P['exterior_offset'],
-                                            P['contrast_epsilon'], P['mask_max_distance'], P['mask_stdamp'])
-        self.last_records = recs
-        masks = self._filled(objects, refined) if P['fill_holes'] else list(refined)
-        glare, = self._glare([(P, objects, g_dev)])
-        return self._decide(P, objects, recs, masks, glare, get_output(out), log_root_dir)
-
-    def process_many(self, datas, cfg, out=None, log_root_dirs=None):
-        """The stage for a set of images, with the contract of ``GlobalEnergyMinimization.process_many`` (a list of pipeline data
-        dicts, one config for all or a list; returns the wall time): the Gaussians of every image as in ``process``, then the background
-        masks, the objects (:func:`process_objects_gpu_multi` with the hole filling behind it) and the glare test of all images, each in
-        one launch (images whose settings for a step differ go to launches of their own), then the decisions image by image.  Equal to
-        ``process`` on every image; ``last_records`` becomes the list of the images' records."""
-        t0 = time.time()
-        datas = list(datas)
-        cfgs = list(cfg) if isinstance(cfg, (list, tuple)) else [cfg] * len(datas)
-        cfgs = [c.get(self.cfgns, {}) for c in cfgs]
-        logs = list(log_root_dirs) if log_root_dirs is not None else [None] * len(datas)
-        out = get_output(out)
-        hosts = [self._prepare_host({inner: d[outer] for outer, inner in self.inputs.items()}, c) for d, c in zip(datas, cfgs)]
+    def _run(self, inputs, cfgs, out, logs):
+        """The stage for a set of images, ``inputs`` = the stage inputs of every image, ``cfgs`` = its stage config: the Gaussians image
+        by image, then the background masks, the objects (:func:`_process_objects` with the hole filling behind the refinement) and the
+        glare test of all images, each in one launch (images whose settings for a step differ go to launches of their own), then the
+        decisions image by image.  Returns what every image produced and its records."""
+        hosts = [self._prepare_host(inp, c) for inp, c in zip(inputs, cfgs)]
         masks = self._background_masks([h[5] for h in hosts])
         prepared = [(P, objects, g_dev, g_mask, bg) for (P, _, objects, g_dev, g_mask, _), bg in zip(hosts, masks)]
         keys = ('exterior_scale', 'exterior_offset', 'contrast_epsilon', 'mask_max_distance', 'mask_stdamp')
         groups = {}
         for i, prep in enumerate(prepared):
             groups.setdefault(tuple(prep[0][k] for k in keys) + (bool(prep[0]['fill_holes']),), []).append(i)
-        per_object = [None] * len(datas)
+        per_object = [None] * len(prepared)
         for settings, members in groups.items():
             res = _process_objects([(prepared[i][1], prepared[i][2], prepared[i][3], prepared[i][4]) for i in members], *settings)
             for i, r in zip(members, res):
                 per_object[i] = r
-        self.last_records = [r[0] for r in per_object]
         glares = self._glare([prep[:3] for prep in prepared])
-        for data, prep, (recs, final), glare, log in zip(datas, prepared, per_object, glares, logs):
-            produced = self._decide(prep[0], prep[1], recs, final, glare, out, log)
+        produced = [self._decide(prep[0], prep[1], recs, final, glare, out, log)
+                    for prep, (recs, final), glare, log in zip(prepared, per_object, glares, logs)]
+        return produced, [r[0] for r in per_object]
+
+    def process(self, input_data, cfg, out, log_root_dir):
+        # one image is the set of one: it takes the route of process_many, which fills the refined windows while they are still on the
+        # device (DESIGN.md section 8)
+        (produced,), (self.last_records,) = self._run([input_data], [cfg], get_output(out), [log_root_dir])
+        return produced
+
+    def process_many(self, datas, cfg, out=None, log_root_dirs=None):
+        """The stage for a set of images, with the contract of ``GlobalEnergyMinimization.process_many`` (a list of pipeline data
+        dicts, one config for all or a list; returns the wall time).  Equal to ``process`` on every image; ``last_records`` becomes the
+        list of the images' records."""
+        t0 = time.time()
+        datas = list(datas)
+        cfgs = list(cfg) if isinstance(cfg, (list, tuple)) else [cfg] * len(datas)
+        cfgs = [c.get(self.cfgns, {}) for c in cfgs]
+        logs = list(log_root_dirs) if log_root_dirs is not None else [None] * len(datas)
+        inputs = [{inner: d[outer] for outer, inner in self.inputs.items()} for d in datas]
+        produced, self.last_records = self._run(inputs, cfgs, get_output(out), logs)
+        for data, result in zip(datas, produced):
             for inner, outer in self.outputs.items():
-                data[outer] = produced[inner]
+                data[outer] = result[inner]
         return time.time() - t0
 
     def _decide(self, P, objects, recs, masks, glare, out, log_root_dir):

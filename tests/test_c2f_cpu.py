@@ -246,3 +246,123 @@ def test_host_restatement_assembles_atoms_seeds_and_adjacencies():
     # the same with the Python heap flood
     again = cr.region_analysis_host(y, dict(background_margin=8), energy=energy, min_atom_radius=4)
     assert np.array_equal(again['atoms'], atoms) and np.array_equal(again['clusters'], clusters)
+
+
+# ---- the lock-step driver of a set of images ------------------------------------------------------------------------------------------
+
+def _fake_energy(y_crop, mask_crop, atoms_map, footprint, dsm_cfg):
+    """The fake energy of test_host_restatement_assembles_atoms_seeds_and_adjacencies."""
+    n = int((np.isin(atoms_map, footprint) & mask_crop).sum())
+    return n / 4000.0
+
+
+class _Rounds:
+    """What the driver reads of an ``EnergyRounds``: every request answered footprint by footprint with ``energy``."""
+
+    def __init__(self, dsm_cfg, energy=_fake_energy):
+        self.dsm_cfg, self.energy, self.log, self.launches = dsm_cfg, energy, [], 0
+
+    def solve(self, requests):
+        self.launches += 1
+        self.log.append(dict(crops=len(requests), plans=1, candidates=sum(len(r[3]) for r in requests), resolved=0, resolve_plans=0, seconds=0.0))
+        return [[self.energy(y, m, a, fp, self.dsm_cfg) for fp in fps] for y, m, a, fps in requests]
+
+
+def _lockstep_images():
+    from superdsm_amd import synth
+    ys = []
+    for shape, n, r, seed in (((96, 128), 6, 12, 7), ((64, 96), 2, 10, 5), ((96, 128), 5, 12, 3)):
+        layout = synth.random_layout(shape, n, r, seed, min_sep=0.9)
+        ys.append(synth.offset_image(synth.render_image(shape, layout, seed), 10))
+    return ys + [-np.ones((20, 30))]
+
+
+def _lockstep(ys, dsm_cfgs, new_rounds=_Rounds):
+    """The driver behind a host stand-in for the device phase, with the Python heap flood."""
+    import scipy.ndimage as ndi
+    from superdsm_amd import c2freganal as cr
+    params = cr._params(min_atom_radius=4)
+    marked = []
+    for y in ys:
+        y_mask, markers = cr.cluster_markers_host(y, params['max_cluster_marker_irregularity'])
+        marked.append((y_mask, markers, int(markers.max()), ndi.distance_transform_edt(markers == 0)))
+    return cr.region_analysis_lockstep(ys, dsm_cfgs, [params] * len(ys), marked, flood=cr.watershed, new_rounds=new_rounds)
+
+
+def _assert_same_outputs(got, want):
+    assert np.array_equal(got['y_mask'], want['y_mask'])
+    assert np.array_equal(got['clusters'], want['clusters'])
+    assert np.array_equal(got['atoms'], want['atoms'])
+    assert [tuple(s) for s in got['seeds']] == [tuple(s) for s in want['seeds']]
+    ga, wa = got['adjacencies'], want['adjacencies']
+    assert ga.atom_labels == wa.atom_labels
+    for a in wa.atom_labels:
+        assert ga[a] == wa[a] and ga.get_cluster_label(a) == wa.get_cluster_label(a)
+
+
+@pytest.fixture(scope='module')
+def lockstep_reference():
+    """The four images and what the sequential definition gives for each, with the same energy and flood."""
+    from superdsm_amd import c2freganal as cr
+    ys = _lockstep_images()
+    return ys, [cr.region_analysis_host(y, dict(background_margin=8), energy=_fake_energy, min_atom_radius=4) for y in ys]
+
+
+def test_lockstep_driver_equals_the_sequential_definition(lockstep_reference):
+    """All clusters of four images in lock step (3, 1, 2 and 0 rounds; 4, 2, 3 and 0 clusters) against ``region_analysis_host`` image by
+    image; the set takes as many rounds as its image with the most; the order of the images does not matter."""
+    ys, want = lockstep_reference
+    cfgs = [dict(background_margin=8) for _ in ys]
+    made = []
+
+    def new_rounds(c):
+        made.append(_Rounds(c))
+        return made[-1]
+
+    outputs, stats, set_stats, errors = _lockstep(ys, cfgs, new_rounds)
+    assert errors == [None] * 4 and len(made) == 1                  # one configuration: one rounds object
+    for got, ref in zip(outputs, want):
+        _assert_same_outputs(got, ref)
+    assert [int(w['clusters'].max()) for w in want] == [4, 2, 3, 0]
+    assert [st['clusters'] for st in stats] == [4, 2, 3, 0]
+    assert set_stats['n_rounds'] == 3 and [len(st['rounds']) for st in stats] == [3, 1, 2, 0]
+    assert len(set_stats['rounds']) == 3 and set_stats['launches'] == made[0].launches == 3
+    assert stats[0]['rounds'][0]['crops'] == 4 and set_stats['rounds'][0]['crops'] == 4 + 2 + 3      # round 1: every cluster's root
+    back, back_stats, back_set, back_errors = _lockstep(ys[::-1], cfgs)
+    assert back_errors == [None] * 4 and back_set['n_rounds'] == 3 and [len(st['rounds']) for st in back_stats] == [0, 2, 1, 3]
+    for got, ref in zip(back[::-1], want):
+        _assert_same_outputs(got, ref)
+
+
+def test_lockstep_driver_takes_a_failing_image_out_of_the_set(lockstep_reference):
+    """The third image has a configuration of its own (so the driver forms two groups) whose rounds object answers None: its first
+    cluster has no normalised energy, the image leaves the set with a ``C2FError`` and the other three finish as they do alone.  The
+    call for a single image raises that image's own exception."""
+    from superdsm_amd import c2freganal as cr
+    ys, want = lockstep_reference
+    cfgs = [dict(background_margin=8) for _ in ys]
+    cfgs[2]['epsilon'] = 2.0
+    made = []
+
+    def new_rounds(c):
+        made.append(_Rounds(c, energy=(lambda *a: None) if 'epsilon' in c else _fake_energy))
+        return made[-1]
+
+    outputs, stats, set_stats, errors = _lockstep(ys, cfgs, new_rounds)
+    assert len(made) == 2 and 'epsilon' in made[1].dsm_cfg and 'epsilon' not in made[0].dsm_cfg
+    assert [e is None for e in errors] == [True, True, False, True] and outputs[2] is None
+    assert isinstance(errors[2], cr.C2FError) and 'cluster 1:' in str(errors[2])
+    for i in (0, 1, 3):
+        _assert_same_outputs(outputs[i], want[i])
+    assert set_stats['n_rounds'] == 3 and [len(st['rounds']) for st in stats] == [3, 1, 1, 0]
+    assert made[1].launches == 1 and made[0].launches == 3 and set_stats['launches'] == 4
+    # the set of one image, as region_analysis_gpu returns it
+    one = _lockstep(ys[2:3], cfgs[2:3], new_rounds)
+    with pytest.raises(cr.C2FError, match='cluster 1:') as info:
+        cr._set_of_one(*one)
+    assert info.value is one[3][0] and not hasattr(info.value, 'image_index')
+    out, st = cr._set_of_one(*_lockstep(ys[:1], cfgs[:1]))
+    _assert_same_outputs(out, want[0])
+    assert st['clusters'] == 4 and len(st['rounds']) == 3 and st['launches'] == 3
+    assert {'crops', 'plans', 'candidates', 'resolved', 'resolve_plans', 'seconds'} <= set(st['rounds'][0])
+    assert {'flood_s', 'host_split_s', 'assemble_s', 'energy_s', 'total_s'} <= set(st)

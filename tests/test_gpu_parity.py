@@ -1667,13 +1667,16 @@ def test_regression_metric_gpu_pipeline_vs_cpu_oracle_pipeline(gpu):
             o.energy, o.is_optimal, o.on_boundary, o.processing_time = float(r['energy']), bool(r['is_optimal']), bool(r['on_boundary']), 0
             o.fg_offset, o.fg_fragment, o.cvxprog_region_size = np.array(r['fg_offset']), f, int(r['N'])
 
-    def cpu_objects(objects, g, gs, bg, scale, offset, eps, dist, amp, device=None):
-        recs = np.zeros(len(objects), _capi.POST_RECORD_DTYPE)
-        refined = []
-        for k, o in enumerate(objects):
-            recs['contrast'][k] = po.compute_contrast(o.fg_offset, o.fg_fragment, g, scale, offset, eps, bg)
-            refined.append(po.process_mask(o.fg_offset, o.fg_fragment, gs, dist, amp, False))
-        return recs, refined
+    def cpu_objects(images, scale, offset, eps, dist, amp, fill_holes):
+        results = []
+        for objects, g, gs, bg in images:           # g: the stage's device image, here a _Host around the host array
+            recs = np.zeros(len(objects), _capi.POST_RECORD_DTYPE)
+            masks = []
+            for k, o in enumerate(objects):
+                recs['contrast'][k] = po.compute_contrast(o.fg_offset, o.fg_fragment, g.a, scale, offset, eps, bg)
+                masks.append(po.process_mask(o.fg_offset, o.fg_fragment, gs, dist, amp, fill_holes))
+            results.append((recs, masks))
+        return results
 
     class _Host:                                    # stands in for the device tensors of the stage: the CPU pipeline never touches the GPU
         def __init__(self, a):
@@ -1681,16 +1684,14 @@ def test_regression_metric_gpu_pipeline_vs_cpu_oracle_pipeline(gpu):
         def cuda(self):
             return self
     with mock.patch.object(globalenergymin, 'compute_objects', oracle_compute), \
-         mock.patch.object(postprocess, 'process_objects_gpu', cpu_objects), \
-         mock.patch.object(postprocess, 'gaussian_filter_gpu', lambda g, sigma: ndi.gaussian_filter(g, sigma)), \
+         mock.patch.object(postprocess, '_process_objects', cpu_objects), \
+         mock.patch.object(postprocess, 'gaussian_filter_gpu', lambda g, sigma: ndi.gaussian_filter(g.a, sigma)), \
          mock.patch('torch.as_tensor', lambda a, *k, **kw: _Host(a)):
         _Host.__array__ = lambda self, *a, **k: self.a
         data = mk()
         globalenergymin.GlobalEnergyMinimization()(data, cfg, out='muted')
         # the stage calls g_dev = torch.as_tensor(g).cuda(); with the patches above g_dev wraps the host array
-        with mock.patch.object(postprocess, 'process_objects_gpu', lambda objs, g, gs, *a, **k: cpu_objects(objs, g.a if isinstance(g, _Host) else g, gs, *a, **k)), \
-             mock.patch.object(postprocess, 'gaussian_filter_gpu', lambda g, sigma: ndi.gaussian_filter(g.a if isinstance(g, _Host) else g, sigma)):
-            postprocess.Postprocessing()(data, cfg, out='muted')
+        postprocess.Postprocessing()(data, cfg, out='muted')
         rows_cpu = render.label_map_rows(render.rasterize_labels(data))
     agree = render.regression_agreement(rows_gpu, rows_cpu)
     assert agree['expected'] > 50

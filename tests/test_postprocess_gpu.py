@@ -175,7 +175,8 @@ def _stage_refined(stage, im, cfg, recs):
     """The refined masks the stage decides on, of every object of an image (those it then discards included): the batch of the
     stage's own prepared inputs, which must give the stage's records."""
     from superdsm_amd import postprocess
-    P, objects, g_dev, g_mask, bg = stage._prepare(_stage_data(im), cfg.get('postprocess', {}))
+    P, _, objects, g_dev, g_mask, item = stage._prepare_host(_stage_data(im), cfg.get('postprocess', {}))
+    bg, = stage._background_masks([item])
     again, refined = postprocess.process_objects_gpu(objects, g_dev, g_mask, bg, P['exterior_scale'], P['exterior_offset'], P['contrast_epsilon'],
                                                      P['mask_max_distance'], P['mask_stdamp'])
     assert again.tobytes() == recs.tobytes()

@@ -1,5 +1,5 @@
 """Wall clock of the coarse-to-fine region analysis, phase by phase, on the 8 BBBC039-like images, synthetic512 and synthetic 4096²:
-markers, EDT, cluster flood, host split logic, energy rounds (count, plans and candidates per round, time), total.  With --host, the
+markers and EDT, cluster flood, host split logic, energy rounds (count, plans and candidates per round, time), total.  With --host, the
 restatement (SciPy markers and EDT, Python heap flood, CPU-oracle energies one request at a time) on the same inputs, for comparison.
 
     python tools/time_c2f.py [--host] [--skip-4096] [--host-4096]
@@ -54,7 +54,7 @@ def main():
         out, st = cr.region_analysis_gpu(y, cfg, **params)
         r = st['rounds']
         print(f'{name} {y.shape[0]}x{y.shape[1]}: clusters {st["clusters"]}, atoms {int(out["atoms"].max())} | '
-              f'markers {1e3 * st["markers_s"]:.1f} ms, EDT {1e3 * st["edt_s"]:.1f} ms, flood {1e3 * st["flood_s"]:.1f} ms, '
+              f'markers+EDT {1e3 * st["markers_edt_s"]:.1f} ms, flood {1e3 * st["flood_s"]:.1f} ms, '
               f'host split logic {1e3 * st["host_split_s"]:.1f} ms, assembly {1e3 * st["assemble_s"]:.1f} ms, '
               f'energy rounds {len(r)} ({1e3 * st["energy_s"]:.1f} ms; plans/round max {max((x["plans"] for x in r), default=0)}, '
               f'candidates/round {min((x["candidates"] for x in r), default=0)}..{max((x["candidates"] for x in r), default=0)}, '
