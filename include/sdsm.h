@@ -518,6 +518,24 @@ int sdsm_measure_labels_multi(const sdsm_set_image *images, int n_images, const 
                               const int32_t *n_labels, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp,
                               sdsm_measure_record *d_out, int32_t *d_bad, void *stream);
 
+/* ---- contingency table of two label maps (no reference counterpart; the definition is overlap_pairs_host of superdsm_amd/compare.py) --
+ * For two label maps of one image (d_a, d_b: int32, packed as the table of the set says) the number of pixels of every pair of labels
+ * (a, b) that occurs, background members included, in a hash table per image: image i owns the slots table_off[i] .. table_off[i] +
+ * capacity[i] - 1 of d_keys and d_counts (table_off, capacity: HOST arrays; capacity a power of two >= 1; the ranges must not
+ * overlap).  The call clears them on the stream.  An occupied slot holds the key (uint64_t)a << 32 | b and the 64-bit count of its
+ * pixels; a free one the key ~0 and the count 0.  The order of the slots is that of the hash; after a sort by key the result does not
+ * depend on the arrival order, the launch or the set size: every atomic is an integer compare-and-swap or add.
+ * d_status: 2 int32 per image, cleared by the call.  [0]: pixels where either label is negative; they are skipped.  [1]: insertions
+ * that found every slot of the table taken; their pixels are dropped, so the table is then incomplete (every count a lower bound) and
+ * the caller launches again with a larger one.  The kernel never waits for a slot.  A table of >= H * W slots cannot fill up.
+ * Limits: labels 0 .. 2^31 - 1, H * W < 2^31 per image (no limit per side: no coordinates are involved), 1 .. SDSM_MAX_SET_IMAGES
+ * images. */
+int sdsm_overlap_pairs_multi(const sdsm_set_image *images, int n_images, const int32_t *d_a, const int32_t *d_b,
+                             const int64_t *table_off, const int64_t *capacity, uint64_t *d_keys, uint64_t *d_counts,
+                             int32_t *d_status /* per image: [0] pixels with a negative label, [1] pairs without a slot */, void *stream);
+int sdsm_overlap_pairs(int H, int W, const int32_t *d_a, const int32_t *d_b, int64_t capacity, uint64_t *d_keys,
+                       uint64_t *d_counts, int32_t *d_status, void *stream);   /* the set of one image */
+
 /* ---- host-side combinatorial steps of the stage (no device access) -------------------------------------------------------------
  * Approximate min-weight set cover (superdsm/minsetcover.py:4-88: greedy + merge phase, retried with beta * gamma on up to max_iter
  * levels) and greedy max-weight set packing (superdsm/maxsetpack.py:8-24) over n objects whose footprints are bit sets of `words`

@@ -12,3 +12,4 @@ if 'GPU_MAX_HW_QUEUES' not in _os.environ and _os.environ.get('SDSM_SET_HW_QUEUE
     _logging.getLogger(__name__).info('GPU_MAX_HW_QUEUES=8 set for this process (SDSM_SET_HW_QUEUES=0: leave the environment alone)')
 
 from .c2freganal import C2F_RegionAnalysis  # noqa: E402,F401
+from . import compare  # noqa: E402,F401

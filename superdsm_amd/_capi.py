@@ -157,6 +157,8 @@ SYMBOLS = {
     'sdsm_measure_objects_multi': (_i32, [C.POINTER(SetImage), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sdsm_measure_labels': (_i32, [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sdsm_measure_labels_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_overlap_pairs': (_i32, [_i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    'sdsm_overlap_pairs_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _vp, _vp, _vp, _vp]),
     'sdsm_minsetcover': (_i32, [_i32, _i32, _vp, _vp, _f64, _i32, _i32, _f64, _vp, _vp]),
     'sdsm_minsetcover_multi': (_i32, [_i32, _vp, _vp, _vp, _vp, _f64, _i32, _i32, _f64, _vp, _vp]),
     'sdsm_maxsetpack': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp]),

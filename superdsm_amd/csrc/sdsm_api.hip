@@ -1278,6 +1278,35 @@ extern "C" int sdsm_measure_labels(int H, int W, const int32_t *d_labels, int n_
     return sdsm_measure_labels_multi(&one, 1, d_labels, &off, &n_labels, d_g, d_gmax_abs, d_scale_exp, d_out, d_bad, stream);
 }
 
+// ---- contingency table of two label maps (sdsm_measure.hip) ---------------------------------------------------------------------------
+extern "C" hipError_t sdsm_overlap_pairs_impl(const sdsm_set_image *images, int n_images, const int32_t *d_a, const int32_t *d_b,
+                                              const int64_t *table_off, const int64_t *capacity, uint64_t *d_keys, uint64_t *d_counts,
+                                              int32_t *d_status, hipStream_t stream);
+
+extern "C" int sdsm_overlap_pairs_multi(const sdsm_set_image *images, int n_images, const int32_t *d_a, const int32_t *d_b, const int64_t *table_off,
+                                        const int64_t *capacity, uint64_t *d_keys, uint64_t *d_counts, int32_t *d_status, void *stream)
+{
+    SET_TABLE("sdsm_overlap_pairs", SET_PIXELS);
+    if (!d_a || !d_b || !table_off || !capacity || !d_keys || !d_counts || !d_status) return fail(SDSM_ERR_ARGUMENT, "sdsm_overlap_pairs: null argument");
+    for (int i = 0; i < n_images; i++) {
+        if (capacity[i] < 1 || (capacity[i] & (capacity[i] - 1)) != 0 || table_off[i] < 0)
+            return fail(SDSM_ERR_ARGUMENT, "sdsm_overlap_pairs: capacity a power of two >= 1 and table_off >= 0 required");
+        for (int j = 0; j < i; j++)
+            if (table_off[i] < table_off[j] + capacity[j] && table_off[j] < table_off[i] + capacity[i])
+                return fail(SDSM_ERR_ARGUMENT, "sdsm_overlap_pairs: the tables of two images overlap");
+    }
+    hipError_t e = sdsm_overlap_pairs_impl(images, n_images, d_a, d_b, table_off, capacity, d_keys, d_counts, d_status, (hipStream_t)stream);
+    SET_DONE("sdsm_overlap_pairs");
+}
+
+extern "C" int sdsm_overlap_pairs(int H, int W, const int32_t *d_a, const int32_t *d_b, int64_t capacity, uint64_t *d_keys, uint64_t *d_counts,
+                                  int32_t *d_status, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    const int64_t off = 0;
+    return sdsm_overlap_pairs_multi(&one, 1, d_a, d_b, &off, &capacity, d_keys, d_counts, d_status, stream);
+}
+
 extern "C" int sdsm_post_background_multi(const sdsm_post_bg_image *images, int n_images, const int32_t *d_boxes, const int64_t *d_bits_off,
                                           const uint32_t *d_bits, int radius, void *stream)
 {

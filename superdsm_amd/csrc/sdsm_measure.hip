@@ -13,6 +13,11 @@
 //                       the occupied slots go to the global records by 64-bit integer atomics at the end of the band.  A label
 //                       without a free slot goes straight to the global atomics.
 //   k_labels_init / k_labels_finish   the identities of the atomics before, the record's final form after
+//   k_overlap_pairs     the contingency table of two label maps (superdsm_amd/compare.py): the bands and segments of k_measure_labels over
+//                       both maps; a thread keeps its current pair (a, b) and the length of its run in registers and flushes on a change
+//                       into an LDS table keyed by the 64-bit pair (64-bit LDS compare-and-swap, 32-bit counts); the occupied slots go
+//                       to the image's global hash table (keys claimed by compare-and-swap, 64-bit counts) at the end of the band.  A
+//                       pair without an LDS slot goes straight there; one without a global slot is counted and dropped, never waited for.
 //
 // Every sum over pixels is an integer sum and every atomic an integer add / min / max / or, so the bytes do not depend on the order,
 // the launch or the set size.  Intensities enter as q = rint(ldexp(g, 62 - e)) in two limbs (bits 0-31, and q >> 32).
@@ -29,6 +34,16 @@ constexpr int LBAND = 16384;                     //   pixels of a band: 4 segmen
 constexpr int LSLOTS = 256;                      //   slots of the LDS table (28 KB: 5 workgroups per compute unit)
 constexpr int LPROBES = 16;                      //   slots tried before a label goes to the global atomics
 constexpr int FIN_RECS = MTPB;                   // k_labels_init / k_labels_finish: records per workgroup
+// k_overlap_pairs: the LDS table of a band.  A slot is 12 bytes (64-bit key, 32-bit count), so 1024 slots are 12 KB: a compute unit holds
+// 32 waves = 8 workgroups of 256 threads, 96 KB of its 160 KB of LDS, and the wave slots bound the occupancy, not the table (2048 slots
+// would: 8 x 24 KB = 192 KB).  A band meets few pairs: 16 384 pixels are 23 rows of a 520 x 696 image or 4 rows of a 4096-wide one, and
+// objects of radius 15 leave about 100 (object, object) and (object, background) pairs there, a load of 0.1.  At a load a of the table
+// an insertion of a new key tries (1 + 1 / (1 - a)^2) / 2 slots on average (linear probing): 1.1 at a = 0.1, 2.5 at a = 0.5, and 8
+// tries fail only behind a cluster of 8 occupied slots, which needs a load near 0.7 (700 pairs in a band) to become common.  Such a
+// pair goes straight to the global table: the result does not depend on either constant, only the time does.
+constexpr int OBITS = 10;
+constexpr int OSLOTS = 1 << OBITS;               //   slots of the LDS table
+constexpr int OPROBES = 8;                       //   slots tried before a pair goes to the global table
 
 typedef unsigned long long u64;
 typedef long long i64;
@@ -358,6 +373,101 @@ __global__ __launch_bounds__(MTPB) void k_measure_labels(MSet S, const int32_t *
     }
 }
 
+// ---- contingency table of two label maps ---------------------------------------------------------------------------------------------
+constexpr u64 OFREE = ~0ull;                     // a free slot of either table (no pair has this key: labels are >= 0)
+
+struct OCap { int64_t cap[SDSM_MAX_SET_IMAGES]; };          // slots of each image's global table, a power of two
+
+__device__ __forceinline__ u64 pair_hash(u64 key)           // multiplicative: the high bits depend on every bit of the key
+{
+    return key * 0x9E3779B97F4A7C15ull;
+}
+
+// n pixels of the pair `key` into the global table of its image: linear probing from the hashed slot, at most cap tries.  A key is
+// written once (free -> key, by compare-and-swap) and never changes, so a slot read as another pair's stays that pair's.  A pair that
+// finds the table full is counted in status[1] and its pixels are dropped: the host launches again with a larger table.
+__device__ __forceinline__ void insert_global(u64 *keys, u64 *counts, int64_t cap, u64 key, u64 n, int32_t *status)
+{
+    const u64 mask = (u64)cap - 1, h = pair_hash(key);
+    u64 s = (h ^ (h >> 31)) & mask;
+    for (int64_t k = 0; k < cap; k++, s = (s + 1) & mask) {
+        u64 old = __hip_atomic_load(keys + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old == OFREE) old = atomicCAS(keys + s, OFREE, key);
+        if (old != OFREE && old != key) continue;
+        atomicAdd(counts + s, n);
+        return;
+    }
+    atomicAdd(status + 1, 1);
+}
+
+struct OTable {                                  // the per-workgroup table
+    u64 key[OSLOTS];                             // OFREE: free
+    uint32_t count[OSLOTS];                      // a band holds LBAND = 16 384 pixels
+};
+
+__device__ __forceinline__ void flush_pair(OTable &T, u64 key, uint32_t n, u64 *keys, u64 *counts, int64_t cap, int32_t *status)
+{
+    uint32_t s = (uint32_t)(pair_hash(key) >> (64 - OBITS));
+    for (int k = 0; k < OPROBES; k++, s = (s + 1) & (OSLOTS - 1)) {
+        const u64 old = atomicCAS(&T.key[s], OFREE, key);
+        if (old != OFREE && old != key) continue;
+        atomicAdd(&T.count[s], n);
+        return;
+    }
+    insert_global(keys, counts, cap, key, n, status);        // no slot: correct and slow
+}
+
+// S.rec_off: first slot of the image's global table; status: per image [0] pixels with a negative label (skipped), [1] pairs without a slot
+__global__ __launch_bounds__(MTPB) void k_overlap_pairs(MSet S, OCap C, const int32_t *a_, const int32_t *b_, u64 *keys_, u64 *counts_, int32_t *status_)
+{
+    __shared__ OTable T;
+    static_assert(LBAND % (LSEG * MTPB) == 0 && LBAND <= 0xffffffffll, "band size and the 32-bit counts of the LDS table");
+    const int im = set_find(S.start, S.n, blockIdx.x), tid = threadIdx.x;
+    const int64_t px = (int64_t)S.H[im] * S.W[im];
+    const int64_t p0 = (int64_t)(blockIdx.x - S.start[im]) * LBAND;
+    const int32_t *la = a_ + S.off[im], *lb = b_ + S.off[im];
+    u64 *keys = keys_ + S.rec_off[im], *counts = counts_ + S.rec_off[im];
+    const int64_t cap = C.cap[im];
+    int32_t *status = status_ + 2 * im;
+    for (int s = tid; s < OSLOTS; s += MTPB) { T.key[s] = OFREE; T.count[s] = 0; }
+    __syncthreads();
+    u64 cur = OFREE;                             // the pair whose run the registers hold; OFREE: none
+    uint32_t run = 0;
+    int n_bad = 0;
+    for (int it = 0; it < LBAND / (LSEG * MTPB); it++) {
+        const int64_t q0 = p0 + ((int64_t)it * MTPB + tid) * LSEG;
+        if (q0 >= px) break;
+        const int n = px - q0 < LSEG ? (int)(px - q0) : LSEG;
+        const bool vec = n == LSEG && ((((uintptr_t)(la + q0)) | ((uintptr_t)(lb + q0))) & 15) == 0;      // 16-byte loads where both segments are whole and aligned
+        int4 t = make_int4(0, 0, 0, 0), u = make_int4(0, 0, 0, 0);
+#pragma unroll 1
+        for (int k = 0; k < n; k++) {            // (one flush site: the loop stays rolled)
+            if ((k & 3) == 0) {
+                if (vec) { t = *(const int4 *)(la + q0 + k); u = *(const int4 *)(lb + q0 + k); }
+                else {
+                    t.x = la[q0 + k]; t.y = k + 1 < n ? la[q0 + k + 1] : 0; t.z = k + 2 < n ? la[q0 + k + 2] : 0; t.w = k + 3 < n ? la[q0 + k + 3] : 0;
+                    u.x = lb[q0 + k]; u.y = k + 1 < n ? lb[q0 + k + 1] : 0; u.z = k + 2 < n ? lb[q0 + k + 2] : 0; u.w = k + 3 < n ? lb[q0 + k + 3] : 0;
+                }
+            }
+            const int32_t x = (k & 3) == 0 ? t.x : (k & 3) == 1 ? t.y : (k & 3) == 2 ? t.z : t.w;
+            const int32_t y = (k & 3) == 0 ? u.x : (k & 3) == 1 ? u.y : (k & 3) == 2 ? u.z : u.w;
+            if ((x | y) < 0) { n_bad++; continue; }          // skipped; the run of the current pair goes on behind it
+            const u64 key = ((u64)(uint32_t)x << 32) | (uint32_t)y;
+            if (key != cur) {
+                if (run) flush_pair(T, cur, run, keys, counts, cap, status);
+                cur = key;
+                run = 0;
+            }
+            run++;
+        }
+    }
+    if (run) flush_pair(T, cur, run, keys, counts, cap, status);
+    if (n_bad) atomicAdd(status, n_bad);
+    __syncthreads();
+    for (int s = tid; s < OSLOTS; s += MTPB)     // one lane per slot
+        if (T.key[s] != OFREE) insert_global(keys, counts, cap, T.key[s], T.count[s], status);
+}
+
 MSet make_mset(const sdsm_set_image *images, int n_images)
 {
     MSet S{};
@@ -416,5 +526,30 @@ extern "C" hipError_t sdsm_measure_labels_impl(const sdsm_set_image *images, int
     grid_pixels(S, LBAND);
     hipLaunchKernelGGL(k_measure_labels, dim3(S.start[n_images]), dim3(MTPB), 0, stream, S, labels, d_g, (const u64 *)d_gmax_abs, out, bad);
     hipLaunchKernelGGL(k_labels_finish, dim3(R.start[n_images]), dim3(MTPB), 0, stream, R, out, d_g ? (const u64 *)d_gmax_abs : nullptr);
+    return hipGetLastError();
+}
+
+// The tables are cleared here, on the stream: keys to OFREE (bytes 0xFF), counts and status to 0; slots of images that follow each
+// other in the buffers are cleared by one call.
+extern "C" hipError_t sdsm_overlap_pairs_impl(const sdsm_set_image *images, int n_images, const int32_t *d_a, const int32_t *d_b,
+                                              const int64_t *table_off, const int64_t *capacity, uint64_t *d_keys, uint64_t *d_counts,
+                                              int32_t *d_status, hipStream_t stream)
+{
+    MSet S = make_mset(images, n_images);
+    OCap C{};
+    for (int i = 0; i < n_images; i++) { S.rec_off[i] = table_off[i]; C.cap[i] = capacity[i]; }
+    for (int i = 0; i < n_images;) {
+        int j = i + 1;
+        while (j < n_images && table_off[j] == table_off[j - 1] + capacity[j - 1]) j++;
+        const size_t first = (size_t)table_off[i], bytes = (size_t)(table_off[j - 1] + capacity[j - 1] - table_off[i]) * sizeof(u64);
+        hipError_t e = hipMemsetAsync(d_keys + first, 0xFF, bytes, stream);
+        if (e == hipSuccess) e = hipMemsetAsync(d_counts + first, 0, bytes, stream);
+        if (e != hipSuccess) return e;
+        i = j;
+    }
+    hipError_t e = hipMemsetAsync(d_status, 0, (size_t)n_images * 2 * sizeof(int32_t), stream);
+    if (e != hipSuccess) return e;
+    grid_pixels(S, LBAND);
+    hipLaunchKernelGGL(k_overlap_pairs, dim3(S.start[n_images]), dim3(MTPB), 0, stream, S, C, d_a, d_b, (u64 *)d_keys, (u64 *)d_counts, d_status);
     return hipGetLastError();
 }
