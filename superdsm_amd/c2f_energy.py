@@ -15,11 +15,38 @@ Semantics kept from the reference:
   solves in full-image coordinates, c2freganal.py:70-73; here the crop's).
 """
 import hashlib
+import math
 
 import numpy as np
 
-from . import _capi, engine
-from .objects import CvxprogError
+from . import _capi
+from .objects import _CPU_ONLY_KEYS, CvxprogError
+
+
+class C2FError(RuntimeError):
+    """The region analysis of a cluster cannot go on where the reference would fail with a TypeError or ValueError."""
+
+
+def energy_config(dsm_cfg):
+    """``(cfg, background margin)`` of the energy batches: without the keys of the CPU implementation, elliptical models only
+    (``smooth_amount = inf``, c2freganal.py:126), ``cvxprog`` called directly (no "single positive pixel" rule, c2freganal.py:72)."""
+    cfg = {k: v for k, v in dsm_cfg.items() if k not in _CPU_ONLY_KEYS}
+    cfg['smooth_amount'] = np.inf
+    cfg['no_trivial_rule'] = True
+    return cfg, float(cfg.pop('background_margin'))
+
+
+def record_result(r, index):
+    """The normalised energy of a record; None for a region without one; errors, a given-up candidate and non-finite values become
+    exception OBJECTS (returned, not raised), never values."""
+    n = int(r['n_pixels'])
+    if n == 0 or r['n_positive'] == n or r['n_negative'] == n:        # c2freganal.py:67-68 (.all() of nothing is True)
+        return None
+    if r['status'] in (_capi.CAND_ERROR, _capi.CAND_UNSUPPORTED):
+        return CvxprogError(cidx=index)
+    if r['status'] == _capi.CAND_GIVEN_UP or not math.isfinite(r['energy']):
+        return C2FError(f'candidate {index}: no energy (status {int(r["status"])}, energy {float(r["energy"])!r})')
+    return float(r['energy']) / n
 
 
 def normalized_energies(y_crop, mask_crop, atoms_map, footprints, dsm_cfg):
@@ -27,29 +54,22 @@ def normalized_energies(y_crop, mask_crop, atoms_map, footprints, dsm_cfg):
 
     y_crop / mask_crop: offset intensities and admissible pixels of the cluster crop; atoms_map: integer labels of the
     crop; footprints: iterable of label sets; dsm_cfg: DSM hyper-parameters (``smooth_amount`` is forced to inf)."""
+    from . import engine
     footprints = [sorted(int(a) for a in fp) for fp in footprints]
     if not footprints:
         return []
-    cfg = {k: v for k, v in dsm_cfg.items() if k not in ('smooth_mat_max_allocations', 'smooth_mat_dtype', 'cachesize', 'cachetest', 'cp_timeout')}
-    cfg['smooth_amount'] = np.inf
-    cfg['no_trivial_rule'] = True
-    margin = cfg.pop('background_margin')
+    cfg, margin = energy_config(dsm_cfg)
     img = engine.DeviceImage(np.ascontiguousarray(y_crop, np.float64), None if mask_crop is None else np.ascontiguousarray(mask_crop, bool),
                              np.ascontiguousarray(atoms_map, np.int32), margin)
     batch = engine.Batch(img, footprints, cfg, latency_mode=True)
-    from .objects import _starting_points
-    _starting_points(batch, cfg)                              # callable dsm/init (objects.py:385-386): init(0) here, G~ is the null matrix
+    batch.starting_points(cfg.get('init'))                    # callable dsm/init (objects.py:385-386): init(0) here, G~ is the null matrix
     batch.launch()
     recs = batch.records()
-    out = []
-    for i, r in enumerate(recs[:len(footprints)]):
-        n = int(r['n_pixels'])
-        if n == 0 or r['n_positive'] == n or r['n_negative'] == n:        # c2freganal.py:67-68 (.all() of nothing is True)
-            out.append(None)
-        elif r['status'] in (_capi.CAND_ERROR, _capi.CAND_UNSUPPORTED):
-            raise CvxprogError(cidx=i)
-        else:
-            out.append(float(r['energy']) / n)
+    if batch.resolve_given_up(recs['status']).size:
+        recs = batch.records()
+    out = [record_result(r, i) for i, r in enumerate(recs)]
+    for error in (v for v in out if isinstance(v, Exception)):
+        raise error
     return out
 
 

@@ -29,6 +29,7 @@ import scipy.ndimage as ndi
 
 from . import _capi, _morph
 from .atoms import AtomAdjacencyGraph
+from .c2f_energy import C2FError, energy_config, record_result
 from .image import Image
 from .imageset import SetLayout, in_sets
 from .objects import CvxprogError, Object
@@ -39,10 +40,6 @@ DEFAULTS = dict(seed_connectivity=8, min_atom_radius=15, max_atom_norm_energy=0.
                 max_cluster_marker_irregularity=0.2)
 MAX_CROPS_PER_PLAN = 16          # cluster crops per engine.Batch plan (sdsm_plan_create_multi takes 1 .. 16 images)
 _CROP_ALIGN = 256                # elements: every crop of a round starts 256-element aligned in the packed device buffers
-
-
-class C2FError(RuntimeError):
-    """The region analysis of a cluster cannot go on where the reference would fail with a TypeError or ValueError."""
 
 
 # ---- the definition: host restatement --------------------------------------------------------------------------------------------
@@ -454,34 +451,13 @@ class _CropImage:
         self.atom_stats = None
 
 
-def _energy_config(dsm_cfg):
-    """The config handling of ``c2f_energy.normalized_energies``."""
-    cfg = {k: v for k, v in dsm_cfg.items() if k not in ('smooth_mat_max_allocations', 'smooth_mat_dtype', 'cachesize', 'cachetest', 'cp_timeout')}
-    cfg['smooth_amount'] = np.inf
-    cfg['no_trivial_rule'] = True
-    return cfg, float(cfg.pop('background_margin'))
-
-
-def _record_result(r, index):
-    """A record as ``normalized_energies`` reads it; errors and non-finite values become exceptions, never values."""
-    n = int(r['n_pixels'])
-    if n == 0 or r['n_positive'] == n or r['n_negative'] == n:
-        return None
-    if r['status'] in (_capi.CAND_ERROR, _capi.CAND_UNSUPPORTED):
-        return CvxprogError(cidx=index)
-    value = float(r['energy']) / n
-    if not math.isfinite(value):
-        return C2FError(f'candidate {index}: non-finite energy (status {int(r["status"])})')
-    return value
-
-
 class EnergyRounds:
     """Solves the energy requests of many cluster crops at once: one upload of the packed crops, ``sdsm_image_prepare`` per crop,
     plans of at most 16 crops queued on the current stream, candidates given up by a workgroup group solved again without groups
     (mode 2)."""
 
     def __init__(self, dsm_cfg):
-        self.cfg, self.margin = _energy_config(dsm_cfg)
+        self.cfg, self.margin = energy_config(dsm_cfg)
         self.log = []                                   # per round: dict(crops, plans, candidates, resolved, seconds)
 
     @property
@@ -491,7 +467,6 @@ class EnergyRounds:
     def solve(self, requests):
         """requests: ``(y_crop, mask_crop, atoms_map, footprints)`` per crop; returns one list of results per request."""
         from . import engine
-        from .objects import _starting_points
         torch = _device()
         L = _capi.lib()
         t0 = time.perf_counter()
@@ -536,32 +511,26 @@ class EnergyRounds:
             fps = [list(fp) for k in ks for fp in requests[k][3]]
             image_of = [j for j, k in enumerate(ks) for _ in requests[k][3]]
             b = engine.Batch([images[k] for k in ks], fps, self.cfg, latency_mode=True, image_of=image_of)
-            _starting_points(b, self.cfg)
+            b.starting_points(self.cfg.get('init'))
             b.launch()
-            batches.append((fps, b))
-        recs = torch.cat([b.records_dev[:b.n * _capi.RECORD_DTYPE.itemsize] for _, b in batches]).cpu().numpy().view(_capi.RECORD_DTYPE).copy()
-        # candidates a workgroup group gave up: again, in plans without groups
-        again = np.flatnonzero(recs['status'] == _capi.CAND_GIVEN_UP)
-        redo, first = [], 0
-        for fps, b in batches:
-            sel = again[(again >= first) & (again < first + b.n)] - first
-            if len(sel):
-                rb = engine.Batch(b.images, [fps[i] for i in sel.tolist()], self.cfg, image_of=b.image_of[sel], mode=2)
-                _starting_points(rb, self.cfg)
-                rb.launch()
-                redo.append((sel + first, rb))
+            batches.append(b)
+        recs = torch.cat([b.records_dev[:b.n * _capi.RECORD_DTYPE.itemsize] for b in batches]).cpu().numpy().view(_capi.RECORD_DTYPE).copy()
+        # candidates a workgroup group gave up: again, in plans without groups; only their rows are read back
+        resolved, resolve_plans, first = 0, 0, 0
+        for b in batches:
+            again = b.resolve_given_up(recs['status'][first:first + b.n])
+            if again.size:
+                recs[first + again] = rr = b.records(again)
+                if (rr['status'] == _capi.CAND_GIVEN_UP).any():
+                    raise C2FError('a candidate was given up in a plan without workgroup groups')
+                resolved, resolve_plans = resolved + again.size, resolve_plans + 1
             first += b.n
-        for sel, rb in redo:
-            rr = rb.records()
-            if (rr['status'] == _capi.CAND_GIVEN_UP).any():
-                raise C2FError('a candidate was given up in a plan without workgroup groups')
-            recs[sel] = rr
         results, i = [], 0
         for r in requests:
-            results.append([_record_result(recs[i + j], i + j) for j in range(len(r[3]))])
+            results.append([record_result(recs[i + j], i + j) for j in range(len(r[3]))])
             i += len(r[3])
-        self.log.append(dict(crops=len(requests), plans=len(batches), candidates=len(recs), resolved=int(len(again)),
-                             resolve_plans=len(redo), seconds=time.perf_counter() - t0))
+        self.log.append(dict(crops=len(requests), plans=len(batches), candidates=len(recs), resolved=int(resolved),
+                             resolve_plans=resolve_plans, seconds=time.perf_counter() - t0))
         return results
 
 
@@ -594,7 +563,7 @@ def region_analysis_lockstep(ys, dsm_cfgs, params, marked, flood=watershed_nativ
     errors = [None] * n
     groups = []                                         # (energy configuration, rounds object, images)
     for i, c in enumerate(dsm_cfgs):
-        key = _energy_config(c)
+        key = energy_config(c)
         for g in groups:
             if _same_config(g[0], key):
                 g[2].append(i)

@@ -83,38 +83,18 @@ def _gpu_solve_local(image, footprints, cfg, mask_info, cache=None):
     """Default local solver of a shard: one engine batch on this rank's GPU.  Returns (records, masks) as uint8 DEVICE tensors
     (nothing is copied to the host here); ``mask_info`` is what every rank expects the shard's mask boxes to be.  ``cache`` (a dict
     owned by a :class:`ShardedBatch`): the plan and workspace are built once and launched again by later steps."""
-    from . import _capi, engine
+    from . import engine
     batch = cache.get('batch') if cache is not None else None
     if batch is None:
-        # scheduling as objects._solve: a shard that cannot fill the GPU runs in latency mode (shortest wall clock of ONE batch), a large
-        # one in throughput mode (results do not depend on the mode)
-        from .objects import LATENCY_MODE_BELOW
-        batch = engine.Batch(image, footprints, cfg, mode=1 if len(footprints) < LATENCY_MODE_BELOW else 0)
+        batch = engine.Batch(image, footprints, cfg, mode=engine.mode_for(len(footprints)))
         assert np.array_equal(batch.mask_info[:len(footprints)], mask_info), 'plan of the shard disagrees with the replicated layout'
-        from .objects import _starting_points
-        batch.start = _starting_points(batch, cfg)           # callable dsm/init: starting points of this shard's candidates (None otherwise)
+        batch.starting_points(cfg.get('init'))               # callable dsm/init: starting points of this shard's candidates
         if cache is not None:
             cache['batch'] = batch
     batch.launch()
-    n = len(footprints)
-    if n:
-        # candidates whose workgroup group was given up (a scheduling event on an oversubscribed GPU, SDSM_CAND_GIVEN_UP) are solved
-        # again without groups on the owning rank, before the all-gather -- as objects._solve does for unsharded batches
-        rec32 = batch.records_dev.view(torch.int32).reshape(-1, 32)
-        again = torch.nonzero(rec32[:n, 16] == _capi.CAND_GIVEN_UP).flatten().cpu().numpy()       # (status: int32 #16 of the 128-byte record)
-        if again.size:
-            sub = engine.Batch(image, [footprints[i] for i in again], cfg, mode=2)
-            if batch.start is not None:
-                sub.set_start([batch.start[i] for i in again])
-            sub.launch()
-            sub32 = sub.records_dev.view(torch.int32).reshape(-1, 32)
-            for j, i in enumerate(again):
-                rec32[i] = sub32[j]
-                nb = 4 * ((int(batch.mask_info[i, 2]) * int(batch.mask_info[i, 3]) + 31) // 32)
-                o, so = int(batch.mask_offset[i]), int(sub.mask_offset[j])
-                batch.masks_dev[o:o + nb] = sub.masks_dev[so:so + nb]
-            torch.cuda.current_stream().synchronize()                      # (sub's buffers are released on return)
-    return batch.records_dev[:n * 128], batch.masks_dev, batch          # (the batch keeps the buffers alive)
+    # given-up candidates are solved again on the owning rank, before the all-gather -- as objects._solve does for unsharded batches
+    batch.resolve_given_up()
+    return batch.records_dev[:batch.n * 128], batch.masks_dev, batch          # (the batch keeps the buffers alive)
 
 
 _gpu_solve_local.supports_cache = True

@@ -6,6 +6,7 @@ fails loudly.
 """
 import ctypes as C
 import itertools
+import os
 import threading
 
 import numpy as np
@@ -150,9 +151,22 @@ def plan_mask_boxes(image, footprints, dsm_cfg):
     return info[:n]
 
 
+# Batches of fewer candidates than this leave most compute units idle: they run in latency mode (256 threads per candidate, regions of
+# more than 3072 pixels split over workgroup groups) also when they span several images (lock-step generations of a small image set).
+# (1024 until round 3: a lock-step batch of 588 candidates of 4 images then took 23.5 ms -- hundreds of group members, a compute unit
+# each -- against 11.6 ms in throughput mode; 8 different BBBC039-like images: 14.4-15.7 -> 13.3-14.2 ms per image with 256.)
+LATENCY_MODE_BELOW = int(os.environ.get('SDSM_LATENCY_BELOW', 256))
+
+
+def mode_for(n_candidates):
+    """Latency mode (1: shortest wall clock of ONE batch) for a batch that cannot fill the GPU, else throughput mode (0); same results."""
+    return 1 if n_candidates < LATENCY_MODE_BELOW else 0
+
+
 class Batch:
     """One ``compute_objects`` call: plan, workspace, launch, results.  ``image`` may be a list of :class:`DeviceImage` (a plan
-    over several images, sdsm_plan_create_multi): ``image_of[i]`` then names the image of candidate ``i``."""
+    over several images, sdsm_plan_create_multi): ``image_of[i]`` then names the image of candidate ``i``.  The batch keeps what it was
+    built from (``footprints``, ``dsm_cfg``, ``image_of``, ``start``): :meth:`resolve_given_up` builds its second attempt from them."""
 
     def __init__(self, image, footprints, dsm_cfg, want_xi=False, latency_mode=False, image_of=None, mode=None):
         """mode: 0 throughput (default), 1 latency (``latency_mode=True``: the largest regions get a group of 512-thread
@@ -161,6 +175,7 @@ class Batch:
         self.images = list(image) if isinstance(image, (list, tuple)) else [image]
         self.image = self.images[0]
         assert 1 <= len(self.images) <= 16, 'a plan covers 1 .. 16 images'
+        self.footprints, self.dsm_cfg, self.start = footprints, dsm_cfg, None
         self.n = len(footprints)
         lens = np.fromiter(map(len, footprints), np.int64, self.n)
         offs = np.zeros(self.n + 1, np.int32)
@@ -223,10 +238,28 @@ class Batch:
                                                    m.ctypes.data_as(C.c_void_p), _stream()), 'sdsm_batch_deform_counts')
         return m[:self.n]
 
+    def starting_points(self, init):
+        """Callable ``dsm/init`` (objects.py:385-386): ``params = init(number of columns of G~)`` per candidate -- the count is a result of
+        the setup kernel, which runs once on its own for it -- set as the starting points of the DSM solves (:meth:`set_start`).  Returns
+        the list of vectors (None for candidates without a solve), or None if ``init`` is not callable."""
+        if not callable(init):
+            return None
+        start = []
+        for i, m in enumerate(self.deform_counts().tolist()):
+            if m < 0:
+                start.append(None)
+                continue
+            p = np.asarray(init(m), np.float64).ravel()
+            if p.size != 6 + m or not np.all(np.isfinite(p)):
+                raise ValueError(f'dsm/init({m}) must return {6 + m} finite parameters (candidate {i}: got {p.size})')
+            start.append(p)
+        self.set_start(start)
+        return start
+
     def set_start(self, params):
         """Starting points of the DSM solves of the following launches (sdsm_plan_set_start): ``params[i]`` = theta (6,
         full-image-normalised) + xi (M) of candidate i, or None for a candidate without a solve.  Only for plans with
-        ``init`` other than ``'elliptical'``."""
+        ``init`` other than ``'elliptical'``.  Kept as ``self.start``."""
         L = _capi.lib()
         xo = self.xi_offsets()
         buf = np.zeros(L.sdsm_plan_eval_param_count(self.plan))
@@ -237,6 +270,34 @@ class Batch:
             buf[6 * i + xo[i]:6 * i + xo[i] + p.size] = p
         self.x0_dev = torch.from_numpy(buf).to(self.image.device)       # (kept alive by the batch)
         _capi.check(L.sdsm_plan_set_start(self.plan, _ptr(self.x0_dev)), 'sdsm_plan_set_start')
+        self.start = list(params)
+
+    def resolve_given_up(self, status=None):
+        """The candidates of the last launch whose workgroup group was given up (SDSM_CAND_GIVEN_UP: a scheduling event on an oversubscribed
+        GPU, not a solver failure) are solved again in one plan without groups (mode 2) from the same starting points; their record rows and
+        mask bytes replace the first attempt's on the device.  ``status``: the statuses if the caller has downloaded them (else they are read
+        on the device).  Returns their indices; with none, nothing is touched.  One that is given up again keeps that status."""
+        if self.xi_dev is not None:
+            raise _capi.SdsmError('resolve_given_up: not for a batch with want_xi (the xi of the second attempt are not copied back)')
+        rows = lambda t: t.view(-1, _capi.RECORD_DTYPE.itemsize)
+        if status is None:
+            status = rows(self.records_dev)[:self.n].view(torch.int32)[:, _capi.RECORD_DTYPE.fields['status'][1] // 4].cpu().numpy()
+        again = np.flatnonzero(np.asarray(status)[:self.n] == _capi.CAND_GIVEN_UP)
+        if not again.size:
+            return again
+        sub = Batch(self.images if len(self.images) > 1 else self.image, [self.footprints[i] for i in again], self.dsm_cfg,
+                    image_of=None if self.image_of is None else self.image_of[again], mode=2)
+        if self.start is not None:
+            sub.set_start([self.start[i] for i in again])
+        sub.launch()
+        with torch.cuda.device(self.image.device):
+            rows(self.records_dev)[torch.from_numpy(again).to(self.image.device)] = rows(sub.records_dev)[:len(again)]
+            for j, i in enumerate(again):
+                nb = 4 * ((int(self.mask_info[i, 2]) * int(self.mask_info[i, 3]) + 31) // 32)
+                o, so = int(self.mask_offset[i]), int(sub.mask_offset[j])
+                self.masks_dev[o:o + nb] = sub.masks_dev[so:so + nb]
+            torch.cuda.current_stream().synchronize()                      # (sub's buffers are released on return)
+        return again
 
     def download(self):
         """Records and bit-packed masks to pinned host staging buffers: two asynchronous copies on the current stream, one
@@ -265,8 +326,10 @@ class Batch:
             _capi.check(_capi.lib().sdsm_batch_solver_counters(self.plan, _ptr(self.ws), out.ctypes.data_as(C.c_void_p)), 'sdsm_batch_solver_counters')
         return dict(evals_reused=int(out[0]))
 
-    def records(self):
-        return self.records_dev.cpu().numpy().view(_capi.RECORD_DTYPE)[:self.n].copy()
+    def records(self, rows=None):
+        """The records on the host (synchronises); ``rows``: only those candidates'."""
+        dev = self.records_dev if rows is None else self.records_dev.view(-1, _capi.RECORD_DTYPE.itemsize)[torch.from_numpy(rows).to(self.records_dev.device)]
+        return dev.cpu().numpy().reshape(-1).view(_capi.RECORD_DTYPE)[:self.n].copy()
 
     def xi_offsets(self):
         off = np.zeros(max(self.n, 1), np.int64)

@@ -106,12 +106,6 @@ class CvxprogError(Exception):
 
 DEFAULT_COMPUTING_STATUS_LINE = ('Computing objects', 'Computed objects')
 
-# Batches of fewer candidates than this leave most compute units idle: they run in latency mode (256 threads per candidate, regions of
-# more than 3072 pixels split over workgroup groups) also when they span several images (lock-step generations of a small image set).
-# (1024 until round 3: a lock-step batch of 588 candidates of 4 images then took 23.5 ms -- hundreds of group members, a compute unit
-# each -- against 11.6 ms in throughput mode; 8 different BBBC039-like images: 14.4-15.7 -> 13.3-14.2 ms per image with 256.)
-LATENCY_MODE_BELOW = int(os.environ.get('SDSM_LATENCY_BELOW', 256))
-
 # keys of dsm_cfg that only steer the reference's CPU implementation
 _CPU_ONLY_KEYS = ('smooth_mat_max_allocations', 'cachesize', 'cachetest', 'smooth_mat_dtype', 'cp_timeout')
 
@@ -178,52 +172,24 @@ def _solve(images, footprints, image_of, cfg, shard, while_waiting=None):
     """One batch over one or several images -> (records, fragments).  Candidates whose workgroup group was given up (a
     scheduling event on an oversubscribed GPU, not a solver failure) are solved again without groups."""
     from . import engine
-    import torch
     if shard is not None:
         assert len(images) == 1, 'sharded batches cover one image'
         return shard.solve(images[0], footprints, cfg)
     batch = engine.Batch(images if len(images) > 1 else images[0], footprints, cfg, image_of=image_of,
-                         mode=1 if len(footprints) < LATENCY_MODE_BELOW else 0)   # a batch that cannot fill the GPU: shortest wall clock
-    start = _starting_points(batch, cfg)
+                         mode=engine.mode_for(len(footprints)))            # a batch that cannot fill the GPU: shortest wall clock
+    batch.starting_points(cfg.get('init'))
     batch.launch()
     if while_waiting is not None:                          # host work of the caller while the kernels run (the launch is asynchronous)
         while_waiting()
     records, masks = batch.download()
+    if batch.resolve_given_up(records['status']).size:
+        records, masks = batch.download()
     records = records.copy()
-    fragments = batch.fragments(records, masks=masks, lazy=True)
-    again = np.flatnonzero(records['status'] == _capi.CAND_GIVEN_UP)
-    if again.size:
-        sub = engine.Batch(images if len(images) > 1 else images[0], [footprints[i] for i in again], cfg,
-                           image_of=None if image_of is None else np.asarray(image_of)[again], mode=2)
-        if start is not None:
-            sub.set_start([start[i] for i in again])
-        sub.launch()
-        rec2, masks2 = sub.download()
-        frag2 = sub.fragments(rec2, masks=masks2, lazy=True)
-        for j, i in enumerate(again):
-            records[i] = rec2[j]
-            fragments[i] = frag2[j]
-    return records, fragments
+    return records, batch.fragments(records, masks=masks, lazy=True)
 
 
 def _starting_points(batch, cfg):
-    """Callable ``dsm/init`` (objects.py:385-386): ``params = init(number of columns of G~)`` per candidate -- the count is a result of
-    the setup kernel, which runs once on its own for it -- handed to the batch as the starting points of its DSM solves.  Returns the
-    list of vectors (None for candidates without a solve), or None if ``init`` is not callable."""
-    init = cfg.get('init')
-    if not callable(init):
-        return None
-    start = []
-    for i, m in enumerate(batch.deform_counts().tolist()):
-        if m < 0:
-            start.append(None)
-            continue
-        p = np.asarray(init(m), np.float64).ravel()
-        if p.size != 6 + m or not np.all(np.isfinite(p)):
-            raise ValueError(f'dsm/init({m}) must return {6 + m} finite parameters (candidate {i}: got {p.size})')
-        start.append(p)
-    batch.set_start(start)
-    return start
+    return batch.starting_points(cfg.get('init'))
 
 
 def _assign(objects, records, fragments, dt, cidx0=0):

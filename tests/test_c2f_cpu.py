@@ -366,3 +366,40 @@ def test_lockstep_driver_takes_a_failing_image_out_of_the_set(lockstep_reference
     assert st['clusters'] == 4 and len(st['rounds']) == 3 and st['launches'] == 3
     assert {'crops', 'plans', 'candidates', 'resolved', 'resolve_plans', 'seconds'} <= set(st['rounds'][0])
     assert {'flood_s', 'host_split_s', 'assemble_s', 'energy_s', 'total_s'} <= set(st)
+
+
+def _energy_record(status=0, energy=-30.0, n=100, pos=40, neg=60):
+    from superdsm_amd import _capi
+    r = np.zeros(1, _capi.RECORD_DTYPE)
+    r['status'], r['energy'], r['n_pixels'], r['n_positive'], r['n_negative'] = status, energy, n, pos, neg
+    return r[0]
+
+
+def test_record_reader_returns_errors_as_objects_and_never_a_non_finite_value():
+    """The one reader of the energy path (``c2f_energy.record_result``): None for a region without an energy, an error object for a
+    failed, given-up or non-finite record, ``energy / n`` otherwise."""
+    from superdsm_amd import _capi, c2f_energy, c2freganal
+    from superdsm_amd.objects import CvxprogError
+    assert c2freganal.C2FError is c2f_energy.C2FError
+    read = c2f_energy.record_result
+    assert read(_energy_record(), 3) == -30.0 / 100 and isinstance(read(_energy_record(), 3), float)
+    assert read(_energy_record(status=_capi.CAND_FALLBACK, energy=12.5, n=8, pos=1, neg=7), 0) == 12.5 / 8
+    for r in (_energy_record(n=0, pos=0, neg=0), _energy_record(pos=100, neg=0), _energy_record(pos=0, neg=100),
+              _energy_record(status=_capi.CAND_GIVEN_UP, energy=np.nan, pos=100, neg=0)):
+        assert read(r, 0) is None
+    for status in (_capi.CAND_ERROR, _capi.CAND_UNSUPPORTED):
+        e = read(_energy_record(status=status), 7)
+        assert isinstance(e, CvxprogError) and e.cidx == 7
+    for r in (_energy_record(status=_capi.CAND_GIVEN_UP, energy=np.nan), _energy_record(status=_capi.CAND_GIVEN_UP),
+              _energy_record(energy=np.nan), _energy_record(energy=np.inf), _energy_record(energy=-np.inf)):
+        e = read(r, 5)
+        assert isinstance(e, c2f_energy.C2FError) and not isinstance(e, float) and 'candidate 5' in str(e)
+
+
+def test_energy_config_drops_every_cpu_only_key():
+    from superdsm_amd import c2f_energy, objects
+    dsm_cfg = dict({k: 1 for k in objects._CPU_ONLY_KEYS}, scale=1000, smooth_amount=4, background_margin=7, init='elliptical')
+    cfg, margin = c2f_energy.energy_config(dsm_cfg)
+    assert len(objects._CPU_ONLY_KEYS) == 5 and not set(objects._CPU_ONLY_KEYS) & set(cfg)
+    assert cfg == dict(scale=1000, smooth_amount=np.inf, no_trivial_rule=True, init='elliptical') and margin == 7.0
+    assert dsm_cfg['smooth_amount'] == 4 and 'background_margin' in dsm_cfg          # the caller's dict is left alone
