@@ -1643,6 +1643,7 @@ __device__ __forceinline__ void solve_candidate(const BatchParams &P, int ci, in
             sdsm_record r = {};
             r.status = st.status == ST_TRIVIAL ? SDSM_CAND_TRIVIAL : (st.status == ST_UNSUPPORTED ? SDSM_CAND_UNSUPPORTED : SDSM_CAND_ERROR);
             r.n_pixels = cd.N;
+            r.n_positive = st.npos; r.n_negative = st.nneg;      // (the region scan of the setup kernel counted them before it stopped)
             *rec = r;
         }
         return;

@@ -282,6 +282,254 @@ def post_reference(g, gs, bg, off, frag, exterior_scale, exterior_offset, contra
 
 
 # ---------------------------------------------------------------------------------------------------------
+# the mask tail of a candidate's solve (tests/test_mask_tail_cpu.py and tests/test_mask_tail_gpu.py): what the foreground bits, the
+# fragment box, ``on_boundary`` and the two counts of a record should BE at given parameters.  NumPy and the CPU oracle's region and G~.
+# ---------------------------------------------------------------------------------------------------------
+TAIL_BAND = 2.0 ** -40
+
+
+def tail_reference(y, y_mask, atoms, footprint, cfg, theta, xi=None):
+    """The result of a candidate at the parameters (theta, xi), pixel by pixel (superdsm/objects.py:198-209, dsm.py:86-94 and 113-128 with
+    ``roi.offset = 0``, image.get_pixel_map): at region pixel (r, c) of the H x W image, u = r / max(H - 1, 1), v = c / max(W - 1, 1),
+
+        S = a1 u^2 + a2 v^2 + 2 a3 u v + 2 b1 u + 2 b2 v + c + (G~ xi)[pixel],
+
+    every operation in np.longdouble (x86: 64-bit significand); the pixel is foreground iff S > 0.  The region is the oracle's
+    (``oracle.region_mask``), G~ the oracle's CSR matrix (``oracle.smooth_matrix``: float32-exact weights, which the setup tests pin bit for
+    bit against the setup kernel).  ``xi`` None or all zero: the polynomial alone (no G~ is built).
+
+    Guard band.  With A = the sum of the absolute values of the six polynomial terms and of every |w xi| product of the pixel, a pixel is
+    DECIDED when |S| > 2^-40 A.  The solve kernel evaluates the surface in a candidate-local basis (centre and half extents of the region
+    box) and the record's theta is that basis converted back; both evaluations are float64 sums of at most 6 + nnz terms (nnz: entries of
+    the pixel's row of G~, a few hundred at the most), each term bounded by the corresponding full-image one, so the kernel's S differs
+    from the exact S at the RECORDED parameters by a few hundred * 2^-53 * A.  2^-40 is about 8000 * 2^-53: a wide margin over that, and
+    still so narrow that on real scenes no pixel falls inside it (tests/test_mask_tail_cpu.py counts them).  The band follows from the number
+    format and the term count alone; it is not fitted to what the kernel returns.
+
+    ``on_boundary`` is the same rule for the polynomial alone (G~ has no rows off the region) on the 2 (W + 2) + 2 (H + 2) positions of the
+    one-pixel ring around the image, r in {-1, H} x c in -1 .. W and c in {-1, W} x r in -1 .. H, corners included: 1 if a ring pixel is
+    decided positive, 0 if all are decided non-positive, None (undecided) otherwise.
+
+    Returns a dict: ``box`` (r0, c0, h, w) the region's bounding box (None for an empty region); over that box ``region``, ``expected``
+    (S > 0), ``decided`` (bool arrays; ``decided`` is False off the region) and ``ratio`` (|S| / A, inf off the region and where A = 0);
+    ``fg_box`` (r0, c0, h, w) of the expected bits, None if there is none; ``on_boundary`` and ``ring_ratio`` (smallest |S| / A on the ring);
+    ``n_pixels``, ``n_positive`` (region pixels with y > 0) and ``n_negative`` (y < 0; zeros of either sign count in neither)."""
+    from oracle import oracle                              # test infrastructure, as this function is
+    X = np.longdouble
+    assert np.finfo(X).eps < 1e-18, 'np.longdouble must be wider than float64'
+    y = np.asarray(y, np.float64)
+    H, W = y.shape
+    band = X(TAIL_BAND)
+    th = [X(float(t)) for t in np.asarray(theta, np.float64).ravel()]
+    assert len(th) == 6
+    a1, a2, a3, b1, b2, c0 = th
+    zu, zv = X(max(H - 1, 1)), X(max(W - 1, 1))
+
+    def poly(r, c):
+        u, v = np.asarray(r).astype(X) / zu, np.asarray(c).astype(X) / zv
+        terms = (a1 * u * u, a2 * v * v, X(2) * a3 * u * v, X(2) * b1 * u, X(2) * b2 * v, c0 + X(0) * u)
+        S, A = terms[0], np.abs(terms[0])
+        for t in terms[1:]:
+            S, A = S + t, A + np.abs(t)
+        return S, A
+
+    region = oracle.region_mask(y, y_mask, atoms, footprint, cfg.get('background_margin', 20))
+    rr, cc = np.nonzero(region)                            # raster order: the order of the rows of G~
+    yr = y[region]
+    out = dict(n_pixels=int(region.sum()), n_positive=int((yr > 0).sum()), n_negative=int((yr < 0).sum()), box=None, fg_box=None)
+    # the ring of the image
+    ring_r = np.concatenate([np.full(W + 2, -1), np.full(W + 2, H), np.arange(-1, H + 1), np.arange(-1, H + 1)])
+    ring_c = np.concatenate([np.arange(-1, W + 1), np.arange(-1, W + 1), np.full(H + 2, -1), np.full(H + 2, W)])
+    Sr, Ar = poly(ring_r, ring_c)
+    dec = np.abs(Sr) > band * Ar
+    out['on_boundary'] = 1 if (dec & (Sr > 0)).any() else (0 if dec.all() else None)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        out['ring_ratio'] = float(np.where(Ar > 0, np.abs(Sr) / Ar, np.inf).min())
+    if out['n_pixels'] == 0:
+        return out
+    S, A = poly(rr, cc)
+    xi = None if xi is None else np.asarray(xi, np.float64).ravel()
+    if xi is not None and xi.size and np.any(xi != 0):
+        sm = oracle.smooth_matrix(region, cfg.get('smooth_amount', 10), cfg.get('gaussian_shape_multiplier', 2), cfg.get('smooth_subsample', 20))
+        assert sm.N == out['n_pixels'] and sm.M == xi.size, (sm.N, sm.M, out['n_pixels'], xi.size)
+        prod = sm.data.astype(X) * xi[sm.indices].astype(X)
+        row = np.repeat(np.arange(sm.N), np.diff(sm.indptr))
+        gs, ga = np.zeros(sm.N, X), np.zeros(sm.N, X)
+        np.add.at(gs, row, prod)
+        np.add.at(ga, row, np.abs(prod))
+        S, A = S + gs, A + ga
+    r0, c0b = int(rr.min()), int(cc.min())
+    h, w = int(rr.max()) - r0 + 1, int(cc.max()) - c0b + 1
+    out['box'] = (r0, c0b, h, w)
+    crop = lambda a: a[r0:r0 + h, c0b:c0b + w]
+    out['region'] = crop(region).copy()
+    expected, decided, ratio = np.zeros((H, W), bool), np.zeros((H, W), bool), np.full((H, W), np.inf)
+    expected[rr, cc] = S > 0
+    decided[rr, cc] = np.abs(S) > band * A
+    with np.errstate(divide='ignore', invalid='ignore'):
+        ratio[rr, cc] = np.where(A > 0, np.abs(S) / A, np.inf).astype(np.float64)
+    out['expected'], out['decided'], out['ratio'] = crop(expected).copy(), crop(decided).copy(), crop(ratio).copy()
+    if expected.any():
+        fr, fc = np.flatnonzero(expected.any(axis=1)), np.flatnonzero(expected.any(axis=0))
+        out['fg_box'] = (int(fr[0]), int(fc[0]), int(fr[-1] - fr[0] + 1), int(fc[-1] - fc[0] + 1))
+    return out
+
+
+def tail_paste(box, a, shape, fill=False):
+    """A box-sized array of :func:`tail_reference` (or of a mask box of a plan) in a full image of ``shape``."""
+    out = np.full(shape, fill, np.asarray(a).dtype)
+    if box is not None:
+        out[box[0]:box[0] + box[2], box[1]:box[1] + box[3]] = a
+    return out
+
+
+def _toy_cfg(**kw):
+    return dict(dict(scale=1000, epsilon=1.0, alpha=0.033, smooth_amount=4, smooth_subsample=8, gaussian_shape_multiplier=2,
+                     background_margin=8, init='elliptical'), **kw)
+
+
+def edge_case_scene():
+    """96 x 120: a nucleus with a hole of ``y_mask`` inside, a nucleus cut by the image border, a single positive pixel (a trivial
+    candidate) and a union of two atoms."""
+    rng = np.random.default_rng(5)
+    H, W = 96, 120
+    rr, cc = np.mgrid[:H, :W]
+    y = -0.2 + 0.02 * rng.standard_normal((H, W))
+    y = np.minimum(y, -0.01)
+    y[((rr - 30) / 11.0) ** 2 + ((cc - 40) / 15.0) ** 2 <= 1] = 0.35          # a nucleus
+    y[((rr - 70) / 9.0) ** 2 + ((cc - 4) / 12.0) ** 2 <= 1] = 0.3             # a nucleus cut by the image border
+    y[60, 90] = 0.4                                                           # a single positive pixel (noise)
+    atoms = np.ones((H, W), np.int32)
+    atoms[:, 70:] = 2
+    atoms[50:, :35] = 3
+    y_mask = np.ones((H, W), bool)
+    y_mask[25:35, 38:41] = False                                              # a hole in the mask inside the nucleus
+    return dict(name='edge cases', y=y, y_mask=y_mask, atoms=atoms, cfg=_toy_cfg(), footprints=[[1], [2], [3], [1, 3]])
+
+
+def dense_grid_scene():
+    """110 x 120, one candidate, smooth_subsample 3: rows of G~ of ~100 entries and a Hessian envelope beyond the LDS classes."""
+    rng = np.random.default_rng(11)
+    H, W = 110, 120
+    rr, cc = np.mgrid[:H, :W]
+    y = -0.15 + 0.03 * rng.standard_normal((H, W))
+    blob = ((rr - 55) / 30.0) ** 2 + ((cc - 60) / 36.0) ** 2
+    y += 0.5 * np.exp(-1.5 * blob)
+    y += 0.25 * np.exp(-(((rr - 40) / 9.0) ** 2 + ((cc - 85) / 7.0) ** 2))       # a bump the ellipse cannot follow
+    atoms = np.ones((H, W), np.int32)
+    return dict(name='dense grid', y=y, y_mask=None, atoms=atoms, cfg=_toy_cfg(alpha=0.05, smooth_subsample=3, background_margin=6), footprints=[[1]])
+
+
+def beyond_setup_tables_scene():
+    """150 x 170, smooth_subsample 2 on a 17 k-pixel region: more grid points (~4300) than the setup kernel's tables hold, beside an
+    ordinary candidate."""
+    rng = np.random.default_rng(8)
+    H, W = 150, 170
+    rr, cc = np.mgrid[:H, :W]
+    y = -0.1 + 0.02 * rng.standard_normal((H, W))
+    y += 0.4 * np.exp(-(((rr - 75) / 50.0) ** 2 + ((cc - 85) / 58.0) ** 2) ** 2)
+    atoms = np.ones((H, W), np.int32)
+    atoms[:, 100:] = 2
+    atoms[55:95, 70:100] = 3                                # a piece of the blob's flank: an ordinary candidate beside the oversized one
+    return dict(name='beyond the setup tables', y=y, y_mask=None, atoms=atoms,
+                cfg=_toy_cfg(alpha=0.05, smooth_amount=2, smooth_subsample=2, background_margin=12), footprints=[[1, 2, 3], [3]])
+
+
+def two_blob_scene(seed=3, H=96, W=128):
+    """Two noisy blobs, one atom each: ``(y, atoms)``."""
+    rng = np.random.default_rng(seed)
+    rr, cc = np.mgrid[:H, :W]
+    y = -0.2 + 0.03 * rng.standard_normal((H, W))
+    y += 0.55 * np.exp(-(((rr - 46) / 17.0) ** 2 + ((cc - 40) / 21.0) ** 2) ** 1.5)
+    y += 0.5 * np.exp(-(((rr - 50) / 15.0) ** 2 + ((cc - 88) / 18.0) ** 2) ** 1.5)
+    atoms = np.ones((H, W), np.int32)
+    atoms[:, 64:] = 2
+    return y, atoms
+
+
+def straddling_rows_scene():
+    """40 x 100, one candidate whose region box is 77 columns wide (> 64, and 77 mod 32 = 13 is coprime with 32: every row of the box
+    begins at another bit of a mask word); exact zeros and -0.0 among the region's intensities."""
+    rng = np.random.default_rng(21)
+    H, W = 40, 100
+    rr, cc = np.mgrid[:H, :W]
+    y = -0.2 + 0.02 * rng.standard_normal((H, W))
+    y += 0.6 * np.exp(-(((rr - 19) / 11.0) ** 2 + ((cc - 46) / 30.0) ** 2) ** 1.5)
+    y += 0.2 * np.exp(-(((rr - 12) / 4.0) ** 2 + ((cc - 70) / 5.0) ** 2))
+    y[8, 20:25] = 0.0
+    y[30, 40:44] = -0.0
+    y[19, 10] = 0.0
+    atoms = np.full((H, W), 2, np.int32)
+    atoms[:, 7:84] = 1
+    return dict(name='straddling rows', y=y, y_mask=None, atoms=atoms, cfg=_toy_cfg(smooth_subsample=6, background_margin=40), footprints=[[1]])
+
+
+TAIL_CRAFTED_SHAPES = ((24, 37), (37, 24))
+
+
+def tail_crafted_image(shape):
+    """An image of one atom whose region is the whole image (positive pixels everywhere within the margin) and the hyper-parameters of
+    the crafted cases: ``alpha = inf`` makes every deformable solve fail, so that a candidate with a callable ``dsm/init`` returns its
+    initialisation (status FALLBACK) and the mask tail runs at parameters of the caller's choice; M > 0."""
+    rng = np.random.default_rng(100 + shape[0])
+    y = np.where(rng.random(shape) < 0.4, 0.3, -0.2) + 0.01 * rng.standard_normal(shape)
+    return dict(y=y, y_mask=None, atoms=np.ones(shape, np.int32), footprint=[1],
+                cfg=_toy_cfg(alpha=np.inf, smooth_amount=2, smooth_subsample=4, background_margin=40))
+
+
+def _pixel_theta(shape, rr=0.0, cc=0.0, r=0.0, c=0.0, k=0.0):
+    """theta of S = rr row^2 + cc col^2 + r row + c col + k, in PIXEL coordinates (small dyadic numbers: S is exact in them)."""
+    zu, zv = float(max(shape[0] - 1, 1)), float(max(shape[1] - 1, 1))
+    return np.array([rr * zu * zu, cc * zv * zv, 0.0, r * zu / 2, c * zv / 2, k])
+
+
+def tail_crafted_cases(shape, M):
+    """``name -> dict(params = theta (6) + xi (M), mask = 'empty' | 'full' | 'reference', on_boundary = 0 | 1)`` for an image of
+    :func:`tail_crafted_image`; what ``mask`` and ``on_boundary`` say is written out by hand here, the reference must agree.
+
+    * a plane positive at ONE ring corner only (0.5 there, -0.5 at its two ring neighbours, falling from there);
+    * a plane positive on ONE ring line only (0.5 there, -0.5 on the adjacent line of the image);
+    * a concave paraboloid, negative on every ring pixel (its zero ellipse has the half axes (H - 1) / 2 + 0.5 and (W - 1) / 2 + 0.5), which
+      alone is negative at the image's corners too -- no quadric is positive on the whole rectangle and negative on the whole ring: the
+      ellipse through ring-edge midpoints cannot hold the rectangle's corners --, lifted above zero on every pixel by a constant xi (G~
+      has rows on the region only, so the ring does not see it);
+    * a constant -0.25 and xi alternating in sign with an amplitude that flips the surface: an intricate mask."""
+    H, W = shape
+    alt = (-1.0) ** np.arange(M)
+    small = alt * 2.0 ** -6                                  # takes every plane through the G~ path without changing a sign (rows of G~ sum to <= 1)
+    C = {}
+    for rname, sr, kr in (('top', 1.0, 1.0), ('bottom', -1.0, float(H))):            # distance of a row from the ring row: sr * row + kr
+        for cname, sc, kc in (('left', 1.0, 1.0), ('right', -1.0, float(W))):
+            C[f'corner {rname} {cname}'] = dict(params=np.concatenate([_pixel_theta(shape, r=-sr, c=-sc, k=0.5 - kr - kc), small]), mask='empty', on_boundary=1)
+    C['row -1'] = dict(params=np.concatenate([_pixel_theta(shape, r=-1.0, k=-0.5), small]), mask='empty', on_boundary=1)
+    C['row H'] = dict(params=np.concatenate([_pixel_theta(shape, r=1.0, k=0.5 - H), small]), mask='empty', on_boundary=1)
+    C['column -1'] = dict(params=np.concatenate([_pixel_theta(shape, c=-1.0, k=-0.5), small]), mask='empty', on_boundary=1)
+    C['column W'] = dict(params=np.concatenate([_pixel_theta(shape, c=1.0, k=0.5 - W), small]), mask='empty', on_boundary=1)
+    # 1 - ((row - (H-1)/2) / (H/2))^2 - ((col - (W-1)/2) / (W/2))^2, times (H W / 4)^2 / 2^14: dyadic coefficients, values within +-4
+    ar, ac, mr, mc = W * W / 4.0, H * H / 4.0, (H - 1) / 2.0, (W - 1) / 2.0
+    bowl = 2.0 ** -14 * np.array([-ar, -ac, 2 * ar * mr, 2 * ac * mc, (H * W / 4.0) ** 2 - ar * mr * mr - ac * mc * mc])
+    C['paraboloid'] = dict(params=np.concatenate([_pixel_theta(shape, *bowl), np.full(M, 64.0)]), mask='full', on_boundary=0)
+    flips = (-1.0) ** (np.arange(M) + np.arange(M) // 7)     # (7 divides neither grid width, 10 and 6: no plain stripes)
+    C['alternating'] = dict(params=np.concatenate([_pixel_theta(shape, k=-0.25), 64.0 * flips]), mask='reference', on_boundary=0)
+    return C
+
+
+def tail_two_image_cases(M_of):
+    """Candidates of a plan over the two crafted images, ``[(image index, name, params, on_boundary)]``: every surface is positive on
+    the ring of its own image (or, for the controls, nowhere on it) and non-positive where the ring of the OTHER image would lie -- the
+    controls are positive only there.  ``M_of``: the number of columns of G~ of the two images' candidates."""
+    (Ha, Wa), (Hb, Wb) = TAIL_CRAFTED_SHAPES
+    z = lambda i: np.zeros(M_of[i])
+    th = lambda i, **kw: np.concatenate([_pixel_theta(TAIL_CRAFTED_SHAPES[i], **kw), z(i)])
+    return [(0, 'column W of the wide image', th(0, c=1.0, k=0.5 - Wa), 1),
+            (1, 'row H of the tall image', th(1, r=1.0, k=0.5 - Hb), 1),
+            (0, 'corner (-1, W) of the wide image', th(0, r=-1.0, c=1.0, k=-0.5 - Wa), 1),
+            (1, 'corner (H, -1) of the tall image', th(1, r=1.0, c=-1.0, k=-0.5 - Hb), 1),
+            (0, 'control: row H of the tall image, on the wide one', th(0, r=1.0, k=0.5 - Hb), 0),
+            (1, 'control: column W of the wide image, on the tall one', th(1, c=1.0, k=0.5 - Wa), 0)]
+
+
+# ---------------------------------------------------------------------------------------------------------
 # the cases of the exact post-processing steps (tests/test_post_steps_gpu.py and tests/test_post_steps_cpu.py): hole filling, the
 # background mask, the glare test.  NumPy only; the CPU file checks what the cases claim about themselves.
 # ---------------------------------------------------------------------------------------------------------

@@ -475,22 +475,10 @@ def test_large_scale_workloads_match_oracle(gpu, workload):
 def test_edge_cases_trivial_masked_border_and_elliptical_only(gpu):
     from oracle import oracle
     from superdsm_amd import _capi, engine, image, objects
-    rng = np.random.default_rng(5)
-    H, W = 96, 120
-    rr, cc = np.mgrid[:H, :W]
-    y = -0.2 + 0.02 * rng.standard_normal((H, W))
-    y = np.minimum(y, -0.01)
-    y[((rr - 30) / 11.0) ** 2 + ((cc - 40) / 15.0) ** 2 <= 1] = 0.35          # a nucleus
-    y[((rr - 70) / 9.0) ** 2 + ((cc - 4) / 12.0) ** 2 <= 1] = 0.3             # a nucleus cut by the image border
-    y[60, 90] = 0.4                                                           # a single positive pixel (noise)
-    atoms = np.ones((H, W), np.int32)
-    atoms[:, 70:] = 2
-    atoms[50:, :35] = 3
-    y_mask = np.ones((H, W), bool)
-    y_mask[25:35, 38:41] = False                                              # a hole in the mask inside the nucleus
-    cfg = dict(scale=1000, epsilon=1.0, alpha=0.033, smooth_amount=4, smooth_subsample=8, gaussian_shape_multiplier=2,
-               background_margin=8, init='elliptical')
-    fps = [[1], [2], [3], [1, 3]]
+    from superdsm_amd import testing
+    sc = testing.edge_case_scene()        # a nucleus with a hole of the mask inside, one cut by the border, a single positive pixel, a union of two atoms
+    y, y_mask, atoms, cfg, fps = sc['y'], sc['y_mask'], sc['atoms'], sc['cfg'], sc['footprints']
+    H, W = y.shape
     img = engine.DeviceImage(y, y_mask, atoms, cfg['background_margin'])
     batch = engine.Batch(img, fps, cfg)
     batch.launch()
@@ -647,16 +635,10 @@ def test_wide_envelope_and_long_rows_use_the_global_memory_class(gpu):
     path) and a Hessian envelope far beyond the LDS classes (class 3: envelope in global memory)."""
     from oracle import oracle
     from superdsm_amd import engine
-    rng = np.random.default_rng(11)
-    H, W = 110, 120
-    rr, cc = np.mgrid[:H, :W]
-    y = -0.15 + 0.03 * rng.standard_normal((H, W))
-    blob = ((rr - 55) / 30.0) ** 2 + ((cc - 60) / 36.0) ** 2
-    y += 0.5 * np.exp(-1.5 * blob)
-    y += 0.25 * np.exp(-(((rr - 40) / 9.0) ** 2 + ((cc - 85) / 7.0) ** 2))       # a bump the ellipse cannot follow
-    atoms = np.ones((H, W), np.int32)
-    cfg = dict(scale=1000, epsilon=1.0, alpha=0.05, smooth_amount=4, smooth_subsample=3, gaussian_shape_multiplier=2,
-               background_margin=6, init='elliptical')
+    from superdsm_amd import testing
+    sc = testing.dense_grid_scene()
+    y, atoms, cfg = sc['y'], sc['atoms'], sc['cfg']
+    H, W = y.shape
     img = engine.DeviceImage(y, None, atoms, cfg['background_margin'])
     batch = engine.Batch(img, [[1]], cfg)
     batch.launch()
@@ -1007,14 +989,8 @@ def test_bbbc039_like_every_candidate_matches_oracle(gpu):
 
 
 def _two_blob_scene(seed=3, H=96, W=128):
-    rng = np.random.default_rng(seed)
-    rr, cc = np.mgrid[:H, :W]
-    y = -0.2 + 0.03 * rng.standard_normal((H, W))
-    y += 0.55 * np.exp(-(((rr - 46) / 17.0) ** 2 + ((cc - 40) / 21.0) ** 2) ** 1.5)
-    y += 0.5 * np.exp(-(((rr - 50) / 15.0) ** 2 + ((cc - 88) / 18.0) ** 2) ** 1.5)
-    atoms = np.ones((H, W), np.int32)
-    atoms[:, 64:] = 2
-    return y, atoms
+    from superdsm_amd import testing
+    return testing.two_blob_scene(seed, H, W)
 
 
 @pytest.mark.parametrize('max_iters', [1, 2, 3, 6])
@@ -1151,18 +1127,9 @@ def test_regions_beyond_the_setup_tables_get_the_elliptical_result_not_an_abort(
     """More grid points than the setup kernel's tables hold (here: smooth_subsample 2 on a 17 k-pixel region: M ~ 4300 > 2048): status
     UNSUPPORTED WITH the elliptical result -- through compute_objects a usable object (the elliptical solution as a fallback with a warning),
     never an abort of the batch (objects.py:399-410: failure => fallback); the other candidates of the batch are solved as usual."""
-    from superdsm_amd import _capi, engine, image, objects
-    rng = np.random.default_rng(8)
-    H, W = 150, 170
-    rr, cc = np.mgrid[:H, :W]
-    y = -0.1 + 0.02 * rng.standard_normal((H, W))
-    y += 0.4 * np.exp(-(((rr - 75) / 50.0) ** 2 + ((cc - 85) / 58.0) ** 2) ** 2)
-    atoms = np.ones((H, W), np.int32)
-    atoms[:, 100:] = 2
-    atoms[55:95, 70:100] = 3                                # a piece of the blob's flank: an ordinary candidate beside the oversized one
-    cfg = dict(scale=1000, epsilon=1.0, alpha=0.05, smooth_amount=2, smooth_subsample=2, gaussian_shape_multiplier=2,
-               background_margin=12, init='elliptical')
-    fps = [[1, 2, 3], [3]]
+    from superdsm_amd import _capi, engine, image, objects, testing
+    sc = testing.beyond_setup_tables_scene()
+    y, atoms, cfg, fps = sc['y'], sc['atoms'], sc['cfg'], sc['footprints']
     img = engine.DeviceImage(y, None, atoms, cfg['background_margin'])
     batch = engine.Batch(img, fps, cfg)
     batch.launch()
