@@ -536,6 +536,62 @@ int sdsm_overlap_pairs_multi(const sdsm_set_image *images, int n_images, const i
 int sdsm_overlap_pairs(int H, int W, const int32_t *d_a, const int32_t *d_b, int64_t capacity, uint64_t *d_keys,
                        uint64_t *d_counts, int32_t *d_status, void *stream);   /* the set of one image */
 
+/* ---- boundary distances between two label maps (no reference counterpart; the definitions are label_boundaries_host and
+ * pair_distances_host of superdsm_amd/boundary.py) -----------------------------------------------------------------------------------
+ * A pixel of label l != 0 is a boundary pixel of l iff one of its 4-neighbours inside the image carries another label (the image border
+ * makes no boundary).  For a pair of labels (a of map A, b of map B) the record below holds, in integers only, what the Hausdorff
+ * distance, the mean surface distance and the normalised sum of distances follow from.  q(d2) = floor(sqrt(d2 * 2^32)) is the distance
+ * in units of 2^-16 pixel, the exact integer root.  Conventions as for the measurement tables: sets as a HOST table of sdsm_set_image,
+ * pixel buffers packed as the table says, the single-image form is the set of that one image; every atomic is an integer add or max,
+ * so the records do not depend on the order, the launch, the set size or the work split, and no output buffer needs clearing.
+ * Limits: labels 0 .. SDSM_BOUNDARY_MAX_LABELS - 1 (others are counted and skipped), H * H + W * W < 2^31 per image: every squared
+ * distance fits int32, every side 16 bits and H * W < 2^30.  64 bytes. */
+#define SDSM_BOUNDARY_MAX_LABELS 65536
+#define SDSM_BOUNDARY_TILE 1024         /* boundary pixels of the target that a workgroup stages through LDS at a time */
+#define SDSM_BOUNDARY_CHUNK 1024        /* query pixels of one work item (one workgroup) */
+typedef struct {
+    int32_t a, b;                       /* the two labels */
+    int32_t boundary_a, boundary_b;     /* boundary pixels of each */
+    int32_t max_d2_ab, max_d2_ba;       /* max over the boundary pixels of one of the min squared distance to the boundary of the other; -1 with a flag */
+    int32_t flags;                      /* bit 0: the boundary of a is empty (also: a does not occur); bit 1: the same for b */
+    int32_t reserved;                   /* 0 */
+    int64_t sum_q_ab, sum_q_ba;         /* sums of q(min d2) over the same pixels as the maxima; 0 with a flag */
+    int64_t nsd_num;                    /* sum over the pixels in exactly one of the two objects of q(min d2 to the boundary of b) */
+    int64_t nsd_den;                    /* the same sum over the pixels in either object */
+} sdsm_pair_distance;
+/* One pass over a label map (d_labels int32, packed): image i owns the 2 * SDSM_BOUNDARY_MAX_LABELS int32 of d_counts from
+ * i * 2 * SDSM_BOUNDARY_MAX_LABELS on: [2 l] the pixels of label l, [2 l + 1] its boundary pixels (0 for l = 0).  d_bad[i] (int32): the
+ * pixels with a label outside the range; they are skipped.  Both are cleared by the call. */
+int sdsm_label_pixel_counts_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, int32_t *d_counts, int32_t *d_bad,
+                                  void *stream);
+int sdsm_label_pixel_counts(int H, int W, const int32_t *d_labels, int32_t *d_counts, int32_t *d_bad, void *stream);
+/* The pixels of every label l >= 1 as one list per image, from the d_counts of the same map: d_start (SDSM_BOUNDARY_MAX_LABELS int32 per
+ * image, written here) = the first entry of label l (the ranges of the labels are disjoint and dense, in no particular order); label l owns the
+ * entries d_start[l] .. d_start[l] + pixels - 1 of the image's part of d_list (uint32, packed as the pixel buffers): its boundary pixels
+ * first, then the others, each as row << 16 | column.  The order inside either part is the arrival order: sort before relying on it.
+ * d_cursor (2 * SDSM_BOUNDARY_MAX_LABELS int32 per image) is scratch.  Entries of d_list that no label owns are not written. */
+int sdsm_label_pixel_lists_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int32_t *d_counts, int32_t *d_start,
+                                 int32_t *d_cursor, uint32_t *d_list, void *stream);
+int sdsm_label_pixel_lists(int H, int W, const int32_t *d_labels, const int32_t *d_counts, int32_t *d_start, int32_t *d_cursor, uint32_t *d_list,
+                           void *stream);
+/* d_records[k] for the n_pairs pairs of d_pairs (4 int32 each: image, label a, label b, 0), from the counts, starts and lists of the two
+ * maps d_a, d_b of the set.  The call initialises every record (a pair whose image or labels are out of range gets both flags).  The
+ * work is the list d_items (n_items x 4 int32: pair, phase, chunk, 0), one workgroup each: phase 0 takes the boundary pixels of a
+ * against the boundary of b (max_d2_ab, sum_q_ab), phase 1 those of b against the boundary of a, phase 2 all pixels of a and phase 3
+ * the pixels of b that do not carry a in d_a, both against the boundary of b (nsd_num, nsd_den); chunk c stands for the entries
+ * c * SDSM_BOUNDARY_CHUNK .. of that phase's pixel list.  A complete list names every chunk of every phase of every pair without a flag
+ * once; an item of a flagged pair, out of range or past the end of its list does nothing.  n_pairs or n_items 0: no launch. */
+int sdsm_pair_distances_multi(const sdsm_set_image *images, int n_images, const int32_t *d_a, const int32_t *d_b, const int32_t *d_counts_a,
+                              const int32_t *d_counts_b, const int32_t *d_start_a, const int32_t *d_start_b, const uint32_t *d_list_a,
+                              const uint32_t *d_list_b, int n_pairs, const int32_t *d_pairs, int64_t n_items, const int32_t *d_items,
+                              sdsm_pair_distance *d_records, void *stream);
+int sdsm_pair_distances(int H, int W, const int32_t *d_a, const int32_t *d_b, const int32_t *d_counts_a, const int32_t *d_counts_b,
+                        const int32_t *d_start_a, const int32_t *d_start_b, const uint32_t *d_list_a, const uint32_t *d_list_b, int n_pairs,
+                        const int32_t *d_pairs, int64_t n_items, const int32_t *d_items, sdsm_pair_distance *d_records, void *stream);
+/* Host helper (no device access): out[k] = q(d2[k]) by the code the kernel runs (a float estimate, then a correction in 64-bit integers
+ * until r * r <= d2 * 2^32 < (r + 1) * (r + 1)); a negative d2 gives 0. */
+int sdsm_quantised_distance(const int32_t *d2, int64_t n, int64_t *out);
+
 /* ---- host-side combinatorial steps of the stage (no device access) -------------------------------------------------------------
  * Approximate min-weight set cover (superdsm/minsetcover.py:4-88: greedy + merge phase, retried with beta * gamma on up to max_iter
  * levels) and greedy max-weight set packing (superdsm/maxsetpack.py:8-24) over n objects whose footprints are bit sets of `words`

@@ -50,6 +50,13 @@ _MEASURE_FIELDS = [('area', 'i8'), ('sum_r', 'i8'), ('sum_c', 'i8'), ('sum_rr', 
                    ('n_finite', 'i8'), ('gsum_lo', 'u8'), ('gsum_hi', 'i8'), ('gmin', 'f8'), ('gmax', 'f8')]
 MEASURE_RECORD_DTYPE = np.dtype(_MEASURE_FIELDS)                                   # sdsm_measure_record
 assert MEASURE_RECORD_DTYPE.itemsize == 112
+BOUNDARY_MAX_LABELS = 65536  # SDSM_BOUNDARY_MAX_LABELS: labels 0 .. 65535 per image of the boundary distances
+BOUNDARY_TILE = 1024         # SDSM_BOUNDARY_TILE: boundary pixels of the target per LDS tile of the distance kernel
+BOUNDARY_CHUNK = 1024        # SDSM_BOUNDARY_CHUNK: query pixels of one work item of the distance kernel
+PAIR_DISTANCE_DTYPE = np.dtype([('a', '<i4'), ('b', '<i4'), ('boundary_a', '<i4'), ('boundary_b', '<i4'), ('max_d2_ab', '<i4'), ('max_d2_ba', '<i4'),
+                                ('flags', '<i4'), ('reserved', '<i4'), ('sum_q_ab', '<i8'), ('sum_q_ba', '<i8'), ('nsd_num', '<i8'),
+                                ('nsd_den', '<i8')])                                 # sdsm_pair_distance
+assert PAIR_DISTANCE_DTYPE.itemsize == 64
 
 
 class MeasureRecord(C.Structure):
@@ -159,6 +166,13 @@ SYMBOLS = {
     'sdsm_measure_labels_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp, _vp]),
     'sdsm_overlap_pairs': (_i32, [_i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     'sdsm_overlap_pairs_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _vp, _vp, _vp, _vp]),
+    'sdsm_label_pixel_counts': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp]),
+    'sdsm_label_pixel_counts_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, _vp, _vp]),
+    'sdsm_label_pixel_lists': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_label_pixel_lists_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_pair_distances': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp]),
+    'sdsm_pair_distances_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp]),
+    'sdsm_quantised_distance': (_i32, [_vp, _i64, _vp]),
     'sdsm_minsetcover': (_i32, [_i32, _i32, _vp, _vp, _f64, _i32, _i32, _f64, _vp, _vp]),
     'sdsm_minsetcover_multi': (_i32, [_i32, _vp, _vp, _vp, _vp, _f64, _i32, _i32, _f64, _vp, _vp]),
     'sdsm_maxsetpack': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp]),

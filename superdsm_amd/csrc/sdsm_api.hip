@@ -1307,6 +1307,90 @@ extern "C" int sdsm_overlap_pairs(int H, int W, const int32_t *d_a, const int32_
     return sdsm_overlap_pairs_multi(&one, 1, d_a, d_b, &off, &capacity, d_keys, d_counts, d_status, stream);
 }
 
+// ---- boundary distances between two label maps (sdsm_measure.hip) ---------------------------------------------------------------------
+extern "C" hipError_t sdsm_label_pixel_counts_impl(const sdsm_set_image *images, int n_images, const int32_t *labels, int32_t *counts, int32_t *bad,
+                                                   hipStream_t stream);
+extern "C" hipError_t sdsm_label_pixel_lists_impl(const sdsm_set_image *images, int n_images, const int32_t *labels, const int32_t *counts,
+                                                  int32_t *start, int32_t *cursor, uint32_t *list, hipStream_t stream);
+extern "C" hipError_t sdsm_pair_distances_impl(const sdsm_set_image *images, int n_images, const int32_t *d_a, const int32_t *d_b,
+                                               const int32_t *counts_a, const int32_t *counts_b, const int32_t *start_a, const int32_t *start_b,
+                                               const uint32_t *list_a, const uint32_t *list_b, int n_pairs, const int32_t *pairs, int64_t n_items,
+                                               const int32_t *items, sdsm_pair_distance *recs, hipStream_t stream);
+extern "C" void sdsm_quantised_distance_impl(const int32_t *d2, int64_t n, int64_t *out);
+
+// H^2 + W^2 < 2^31: every squared distance fits int32 (and so every side 16 bits, H * W 30 bits)
+static bool boundary_shapes_ok(const sdsm_set_image *images, int n_images)
+{
+    for (int i = 0; i < n_images; i++)
+        if ((int64_t)images[i].H * images[i].H + (int64_t)images[i].W * images[i].W >= (int64_t)1 << 31) return false;
+    return true;
+}
+#define BOUNDARY_TABLE(name) \
+    SET_TABLE(name, 0); \
+    if (!boundary_shapes_ok(images, n_images)) return fail(SDSM_ERR_ARGUMENT, name ": H * H + W * W < 2^31 required")
+
+extern "C" int sdsm_label_pixel_counts_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, int32_t *d_counts, int32_t *d_bad,
+                                             void *stream)
+{
+    BOUNDARY_TABLE("sdsm_label_pixel_counts");
+    if (!d_labels || !d_counts || !d_bad) return fail(SDSM_ERR_ARGUMENT, "sdsm_label_pixel_counts: null argument");
+    hipError_t e = sdsm_label_pixel_counts_impl(images, n_images, d_labels, d_counts, d_bad, (hipStream_t)stream);
+    SET_DONE("sdsm_label_pixel_counts");
+}
+
+extern "C" int sdsm_label_pixel_counts(int H, int W, const int32_t *d_labels, int32_t *d_counts, int32_t *d_bad, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_label_pixel_counts_multi(&one, 1, d_labels, d_counts, d_bad, stream);
+}
+
+extern "C" int sdsm_label_pixel_lists_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int32_t *d_counts,
+                                            int32_t *d_start, int32_t *d_cursor, uint32_t *d_list, void *stream)
+{
+    BOUNDARY_TABLE("sdsm_label_pixel_lists");
+    if (!d_labels || !d_counts || !d_start || !d_cursor || !d_list) return fail(SDSM_ERR_ARGUMENT, "sdsm_label_pixel_lists: null argument");
+    hipError_t e = sdsm_label_pixel_lists_impl(images, n_images, d_labels, d_counts, d_start, d_cursor, d_list, (hipStream_t)stream);
+    SET_DONE("sdsm_label_pixel_lists");
+}
+
+extern "C" int sdsm_label_pixel_lists(int H, int W, const int32_t *d_labels, const int32_t *d_counts, int32_t *d_start, int32_t *d_cursor,
+                                      uint32_t *d_list, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_label_pixel_lists_multi(&one, 1, d_labels, d_counts, d_start, d_cursor, d_list, stream);
+}
+
+extern "C" int sdsm_pair_distances_multi(const sdsm_set_image *images, int n_images, const int32_t *d_a, const int32_t *d_b, const int32_t *d_counts_a,
+                                         const int32_t *d_counts_b, const int32_t *d_start_a, const int32_t *d_start_b, const uint32_t *d_list_a,
+                                         const uint32_t *d_list_b, int n_pairs, const int32_t *d_pairs, int64_t n_items, const int32_t *d_items,
+                                         sdsm_pair_distance *d_records, void *stream)
+{
+    BOUNDARY_TABLE("sdsm_pair_distances");
+    if (n_pairs < 0 || n_items < 0 || n_items > INT_MAX) return fail(SDSM_ERR_ARGUMENT, "sdsm_pair_distances: 0 <= n_pairs, 0 <= n_items < 2^31 required");
+    if (n_pairs == 0) return SDSM_OK;
+    if (!d_a || !d_b || !d_counts_a || !d_counts_b || !d_start_a || !d_start_b || !d_list_a || !d_list_b || !d_pairs || !d_records || (n_items > 0 && !d_items))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_pair_distances: null argument");
+    hipError_t e = sdsm_pair_distances_impl(images, n_images, d_a, d_b, d_counts_a, d_counts_b, d_start_a, d_start_b, d_list_a, d_list_b, n_pairs, d_pairs,
+                                            n_items, d_items, d_records, (hipStream_t)stream);
+    SET_DONE("sdsm_pair_distances");
+}
+
+extern "C" int sdsm_pair_distances(int H, int W, const int32_t *d_a, const int32_t *d_b, const int32_t *d_counts_a, const int32_t *d_counts_b,
+                                   const int32_t *d_start_a, const int32_t *d_start_b, const uint32_t *d_list_a, const uint32_t *d_list_b, int n_pairs,
+                                   const int32_t *d_pairs, int64_t n_items, const int32_t *d_items, sdsm_pair_distance *d_records, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_pair_distances_multi(&one, 1, d_a, d_b, d_counts_a, d_counts_b, d_start_a, d_start_b, d_list_a, d_list_b, n_pairs, d_pairs, n_items, d_items,
+                                     d_records, stream);
+}
+
+extern "C" int sdsm_quantised_distance(const int32_t *d2, int64_t n, int64_t *out)
+{
+    if (n < 0 || (n > 0 && (!d2 || !out))) return fail(SDSM_ERR_ARGUMENT, "sdsm_quantised_distance: null argument");
+    sdsm_quantised_distance_impl(d2, n, out);
+    return SDSM_OK;
+}
+
 extern "C" int sdsm_post_background_multi(const sdsm_post_bg_image *images, int n_images, const int32_t *d_boxes, const int64_t *d_bits_off,
                                           const uint32_t *d_bits, int radius, void *stream)
 {

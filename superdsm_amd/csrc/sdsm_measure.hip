@@ -19,11 +19,19 @@
 //                       to the image's global hash table (keys claimed by compare-and-swap, 64-bit counts) at the end of the band.  A
 //                       pair without an LDS slot goes straight there; one without a global slot is counted and dropped, never waited for.
 //
+//   k_label_pixel_counts / k_label_starts / k_label_pixel_lists   boundary distances (superdsm_amd/boundary.py): per label its pixels and
+//                       boundary pixels (bands and segments as above, an LDS table keyed by label), the exclusive sum of the counts, and
+//                       every label's pixels scattered into one coordinate list, boundary pixels first (one atomic per run and part)
+//   k_pair_init / k_pair_distances   one workgroup per (pair of labels, phase, chunk of query pixels): the target's boundary list goes
+//                       through LDS in tiles, a lane keeps the 32-bit integer minima of its query pixels, q = floor(sqrt(d2 * 2^32))
+//                       once per query pixel, wavefront reductions, integer atomicMax / 64-bit atomicAdd into the pair's record
+//
 // Every sum over pixels is an integer sum and every atomic an integer add / min / max / or, so the bytes do not depend on the order,
 // the launch or the set size.  Intensities enter as q = rint(ldexp(g, 62 - e)) in two limbs (bits 0-31, and q >> 32).
 #include "sdsm_common.h"
 #include "sdsm_set.h"
 #include <climits>
+#include <cmath>
 
 namespace {
 
@@ -499,7 +507,330 @@ hipError_t launch_scale(MSet S, const double *d_g, double *d_gmax_abs, int32_t *
     return hipGetLastError();
 }
 
+// ---- boundary distances between two label maps -----------------------------------------------------------------------------------------
+constexpr int BMAXL = SDSM_BOUNDARY_MAX_LABELS;
+constexpr int BBITS = 10;
+constexpr int BSLOTS = 1 << BBITS;               // k_label_pixel_counts: slots of the LDS table (12 KB, as k_overlap_pairs)
+constexpr int BPROBES = 8;                       //   slots tried before a label goes to the global atomics
+constexpr int DTILE = SDSM_BOUNDARY_TILE;        // k_pair_distances: target pixels per LDS tile (8 KB as (row, column) pairs)
+constexpr int DCHUNK = SDSM_BOUNDARY_CHUNK;      //   query pixels of a workgroup
+constexpr int DQ = DCHUNK / MTPB;                //   query pixels of a lane
+static_assert(DCHUNK % MTPB == 0 && BMAXL % MTPB == 0 && BMAXL <= 65536, "chunk and label range");
+
+// one of the 4-neighbours of pixel p = (r, c) inside the image carries another label than l
+__device__ __forceinline__ bool on_boundary(const int32_t *lab, int64_t p, int r, int c, int H, int W, int32_t l)
+{
+    return (r > 0 && lab[p - W] != l) || (r + 1 < H && lab[p + W] != l) || (c > 0 && lab[p - 1] != l) || (c + 1 < W && lab[p + 1] != l);
+}
+
+struct BTable {                                  // the per-workgroup table of k_label_pixel_counts
+    int32_t key[BSLOTS];                         // -1: free
+    uint32_t area[BSLOTS], edge[BSLOTS];
+};
+
+__device__ __forceinline__ void flush_counts(BTable &T, int32_t label, uint32_t area, uint32_t edge, int32_t *counts)
+{
+    uint32_t s = ((uint32_t)label * 2654435761u) >> (32 - BBITS);
+    for (int k = 0; k < BPROBES; k++, s = (s + 1) & (BSLOTS - 1)) {
+        const int32_t old = atomicCAS(&T.key[s], -1, label);
+        if (old != -1 && old != label) continue;
+        atomicAdd(&T.area[s], area);
+        if (edge) atomicAdd(&T.edge[s], edge);
+        return;
+    }
+    atomicAdd(counts + 2 * label, (int32_t)area);            // no slot: correct and slow
+    if (edge) atomicAdd(counts + 2 * label + 1, (int32_t)edge);
+}
+
+// the bands and segments of k_measure_labels; a thread keeps the counts of its current label in registers while the label does not change
+__global__ __launch_bounds__(MTPB) void k_label_pixel_counts(MSet S, const int32_t *labels_, int32_t *counts_, int32_t *bad)
+{
+    __shared__ BTable T;
+    const int im = set_find(S.start, S.n, blockIdx.x), tid = threadIdx.x;
+    const int H = S.H[im], W = S.W[im];
+    const int64_t px = (int64_t)H * W;
+    const int64_t p0 = (int64_t)(blockIdx.x - S.start[im]) * LBAND;
+    const int32_t *lab = labels_ + S.off[im];
+    int32_t *counts = counts_ + (int64_t)im * 2 * BMAXL;
+    for (int s = tid; s < BSLOTS; s += MTPB) { T.key[s] = -1; T.area[s] = T.edge[s] = 0; }
+    __syncthreads();
+    int32_t cur = -1;                            // the label whose counts the registers hold; -1: none
+    uint32_t area = 0, edge = 0;
+    int n_bad = 0;
+    for (int it = 0; it < LBAND / (LSEG * MTPB); it++) {
+        const int64_t q0 = p0 + ((int64_t)it * MTPB + tid) * LSEG;
+        if (q0 >= px) break;
+        const int n = px - q0 < LSEG ? (int)(px - q0) : LSEG;
+        int r = (int)(q0 / W), c = (int)(q0 % W);
+#pragma unroll 1
+        for (int k = 0; k < n; k++) {
+            const int32_t l = lab[q0 + k];
+            if (l != cur) {
+                if (cur >= 0) flush_counts(T, cur, area, edge, counts);
+                area = edge = 0;
+                cur = (l >= 0 && l < BMAXL) ? l : -1;
+            }
+            if (cur >= 0) {
+                area++;
+                if (cur != 0 && on_boundary(lab, q0 + k, r, c, H, W, cur)) edge++;
+            } else {
+                n_bad++;
+            }
+            if (++c == W) { c = 0; r++; }
+        }
+    }
+    if (cur >= 0) flush_counts(T, cur, area, edge, counts);
+    if (n_bad) atomicAdd(bad + im, n_bad);
+    __syncthreads();
+    for (int s = tid; s < BSLOTS; s += MTPB) {
+        const int32_t label = T.key[s];
+        if (label < 0) continue;
+        atomicAdd(counts + 2 * label, (int32_t)T.area[s]);
+        if (T.edge[s]) atomicAdd(counts + 2 * label + 1, (int32_t)T.edge[s]);
+    }
+}
+
+// one workgroup per image: every label >= 1 gets its own range of the image's list (fewer than 2^30 entries in all), and the cursors of the
+// scatter are cleared.  Thread t lays the labels t, t + 256, ... one behind the other (coalesced reads and writes), behind the ranges of
+// the threads before it: the ranges are disjoint and dense, their order is not that of the labels.
+__global__ __launch_bounds__(MTPB) void k_label_starts(const int32_t *counts_, int32_t *start_, int32_t *cursor_)
+{
+    __shared__ int32_t part[MTPB];
+    const int tid = threadIdx.x;
+    const int2 *counts = (const int2 *)(counts_ + (int64_t)blockIdx.x * 2 * BMAXL);
+    int32_t *start = start_ + (int64_t)blockIdx.x * BMAXL;
+    int2 *cursor = (int2 *)(cursor_ + (int64_t)blockIdx.x * 2 * BMAXL);
+    int32_t s = 0;
+    for (int l = tid; l < BMAXL; l += MTPB) s += l ? counts[l].x : 0;
+    part[tid] = s;
+    __syncthreads();
+    int32_t base = 0;
+    for (int k = 0; k < tid; k++) base += part[k];
+    for (int l = tid; l < BMAXL; l += MTPB) {
+        start[l] = base;
+        base += l ? counts[l].x : 0;
+        cursor[l] = make_int2(0, 0);
+    }
+}
+
+// A thread walks its segments run by run: the boundary pixels of a run of one label as a bit mask, one atomic per run and part of the
+// label's list, then the coordinates.  An entry past the image's part of the list (counts of another map) is dropped, never written.
+__global__ __launch_bounds__(MTPB) void k_label_pixel_lists(MSet S, const int32_t *labels_, const int32_t *counts_, const int32_t *start_,
+                                                            int32_t *cursor_, uint32_t *list_)
+{
+    static_assert(LSEG <= 32, "the boundary mask of a run");
+    const int im = set_find(S.start, S.n, blockIdx.x), tid = threadIdx.x;
+    const int H = S.H[im], W = S.W[im];
+    const int64_t px = (int64_t)H * W;
+    const int64_t p0 = (int64_t)(blockIdx.x - S.start[im]) * LBAND;
+    const int32_t *lab = labels_ + S.off[im];
+    const int32_t *counts = counts_ + (int64_t)im * 2 * BMAXL, *start = start_ + (int64_t)im * BMAXL;
+    int32_t *cursor = cursor_ + (int64_t)im * 2 * BMAXL;
+    uint32_t *list = list_ + S.off[im];
+    for (int it = 0; it < LBAND / (LSEG * MTPB); it++) {
+        const int64_t q0 = p0 + ((int64_t)it * MTPB + tid) * LSEG;
+        if (q0 >= px) break;
+        const int n = px - q0 < LSEG ? (int)(px - q0) : LSEG;
+        int r = (int)(q0 / W), c = (int)(q0 % W);
+        int k = 0;
+        while (k < n) {
+            const int32_t l = lab[q0 + k];
+            const bool listed = l > 0 && l < BMAXL;
+            int k1 = k, rr = r, cc = c;
+            uint32_t mask = 0;
+            while (k1 < n && lab[q0 + k1] == l) {
+                if (listed && on_boundary(lab, q0 + k1, rr, cc, H, W, l)) mask |= 1u << (k1 - k);
+                if (++cc == W) { cc = 0; rr++; }
+                k1++;
+            }
+            if (listed) {
+                const int nb = __popc(mask), ni = (k1 - k) - nb;
+                uint32_t pb = (uint32_t)start[l] + (nb ? (uint32_t)atomicAdd(cursor + 2 * l, nb) : 0u);
+                uint32_t pi = (uint32_t)start[l] + (uint32_t)counts[2 * l + 1] + (ni ? (uint32_t)atomicAdd(cursor + 2 * l + 1, ni) : 0u);
+                for (int j = k; j < k1; j++) {
+                    const uint32_t v = ((uint32_t)r << 16) | (uint32_t)c;
+                    const uint32_t pos = ((mask >> (j - k)) & 1u) ? pb++ : pi++;
+                    if (pos < (uint64_t)px) list[pos] = v;
+                    if (++c == W) { c = 0; r++; }
+                }
+            } else {
+                r = rr; c = cc;
+            }
+            k = k1;
+        }
+    }
+}
+
+// q(d2) = floor(sqrt(d2 * 2^32)): a float estimate (relative error below 2^-22), one Newton step from the exact 64-bit residual, which
+// leaves it within a few units, then the correction that makes it the integer root by construction.  d2 < 2^31: x < 2^63, r < 2^32.
+__host__ __device__ inline u64 quantised_distance(int32_t d2)
+{
+    if (d2 <= 0) return 0;
+    const u64 x = (u64)(uint32_t)d2 << 32;
+    u64 r = (u64)(sqrtf((float)d2) * 65536.0f);              // >= 65536
+    const i64 e = (i64)(x - r * r);                          // (the difference of the unsigned products, read as signed)
+    r = (u64)((i64)r + (i64)floorf((float)e / (2.0f * (float)r)));
+    while (r * r > x) r--;
+    while ((r + 1) * (r + 1) <= x) r++;
+    return r;
+}
+
+struct DArgs {
+    const int32_t *a, *b, *counts_a, *counts_b, *start_a, *start_b;
+    const uint32_t *list_a, *list_b;
+};
+
+__device__ __forceinline__ bool pair_ok(const MSet &S, int im, int la, int lb)
+{
+    return im >= 0 && im < S.n && la > 0 && la < BMAXL && lb > 0 && lb < BMAXL;
+}
+
+__global__ __launch_bounds__(MTPB) void k_pair_init(MSet S, DArgs A, int n_pairs, const int32_t *pairs, sdsm_pair_distance *recs)
+{
+    const int i = blockIdx.x * MTPB + threadIdx.x;
+    if (i >= n_pairs) return;
+    const int im = pairs[4 * i], la = pairs[4 * i + 1], lb = pairs[4 * i + 2];
+    const bool ok = pair_ok(S, im, la, lb);
+    sdsm_pair_distance R;
+    R.a = la; R.b = lb;
+    R.boundary_a = ok ? A.counts_a[(int64_t)im * 2 * BMAXL + 2 * la + 1] : 0;
+    R.boundary_b = ok ? A.counts_b[(int64_t)im * 2 * BMAXL + 2 * lb + 1] : 0;
+    R.max_d2_ab = R.max_d2_ba = -1;
+    R.flags = (R.boundary_a == 0 ? 1 : 0) | (R.boundary_b == 0 ? 2 : 0);
+    R.reserved = 0;
+    R.sum_q_ab = R.sum_q_ba = R.nsd_num = R.nsd_den = 0;
+    recs[i] = R;
+}
+
+// One workgroup per item (pair, phase, chunk).  A lane owns DQ query pixels and their running minima; the target's boundary goes through
+// LDS in tiles of DTILE pixels, every lane reading the same entry (a broadcast).  Rows and columns differ by less than 2^16, so the
+// squares are 24-bit multiplies and their sum fits int32.  q is applied once per query pixel, after the last tile.
+__global__ __launch_bounds__(MTPB) void k_pair_distances(MSet S, DArgs A, int n_pairs, const int32_t *pairs, const int32_t *items, sdsm_pair_distance *recs)
+{
+    __shared__ int2 tile[DTILE];
+    __shared__ u64 red1[MTPB / 64], red2[MTPB / 64];
+    __shared__ int32_t redm[MTPB / 64];
+    const int tid = threadIdx.x;
+    const int32_t *item = items + 4 * (int64_t)blockIdx.x;
+    const int pair = item[0], phase = item[1], chunk = item[2];
+    if (pair < 0 || pair >= n_pairs || phase < 0 || phase > 3 || chunk < 0) return;          // (uniform: the whole workgroup leaves)
+    const int im = pairs[4 * pair], la = pairs[4 * pair + 1], lb = pairs[4 * pair + 2];
+    if (!pair_ok(S, im, la, lb)) return;
+    const int H = S.H[im], W = S.W[im];
+    const int64_t px = (int64_t)H * W;
+    const int32_t *ca = A.counts_a + (int64_t)im * 2 * BMAXL, *cb = A.counts_b + (int64_t)im * 2 * BMAXL;
+    const int64_t sa = A.start_a[(int64_t)im * BMAXL + la], sb = A.start_b[(int64_t)im * BMAXL + lb];
+    const int64_t nba = ca[2 * la + 1], nbb = cb[2 * lb + 1];
+    if (nba <= 0 || nbb <= 0) return;            // a flagged pair keeps the record of k_pair_init
+    const bool q_of_a = phase == 0 || phase == 2, t_of_a = phase == 1;
+    const int64_t q_n = phase == 0 ? nba : phase == 1 ? nbb : phase == 2 ? ca[2 * la] : cb[2 * lb];
+    const int64_t t_n = t_of_a ? nba : nbb;
+    const int64_t q_s = q_of_a ? sa : sb, t_s = t_of_a ? sa : sb;
+    if (q_s < 0 || t_s < 0 || q_s + q_n > px || t_s + t_n > px) return;                     // (tables of another map: nothing outside the lists is read)
+    const uint32_t *qlist = (q_of_a ? A.list_a : A.list_b) + S.off[im] + q_s;
+    const uint32_t *tlist = (t_of_a ? A.list_a : A.list_b) + S.off[im] + t_s;
+    const int64_t q0 = (int64_t)chunk * DCHUNK;
+    if (q0 >= q_n) return;
+    int qr[DQ], qc[DQ], m[DQ];
+#pragma unroll
+    for (int j = 0; j < DQ; j++) {
+        const int64_t idx = q0 + j * MTPB + tid;
+        const uint32_t v = idx < q_n ? qlist[idx] : 0u;
+        qr[j] = (int)(v >> 16); qc[j] = (int)(v & 0xffffu); m[j] = INT_MAX;
+    }
+    for (int64_t t0 = 0; t0 < t_n; t0 += DTILE) {
+        const int nt = t_n - t0 < DTILE ? (int)(t_n - t0) : DTILE;
+        __syncthreads();
+        for (int k = tid; k < nt; k += MTPB) {
+            const uint32_t v = tlist[t0 + k];
+            tile[k] = make_int2((int)(v >> 16), (int)(v & 0xffffu));
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int k = 0; k < nt; k++) {
+            const int2 t = tile[k];
+#pragma unroll
+            for (int j = 0; j < DQ; j++) {
+                const int dr = qr[j] - t.x, dc = qc[j] - t.y;
+                const int d = __mul24(dr, dr) + __mul24(dc, dc);
+                m[j] = d < m[j] ? d : m[j];
+            }
+        }
+    }
+    int32_t mx = -1;
+    u64 s1 = 0, s2 = 0;                          // phases 0, 1: the sum of q; phases 2, 3: numerator and denominator
+    const int32_t *other = (phase == 2 ? A.b : A.a) + S.off[im];
+    const int32_t other_label = phase == 2 ? lb : la;
+#pragma unroll
+    for (int j = 0; j < DQ; j++) {
+        if (q0 + j * MTPB + tid >= q_n) continue;
+        const u64 q = quantised_distance(m[j]);
+        if (phase < 2) {
+            mx = m[j] > mx ? m[j] : mx;
+            s1 += q;
+        } else {
+            const bool both = qr[j] < H && qc[j] < W && other[(int64_t)qr[j] * W + qc[j]] == other_label;
+            if (phase == 2) { s2 += q; if (!both) s1 += q; }
+            else if (!both) { s1 += q; s2 += q; }            // (a pixel of both objects was visited in phase 2)
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const int32_t tm = __shfl_down(mx, o);
+        mx = tm > mx ? tm : mx;
+        s1 += __shfl_down(s1, o);
+        s2 += __shfl_down(s2, o);
+    }
+    if ((tid & 63) == 0) { redm[tid >> 6] = mx; red1[tid >> 6] = s1; red2[tid >> 6] = s2; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int k = 1; k < MTPB / 64; k++) { mx = redm[k] > mx ? redm[k] : mx; s1 += red1[k]; s2 += red2[k]; }
+        sdsm_pair_distance *R = recs + pair;
+        if (phase == 0) { atomicMax(&R->max_d2_ab, mx); atomicAdd((u64 *)&R->sum_q_ab, s1); }
+        else if (phase == 1) { atomicMax(&R->max_d2_ba, mx); atomicAdd((u64 *)&R->sum_q_ba, s1); }
+        else { if (s1) atomicAdd((u64 *)&R->nsd_num, s1); if (s2) atomicAdd((u64 *)&R->nsd_den, s2); }
+    }
+}
+
 }  // namespace
+
+extern "C" hipError_t sdsm_label_pixel_counts_impl(const sdsm_set_image *images, int n_images, const int32_t *labels, int32_t *counts, int32_t *bad,
+                                                   hipStream_t stream)
+{
+    MSet S = make_mset(images, n_images);
+    hipError_t e = hipMemsetAsync(counts, 0, (size_t)n_images * 2 * BMAXL * sizeof(int32_t), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(bad, 0, (size_t)n_images * sizeof(int32_t), stream);
+    if (e != hipSuccess) return e;
+    grid_pixels(S, LBAND);
+    hipLaunchKernelGGL(k_label_pixel_counts, dim3(S.start[n_images]), dim3(MTPB), 0, stream, S, labels, counts, bad);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t sdsm_label_pixel_lists_impl(const sdsm_set_image *images, int n_images, const int32_t *labels, const int32_t *counts,
+                                                  int32_t *start, int32_t *cursor, uint32_t *list, hipStream_t stream)
+{
+    MSet S = make_mset(images, n_images);
+    hipLaunchKernelGGL(k_label_starts, dim3(n_images), dim3(MTPB), 0, stream, counts, start, cursor);
+    grid_pixels(S, LBAND);
+    hipLaunchKernelGGL(k_label_pixel_lists, dim3(S.start[n_images]), dim3(MTPB), 0, stream, S, labels, counts, start, cursor, list);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t sdsm_pair_distances_impl(const sdsm_set_image *images, int n_images, const int32_t *d_a, const int32_t *d_b,
+                                               const int32_t *counts_a, const int32_t *counts_b, const int32_t *start_a, const int32_t *start_b,
+                                               const uint32_t *list_a, const uint32_t *list_b, int n_pairs, const int32_t *pairs, int64_t n_items,
+                                               const int32_t *items, sdsm_pair_distance *recs, hipStream_t stream)
+{
+    MSet S = make_mset(images, n_images);
+    const DArgs A = {d_a, d_b, counts_a, counts_b, start_a, start_b, list_a, list_b};
+    hipLaunchKernelGGL(k_pair_init, dim3((n_pairs + MTPB - 1) / MTPB), dim3(MTPB), 0, stream, S, A, n_pairs, pairs, recs);
+    if (n_items > 0) hipLaunchKernelGGL(k_pair_distances, dim3((unsigned)n_items), dim3(MTPB), 0, stream, S, A, n_pairs, pairs, items, recs);
+    return hipGetLastError();
+}
+
+extern "C" void sdsm_quantised_distance_impl(const int32_t *d2, int64_t n, int64_t *out)
+{
+    for (int64_t k = 0; k < n; k++) out[k] = (int64_t)quantised_distance(d2[k]);
+}
 
 extern "C" hipError_t sdsm_measure_objects_impl(const sdsm_set_image *images, int n_images, int n, const int32_t *obj_image, const int32_t *boxes,
                                                 const int64_t *bits_off, const uint32_t *bits, const double *d_g, double *d_gmax_abs,
