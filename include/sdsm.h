@@ -662,11 +662,24 @@ int sdsm_set_debug_buffer(void *d_buf);
  * (SDSM_CAND_GIVEN_UP: the caller solves it again in a plan without groups, sdsm_plan_set_latency_mode(plan, 2)); <= 0 restores the
  * default of 50 ms.  Applies to the launches of the calling thread. */
 int sdsm_set_group_timeout_us(double us);
-/* A launch runs its solve classes on the caller's stream and three side streams of the library.  1: they ran side by side when the
- * library probed them (first launch that needed them); 0: they share hardware queues (GPU_MAX_HW_QUEUES was too small when the process
- * first touched the GPU) -- launches are correct but their classes run one after the other, a warning went to stderr once; -1: not
- * probed yet.  No reference counterpart (the reference's parallelism is Ray, objects.py:270-284). */
+/* A launch runs its solve classes on the caller's stream and three side streams of the library (four for plans whose class 2b has a queue
+ * of its own), which must sit on different hardware queues (HIP's default of 4 suffices).  The library keeps a pool of up to 8 side
+ * streams per device and, the first time it sees a caller stream, probes which of them run side by side with that stream and with each
+ * other (before any work of that launch is queued; it synchronises the caller's stream once).  Of the last launch of this process that
+ * needed side streams -- 1: they run side by side; 0: fewer than three side streams with a queue of their own were found -- launches are
+ * correct but classes run one after the other, a warning went to stderr once; -1: not known (no such launch yet, or the probe stayed
+ * undecided on a busy chip: it is repeated at later launches).  No reference counterpart (the reference's parallelism is Ray,
+ * objects.py:270-284). */
 int sdsm_side_queues_distinct(void);
+/* The same launch in figures: out[0] streams in the pool, out[1] side streams with a queue of their own found for the caller's stream,
+ * out[2] probes made so far, out[3 .. 6] pool indices used for side 1 .. 4 (-1: none), out[7] probes that stayed undecided so far. */
+int sdsm_side_queue_report(int32_t out[8]);
+/* The choice itself as a pure host function (no GPU): shares is an (n_pool + 1) x (n_pool + 1) "share a hardware queue" relation, index 0
+ * the caller's stream, 1 + i pool stream i, read symmetrically.  Greedy in pool order: a stream is taken if it shares with neither the
+ * caller's stream nor a stream taken before, until `want` are found; returns how many were found and writes `want` pool indices to out.
+ * Missing ones are replaced: out[2] = out[1] (class 1b behind the groups / class 2), then out[1] = out[0]; nothing found: pool stream 0
+ * throughout; entries from the fourth on, and every entry of an empty pool: -1.  Returns -1 for a bad argument. */
+int sdsm_choose_sides_host(int n_pool, const uint8_t *shares, int want, int32_t *out);
 
 #ifdef __cplusplus
 }

@@ -191,6 +191,8 @@ SYMBOLS = {
     'sdsm_set_debug_buffer': (_i32, [_vp]),
     'sdsm_set_group_timeout_us': (_i32, [_f64]),
     'sdsm_side_queues_distinct': (_i32, []),
+    'sdsm_side_queue_report': (_i32, [_vp]),
+    'sdsm_choose_sides_host': (_i32, [_i32, _vp, _i32, _vp]),
 }
 
 _lib = None

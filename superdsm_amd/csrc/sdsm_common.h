@@ -68,6 +68,11 @@ typedef const u16x4 SDSM_GLOBAL *g_cu16x4_p;
 #define SDSM_MAX_N_GLOBAL 2048     // 6 + M handled by the global-memory class (vectors of that many unknowns in LDS, Hessian + factor in global memory): every grid the
                                    //   setup kernel can build (SDSM_MAX_GRID points) has a DSM solve; beyond (and regions beyond the setup tables): the elliptical result, flagged
 
+#define SDSM_SIDE_POOL 8           // side streams per device, created on demand; a caller stream uses three (four) of them that have hardware queues of their own
+#define SDSM_SIDE_CACHE 16         // caller streams whose choice of side streams is remembered (the oldest is replaced)
+#define SDSM_PROBE_MAX (SDSM_SIDE_POOL + 1)        // participants of a queue probe
+#define SDSM_PROBE_BYTES (16 + 16 * SDSM_PROBE_MAX)
+
 #ifdef SDSM_PROFILE
 #define PROF_NOW() ((long long)__builtin_readcyclecounter())
 #define PROF_ADD(slot, t0) do { long long _t = PROF_NOW(); prof_acc[slot] += _t - (t0); (t0) = _t; } while (0)

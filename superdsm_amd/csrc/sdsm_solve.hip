@@ -2107,8 +2107,8 @@ extern "C" hipError_t sdsm_launch_setup_rows(const BatchParams &P, hipStream_t s
 // chip none becomes free before class 1 is through -- yet the few long candidates of the large classes ARE the end of a launch.  Class 1
 // therefore starts when the FIRST kernel of every side queue has its work in resident workgroups: one wavefront on the caller's stream polls the
 // heads of their launch lists (a head at the end of its list: every entry has been claimed by a resident workgroup) and the ticket counters
-// of the workgroup groups (all tickets drawn: every member has started), with a cap -- side queues that share a hardware queue with the
-// caller's stream (GPU_MAX_HW_QUEUES too small) cannot start before this kernel ends.  (Rounds 2-3: a fixed wait of 60 / 120 us, tuned on one
+// of the workgroup groups (all tickets drawn: every member has started), with a cap -- where fewer than three side streams with a queue of their own were found (choose_sides,
+// sdsm_api.hip) class 1b sits behind the groups on its stream and its list is not claimed before they end: the gate then leaves by its stall rule or its cap.  (Rounds 2-3: a fixed wait of 60 / 120 us, tuned on one
 // workload mix; the wait is now what the launch needs: tens of microseconds for short lists.)
 __global__ void sdsm_k_gate(const int32_t *cls_count, const int32_t *ticket, int l0, int n0, int l1, int n1, int l2, int n2, long long cap_ticks, long long stall_ticks)
 {
@@ -2138,21 +2138,27 @@ __global__ void sdsm_k_gate(const int32_t *cls_count, const int32_t *ticket, int
 #define SDSM_GATE_STALL_US 20
 #endif
 
-// Do the caller's stream and the three side streams run side by side?  Four one-wavefront kernels, one per stream, each waits (at most
-// `cap_ticks`) until all four have started; *timed_out is set if one gave up: some of the streams share a hardware queue.
-__global__ void sdsm_k_queue_probe(int32_t *arrived, int32_t *timed_out, long long cap_ticks)
+// Do `n` streams run side by side?  One one-wavefront kernel per stream; its first lane counts itself in and waits (at most `cap_ticks`) until all
+// `n` have started; *timed_out is set if one gave up: two of the streams share a hardware queue (the second one starts when the first has ended),
+// or the chip had no slot for a wavefront for that long.  Every participant leaves its start and end on the 100 MHz wall clock, so that the host
+// sees which of them ran one after the other.
+__global__ void sdsm_k_queue_probe(int32_t *arrived, int32_t *timed_out, long long *stamp, int n, long long cap_ticks)
 {
-    __hip_atomic_fetch_add(arrived, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x != 0) return;
     const long long t0 = wall_clock64();
-    while (__hip_atomic_load(arrived, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 4) {
+    __hip_atomic_fetch_add(arrived, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    while (__hip_atomic_load(arrived, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < n) {
         if (wall_clock64() - t0 > cap_ticks) { __hip_atomic_store(timed_out, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
         __builtin_amdgcn_s_sleep(16);
     }
+    stamp[0] = t0;
+    stamp[1] = wall_clock64();
 }
-extern "C" hipError_t sdsm_launch_queue_probe(int32_t *d_words /* 2, zeroed */, hipStream_t s0, hipStream_t s1, hipStream_t s2, hipStream_t s3)
+// d_words: SDSM_PROBE_BYTES, zeroed: [0] arrived, [1] timed out, from byte 16: (start, end) of participant i as two int64
+extern "C" hipError_t sdsm_launch_queue_probe(int32_t *d_words, const hipStream_t *streams, int n)
 {
-    hipStream_t st[4] = {s0, s1, s2, s3};
-    for (int i = 0; i < 4; i++) hipLaunchKernelGGL(sdsm_k_queue_probe, dim3(1), dim3(64), 0, st[i], d_words, d_words + 1, 200000ll);   // cap: 2 ms
+    if (n < 1 || n > SDSM_PROBE_MAX) return hipErrorInvalidValue;
+    for (int i = 0; i < n; i++) hipLaunchKernelGGL(sdsm_k_queue_probe, dim3(1), dim3(64), 0, streams[i], d_words, d_words + 1, (long long *)(d_words + 4) + 2 * i, n, 200000ll);   // cap: 2 ms
     return hipGetLastError();
 }
 
@@ -2163,6 +2169,9 @@ extern "C" hipError_t sdsm_launch_queue_probe(int32_t *d_words /* 2, zeroed */, 
 #define SDSM_RESIDENT_3 64          // global-memory class (34 there, 23-33 ms each: none may wait for another; usually none at all)
 #define SDSM_RESIDENT_1B 512        // class 1b: two per compute unit
 #define SDSM_RESIDENT_1 1280        // class 1: four (192 threads) or three (256 threads) per compute unit + a margin that starts as slots free up
+
+// class 2b on a queue of its own (side4): see own_2b below
+extern "C" int sdsm_solve_wants_own_2b(int n_w, int n_d) { return n_w == 0 && n_d >= 2 * SDSM_RESIDENT_2B; }
 
 extern "C" hipError_t sdsm_launch_solve(const BatchParams &P, sdsm_record *records, uint32_t *masks, double *xi_out,
                                         hipStream_t stream, hipStream_t side1, hipStream_t side2, hipStream_t side3, hipStream_t side4, hipEvent_t *ev /* 5 */,
@@ -2189,8 +2198,9 @@ extern "C" hipError_t sdsm_launch_solve(const BatchParams &P, sdsm_record *recor
     //   side2: the workgroup groups of the very large regions, then class 2;
     //   side3: class 1b (two workgroups per compute unit);
     //   caller's stream: class 1 (all candidates in the host's order, largest first; the others leave at once).
-    // The driver maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4): with another stream in use by the caller a side
-    // stream may share a queue and wait behind its neighbour -- superdsm_amd sets the variable to 8 when it is imported first.
+    // The driver maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and kernels of streams that share a queue run one after the other: the caller
+    // passes side streams it has probed to run side by side with `stream` and with each other (choose_sides, sdsm_api.hip).  Where it found fewer than three, two of
+    // the arguments are the same stream (side3 == side2: class 1b behind the groups / class 2; then side2 == side1 as well): fork, launches in order, join all hold.
     // An error while enqueueing (a launch that fails) must not leave forked work behind on the side streams, which all plans of the device share: the first error
     // is kept, nothing further is launched, but every side stream that was forked is still recorded and joined below.
     hipError_t first = hipSuccess;
@@ -2202,7 +2212,7 @@ extern "C" hipError_t sdsm_launch_solve(const BatchParams &P, sdsm_record *recor
     // they are (a fourth stream for class 2 beside the groups was measured slower in round 3: its resident workgroups take compute units from the group members).
     // (only where the list is long: on the 8-copies step, whose list of 2b / 3 candidates holds a few dozen upper bounds and no real candidate, the 128 more resident
     // workgroups at the start cost 0.2 of 4.9 ms)
-    const bool own_2b = n_w == 0 && n_d >= 2 * SDSM_RESIDENT_2B && side4 != nullptr;
+    const bool own_2b = sdsm_solve_wants_own_2b(n_w, n_d) && side4 != nullptr;
     if (n_d > 0 || n_w > 0) {
         if (keep(hipStreamWaitEvent(side1, ev[0], 0))) {
             forked1 = true;

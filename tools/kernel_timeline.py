@@ -19,7 +19,7 @@ lines = ['kernel trace of `python3 bench.py --full --no-cpu --no-extras --steps 
 for r in rows[last[0]:]:
     s, e = (int(r['Start_Timestamp']) - t0) / 1e6, (int(r['End_Timestamp']) - t0) / 1e6
     name = r['Kernel_Name'].split('(')[0].replace('void ', '')
-    lines.append(f'{name:62s} start {s:9.3f}  end {e:9.3f}  dur {e - s:7.3f}  grid {r.get("Grid_Size", r.get("Grid_Size_X", "?"))} wg {r.get("Workgroup_Size", r.get("Workgroup_Size_X", "?"))}  '
+    lines.append(f'{name:62s} start {s:9.3f}  end {e:9.3f}  dur {e - s:7.3f}  queue {r.get("Queue_Id", "?")} stream {r.get("Stream_Id", "?")}  grid {r.get("Grid_Size", r.get("Grid_Size_X", "?"))} wg {r.get("Workgroup_Size", r.get("Workgroup_Size_X", "?"))}  '
                  f'vgpr {r.get("VGPR_Count", "?")} accum {r.get("Accum_VGPR_Count", "?")} sgpr {r.get("SGPR_Count", "?")} lds {r.get("LDS_Block_Size", "?")} scratch {r.get("Scratch_Size", "?")}')
 open(os.path.join(root, 'profiles', f'{tag}_kernel_timeline.txt'), 'w').write('\n'.join(lines) + '\n')
 print('\n'.join(lines[:12]))
