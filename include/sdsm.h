@@ -176,6 +176,15 @@ int sdsm_plan_set_latency_mode(sdsm_plan *plan, int mode);
  * solves candidate i (0: a single workgroup), rows_workgroups[i] = workgroups that build its rows of G~ (0: the setup workgroup itself).
  * Either pointer may be NULL. */
 int sdsm_plan_schedule(const sdsm_plan *plan, int32_t *group_members, int32_t *rows_workgroups);
+/* The solve class of every candidate in the plan's current mode (host only, diagnostics and tests), given what the setup kernel found for it
+ * (status, M and env_size of its state): 0 class 1, 1 class 1b, 2 class 2, 3 class 2b, 4 the global-memory class, 5 / 6 / 7 a workgroup
+ * group with the LDS layout of class 2 / of class 2b / the light layout (at most 288 unknowns and 12 400 envelope doubles: its members
+ * share their compute units with class 1), -1 none (status != 0).  Results do not depend on the class. */
+int sdsm_plan_solve_classes(const sdsm_plan *plan, const int32_t *status, const int32_t *M, const int32_t *env_size, int32_t *cls);
+/* Diagnostic, process-wide, taken by every following launch and by sdsm_plan_solve_classes: the envelope limit (doubles) of the light
+ * group class, in every plan with groups; 0 = no light groups, negative = the default (12 400 in plans of more than 1024 candidates -- a class-1 slot beside a member
+ * helps only where class-1 candidates outnumber the chip's class-1 slots --, none in smaller plans), more than 12 400: SDSM_ERR_ARGUMENT. */
+int sdsm_set_light_envelope_limit(int doubles);
 int sdsm_plan_xi_offsets(const sdsm_plan *plan, int64_t *xi_offset);
 
 /* ---- post-processing, per-object work (superdsm/postprocess.py:254-337) ------------------------------------- */

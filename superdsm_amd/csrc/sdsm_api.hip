@@ -146,6 +146,7 @@ struct sdsm_plan {
     int mode = 0;                // sdsm_plan_set_latency_mode: 0 throughput, 1 latency, 2 no workgroup groups
     int wide_pixels = INT_MAX;   // throughput mode by default
     int boost_pixels = INT_MAX;  // regions above run their pixel passes at a raised priority (throughput mode, layout_plan)
+    int wide_rest = 0;           // some group's bound on M admits more unknowns than the layout of class 2b holds (layout_plan; see sdsm_launch_solve)
     std::vector<float> psf;
     std::vector<int32_t> mask_info, n_pixels;
     std::vector<int64_t> mask_off_bytes, xi_off;
@@ -170,6 +171,7 @@ struct sdsm_plan {
 // stream of PyTorch's pool: classes 1b and 2 on one queue, 10.1 instead of 6.4 ms): hence the pool and the choice per caller stream below.
 // Launches enqueue under the set's mutex (fork and join events belong to the set); launches from different caller streams share the pool.
 static std::mutex g_pool_mutex;
+static std::atomic<int> g_light_emax{-1};   // sdsm_set_light_envelope_limit (process-wide): -1 = the rule of light_limit()
 static std::vector<SideSet *> g_side_sets;
 
 static hipError_t acquire_sides(const sdsm_plan *p, hipStream_t caller)
@@ -233,7 +235,30 @@ static uint32_t perm_inverse(uint32_t N)
 #ifndef SDSM_WIDE_MAX_MEMBERS
 #define SDSM_WIDE_MAX_MEMBERS 256    // throughput mode: group members of one launch (= compute units of an MI355X); the largest regions first
 #endif
+// Throughput mode: the grouped regions that END a launch get members beyond one per SDSM_WIDE_SLICE pixels -- those that may not be light (their bound on M
+// exceeds the light class's unknowns, so they keep a compute unit per member whatever they get) and have at least SDSM_WIDE_BONUS_PCT per cent of the pixels
+// of the plan's largest grouped region.  A member more shortens the passes over the pixels and costs a compute unit.
+#ifndef SDSM_WIDE_BONUS
+#define SDSM_WIDE_BONUS 1            // members more (0: the rule is off; 1 and 2 at 90 %, 1 at 60 % measured on the 8-image step: DESIGN section 9 (z))
+#endif
+#ifndef SDSM_WIDE_BONUS_PCT
+#define SDSM_WIDE_BONUS_PCT 90
+#endif
+// Envelope limit of the light group class for a plan's launches (0: none).  A class-1 slot beside a group member only helps a launch whose class-1 candidates
+// outnumber the class-1 workgroups the chip holds (about 1000, r04_occupancy_probe): in a smaller plan every candidate has a slot at once and the light members
+// would only pay for their third wavefront per SIMD (they run 7-19 % longer; NIH3T3-like, 234 candidates: 5.75 -> 5.89 ms per launch with light groups).
+// An explicit limit (sdsm_set_light_envelope_limit, tests) holds for every plan with groups.
+#ifndef SDSM_LIGHT_MIN_CANDIDATES
+#define SDSM_LIGHT_MIN_CANDIDATES 1024
+#endif
 // Workgroup groups, launch lists and workspace layout (repeated when the scheduling mode changes).
+static int light_limit(const sdsm_plan *p)
+{
+    if (!SDSM_LIGHT_GROUPS || p->n_order_w <= 0) return 0;
+    const int v = g_light_emax.load(std::memory_order_relaxed);
+    if (v >= 0) return v;
+    return p->n > SDSM_LIGHT_MIN_CANDIDATES ? SDSM_KL_EMAX : 0;
+}
 static void layout_plan(sdsm_plan *p)
 {
     const int n = p->n;
@@ -279,7 +304,7 @@ static void layout_plan(sdsm_plan *p)
     };
     // the member budget (both modes: a single image with many large clusters -- 636 candidates, 16 k-pixel regions -- asked for several hundred
     // members in latency mode and took 15 ms instead of 12)
-    std::vector<char> grouped(n, 1);
+    std::vector<char> grouped(n, 1), bonus(n, 0);
     {
         std::vector<int> big;
         for (int i = 0; i < n; i++) if (group_size(p->cand[i].N) > 0) big.push_back(i);
@@ -291,13 +316,24 @@ static void layout_plan(sdsm_plan *p)
             if (members > SDSM_WIDE_MAX_MEMBERS) { cutoff = p->cand[i].N; break; }
         }
         for (int i : big) if (p->cand[i].N <= cutoff) grouped[i] = 0;
+        // the bonus members, inside the same budget, the largest regions first
+        if (SDSM_WIDE_BONUS > 0 && groups && !latency) {
+            long used = 0, nmax = 0;
+            for (int i : big) if (grouped[i]) { used += group_size(p->cand[i].N); nmax = std::max<long>(nmax, p->cand[i].N); }
+            for (int i : big) {
+                if (!grouped[i] || 6 + (long)p->cand[i].Mcap <= SDSM_KL_NMAX || (long long)p->cand[i].N * 100 < (long long)nmax * SDSM_WIDE_BONUS_PCT) continue;
+                const long g = group_size(p->cand[i].N);
+                const long b = std::min<long>(std::min<long>(SDSM_WIDE_BONUS, SDSM_WIDE_MAX_G - g), SDSM_WIDE_MAX_MEMBERS - used);
+                if (b > 0) { bonus[i] = (char)b; used += b; }
+            }
+        }
     }
     long rows_regions = 0;
     for (int i = 0; i < n; i++) rows_regions += p->cand[i].N > SDSM_ROWS_MIN_PIXELS;
     const bool rows_multi = rows_regions <= SDSM_ROWS_MAX_REGIONS;
     for (int i = 0; i < n; i++) {
         CandDesc &c = p->cand[i];
-        const long G = grouped[i] ? group_size(c.N) : 0;
+        const long G = grouped[i] ? group_size(c.N) + bonus[i] : 0;
         // rows of G~ by several workgroups for every large region, whether or not a workgroup group solves it (a 12 k-pixel region took a
         // single setup workgroup 0.5-1 ms: the end of the setup kernel)
         // (only while such regions are few enough to be the END of the setup kernel: with the 5000 of the synthetic 4096^2 plan the setup kernel is
@@ -309,6 +345,8 @@ static void layout_plan(sdsm_plan *p)
         if (G > 0 || c.rows_g > 0) { c.wide_off = p->n_wide; p->n_wide += SDSM_WIDE_SYNC + (int64_t)2 * G * SDSM_WIDE_PBUF; }
         else c.wide_off = -1;
     }
+    p->wide_rest = 0;
+    for (int i = 0; i < n; i++) if (p->cand[i].wide_g > 0 && 6 + (long)p->cand[i].Mcap > SDSM_K2B_NMAX) p->wide_rest = 1;
     p->n_order_c = p->n_order_d = p->n_order_w = p->n_order_r = 0;
     p->rows_mcap = 1;
     p->order.resize(n);
@@ -494,6 +532,16 @@ extern "C" int sdsm_plan_schedule(const sdsm_plan *p, int32_t *group_members, in
         if (group_members) group_members[i] = p->cand[i].wide_g;
         if (rows_workgroups) rows_workgroups[i] = p->cand[i].rows_g;
     }
+    return SDSM_OK;
+}
+
+// The solve class (SDSM_CLS_* of sdsm_solve_class: 0 class 1, 1 class 1b, 2 class 2, 3 class 2b, 4 global memory, 5 / 6 / 7 groups of class-2 / class-2b / light
+// layout, -1 none) of every candidate of the plan in its current mode, given what the setup kernel found (status, M and env_size of its CandState).
+extern "C" int sdsm_plan_solve_classes(const sdsm_plan *p, const int32_t *status, const int32_t *M, const int32_t *env_size, int32_t *cls)
+{
+    if (!p || !status || !M || !env_size || !cls) return fail(SDSM_ERR_ARGUMENT, "sdsm_plan_solve_classes: null argument");
+    const int light = light_limit(p);
+    for (int i = 0; i < p->n; i++) cls[i] = sdsm_solve_class(status[i], M[i], env_size[i], p->cand[i].N, p->cand[i].wide_g, p->wide_pixels, light);
     return SDSM_OK;
 }
 
@@ -700,6 +748,7 @@ static BatchParams make_params(const sdsm_plan *p, void *d_ws)
     for (size_t i = 0; i < p->images.size(); i++) { P.img[i].H = p->images[i].H; P.img[i].W = p->images[i].W; }   // device pointers: filled by the launch
     P.k = p->k; P.R = p->R; P.subsample = p->cfg.smooth_subsample; P.zcap = p->zcap; P.zcap_run = p->zcap_run; P.zshift = p->zshift; P.no_deform = p->no_deform; P.no_trivial_rule = p->cfg.flags & 1;
     P.init_elliptical = p->cfg.init_elliptical; P.max_iters = p->cfg.max_iters; P.k1_pixmax = p->wide_pixels; P.boost_pixels = p->boost_pixels; P.rows_mcap = p->rows_mcap; P.pad2 = g_solver_diag.load(std::memory_order_relaxed);
+    P.light_emax = light_limit(p); P.pad3 = p->wide_rest;
     P.scale = p->cfg.scale; P.epsilon = p->cfg.epsilon; P.alpha = p->cfg.alpha; P.reg_unit = p->cfg.alpha * std::sqrt(p->cfg.epsilon);
     P.cand = (const CandDesc *)(b + p->off_cand); P.state = (CandState *)(b + p->off_state);
     P.fp_labels = (const int32_t *)(b + p->off_fp); P.order = (const int32_t *)(b + p->off_order);
@@ -746,6 +795,14 @@ extern "C" int sdsm_set_solver_diagnostics(int flags)
 {
     if (flags & ~1) return fail(SDSM_ERR_ARGUMENT, "sdsm_set_solver_diagnostics: unknown flag bit (1: recompute at unchanged iterates)");
     g_solver_diag.store(flags, std::memory_order_relaxed);
+    return SDSM_OK;
+}
+
+// Diagnostic: the envelope limit of the light group class for the launches that follow, in every plan with groups (tests move a small region across it); negative: the default (light_limit).
+extern "C" int sdsm_set_light_envelope_limit(int doubles)
+{
+    if (doubles > SDSM_KL_EMAX) return fail(SDSM_ERR_ARGUMENT, "sdsm_set_light_envelope_limit: at most SDSM_KL_EMAX (12400) doubles fit the light layout");
+    g_light_emax.store(doubles < 0 ? -1 : doubles, std::memory_order_relaxed);
     return SDSM_OK;
 }
 

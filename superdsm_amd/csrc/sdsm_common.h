@@ -39,6 +39,12 @@ typedef const u16x4 SDSM_GLOBAL *g_cu16x4_p;
 #define SDSM_WIDE_SLICE 8192
 #endif
 #define SDSM_WIDE_MAX_G 8
+// Light groups: members whose LDS layout (and register budget, sdsm_solve.hip) leaves room for ONE class-1 workgroup on the same compute unit.
+#define SDSM_KL_NMAX 288           // solve class "light group": 6 + M <= 288 and envelope <= 12400 doubles: 512 threads, LDS 126 576 bytes (sdsm_solve.hip: the
+#define SDSM_KL_EMAX 12400         //   static_assert next to the layouts adds class 1's 36 176 bytes to it, allocation granule included)
+#ifndef SDSM_LIGHT_GROUPS
+#define SDSM_LIGHT_GROUPS 1        // 0: a build without the light class (A/B runs)
+#endif
 #define SDSM_WIDE_SYNC 16           // doubles reserved for the group's counters at the start of its pool block
 #define SDSM_WIDE_FCAP 4104         // of them for the psi-type sums of the member's super-chunks (1 count + 4 * 1024 + pad: slices of up to 2 M pixels)
 #define SDSM_WIDE_PBUF (SDSM_K2B_EMAX + SDSM_MAX_N_SOLVE + 64 + SDSM_WIDE_FCAP)   // doubles one workgroup publishes per exchange (the larger envelope of the two group layouts: class 2 / class 2b)
@@ -145,6 +151,7 @@ struct BatchParams {
     double reg_unit;                   // alpha * sqrt(epsilon): the regulariser's value per grid point at xi = 0 (dsm.py:325-326), computed on the host
     float hess_thr;                    // Hessian ignores row entries < hess_thr * row maximum (solver approximation)
     int32_t boost_pixels;              // throughput mode: regions with more pixels run their passes over the pixels at a raised issue priority (the long chains of a launch; layout_plan)
+    int32_t light_emax, pad3;          // envelope limit of the light group class in this launch (SDSM_KL_EMAX; smaller: sdsm_set_light_envelope_limit; 0: no light class); pad3: a group's bound on M exceeds class 2b's unknowns
     int32_t rows_mcap, pad2;           // largest bound on M among the regions whose rows sdsm_k_setup_rows builds (sizes its LDS tables); pad2: solver diagnostics (sdsm_set_solver_diagnostics)
     const CandDesc *cand;
     CandState *state;
@@ -178,7 +185,7 @@ struct BatchParams {
     int32_t *env_rb;
     const float *psf;
     double *wide_pool;                 // sync words and all-reduce buffers of the workgroup groups (CandDesc.wide_off)
-    int32_t *wide_ticket;              // [0] / [1] (the groups of class-2 / class-2b layout): next entry of the group launch list (members are claimed in the order in which workgroups START, see sdsm_solve.hip)
+    int32_t *wide_ticket;              // [0] / [1] / [2] (the groups of class-2 / class-2b / light layout): next entry of the group launch list (members are claimed in the order in which workgroups START, see sdsm_solve.hip)
     long long wide_timeout;            // ticks of the 100 MHz wall clock a group member waits for its partners before the group is given up
 #define SDSM_SOLVER_COUNTERS 32        // cls_count + 32 (int32 words; byte 192 of the zeroed block): 64-bit event counters of the launch (sdsm_batch_solver_counters)
     int32_t *cls_count;                // [l]: next entry of launch list l that a resident workgroup of a class beyond 1 takes (sdsm_k_solve; zeroed before every launch)
@@ -190,13 +197,20 @@ struct BatchParams {
 
 // Solve class of a candidate once its setup is complete: the FIRST class whose limits (6 + M <= NMAX, Hessian envelope <= EMAX
 // doubles, region <= k1_pixmax pixels for the 256-thread classes) it meets.  Results do not depend on the class.
-enum { SDSM_CLS_NONE = -1, SDSM_CLS_1 = 0, SDSM_CLS_1B = 1, SDSM_CLS_2 = 2, SDSM_CLS_2B = 3, SDSM_CLS_3 = 4, SDSM_CLS_WIDE = 5, SDSM_CLS_WIDE2B = 6 };
-__host__ __device__ __forceinline__ int sdsm_solve_class(int status, int M, int env_size, int N, int wide_g, int k1_pixmax)
+// light_emax > 0 (a launch with the light group class, BatchParams.light_emax): the groups try the light layout first, then the layout of class 2b, then that of
+// class 2 -- every group the light class leaves is then on ONE side queue (sdsm_launch_solve; only a group of more than SDSM_K2B_NMAX unknowns
+// still takes the layout of class 2 and waits behind the light ones).  light_emax == 0: the order of the two layouts as it was.
+enum { SDSM_CLS_NONE = -1, SDSM_CLS_1 = 0, SDSM_CLS_1B = 1, SDSM_CLS_2 = 2, SDSM_CLS_2B = 3, SDSM_CLS_3 = 4, SDSM_CLS_WIDE = 5, SDSM_CLS_WIDE2B = 6, SDSM_CLS_WIDE_LIGHT = 7 };
+__host__ __device__ __forceinline__ int sdsm_solve_class(int status, int M, int env_size, int N, int wide_g, int k1_pixmax, int light_emax)
 {
     if (status != ST_OK) return SDSM_CLS_NONE;
     int Mfull = M;
     if (6 + Mfull > SDSM_MAX_N_GLOBAL) Mfull = 0;                            // elliptical result only (flagged unsupported)
     const int nfull = 6 + Mfull, efull = Mfull > 0 ? env_size : 21;
+    if (wide_g > 0 && light_emax > 0) {
+        if (nfull <= SDSM_KL_NMAX && efull <= light_emax) return SDSM_CLS_WIDE_LIGHT;
+        if (nfull <= SDSM_K2B_NMAX && efull <= SDSM_K2B_EMAX) return SDSM_CLS_WIDE2B;
+    }
     if (wide_g > 0 && nfull <= SDSM_MAX_N_SOLVE && efull <= SDSM_K2_EMAX) return SDSM_CLS_WIDE;
     if (wide_g > 0 && nfull <= SDSM_K2B_NMAX && efull <= SDSM_K2B_EMAX) return SDSM_CLS_WIDE2B;      // groups with the LDS layout of class 2b
     if (nfull <= SDSM_K1_NMAX && efull <= SDSM_K1_EMAX && N <= k1_pixmax) return SDSM_CLS_1;

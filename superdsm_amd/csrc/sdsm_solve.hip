@@ -68,6 +68,10 @@ namespace {
 #define SDSM_K1B_WPE 2
 #endif
 #endif
+#ifndef SDSM_KL_THREADS
+#define SDSM_KL_THREADS 512        // threads of a light group member: 512 at three wavefronts per SIMD, or 256 (one wavefront per SIMD: any register count fits beside class 1)
+#endif
+#define SDSM_KL_WPE (SDSM_KL_THREADS == 512 ? 3 : 2)
 #define HZREG SDSM_HZREG   // leading ('significant') entries of a run unrolled for the approximate Hessian
 #define NSLOT SDSM_MSLOTS
 
@@ -91,6 +95,15 @@ struct Lay {
     static constexpr int END = HP + (GLOBALH ? 0 : EMAX);
     static constexpr int TOTAL_BYTES = ((END * 8 + 15) / 16) * 16;
 };
+
+// The light group class shares its compute unit with one class-1 workgroup: LDS is handed out in granules of 1280 bytes (the 163 840 bytes of a gfx950
+// compute unit are 128 of them; 512 on its predecessors -- both are checked).  Lay<288, 12400, false, 512> ends at double 15 821 = 126 576 bytes = 99 granules,
+// class 1 (192 threads: 36 176 bytes, latency mode's 256 threads: 36 432 bytes) takes 29: 128 granules, the whole compute unit.
+constexpr int lds_granules(int bytes, int granule) { return (bytes + granule - 1) / granule; }
+#define SDSM_LIGHT_FITS(K1T, GRAN) (lds_granules(Lay<SDSM_KL_NMAX, SDSM_KL_EMAX, false, SDSM_KL_THREADS>::TOTAL_BYTES, GRAN) + lds_granules(Lay<SDSM_K1_NMAX, SDSM_K1_EMAX, false, K1T>::TOTAL_BYTES, GRAN) <= 160 * 1024 / (GRAN))
+static_assert(Lay<SDSM_KL_NMAX, SDSM_KL_EMAX, false, SDSM_KL_THREADS>::TOTAL_BYTES <= 126576 && Lay<SDSM_K1_NMAX, SDSM_K1_EMAX, false, SDSM_K1_THREADS>::TOTAL_BYTES <= 36432, "light group layout: 126 576 bytes beside class 1's 36 176 (36 432 at 256 threads)");
+static_assert(SDSM_LIGHT_FITS(SDSM_K1_THREADS, 1280) && SDSM_LIGHT_FITS(256, 1280) && SDSM_LIGHT_FITS(SDSM_K1_THREADS, 512) && SDSM_LIGHT_FITS(256, 512), "a light group member and one class-1 workgroup share the 160 KB of a compute unit");
+static_assert(SDSM_KL_EMAX + SDSM_KL_NMAX <= SDSM_K2B_EMAX + SDSM_MAX_N_SOLVE && SDSM_KL_NMAX <= SDSM_K2B_NMAX && SDSM_KL_EMAX <= SDSM_K2B_EMAX, "SDSM_WIDE_PBUF is sized by the largest group layout; every light group fits the layout of class 2b");
 
 #define SD ((double *)sdsm_smem)
 
@@ -1419,11 +1432,11 @@ __device__ __forceinline__ int factor_solve(const Cand &c, int M, double tau_in,
     // back substitution L^T z = yrow: by one wavefront in registers when n <= 512 (back_substitute_wave; which variant depends on n
     // alone, and all of them do the same arithmetic per row), else blocked like the factorisation (one barrier per panel: 64 us per solve
     // of 258 unknowns against 37 us of the wavefront version at 249)
-    if (L::NMAX <= 128 || n <= 256 || (L::NMAX >= 512 && n <= 512)) {
+    if (L::NMAX <= 128 || n <= 256 || (L::NMAX > 256 && n <= 512)) {
         if (n <= 64) back_substitute_wave<1>(Hp, yrow, dg, rbp, fstp, zl, n, tid);
         else if constexpr (L::NMAX <= 128) back_substitute_wave<2>(Hp, yrow, dg, rbp, fstp, zl, n, tid);
         else if (n <= 256) back_substitute_wave<4>(Hp, yrow, dg, rbp, fstp, zl, n, tid);
-        else if constexpr (L::NMAX >= 512) back_substitute_wave<8>(Hp, yrow, dg, rbp, fstp, zl, n, tid);
+        else if constexpr (L::NMAX > 256) back_substitute_wave<(L::NMAX < 512 ? (L::NMAX + 63) / 64 : 8)>(Hp, yrow, dg, rbp, fstp, zl, n, tid);   // (the light groups' 288 unknowns: 5 rows per lane)
         __syncthreads();
     } else {
         // back substitution L^T z = yrow, blocked the same way: the threads that have a row to update (or write the block's
@@ -1653,7 +1666,7 @@ __device__ __forceinline__ void solve_candidate(const BatchParams &P, int ci, in
     if (6 + Mfull > SDSM_MAX_N_GLOBAL) { unsupported = true; Mfull = 0; }    // elliptical result only (flagged)
     const int efull = Mfull > 0 ? st.env_size : 21;
     {
-        const int cls = sdsm_solve_class(st.status, st.M, st.env_size, cd.N, cd.wide_g, P.k1_pixmax);
+        const int cls = sdsm_solve_class(st.status, st.M, st.env_size, cd.N, cd.wide_g, P.k1_pixmax, P.light_emax);
         if (accept_any ? !(cls >= SDSM_CLS_1B && cls <= SDSM_CLS_3) : cls != CLS) return;
     }
     if (GLOBALH && cd.hglob_off < 0) {                          // cannot happen (the host reserves a slot whenever Mcap admits it)
@@ -1941,7 +1954,7 @@ __global__ __launch_bounds__(WGSIZE, WPE) void sdsm_k_solve(BatchParams P, int h
     }
     if constexpr (WIDE) {                                    // members are claimed in start order, not by workgroup index (see wide_barrier)
         int *tk = reinterpret_cast<int *>(SD + L::FLAG);
-        if (tid == 0) *tk = __hip_atomic_fetch_add(P.wide_ticket + (CLS == SDSM_CLS_WIDE2B ? 1 : 0), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) *tk = __hip_atomic_fetch_add(P.wide_ticket + (CLS == SDSM_CLS_WIDE_LIGHT ? 2 : CLS == SDSM_CLS_WIDE2B ? 1 : 0), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
         const int slot = uni(*tk);
         __syncthreads();
@@ -2195,7 +2208,7 @@ extern "C" hipError_t sdsm_launch_solve(const BatchParams &P, sdsm_record *recor
     if (n_c > 0 || n_d > 0 || n_w > 0) { if ((e = hipEventRecord(ev[0], stream)) != hipSuccess) return e; }
     // Queues (kernels of one stream run one after the other; the longest chains first on each):
     //   side1: the global-memory class (one candidate takes tens of milliseconds), then class 2b;
-    //   side2: the workgroup groups of the very large regions, then class 2;
+    //   side2: the workgroup groups of the very large regions (the light ones, or those of class-2 layout), then class 2;
     //   side3: class 1b (two workgroups per compute unit);
     //   caller's stream: class 1 (all candidates in the host's order, largest first; the others leave at once).
     // The driver maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and kernels of streams that share a queue run one after the other: the caller
@@ -2206,6 +2219,7 @@ extern "C" hipError_t sdsm_launch_solve(const BatchParams &P, sdsm_record *recor
     hipError_t first = hipSuccess;
     auto keep = [&](hipError_t r) { if (first == hipSuccess && r != hipSuccess) first = r; return first == hipSuccess; };
     bool forked1 = false, forked2 = false, forked3 = false, forked4 = false;
+    const bool light = SDSM_LIGHT_GROUPS && P.light_emax > 0;
     // Plans WITHOUT workgroup groups (synthetic 4096^2: every class has hundreds of candidates of its own): class 2b on a queue of its own instead of behind the
     // global-memory class -- a kernel behind another one starts when class 1 already holds the chip with resident workgroups, and a 512-thread workgroup then gets no
     // compute unit before class 1 is through (start / end stamps of that launch: class 2b started at 50 of 59 ms and was its last 9 ms).  With groups the queues stay as
@@ -2231,7 +2245,15 @@ extern "C" hipError_t sdsm_launch_solve(const BatchParams &P, sdsm_record *recor
     if ((n_w > 0 || n_c > 0) && first == hipSuccess) {
         if (keep(hipStreamWaitEvent(side2, ev[0], 0))) {
             forked2 = true;
-            if (n_w > 0 && first == hipSuccess) keep(launch_class<SDSM_MAX_N_SOLVE, SDSM_K2_EMAX, 2, false, 512, true, SDSM_CLS_WIDE>(Pw, n_w, -1, 0, records, masks, xi_out, side2));
+            // Light groups (a launch with P.light_emax > 0): THREE wavefronts per SIMD, i.e. at most 168 registers -- a member's two wavefronts per SIMD and the one of a
+            // class-1 workgroup (168 as well) are 504 of the 512 registers of a lane, its LDS leaves class 1's 36 KB free: the compute unit of a member, which waits on LDS
+            // round trips and barriers most of the time, also runs a class-1 candidate.  Every group the light class leaves has the layout of class 2b (side 1) in such
+            // a launch (sdsm_solve_class), so no group kernel stands behind this one.
+            if (n_w > 0 && light && first == hipSuccess) keep(launch_class<SDSM_KL_NMAX, SDSM_KL_EMAX, SDSM_KL_WPE, false, SDSM_KL_THREADS, true, SDSM_CLS_WIDE_LIGHT>(Pw, n_w, -1, 0, records, masks, xi_out, side2));
+            // (P.pad3: the bound on M of some group admits more unknowns than class 2b holds -- the groups of class-2 layout, if there are any after all, wait behind the light
+            // ones and are not seen by the gate of class 1: slow for them, and 6 + M > 512 at an envelope of at most 11 000 doubles is a region of hundreds of thousands of pixels
+            // a few grid points wide)
+            if (n_w > 0 && (!light || P.pad3) && first == hipSuccess) keep(launch_class<SDSM_MAX_N_SOLVE, SDSM_K2_EMAX, 2, false, 512, true, SDSM_CLS_WIDE>(Pw, n_w, -1, 0, records, masks, xi_out, side2));
             if (n_c > 0 && first == hipSuccess) keep(launch_class<SDSM_MAX_N_SOLVE, SDSM_K2_EMAX, 2, false, 512, false, SDSM_CLS_2>(Pc, g_c, 1, 0, records, masks, xi_out, side2));
         }
     }
@@ -2254,9 +2276,9 @@ extern "C" hipError_t sdsm_launch_solve(const BatchParams &P, sdsm_record *recor
     // microseconds after them -- their resident workgroups are in place by then, the ones without work gone again.
     if ((n_c > 0 || n_d > 0 || n_w > 0) && first == hipSuccess) {
         // the first kernel of every side queue: side 1: groups of class-2b layout (ticket [1]), else the global-memory class (list 3); side 2: groups of
-        // class-2 layout (ticket [0]), else class 2 (list 1); side 3: class 1b (list 0)
+        // class-2 layout (ticket [0]) or of the light layout (ticket [2]), else class 2 (list 1); side 3: class 1b (list 0)
         const int l0 = n_w > 0 ? -2 : 3, c0 = n_w > 0 ? n_w : n_d;
-        const int l1 = n_w > 0 ? -1 : 1, c1 = n_w > 0 ? n_w : n_c;
+        const int l1 = n_w > 0 ? (light ? -3 : -1) : 1, c1 = n_w > 0 ? n_w : n_c;
         hipLaunchKernelGGL(sdsm_k_gate, dim3(1), dim3(64), 0, stream, (const int32_t *)P.cls_count, (const int32_t *)P.wide_ticket, l0, c0, l1, c1, 0, n_c,
                            (long long)SDSM_GATE_CAP_US * 100, (long long)SDSM_GATE_STALL_US * 100);
     }

@@ -63,6 +63,19 @@ for c in range(6):
 print('the last 15 to end (end, start, duration ms, class, N, M):')
 for k in np.argsort(-np.where(ok, en, -1))[:15]:
     print('  end %.2f start %.2f dur %.2f %s N=%d M=%d' % (en[k], st[k], en[k] - st[k], names[cls[k]], N[k], recs['n_deform'][k]))
+# the workgroup groups one by one, with the class each ran in (5 / 6: members with a compute unit of their own, 7: light members, which share theirs with class 1)
+gcls = np.full(batch.n, -1, np.int32)
+if hasattr(_capi.lib(), 'sdsm_plan_solve_classes'):
+    q = lambda a: np.ascontiguousarray(a, np.int32)
+    s_status, s_M, s_env = q(state[:, 1]), q(state[:, 0]), q(state[:, 15])
+    _capi.check(_capi.lib().sdsm_plan_solve_classes(batch.plan, s_status.ctypes.data_as(C.c_void_p), s_M.ctypes.data_as(C.c_void_p), s_env.ctypes.data_as(C.c_void_p), gcls.ctypes.data_as(C.c_void_p)), 'classes')
+print('groups (class, members, N, M, env, start, end, duration ms), largest first; class -1: a library without sdsm_plan_solve_classes')
+for k in np.argsort(-N):
+    if grp[k]:
+        print('  cls %d g=%d N=%d M=%d env=%d start %.2f end %.2f dur %.2f' % (gcls[k], gm[k], N[k], recs['n_deform'][k], env[k], st[k], en[k], en[k] - st[k]))
+light = grp & (gcls == 7)
+if light.any():
+    print('light groups: %d candidates, %d members, duration median %.2f max %.2f ms; other groups: %d candidates, %d members' % (light.sum(), gm[light].sum(), np.median((en - st)[light]), (en - st)[light].max(), (grp & ~light).sum(), gm[grp & ~light].sum()))
 # residency: workgroups of class 1 running at time t
 for t in (0.25, 0.5, 1, 2, 3, 4, 5, 6):
     print('  t=%.2f ms: running K1 %d  K1b %d  others %d' % (t, int((ok & (cls == 0) & (st <= t) & (en > t)).sum()), int((ok & (cls == 1) & (st <= t) & (en > t)).sum()), int((ok & (cls > 1) & (st <= t) & (en > t)).sum())))
