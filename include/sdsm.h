@@ -652,6 +652,17 @@ int sdsm_plan_set_start(const sdsm_plan *plan, const double *d_x0);
 int64_t sdsm_plan_eval_param_count(const sdsm_plan *plan);
 int64_t sdsm_plan_eval_out_count(const sdsm_plan *plan);
 int sdsm_batch_eval(const sdsm_plan *plan, void *d_workspace, size_t workspace_bytes, const double *d_params, double *d_out, void *stream);
+/* Parity / debug: the scalar arithmetic every pass over the pixels goes through, element by element -- the device functions of the
+ * solve kernels as compiled (no host copy), with the table of the logarithm where those kernels keep it.  d_y, d_S, d_x: n doubles each
+ * (device memory), 0 <= n <= SDSM_PROBE_LOSS_MAX; d_out: SDSM_PROBE_N arrays of n doubles, array k at d_out + k * n.  With
+ * t = d_y[i] * d_S[i] and u = exp_neg(min(|t|, 750)) (a NaN t counts as 750, as in the kernels):
+ *   SDSM_PROBE_T t   SDSM_PROBE_EXP u   SDSM_PROBE_LOG log_w(u, 1 + u)   SDSM_PROBE_SOFTPLUS softplus_neg(t) = log(1 + exp(-t))
+ *   SDSM_PROBE_PHI / _R / _DCURV the three results of loss_terms(d_y[i], d_S[i]): phi = log(1 + exp(-t)), r = -y theta with
+ *   theta = 1 / (1 + exp(t)), dcurv = y^2 u / (1 + u)^2   SDSM_PROBE_RCP rcp_f64(d_x[i])   SDSM_PROBE_RSQRT rsqrt_f64(d_x[i])
+ * Asynchronous on `stream`. */
+#define SDSM_PROBE_LOSS_MAX (1 << 20)
+enum { SDSM_PROBE_T = 0, SDSM_PROBE_EXP, SDSM_PROBE_LOG, SDSM_PROBE_SOFTPLUS, SDSM_PROBE_PHI, SDSM_PROBE_R, SDSM_PROBE_DCURV, SDSM_PROBE_RCP, SDSM_PROBE_RSQRT, SDSM_PROBE_N };
+int sdsm_probe_loss_arithmetic(int64_t n, const double *d_y, const double *d_S, const double *d_x, double *d_out, void *stream);
 
 /* Timing of the dominant kernel with HIP events on the launch stream: after sdsm_batch_launch returns,
  * sdsm_last_solve_kernel_ms() synchronises on the recorded events and returns the solve kernels' duration. */

@@ -183,6 +183,7 @@ SYMBOLS = {
     'sdsm_plan_eval_param_count': (_i64, [_vp]),
     'sdsm_plan_eval_out_count': (_i64, [_vp]),
     'sdsm_batch_eval': (_i32, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    'sdsm_probe_loss_arithmetic': (_i32, [_i64, _vp, _vp, _vp, _vp, _vp]),
     'sdsm_batch_deform_counts': (_i32, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     'sdsm_plan_set_start': (_i32, [_vp, _vp]),
     'sdsm_enable_kernel_timing': (_i32, [_i32]),

@@ -926,6 +926,19 @@ extern "C" int sdsm_batch_eval(const sdsm_plan *p, void *d_ws, size_t ws_bytes, 
     return SDSM_OK;
 }
 
+// ---- the scalar loss arithmetic of the solve kernels, element by element (parity tests) ---------------------
+extern "C" hipError_t sdsm_launch_probe_loss(long long n, const double *y, const double *S, const double *x, double *out, hipStream_t stream);
+
+extern "C" int sdsm_probe_loss_arithmetic(int64_t n, const double *d_y, const double *d_S, const double *d_x, double *d_out, void *stream)
+{
+    if (n < 0 || n > SDSM_PROBE_LOSS_MAX) return fail(SDSM_ERR_ARGUMENT, "sdsm_probe_loss_arithmetic: n out of range");
+    if (n == 0) return SDSM_OK;
+    if (!d_y || !d_S || !d_x || !d_out) return fail(SDSM_ERR_ARGUMENT, "sdsm_probe_loss_arithmetic: null argument");
+    hipError_t e;
+    if ((e = sdsm_launch_probe_loss((long long)n, d_y, d_S, d_x, d_out, (hipStream_t)stream)) != hipSuccess) return hipfail(e, "launch probe");
+    return SDSM_OK;
+}
+
 // ---- host helper: foreground fragments out of the bit-packed masks (objects.py:148-174 applied to the region-bbox masks) -------
 // One byte per pixel of every fragment into `out` (fragment i: fg_h * fg_w bytes, row-major, at out_offset[i]); candidates
 // without a foreground (fg_h <= 0, trivial, failed) get the single byte 0 = [[False]] (objects.py:172-174, 185-186).

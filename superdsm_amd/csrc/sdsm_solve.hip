@@ -217,7 +217,7 @@ template <class L> __device__ __forceinline__ double *hess_ptr(const Cand &c) { 
 // barrier, every member adds the wG partials in the same order, so all copies stay bit-identical and take the same
 // branches.  Barrier: a monotonic counter, arrival = agent-scope release add by one lane after the workgroup barrier,
 // wait = agent-scope acquire loads by that lane (the members sit on different XCDs, whose L2s are not coherent), with a
-// time limit: a member that waits longer than ~10 s flags the group and every member gives the candidate up (status
+// time limit: a member that waits longer than c.wtimeout (50 ms by default, sdsm_set_group_timeout_us) flags the group and every member gives the candidate up (status
 // SDSM_CAND_GIVEN_UP: the host solves it again without a group) instead of hanging.  Two publication slots alternate: a
 // member can be at most one all-reduce ahead.
 // Residency: a member is not bound to its workgroup index.  Every workgroup of the group launch draws a TICKET when it
@@ -242,7 +242,7 @@ __device__ __forceinline__ bool wide_barrier(const Cand &c, int phase0)
         const long long t0 = wall_clock64();
         while (__hip_atomic_load(&sync[0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < target) {
             if (__hip_atomic_load(&sync[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-            if (wall_clock64() - t0 > c.wtimeout) { __hip_atomic_store(&sync[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }   // constant 100 MHz clock; default 10 s
+            if (wall_clock64() - t0 > c.wtimeout) { __hip_atomic_store(&sync[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }   // constant 100 MHz clock; default 50 ms
             __builtin_amdgcn_s_sleep(8);
         }
     }
@@ -367,9 +367,15 @@ __device__ __forceinline__ void load_log_table(int tid)
 // log1p(s); the table (LDS, sdsm_logtab.h: 1 / c_j rounded and the logarithm of ITS reciprocal, so s = fma(w, 1 / c_j, -1) is exact for
 // what the table means) and a degree-7 series: 1.1e-16 absolute, 5e-16 relative (w = 1 gives 0, w = 2 the rounded ln 2).  12
 // instructions; the atanh series without a table took 40 and eleven 64-bit constants (round 4).
+// The table point is chosen from w, the rounded sum the series runs on, not from u: j = floor(64 (w - 1) + 1 / 2) only depends on the
+// bits of w down to 2^-7, all in its high word (1 <= w <= 2: exponent 0x3ff, or 0x400 with a zero mantissa for w = 2) -- two integer
+// instructions instead of a multiply-add and a conversion --, and two u that round to the same w return the same bits.  (Chosen
+// from u, arguments on either side of a bin edge with ONE w took different table entries and the result DEcreased by up to 1.1e-16
+// where u increased, at 11 of the 64 edges: log_w is monotone in u only this way -- tests/test_loss_arithmetic_gpu.py.)
 __device__ __forceinline__ double log_w(double u, double w)
 {
-    const int j = (int)fma(u, 64.0, 0.5);
+    (void)u;
+    const int j = (__double2hiint(w) - 0x3ff00000 + 0x2000) >> 14;
     const f64x2 e = reinterpret_cast<const f64x2 *>(SD)[j];
     const double s = fma(w, e.x, -1.0);
     double p = 1.0 / 7.0;
@@ -2081,6 +2087,42 @@ extern "C" hipError_t sdsm_launch_eval(const BatchParams &P, const double *param
         if ((e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
         hipLaunchKernelGGL(kern, dim3(P.n), dim3(512), lds, stream, P, SDSM_MAX_N_SOLVE, SDSM_K2_EMAX, params, out);
     }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The scalar arithmetic of the passes, element by element, for parity tests (sdsm_probe_loss_arithmetic): what exp_neg, log_w
+// (with the table where the solve kernels keep it: load_log_table at the start of dynamic LDS), softplus_neg, loss_terms, rcp_f64
+// and rsqrt_f64 return, called as they stand.  out: nine arrays of n doubles, SDSM_PROBE_* of include/sdsm.h.
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sdsm_k_probe_loss(long long n, const double *y, const double *S, const double *x, double *out)
+{
+    load_log_table(threadIdx.x);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const double yv = y[i], Sv = S[i], xv = x[i];
+        const double t = yv * Sv;
+        double a = fabs(t);
+        a = a < 750.0 ? a : 750.0;                           // the clamp of softplus_neg / loss_terms (NaN -> 750)
+        const double u = exp_neg(a);
+        double phi, r, dcurv;
+        loss_terms(yv, Sv, &phi, &r, &dcurv);
+        out[i] = t;
+        out[n + i] = u;
+        out[2 * n + i] = log_w(u, 1.0 + u);
+        out[3 * n + i] = softplus_neg(t);
+        out[4 * n + i] = phi;
+        out[5 * n + i] = r;
+        out[6 * n + i] = dcurv;
+        out[7 * n + i] = rcp_f64(xv);
+        out[8 * n + i] = rsqrt_f64(xv);
+    }
+}
+
+extern "C" hipError_t sdsm_launch_probe_loss(long long n, const double *y, const double *S, const double *x, double *out, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    const long long blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(sdsm_k_probe_loss, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 2 * SDSM_LOGTAB_N * sizeof(double), stream, n, y, S, x, out);
     return hipGetLastError();
 }
 

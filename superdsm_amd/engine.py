@@ -44,6 +44,27 @@ def preprocess(g_raw, sigma1=np.sqrt(2), sigma2=40, offset_clip=3, lower_clip_me
     return y if return_tensor else y.cpu().numpy()
 
 
+PROBE_FIELDS = ('t', 'exp', 'log', 'softplus', 'phi', 'r', 'dcurv', 'rcp', 'rsqrt')      # SDSM_PROBE_* of include/sdsm.h
+
+
+def probe_loss_arithmetic(y, S, x, device=None):
+    """The scalar loss arithmetic of the solve kernels, element by element (sdsm_probe_loss_arithmetic, one launch): ``y``, ``S`` and
+    ``x`` of one length n <= 2^20.  Returns a dict of float64 arrays named by PROBE_FIELDS; for parity tests."""
+    _require_gpu()
+    L = _capi.lib()
+    dev = torch.device(device if device is not None else 'cuda')
+    arrs = [np.ascontiguousarray(a, np.float64).ravel() for a in (y, S, x)]
+    n = arrs[0].size
+    if not all(a.size == n for a in arrs):
+        raise ValueError('probe_loss_arithmetic: y, S and x must have one length')
+    d_in = [torch.from_numpy(a).to(dev) for a in arrs]
+    d_out = torch.empty(len(PROBE_FIELDS) * max(n, 1), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _capi.check(L.sdsm_probe_loss_arithmetic(n, _ptr(d_in[0]), _ptr(d_in[1]), _ptr(d_in[2]), _ptr(d_out), _stream()), 'sdsm_probe_loss_arithmetic')
+    out = d_out.cpu().numpy()
+    return {k: out[i * n:(i + 1) * n].copy() for i, k in enumerate(PROBE_FIELDS)}
+
+
 class DeviceImage:
     """Per-image device state: y, atoms, the candidate-independent validity mask and per-atom extents.
 

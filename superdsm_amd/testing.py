@@ -737,3 +737,206 @@ def post_steps_stage_images():
     b['g'] += 0.8 * _peaks((64, 72), [(45, 28), (45, 52)], 4)      # object 1 of the second image: two bright spots
     shared, unrefined = dict(min_contrast=1.2, min_glare_radius=6.0, exterior_offset=3), dict(min_contrast=1.2, mask_stdamp=0)
     return [a, b, c, d, e], [dict(exterior_scale=2.5, min_contrast=1.2, fill_holes=False), shared, dict(shared), unrefined, dict(unrefined)]
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the loss arithmetic of the solve kernels (tests/test_loss_arithmetic_cpu.py and tests/test_loss_arithmetic_gpu.py): the inputs of the
+# element-by-element probe (sdsm_probe_loss_arithmetic) and what the scalar functions should return, in np.longdouble (x86: 64-bit
+# significand, expl / log1pl; the CPU file checks these references against mpmath).  NumPy only.
+# ---------------------------------------------------------------------------------------------------------
+LOSS_GUARD = 750.0               # the exp guard of softplus_neg / loss_terms (sdsm_solve.hip)
+LOSS_PROBE_MAX = 1 << 20         # SDSM_PROBE_LOSS_MAX of include/sdsm.h
+_LN2L = np.log(np.longdouble(2))
+
+
+def longdouble_is_extended():
+    """np.longdouble has at least the 64-bit significand of x87 extended precision (what the references below need)."""
+    return np.finfo(np.longdouble).nmant >= 63
+
+
+def ulp_neighbours(v, k=4):
+    """Every double within ``k`` units in the last place of each element of ``v`` (2 k + 1 values per element, v itself included)."""
+    v = np.atleast_1d(np.asarray(v, np.float64))
+    out = [v]
+    lo, hi = v, v
+    for _ in range(k):
+        lo, hi = np.nextafter(lo, -np.inf), np.nextafter(hi, np.inf)
+        out += [lo, hi]
+    return np.concatenate(out)
+
+
+def loss_table_points():
+    """The 65 table points u = j / 64 of log_w and the 64 bin edges (j + 1/2) / 64 between them (exact doubles)."""
+    return np.arange(65) / 64.0, (np.arange(64) + 0.5) / 64.0
+
+
+def loss_probe_inputs(seed=2024):
+    """The (y, S) pairs and the values x of the probe, fewer than LOSS_PROBE_MAX of each: ``dict(y, S, x_unit, x_normal)``.
+    t = y S is formed on the device; the cases with an exact target (table points, zeros, the guard) use y = 1 or a power of two.
+
+    t:  -ln u for every table point and bin edge of log_w and its neighbours within 4 ulp -- of u, and of w = 1 + u, which decides the
+    bin --, and the neighbours within 4 ulp of those t (the exponential moves them by about as many ulp of u: the returned u fall on
+    the points and on both sides); +-0 and +-2^-1074;
+    the t at which 1 + u starts to round to 1 (u = 2^-52, 2^-53, 2^-54), +-4 ulp; the odd multiples of ln 2 / 2 up to 750 (rint
+    switches k), +-4 ulp; 708.4 .. 745.2 (ldexp makes subnormals); 750 and the first doubles on either side; beyond 750 up to 1e300;
+    +-inf and NaN (also as 0 * inf); log-uniform and uniform samples; all of them with both signs.  y: 1 where t must be exact,
+    else +-2^U(-20, 20) with S = t / y.
+    x: uniform on [1, 2] with the end points and their neighbours (``x_unit``: the w = 1 + u of the passes); log-uniform over the
+    normal range (``x_normal``)."""
+    X = np.longdouble
+    rng = np.random.default_rng(seed)
+    pts, edges = loss_table_points()
+    u = ulp_neighbours(np.concatenate([pts[1:], edges]), 4)               # (u = 0 is reached through the guard: t = 750)
+    u = np.concatenate([u, ulp_neighbours(1.0 + np.concatenate([pts, edges]), 4) - 1.0])     # ... and the neighbours of w = 1 + u (an ulp of w is many of u)
+    u = u[(u > 0) & (u <= 1)]
+    t_tab = ulp_neighbours((-np.log(u.astype(X))).astype(np.float64), 4)
+    t_one = ulp_neighbours((np.array([52, 53, 54]) * _LN2L).astype(np.float64), 4)
+    m = np.arange(0, 1082)
+    t_rint = ulp_neighbours(((2 * m + 1) * (_LN2L / 2)).astype(np.float64), 4)
+    t_rint = t_rint[t_rint <= LOSS_GUARD]
+    t_sub = np.concatenate([rng.uniform(708.4, 745.2, 20000), ulp_neighbours([708.4, 745.2, 1022 * float(_LN2L), 1074 * float(_LN2L), 1075 * float(_LN2L)], 4)])
+    t_guard = np.array([LOSS_GUARD, np.nextafter(LOSS_GUARD, 0), np.nextafter(LOSS_GUARD, np.inf)])
+    t_far = np.concatenate([10.0 ** rng.uniform(np.log10(LOSS_GUARD), 300, 2000), [751.0, 1e3, 1e300]])
+    t_tiny = np.array([0.0, 2.0 ** -1074])
+    exact = np.concatenate([t_tab, t_one, t_rint, t_sub, t_guard, t_far, t_tiny])
+    exact = np.concatenate([exact, -exact])
+    y_exact = np.ones(exact.size)
+    y_exact[1::3] = 2.0 ** rng.integers(-20, 21, y_exact[1::3].size)       # powers of two: y S is still exact (S = t / y; 2^-1074 / y may round: t is what the device forms)
+    y_exact[np.abs(exact) < 1e-300] = 1.0
+    special = np.array([np.inf, -np.inf, np.nan, np.inf, -np.inf])
+    y_special = np.array([1.0, 1.0, 1.0, 0.0, 2.0 ** -20])
+    t_rand = np.concatenate([10.0 ** rng.uniform(-320, np.log10(LOSS_GUARD), 150000), rng.uniform(0, LOSS_GUARD, 150000), rng.uniform(0, 40, 150000), rng.uniform(0, 1, 100000)])
+    t_rand = t_rand * rng.choice([-1.0, 1.0], t_rand.size)
+    y_rand = 2.0 ** rng.uniform(-20, 20, t_rand.size) * rng.choice([-1.0, 1.0], t_rand.size)
+    t = np.concatenate([exact, t_rand])
+    y = np.concatenate([y_exact, y_rand])
+    with np.errstate(all='ignore'):
+        S = np.concatenate([t / y, special])
+    y = np.concatenate([y, y_special])
+    x_unit = np.concatenate([rng.uniform(1, 2, 300000), ulp_neighbours([1.0, 2.0, 1.5], 4)])
+    x_unit = x_unit[(x_unit >= 1) & (x_unit <= 2)]
+    x_normal = np.concatenate([2.0 ** rng.uniform(-1022, 1024, 300000), [2.0 ** -1022, np.finfo(np.float64).max, 1.0, 4.0]])
+    x_normal = x_normal[np.isfinite(x_normal) & (x_normal >= 2.0 ** -1022)]
+    assert max(y.size, x_unit.size + x_normal.size) <= LOSS_PROBE_MAX
+    return dict(y=y, S=S, x_unit=x_unit, x_normal=x_normal)
+
+
+def loss_reference(t, y=None):
+    """What the scalar functions of the passes should return at the doubles ``t``, in np.longdouble: ``E`` = exp(-min(|t|, 750))
+    (exp_neg's argument is clamped by its callers), ``softplus`` = log(1 + exp(-t)) = max(-t, 0) + log1p(exp(-|t|)), ``theta`` =
+    1 / (1 + exp(t)) (as exp(-|t|) / (1 + exp(-|t|)) for t >= 0: no overflow) and ``kappa`` = theta (1 - theta) =
+    exp(-|t|) / (1 + exp(-|t|))^2 -- none of these forms cancels.  With ``y``: also ``r`` = -y theta and ``dcurv`` = y^2 kappa.
+    Non-finite t: NaN everywhere."""
+    X = np.longdouble
+    t = np.asarray(t, np.float64)
+    with np.errstate(all='ignore'):
+        tl = np.where(np.isfinite(t), t, np.nan).astype(X)
+        a = np.abs(tl)
+        E = np.exp(-a)
+        out = dict(E=np.exp(-np.minimum(a, X(LOSS_GUARD))), softplus=np.maximum(-tl, X(0)) + np.log1p(E),
+                   theta=np.where(tl >= 0, E / (1 + E), 1 / (1 + E)), kappa=E / ((1 + E) * (1 + E)))
+        if y is not None:
+            yl = np.asarray(y, np.float64).astype(X)
+            out['r'], out['dcurv'] = -yl * out['theta'], yl * yl * out['kappa']
+    return out
+
+
+def log_reference(w):
+    """log(w) of the doubles ``w`` in np.longdouble, as log1p(w - 1) (w - 1 is exact for 1 <= w <= 2)."""
+    w = np.asarray(w, np.float64).astype(np.longdouble)
+    return np.log1p(w - 1)
+
+
+ENERGY_F = np.array([1.0, 1.0, 2.0, 2.0, 2.0, 1.0])     # q = (u^2, v^2, 2 u v, 2 u, 2 v, 1): |q_k| <= ENERGY_F[k] for |u|, |v| <= 1
+
+
+def energy_reference(y, y_mask, atoms, fp, cfg, theta, xi=None, box=None):
+    """psi, its full gradient (theta, then xi) and the 6 x 6 theta block of its Hessian at (theta, xi) in np.longdouble
+    (superdsm/dsm.py:298-385: psi = sum_i phi(y_i S_i) + alpha sum_j (sqrt(xi_j^2 + epsilon) - sqrt(epsilon)), clamped at 0), with the
+    surface of :func:`tail_reference` -- S = a1 u^2 + a2 v^2 + 2 a3 u v + 2 b1 u + 2 b2 v + c + (G~ xi), u = r / max(H - 1, 1), v =
+    c / max(W - 1, 1), over the oracle's region and with the oracle's G~ -- and the loss terms of :func:`loss_reference`.
+    ``smooth_amount = inf`` (or ``xi`` None): the elliptical model, M = 0.
+
+    Beside ``psi``, ``grad`` and ``hess_theta`` the dict holds what a bound on a float64 evaluation needs:
+    ``phi_sum``, ``reg_sum`` = alpha sum sqrt(xi^2 + epsilon) and ``reg0`` = alpha sqrt(epsilon) M; per pixel (raster order) ``y``,
+    ``t``, ``theta_hat`` = 1 / (1 + e^t), ``kappa``, ``nnz`` (entries of the pixel's row of G~) and ``A``: the sum of the absolute values
+    of the terms of S in the candidate's LOCAL frame, in which the solve kernels evaluate it (coordinates centred on ``box`` = (r0, c0,
+    h, w) -- the candidate's box of the plan; default: the region's bounding box -- and scaled by its half extents, |u|, |v| <= 1;
+    theta_local = R theta); ``R`` (6 x 6, theta_local = R @ theta; all
+    entries >= 0), ``theta_local`` and ``theta_local_abs`` (the sums of the absolute values of the terms that form each local
+    coefficient); ``abs_r`` = sum |y theta_hat|, ``abs_d`` = sum y^2 kappa: every term of a theta-gradient (theta-Hessian) entry in the
+    local frame is at most ENERGY_F[k] |r_i| (ENERGY_F[k] ENERGY_F[l] d_i); ``smat`` = (indptr, indices, data) of G~ or None;
+    ``yexp``: |y| < 2^yexp over the region; ``N``, ``M``."""
+    from oracle import oracle                              # test infrastructure, as this function is
+    X = np.longdouble
+    assert longdouble_is_extended(), 'np.longdouble must be wider than float64'
+    y = np.asarray(y, np.float64)
+    Himg, Wimg = y.shape
+    region = oracle.region_mask(y, y_mask, atoms, fp, cfg.get('background_margin', 20))
+    rr, cc = np.nonzero(region)
+    N = rr.size
+    yl = y[region].astype(X)
+    th = np.asarray(theta, np.float64).ravel().astype(X)
+    assert th.size == 6 and N > 0
+    deform = np.isfinite(cfg.get('smooth_amount', 10)) and xi is not None
+    zu, zv = X(max(Himg - 1, 1)), X(max(Wimg - 1, 1))
+    u, v = rr.astype(X) / zu, cc.astype(X) / zv
+    q = np.stack([u * u, v * v, 2 * u * v, 2 * u, 2 * v, np.ones(N, X)])
+    S = (th[:, None] * q).sum(axis=0)
+    # the local frame (sdsm_solve.hip: load_run, reparam): u = O0 + P0 u_loc, v = O1 + P1 v_loc
+    r0, c0, bh, bw = (int(rr.min()), int(cc.min()), int(rr.max() - rr.min() + 1), int(cc.max() - cc.min() + 1)) if box is None else [int(b) for b in box]
+    assert r0 <= rr.min() and rr.max() < r0 + bh and c0 <= cc.min() and cc.max() < c0 + bw
+    hr, hc = X(bh - 1) / 2, X(bw - 1) / 2
+    P0, P1 = (hr if hr >= 1 else X(1)) / zu, (hc if hc >= 1 else X(1)) / zv
+    O0, O1 = (r0 + hr) / zu, (c0 + hc) / zv
+    R = np.zeros((6, 6), X)
+    R[0, 0], R[3, 0], R[5, 0] = P0 * P0, P0 * O0, O0 * O0
+    R[1, 1], R[4, 1], R[5, 1] = P1 * P1, P1 * O1, O1 * O1
+    R[2, 2], R[3, 2], R[4, 2], R[5, 2] = P0 * P1, P0 * O1, P1 * O0, 2 * O0 * O1
+    R[3, 3], R[5, 3] = P0, 2 * O0
+    R[4, 4], R[5, 4] = P1, 2 * O1
+    R[5, 5] = 1
+    thl, thl_abs = R @ th, R @ np.abs(th)
+    ul, vl = (u - O0) / P0, (v - O1) / P1
+    ql = np.abs(np.stack([ul * ul, vl * vl, 2 * ul * vl, 2 * ul, 2 * vl, np.ones(N, X)]))
+    A = (np.abs(thl)[:, None] * ql).sum(axis=0)
+    out = dict(N=N, M=0, smat=None, R=R, theta_local=thl, theta_local_abs=thl_abs, nnz=np.zeros(N, np.int64))
+    M = 0
+    if deform:
+        sm = oracle.smooth_matrix(region, cfg.get('smooth_amount', 10), cfg.get('gaussian_shape_multiplier', 2), cfg.get('smooth_subsample', 20))
+        M = sm.M
+        xil = np.asarray(xi, np.float64).ravel().astype(X)
+        assert sm.N == N and xil.size == M, (sm.N, N, xil.size, M)
+        row = np.repeat(np.arange(N), np.diff(sm.indptr))
+        data = sm.data.astype(X)
+        prod = data * xil[sm.indices]
+        gs, ga = np.zeros(N, X), np.zeros(N, X)
+        np.add.at(gs, row, prod)
+        np.add.at(ga, row, np.abs(prod))
+        S, A = S + gs, A + ga
+        out.update(M=M, smat=(sm.indptr.copy(), sm.indices.copy(), sm.data.copy()), nnz=np.diff(sm.indptr))
+    t = yl * S
+    with np.errstate(all='ignore'):
+        a = np.abs(t)
+        E = np.exp(-a)
+        phi = np.maximum(-t, X(0)) + np.log1p(E)
+        theta_hat = np.where(t >= 0, E / (1 + E), 1 / (1 + E))
+        kappa = E / ((1 + E) * (1 + E))
+    r, d = -yl * theta_hat, yl * yl * kappa
+    grad = np.zeros(6 + M, X)
+    grad[:6] = (q * r).sum(axis=1)
+    hess = np.einsum('ai,bi->ab', q * d, q)
+    psi = phi.sum()
+    out.update(phi_sum=psi, reg_sum=X(0), reg0=X(0))
+    if deform and M > 0:
+        np.add.at(grad[6:], sm.indices, data * r[row])
+        al, ep = X(float(cfg.get('alpha', 0.5))), X(float(cfg.get('epsilon', 1.0)))
+        t2 = np.sqrt(xil * xil + ep)
+        grad[6:] += al * xil / t2
+        reg_sum, reg0 = al * t2.sum(), al * np.sqrt(ep) * M
+        psi = psi + max(reg_sum - reg0, X(0))
+        out.update(reg_sum=reg_sum, reg0=reg0)
+    ymax = float(np.abs(y[region]).max())
+    out.update(psi=psi, grad=grad, hess_theta=hess, y=y[region].copy(), t=t, theta_hat=theta_hat, kappa=kappa, A=A,
+               abs_r=np.abs(r).sum(), abs_d=d.sum(), yexp=int(np.frexp(ymax)[1]) if ymax > 0 else -400)
+    return out
