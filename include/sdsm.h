@@ -176,6 +176,11 @@ int sdsm_plan_set_latency_mode(sdsm_plan *plan, int mode);
  * solves candidate i (0: a single workgroup), rows_workgroups[i] = workgroups that build its rows of G~ (0: the setup workgroup itself).
  * Either pointer may be NULL. */
 int sdsm_plan_schedule(const sdsm_plan *plan, int32_t *group_members, int32_t *rows_workgroups);
+/* The launch lists of the plan in its current mode (host only, diagnostics and tests): spans = (first, count) of the seven lists
+ * [all candidates, largest first | those whose bound on M admits more than class 1 | more than class 2 | members of the workgroup groups |
+ * workgroups that build rows of G~ | setup by the small class | setup by the large class] in one array of entries; order, if not NULL,
+ * receives that array (as many int32 as the counts add up to; member lists hold candidate | member << 24). */
+int sdsm_plan_lists(const sdsm_plan *plan, int32_t spans[14], int32_t *order);
 /* The solve class of every candidate in the plan's current mode (host only, diagnostics and tests), given what the setup kernel found for it
  * (status, M and env_size of its state): 0 class 1, 1 class 1b, 2 class 2, 3 class 2b, 4 the global-memory class, 5 / 6 / 7 a workgroup
  * group with the LDS layout of class 2 / of class 2b / the light layout (at most 288 unknowns and 12 400 envelope doubles: its members

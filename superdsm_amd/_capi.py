@@ -113,6 +113,7 @@ SYMBOLS = {
     'sdsm_plan_xi_offsets': (_i32, [_vp, _vp]),
     'sdsm_plan_layout': (_i32, [_vp, _vp]),
     'sdsm_plan_schedule': (_i32, [_vp, _vp, _vp]),
+    'sdsm_plan_lists': (_i32, [_vp, _vp, _vp]),
     'sdsm_plan_solve_classes': (_i32, [_vp, _vp, _vp, _vp, _vp]),
     'sdsm_set_light_envelope_limit': (_i32, [_i32]),
     'sdsm_plan_set_latency_mode': (_i32, [_vp, _i32]),

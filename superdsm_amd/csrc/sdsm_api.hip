@@ -10,15 +10,12 @@
 #include <string>
 #include <vector>
 
-#include "sdsm_common.h"
+#include "sdsm_launch.h"
 #include <climits>
 
-extern "C" hipError_t sdsm_launch_solve(const BatchParams &P, sdsm_record *records, uint32_t *masks, double *xi_out, hipStream_t stream,
-                                        hipStream_t side1, hipStream_t side2, hipStream_t side3, hipStream_t side4, hipEvent_t *ev, int n_c, int n_d, int n_w, int n_r);
 extern "C" hipError_t sdsm_image_prepare_impl(const double *, const uint8_t *, const int32_t *, int, int, double, int, uint8_t *, int32_t *, void *, hipStream_t);
 extern "C" hipError_t sdsm_preprocess_impl(const double *, int, int, double, double, double, int, double *, void *, hipStream_t);
 extern "C" void sdsm_gauss_kernel_host(double sigma, int radius, double *w);
-extern "C" hipError_t sdsm_launch_setup(const BatchParams &P, hipStream_t stream, const int32_t *order_w, int n_w, int cls, const int32_t *order_small, int n_small, const int32_t *order_big, int n_big);
 extern "C" int sdsm_setup_fits_small(int h, int w, int mcap, int max_label, int k);
 extern "C" int sdsm_setup_class(int max_dim, int max_mcap, int max_label, int k);
 
@@ -137,11 +134,10 @@ struct sdsm_plan {
     sdsm_dsm_config cfg{};
     int k = 1, R = 0, zcap = 1, zcap_run = 1, zshift = 0, no_deform = 0;
     std::vector<CandDesc> cand;
-    std::vector<int32_t> fp_labels, order;     // order: all candidates (largest first), then those whose bound on M admits more than solve class 1, then more than class 2
-    int n_order_c = 0, n_order_d = 0, n_order_w = 0;   // the last list: (candidate | member << 24) of the workgroup groups
-    int n_order_r = 0;                                  // then: (candidate | member << 24) of sdsm_k_setup_rows
-    int rows_mcap = 1;                                  // largest bound on M among them
-    int n_setup_small = 0, n_setup_big = 0, max_label = 1;   // setup in two launches (plans that mix small and large regions): lists behind the others
+    std::vector<int32_t> fp_labels, order;     // order: the launch lists, one behind the other
+    LaunchLists lists{};                        // where each of them is (layout_plan)
+    int rows_mcap = 1;                          // largest bound on M among the regions of the list of row members
+    int max_label = 1;
     int setup_class = 2;         // LDS limits of the setup kernel that hold this plan (sdsm_setup_class)
     int mode = 0;                // sdsm_plan_set_latency_mode: 0 throughput, 1 latency, 2 no workgroup groups
     int wide_pixels = INT_MAX;   // throughput mode by default
@@ -152,7 +148,7 @@ struct sdsm_plan {
     std::vector<int64_t> mask_off_bytes, xi_off;
     int64_t total_pixels = 0, total_runs = 0, total_ell = 0, total_xi = 0, total_mask_words = 0, n_hglob = 0, n_wide = 0;
     size_t off_cand = 0, off_state = 0, off_fp = 0, off_order = 0, off_crop_y = 0, off_crop_rc = 0, off_crop_cc = 0, off_dist = 0, off_tmp_y = 0, off_tmp_rc = 0, off_inv = 0, off_run_meta = 0,
-           off_run_q0 = 0, off_run_aux = 0, off_grid = 0, off_ell_im = 0, off_ell_w = 0, off_psf = 0, off_env_fst = 0, off_env_rb = 0, off_hglob = 0, off_wide = 0, off_ticket = 0, total = 0;
+           off_run_q0 = 0, off_run_aux = 0, off_grid = 0, off_ell_im = 0, off_ell_w = 0, off_psf = 0, off_env_fst = 0, off_env_rb = 0, off_hglob = 0, off_wide = 0, off_words = 0, total = 0;
     // The launch lists and CandDesc.wide_* live in the workspace (sdsm_batch_upload): a layout change after the upload
     // (sdsm_plan_set_latency_mode) would leave stale tables on the device, so launches check the generation they were uploaded at.
     uint64_t layout_gen = 0;
@@ -254,7 +250,7 @@ static uint32_t perm_inverse(uint32_t N)
 // Workgroup groups, launch lists and workspace layout (repeated when the scheduling mode changes).
 static int light_limit(const sdsm_plan *p)
 {
-    if (!SDSM_LIGHT_GROUPS || p->n_order_w <= 0) return 0;
+    if (!SDSM_LIGHT_GROUPS || p->lists.group_members.count <= 0) return 0;
     const int v = g_light_emax.load(std::memory_order_relaxed);
     if (v >= 0) return v;
     return p->n > SDSM_LIGHT_MIN_CANDIDATES ? SDSM_KL_EMAX : 0;
@@ -347,39 +343,32 @@ static void layout_plan(sdsm_plan *p)
     }
     p->wide_rest = 0;
     for (int i = 0; i < n; i++) if (p->cand[i].wide_g > 0 && 6 + (long)p->cand[i].Mcap > SDSM_K2B_NMAX) p->wide_rest = 1;
-    p->n_order_c = p->n_order_d = p->n_order_w = p->n_order_r = 0;
     p->rows_mcap = 1;
-    p->order.resize(n);
-    std::iota(p->order.begin(), p->order.end(), 0);
-    std::stable_sort(p->order.begin(), p->order.end(), [&](int a, int b) { return p->cand[a].N > p->cand[b].N; });
+    std::vector<int32_t> all(n), beyond_1, beyond_2, group_members, row_members, setup_small, setup_big;
+    std::iota(all.begin(), all.end(), 0);
+    std::stable_sort(all.begin(), all.end(), [&](int a, int b) { return p->cand[a].N > p->cand[b].N; });
     // a candidate can only belong to a larger size class if its upper bound Mcap allows it: the larger classes get
     // their own (shorter) launch lists instead of n workgroups that exit immediately
-    for (int k = 0; k < n; k++) if (6 + p->cand[p->order[k]].Mcap > SDSM_K1_DENSE_N || p->cand[p->order[k]].N > SDSM_WIDE_PIXELS) { p->order.push_back(p->order[k]); p->n_order_c++; }
-    for (int k = 0; k < n; k++) if (6 + p->cand[p->order[k]].Mcap > SDSM_ENV_DENSE_N) { p->order.push_back(p->order[k]); p->n_order_d++; }
-    for (int k = 0; k < n; k++) {
-        const int ci = p->order[k];
-        for (int g = 0; g < p->cand[ci].wide_g; g++) { p->order.push_back(ci | (g << 24)); p->n_order_w++; }
-    }
-    for (int k = 0; k < n; k++) {
-        const int ci = p->order[k];
-        for (int g = 0; g < p->cand[ci].rows_g; g++) { p->order.push_back(ci | (g << 24)); p->n_order_r++; }
+    for (int ci : all) if (6 + p->cand[ci].Mcap > SDSM_K1_DENSE_N || p->cand[ci].N > SDSM_WIDE_PIXELS) beyond_1.push_back(ci);
+    for (int ci : all) if (6 + p->cand[ci].Mcap > SDSM_ENV_DENSE_N) beyond_2.push_back(ci);
+    for (int ci : all) for (int g = 0; g < p->cand[ci].wide_g; g++) group_members.push_back(ci | (g << 24));
+    for (int ci : all) {
+        for (int g = 0; g < p->cand[ci].rows_g; g++) row_members.push_back(ci | (g << 24));
         if (p->cand[ci].rows_g > 0) p->rows_mcap = std::max(p->rows_mcap, (int)std::min<int64_t>(p->cand[ci].Mcap, SDSM_MAX_N_GLOBAL));
     }
     // Setup: a plan whose largest region needs the large tables of the setup kernel (1024 threads per candidate) but whose candidates are
     // mostly small (an image set with a few big clusters) sets the small ones up with the 256-thread class in a launch of its own
-    p->n_setup_small = p->n_setup_big = 0;
     if (p->setup_class != 0) {
-        std::vector<int32_t> small, big;
-        for (int k = 0; k < n; k++) {
-            const CandDesc &c = p->cand[p->order[k]];
-            (c.N <= SDSM_SETUP_SMALL_PIXELS && sdsm_setup_fits_small(c.h, c.w, c.Mcap, p->max_label, p->k) ? small : big).push_back(p->order[k]);
+        for (int ci : all) {
+            const CandDesc &c = p->cand[ci];
+            (c.N <= SDSM_SETUP_SMALL_PIXELS && sdsm_setup_fits_small(c.h, c.w, c.Mcap, p->max_label, p->k) ? setup_small : setup_big).push_back(ci);
         }
-        if (small.size() >= 256) {
-            p->n_setup_small = (int)small.size(); p->n_setup_big = (int)big.size();
-            p->order.insert(p->order.end(), small.begin(), small.end());
-            p->order.insert(p->order.end(), big.begin(), big.end());
-        }
+        if (setup_small.size() < 256) { setup_small.clear(); setup_big.clear(); }
     }
+    // the one place that lays the lists out in `order` (the initialisers run left to right)
+    p->order.clear();
+    auto put = [&](const std::vector<int32_t> &list) { const ListSpan at{(int32_t)p->order.size(), (int32_t)list.size()}; p->order.insert(p->order.end(), list.begin(), list.end()); return at; };
+    p->lists = LaunchLists{put(all), put(beyond_1), put(beyond_2), put(group_members), put(row_members), put(setup_small), put(setup_big)};
     // workspace layout
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o += al(bytes); return r; };
@@ -406,7 +395,7 @@ static void layout_plan(sdsm_plan *p)
     p->off_env_rb = take(4 * (size_t)std::max<int64_t>(p->total_xi, 1));
     p->off_hglob = take(8 * (size_t)std::max<int64_t>(p->n_hglob, 1));      // n_hglob counts doubles
     p->off_wide = take(8 * (size_t)std::max<int64_t>(p->n_wide, 1));        // n_wide counts doubles
-    p->off_ticket = take(256);                                                // [0] ticket of the workgroup groups; [16 ..] heads of the launch lists of the classes beyond 1 (zeroed before every launch)
+    p->off_words = take(sizeof(LaunchWords));                                 // zeroed before every launch
     p->total = o;
 }
 extern "C" sdsm_plan *sdsm_plan_create_multi(int n_images, const int32_t *H, const int32_t *W, const int32_t *n_atoms, const int32_t *const *atom_stats,
@@ -535,6 +524,16 @@ extern "C" int sdsm_plan_schedule(const sdsm_plan *p, int32_t *group_members, in
     return SDSM_OK;
 }
 
+// The launch lists of the plan in its current mode: spans = (first, count) in `order` of [all | beyond class 1 | beyond class 2 | group members |
+// row members | setup small | setup big]; order (if given): the entries of all lists, as many as the counts add up to.
+extern "C" int sdsm_plan_lists(const sdsm_plan *p, int32_t spans[14], int32_t *order)
+{
+    if (!p || !spans) return fail(SDSM_ERR_ARGUMENT, "sdsm_plan_lists: null argument");
+    memcpy(spans, &p->lists, sizeof(LaunchLists));
+    if (order) memcpy(order, p->order.data(), p->order.size() * 4);
+    return SDSM_OK;
+}
+
 // The solve class (SDSM_CLS_* of sdsm_solve_class: 0 class 1, 1 class 1b, 2 class 2, 3 class 2b, 4 global memory, 5 / 6 / 7 groups of class-2 / class-2b / light
 // layout, -1 none) of every candidate of the plan in its current mode, given what the setup kernel found (status, M and env_size of its CandState).
 extern "C" int sdsm_plan_solve_classes(const sdsm_plan *p, const int32_t *status, const int32_t *M, const int32_t *env_size, int32_t *cls)
@@ -574,7 +573,7 @@ extern "C" int sdsm_batch_upload(const sdsm_plan *p, void *d_ws, size_t ws_bytes
     if (!p->fp_labels.empty() && (e = hipMemcpyAsync(b + p->off_fp, p->fp_labels.data(), 4 * p->fp_labels.size(), hipMemcpyHostToDevice, s)) != hipSuccess) return hipfail(e, "upload footprints");
     if ((e = hipMemcpyAsync(b + p->off_order, p->order.data(), 4 * p->order.size(), hipMemcpyHostToDevice, s)) != hipSuccess) return hipfail(e, "upload order");
     if ((e = hipMemcpyAsync(b + p->off_psf, p->psf.data(), 4 * p->psf.size(), hipMemcpyHostToDevice, s)) != hipSuccess) return hipfail(e, "upload psf");
-    if ((e = hipMemsetAsync(b + p->off_ticket, 0, 256, s)) != hipSuccess) return hipfail(e, "hipMemsetAsync");   // (the event counters read 0 before the first launch)
+    if ((e = hipMemsetAsync(b + p->off_words, 0, sizeof(LaunchWords), s)) != hipSuccess) return hipfail(e, "hipMemsetAsync");   // (the event counters read 0 before the first launch)
     p->uploaded_gen = p->layout_gen; p->uploaded_ws = d_ws;
     return SDSM_OK;
 }
@@ -747,8 +746,8 @@ static BatchParams make_params(const sdsm_plan *p, void *d_ws)
     P.n = p->n; P.n_total = p->n; P.latency = p->mode == 1; P.n_images = (int)p->images.size();
     for (size_t i = 0; i < p->images.size(); i++) { P.img[i].H = p->images[i].H; P.img[i].W = p->images[i].W; }   // device pointers: filled by the launch
     P.k = p->k; P.R = p->R; P.subsample = p->cfg.smooth_subsample; P.zcap = p->zcap; P.zcap_run = p->zcap_run; P.zshift = p->zshift; P.no_deform = p->no_deform; P.no_trivial_rule = p->cfg.flags & 1;
-    P.init_elliptical = p->cfg.init_elliptical; P.max_iters = p->cfg.max_iters; P.k1_pixmax = p->wide_pixels; P.boost_pixels = p->boost_pixels; P.rows_mcap = p->rows_mcap; P.pad2 = g_solver_diag.load(std::memory_order_relaxed);
-    P.light_emax = light_limit(p); P.pad3 = p->wide_rest;
+    P.init_elliptical = p->cfg.init_elliptical; P.max_iters = p->cfg.max_iters; P.k1_pixmax = p->wide_pixels; P.boost_pixels = p->boost_pixels; P.rows_mcap = p->rows_mcap; P.solver_diag = g_solver_diag.load(std::memory_order_relaxed);
+    P.light_emax = light_limit(p); P.wide_rest = p->wide_rest;
     P.scale = p->cfg.scale; P.epsilon = p->cfg.epsilon; P.alpha = p->cfg.alpha; P.reg_unit = p->cfg.alpha * std::sqrt(p->cfg.epsilon);
     P.cand = (const CandDesc *)(b + p->off_cand); P.state = (CandState *)(b + p->off_state);
     P.fp_labels = (const int32_t *)(b + p->off_fp); P.order = (const int32_t *)(b + p->off_order);
@@ -761,8 +760,8 @@ static BatchParams make_params(const sdsm_plan *p, void *d_ws)
     P.psf = (const float *)(b + p->off_psf);
     P.env_fst = (int32_t *)(b + p->off_env_fst); P.env_rb = (int32_t *)(b + p->off_env_rb);
     P.hglob = (double *)(b + p->off_hglob); P.wide_pool = (double *)(b + p->off_wide);
-    P.wide_ticket = (int32_t *)(b + p->off_ticket); P.wide_timeout = g_wide_timeout;
-    P.cls_count = (int32_t *)(b + p->off_ticket) + 16;
+    P.wide_ticket = (int32_t *)(b + p->off_words + offsetof(LaunchWords, ticket)); P.wide_timeout = g_wide_timeout;
+    P.cls_count = (int32_t *)(b + p->off_words + offsetof(LaunchWords, list_head));
     P.prof = g_prof; P.prof2 = g_prof ? g_prof + (size_t)16 * p->n : nullptr;
     P.x0 = p->x0;
     return P;
@@ -814,47 +813,54 @@ extern "C" int sdsm_batch_solver_counters(const sdsm_plan *p, void *d_ws, int64_
     if (p->n == 0) return SDSM_OK;
     hipError_t e;
     if ((e = hipDeviceSynchronize()) != hipSuccess) return hipfail(e, "hipDeviceSynchronize");
-    if ((e = hipMemcpy(out, (const uint8_t *)d_ws + p->off_ticket + 64 + 4 * SDSM_SOLVER_COUNTERS, 8, hipMemcpyDeviceToHost)) != hipSuccess) return hipfail(e, "hipMemcpy");
+    if ((e = hipMemcpy(out, (const uint8_t *)d_ws + p->off_words + offsetof(LaunchWords, counters), sizeof(int64_t), hipMemcpyDeviceToHost)) != hipSuccess) return hipfail(e, "hipMemcpy");
     return SDSM_OK;
 }
 extern "C" double sdsm_last_solve_kernel_ms(void) { return elapsed(1, 2); }
 
+// What the launch entry points check and prepare alike: the arguments (`outputs`: the entry point's own result pointers are all there), the
+// upload, the workspace; then *P = the plan's kernel arguments in d_ws with the image pointers bound (not for an empty plan).  who: the caller's
+// name in the messages; upload_hint: what it tells about a missing upload.
+static int launch_front(const std::string &who, const char *upload_hint, const sdsm_plan *p, const double *const *d_y, const int32_t *const *d_atoms, const uint8_t *const *d_valid,
+                        void *d_ws, size_t ws_bytes, bool outputs, BatchParams *P)
+{
+    if (!p || !d_y || !d_atoms || !d_valid || !d_ws || !outputs) return fail(SDSM_ERR_ARGUMENT, who + ": null argument");
+    for (size_t i = 0; i < p->images.size(); i++) if (!d_y[i] || !d_atoms[i] || !d_valid[i]) return fail(SDSM_ERR_ARGUMENT, who + ": null image pointer");
+    if (p->uploaded_gen != p->layout_gen || p->uploaded_ws != d_ws) return fail(SDSM_ERR_ARGUMENT, who + ": the plan's tables in this workspace are missing or stale (" + upload_hint + ")");
+    if (ws_bytes < p->total) return fail(SDSM_ERR_WORKSPACE, who + ": workspace too small");
+    if (p->n == 0) return SDSM_OK;
+    *P = make_params(p, d_ws);
+    for (size_t i = 0; i < p->images.size(); i++) { P->img[i].y = d_y[i]; P->img[i].atoms = d_atoms[i]; P->img[i].valid = d_valid[i]; }
+    return SDSM_OK;
+}
+
 extern "C" int sdsm_batch_launch_multi(const sdsm_plan *p, const double *const *d_y, const int32_t *const *d_atoms, const uint8_t *const *d_valid,
                                        void *d_ws, size_t ws_bytes, sdsm_record *d_records, uint32_t *d_masks, double *d_xi, void *stream)
 {
-    if (!p || !d_y || !d_atoms || !d_valid || !d_ws || !d_records || !d_masks) return fail(SDSM_ERR_ARGUMENT, "sdsm_batch_launch: null argument");
-    for (size_t i = 0; i < p->images.size(); i++) if (!d_y[i] || !d_atoms[i] || !d_valid[i]) return fail(SDSM_ERR_ARGUMENT, "sdsm_batch_launch: null image pointer");
-    if (p->uploaded_gen != p->layout_gen || p->uploaded_ws != d_ws)
-        return fail(SDSM_ERR_ARGUMENT, "sdsm_batch_launch: the plan's tables in this workspace are missing or stale (sdsm_batch_upload must follow sdsm_plan_create and every sdsm_plan_set_latency_mode)");
-    if (ws_bytes < p->total) return fail(SDSM_ERR_WORKSPACE, "sdsm_batch_launch: workspace too small");
-    if (p->n == 0) return SDSM_OK;
-    hipStream_t s = (hipStream_t)stream;
-    BatchParams P = make_params(p, d_ws);
-    for (size_t i = 0; i < p->images.size(); i++) { P.img[i].y = d_y[i]; P.img[i].atoms = d_atoms[i]; P.img[i].valid = d_valid[i]; }
+    BatchParams P;
+    const int rc = launch_front("sdsm_batch_launch", "sdsm_batch_upload must follow sdsm_plan_create and every sdsm_plan_set_latency_mode", p, d_y, d_atoms, d_valid, d_ws, ws_bytes, d_records && d_masks, &P);
+    if (rc != SDSM_OK || p->n == 0) return rc;
     hipError_t e;
     // the side streams of this caller stream first: a stream seen for the first time is probed (one hipStreamSynchronize of it), before any of the launch's work is queued
-    hipStream_t s1 = nullptr, s2 = nullptr, s3 = nullptr, s4 = nullptr;
-    hipEvent_t *fj = nullptr;
-    if (p->n_order_c > 0 || p->n_order_d > 0 || p->n_order_w > 0) {
+    LaunchStreams st{(hipStream_t)stream, {nullptr, nullptr, nullptr, nullptr}, nullptr};
+    const hipStream_t s = st.caller;
+    if (p->lists.forks()) {
         if ((e = acquire_sides(p, s)) != hipSuccess) return hipfail(e, "side streams (the stream must belong to the current device; a plan stays with the device of its first launch)");
         SideSet *q = p->sides;
         SideChoice c;
         std::lock_guard<std::mutex> lock(q->enqueue);
-        if ((e = choose_sides(q, s, sdsm_solve_wants_own_2b(p->n_order_w, p->n_order_d) ? 4 : 3, &c)) != hipSuccess) return hipfail(e, "side streams");
-        s1 = q->pool[c.idx[0]]; s2 = q->pool[c.idx[1]]; s3 = q->pool[c.idx[2]]; s4 = c.idx[3] >= 0 ? q->pool[c.idx[3]] : nullptr; fj = q->fj;
+        if ((e = choose_sides(q, s, sdsm_solve_wants_own_2b(p->lists.group_members.count, p->lists.beyond_2.count) ? 4 : 3, &c)) != hipSuccess) return hipfail(e, "side streams");
+        for (int i = 0; i < 4; i++) st.side[i] = c.idx[i] >= 0 ? q->pool[c.idx[i]] : nullptr;
+        st.ev = q->fj;
     }
     if (g_timing && (e = hipEventRecord(g_ev[0], s)) != hipSuccess) return hipfail(e, "hipEventRecord");
-    if ((e = hipMemsetAsync((uint8_t *)d_ws + p->off_ticket, 0, 256, s)) != hipSuccess) return hipfail(e, "hipMemsetAsync");   // ticket, work-list counters
-    {
-        const int32_t *lists = P.order + p->n + p->n_order_c + p->n_order_d;
-        if ((e = sdsm_launch_setup(P, s, lists, p->n_order_w, p->setup_class, lists + p->n_order_w + p->n_order_r, p->n_setup_small, lists + p->n_order_w + p->n_order_r + p->n_setup_small, p->n_setup_big)) != hipSuccess)
-            return hipfail(e, "launch setup");
-    }
+    if ((e = hipMemsetAsync((uint8_t *)d_ws + p->off_words, 0, sizeof(LaunchWords), s)) != hipSuccess) return hipfail(e, "hipMemsetAsync");   // tickets, list heads, counters
+    if ((e = sdsm_launch_setup(P, s, p->lists, p->setup_class)) != hipSuccess) return hipfail(e, "launch setup");
     if (g_timing && (e = hipEventRecord(g_ev[1], s)) != hipSuccess) return hipfail(e, "hipEventRecord");
     {
         std::unique_lock<std::mutex> enq;
-        if (fj) enq = std::unique_lock<std::mutex>(p->sides->enqueue);
-        if ((e = sdsm_launch_solve(P, d_records, d_masks, d_xi, s, s1, s2, s3, s4, fj, p->n_order_c, p->n_order_d, p->n_order_w, p->n_order_r)) != hipSuccess) return hipfail(e, "launch solve");
+        if (st.ev) enq = std::unique_lock<std::mutex>(p->sides->enqueue);
+        if ((e = sdsm_launch_solve(P, SolveOutputs{d_records, d_masks, d_xi}, st, p->lists)) != hipSuccess) return hipfail(e, "launch solve");
     }
     if (g_timing) { if ((e = hipEventRecord(g_ev[2], s)) != hipSuccess) return hipfail(e, "hipEventRecord"); g_ev_valid = 1; }
     return SDSM_OK;
@@ -867,18 +873,12 @@ extern "C" int sdsm_batch_launch_multi(const sdsm_plan *p, const double *const *
 extern "C" int sdsm_batch_deform_counts(const sdsm_plan *p, const double *const *d_y, const int32_t *const *d_atoms, const uint8_t *const *d_valid,
                                         void *d_ws, size_t ws_bytes, int32_t *n_deform, void *stream)
 {
-    if (!p || !d_y || !d_atoms || !d_valid || !d_ws || !n_deform) return fail(SDSM_ERR_ARGUMENT, "sdsm_batch_deform_counts: null argument");
-    for (size_t i = 0; i < p->images.size(); i++) if (!d_y[i] || !d_atoms[i] || !d_valid[i]) return fail(SDSM_ERR_ARGUMENT, "sdsm_batch_deform_counts: null image pointer");
-    if (p->uploaded_gen != p->layout_gen || p->uploaded_ws != d_ws) return fail(SDSM_ERR_ARGUMENT, "sdsm_batch_deform_counts: the plan's tables in this workspace are missing or stale (sdsm_batch_upload)");
-    if (ws_bytes < p->total) return fail(SDSM_ERR_WORKSPACE, "sdsm_batch_deform_counts: workspace too small");
-    if (p->n == 0) return SDSM_OK;
+    BatchParams P;
+    const int rc = launch_front("sdsm_batch_deform_counts", "sdsm_batch_upload", p, d_y, d_atoms, d_valid, d_ws, ws_bytes, n_deform != nullptr, &P);
+    if (rc != SDSM_OK || p->n == 0) return rc;
     hipStream_t s = (hipStream_t)stream;
-    BatchParams P = make_params(p, d_ws);
-    for (size_t i = 0; i < p->images.size(); i++) { P.img[i].y = d_y[i]; P.img[i].atoms = d_atoms[i]; P.img[i].valid = d_valid[i]; }
     hipError_t e;
-    const int32_t *lists = P.order + p->n + p->n_order_c + p->n_order_d;
-    if ((e = sdsm_launch_setup(P, s, lists, p->n_order_w, p->setup_class, lists + p->n_order_w + p->n_order_r, p->n_setup_small, lists + p->n_order_w + p->n_order_r + p->n_setup_small, p->n_setup_big)) != hipSuccess)
-        return hipfail(e, "launch setup");
+    if ((e = sdsm_launch_setup(P, s, p->lists, p->setup_class)) != hipSuccess) return hipfail(e, "launch setup");
     std::vector<CandState> st(p->n);
     if ((e = hipMemcpyAsync(st.data(), (const uint8_t *)d_ws + p->off_state, sizeof(CandState) * p->n, hipMemcpyDeviceToHost, s)) != hipSuccess) return hipfail(e, "hipMemcpyAsync");
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return hipfail(e, "hipStreamSynchronize");

@@ -1,6 +1,7 @@
 // Shared device-side structures and workgroup primitives (gfx950, wave64, 256-thread workgroups).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "../../include/sdsm.h"
 
@@ -151,8 +152,8 @@ struct BatchParams {
     double reg_unit;                   // alpha * sqrt(epsilon): the regulariser's value per grid point at xi = 0 (dsm.py:325-326), computed on the host
     float hess_thr;                    // Hessian ignores row entries < hess_thr * row maximum (solver approximation)
     int32_t boost_pixels;              // throughput mode: regions with more pixels run their passes over the pixels at a raised issue priority (the long chains of a launch; layout_plan)
-    int32_t light_emax, pad3;          // envelope limit of the light group class in this launch (SDSM_KL_EMAX; smaller: sdsm_set_light_envelope_limit; 0: no light class); pad3: a group's bound on M exceeds class 2b's unknowns
-    int32_t rows_mcap, pad2;           // largest bound on M among the regions whose rows sdsm_k_setup_rows builds (sizes its LDS tables); pad2: solver diagnostics (sdsm_set_solver_diagnostics)
+    int32_t light_emax, wide_rest;     // envelope limit of the light group class in this launch (SDSM_KL_EMAX; smaller: sdsm_set_light_envelope_limit; 0: no light class); wide_rest: a group's bound on M exceeds class 2b's unknowns
+    int32_t rows_mcap, solver_diag;    // largest bound on M among the regions whose rows sdsm_k_setup_rows builds (sizes its LDS tables); solver_diag: solver diagnostics (sdsm_set_solver_diagnostics)
     const CandDesc *cand;
     CandState *state;
     const int32_t *fp_labels;
@@ -185,15 +186,16 @@ struct BatchParams {
     int32_t *env_rb;
     const float *psf;
     double *wide_pool;                 // sync words and all-reduce buffers of the workgroup groups (CandDesc.wide_off)
-    int32_t *wide_ticket;              // [0] / [1] / [2] (the groups of class-2 / class-2b / light layout): next entry of the group launch list (members are claimed in the order in which workgroups START, see sdsm_solve.hip)
+    int32_t *wide_ticket;              // LaunchWords.ticket (sdsm_launch.h): [0] / [1] / [2] (the groups of class-2 / class-2b / light layout): next entry of the group launch list (members are claimed in the order in which workgroups START, see sdsm_solve.hip)
     long long wide_timeout;            // ticks of the 100 MHz wall clock a group member waits for its partners before the group is given up
-#define SDSM_SOLVER_COUNTERS 32        // cls_count + 32 (int32 words; byte 192 of the zeroed block): 64-bit event counters of the launch (sdsm_batch_solver_counters)
-    int32_t *cls_count;                // [l]: next entry of launch list l that a resident workgroup of a class beyond 1 takes (sdsm_k_solve; zeroed before every launch)
+#define SDSM_SOLVER_COUNTERS 32        // cls_count + 32 (int32 words; LaunchWords.counters): 64-bit event counters of the launch (sdsm_batch_solver_counters)
+    int32_t *cls_count;                // LaunchWords.list_head: [l]: next entry of launch list l that a resident workgroup of a class beyond 1 takes (sdsm_k_solve; zeroed before every launch)
     double *hglob;                     // Hessian pool of the global-memory class (envelope too large for LDS), CandDesc.hglob_off
     long long *prof;                   // diagnostic build only (-DSDSM_PROFILE): 16 cycle counters per candidate (solve kernel)
     long long *prof2;                  // diagnostic build only: 8 cycle counters per candidate (setup kernel), behind the 16 n solve counters
     const double *x0;                  // null, or the caller's starting points of the DSM solves (callable dsm/init, objects.py:385-386): candidate i's theta[6] (full-image-normalised) + xi[M] at 6 i + xi_off(i), as sdsm_batch_eval takes them; only read if init_elliptical == 0
 };
+static_assert(sizeof(BatchParams) == 856 && offsetof(BatchParams, wide_rest) == 620 && offsetof(BatchParams, solver_diag) == 628, "BatchParams layout");
 
 // Solve class of a candidate once its setup is complete: the FIRST class whose limits (6 + M <= NMAX, Hessian envelope <= EMAX
 // doubles, region <= k1_pixmax pixels for the 256-thread classes) it meets.  Results do not depend on the class.
@@ -201,7 +203,7 @@ struct BatchParams {
 // class 2 -- every group the light class leaves is then on ONE side queue (sdsm_launch_solve; only a group of more than SDSM_K2B_NMAX unknowns
 // still takes the layout of class 2 and waits behind the light ones).  light_emax == 0: the order of the two layouts as it was.
 enum { SDSM_CLS_NONE = -1, SDSM_CLS_1 = 0, SDSM_CLS_1B = 1, SDSM_CLS_2 = 2, SDSM_CLS_2B = 3, SDSM_CLS_3 = 4, SDSM_CLS_WIDE = 5, SDSM_CLS_WIDE2B = 6, SDSM_CLS_WIDE_LIGHT = 7 };
-__host__ __device__ __forceinline__ int sdsm_solve_class(int status, int M, int env_size, int N, int wide_g, int k1_pixmax, int light_emax)
+__host__ __device__ __forceinline__ constexpr int sdsm_solve_class(int status, int M, int env_size, int N, int wide_g, int k1_pixmax, int light_emax)
 {
     if (status != ST_OK) return SDSM_CLS_NONE;
     int Mfull = M;

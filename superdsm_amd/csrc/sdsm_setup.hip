@@ -10,7 +10,7 @@
 //   mask compression, "too small" rule       superdsm/dsm.py:185-187
 //   greedy grid   superdsm/dsm.py:164-181
 //   PSF gather + float32 row normalisation   superdsm/dsm.py:145-161,192-193,232
-#include "sdsm_common.h"
+#include "sdsm_launch.h"
 
 namespace {
 
@@ -902,34 +902,28 @@ extern "C" int sdsm_setup_fits_small(int h, int w, int mcap, int max_label, int 
     return h <= SetupLimS::DIM && w <= SetupLimS::DIM && mcap <= SetupLimS::GRID && max_label <= SetupLimS::LABELS && k * k <= SetupLimS::PSFW;
 }
 
-extern "C" hipError_t sdsm_launch_setup(const BatchParams &P, hipStream_t stream, const int32_t *order_w, int n_w, int cls, const int32_t *order_small, int n_small,
-                                        const int32_t *order_big, int n_big)
+extern "C" hipError_t sdsm_launch_setup(const BatchParams &P, hipStream_t stream, const LaunchLists &lists, int cls)
 {
-    BatchParams Pb = P;
-    if (n_small > 0) {                                   // the large regions first (longest), the many small ones behind them: the two launches overlap
-        Pb.order = order_big; Pb.n = n_big;
-        BatchParams Ps = P;
-        Ps.order = order_small; Ps.n = n_small;
-        if (n_big > 0) {
-            if (cls == 1) hipLaunchKernelGGL(sdsm_k_setup<SetupLimM>, dim3(n_big), dim3(SetupLimM::WG), 0, stream, Pb);
-            else hipLaunchKernelGGL(sdsm_k_setup<SetupLimL>, dim3(n_big), dim3(SetupLimL::WG), 0, stream, Pb);
+    if (lists.setup_small.count > 0) {                   // the large regions first (longest), the many small ones behind them: the two launches overlap
+        const BatchParams Pb = list_view(P, lists.setup_big), Ps = list_view(P, lists.setup_small);
+        if (Pb.n > 0) {
+            if (cls == 1) hipLaunchKernelGGL(sdsm_k_setup<SetupLimM>, dim3(Pb.n), dim3(SetupLimM::WG), 0, stream, Pb);
+            else hipLaunchKernelGGL(sdsm_k_setup<SetupLimL>, dim3(Pb.n), dim3(SetupLimL::WG), 0, stream, Pb);
         }
-        hipLaunchKernelGGL(sdsm_k_setup<SetupLimS>, dim3(n_small), dim3(SetupLimS::WG), 0, stream, Ps);
+        hipLaunchKernelGGL(sdsm_k_setup<SetupLimS>, dim3(Ps.n), dim3(SetupLimS::WG), 0, stream, Ps);
     }
     else if (cls == 0) hipLaunchKernelGGL(sdsm_k_setup<SetupLimS>, dim3(P.n), dim3(SetupLimS::WG), 0, stream, P);
     else if (cls == 1) hipLaunchKernelGGL(sdsm_k_setup<SetupLimM>, dim3(P.n), dim3(SetupLimM::WG), 0, stream, P);
     else hipLaunchKernelGGL(sdsm_k_setup<SetupLimL>, dim3(P.n), dim3(SetupLimL::WG), 0, stream, P);
-    (void)order_w; (void)n_w;                            // the rows of the very large regions: sdsm_launch_setup_rows, on the stream of their workgroup groups
-    return hipGetLastError();
+    return hipGetLastError();                            // (the rows of the very large regions: sdsm_launch_setup_rows)
 }
 
-// Rows of G~ of the very large regions (one workgroup per member of their workgroup groups): queued by sdsm_launch_solve on the side
-// stream of the groups, in front of them -- no other solve class waits for it.
-extern "C" hipError_t sdsm_launch_setup_rows(const BatchParams &P, hipStream_t stream, const int32_t *order_w, int n_w)
+// Rows of G~ of the very large regions (one workgroup per entry of the plan's list of row members): queued by sdsm_launch_solve on the
+// caller's stream right behind the setup kernel, in front of the fork.
+extern "C" hipError_t sdsm_launch_setup_rows(const BatchParams &P, hipStream_t stream, ListSpan row_members)
 {
-    if (n_w <= 0) return hipSuccess;
-    BatchParams Pw = P;
-    Pw.order = order_w; Pw.n = n_w;                      // (candidate | member << 24) of the workgroup groups
-    hipLaunchKernelGGL(sdsm_k_setup_rows, dim3(n_w), dim3(SDSM_WG), (size_t)8 * (Pw.rows_mcap > 0 ? Pw.rows_mcap : 1), stream, Pw);
+    if (row_members.count <= 0) return hipSuccess;
+    const BatchParams Pr = list_view(P, row_members);
+    hipLaunchKernelGGL(sdsm_k_setup_rows, dim3(Pr.n), dim3(SDSM_WG), (size_t)8 * (Pr.rows_mcap > 0 ? Pr.rows_mcap : 1), stream, Pr);
     return hipGetLastError();
 }

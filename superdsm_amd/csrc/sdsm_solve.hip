@@ -26,7 +26,7 @@
 //   64 runs by a wavefront butterfly and the chunk totals are added in a fixed order.  A candidate's numbers therefore do not
 //   depend on the workgroup size, the size class, the number of workgroups that share it or anything else in its launch.
 //   One line-search sweep evaluates psi(x + t d) for 4 step lengths in a single pass (S is linear in t).
-#include "sdsm_common.h"
+#include "sdsm_launch.h"
 #include "sdsm_logtab.h"
 #include <climits>
 #include <cstdlib>
@@ -806,7 +806,7 @@ template <class L> __device__ __forceinline__ double *Hp_tail(const Cand &c) { r
 struct KeptState {
     double psi_pix; int fxh_hi, fxg_hi;
     unsigned long long *counters;       // BatchParams.cls_count + SDSM_SOLVER_COUNTERS: [0] evaluations served from the kept sums
-    int diag, pad;                      // BatchParams.pad2 (sdsm_set_solver_diagnostics): bit 0 recompute at unchanged iterates
+    int diag, pad;                      // BatchParams.solver_diag (sdsm_set_solver_diagnostics): bit 0 recompute at unchanged iterates
 };
 static_assert(sizeof(KeptState) == 32, "L::KEPT holds four doubles");
 #define KEPT (reinterpret_cast<KeptState *>(SD + L::KEPT))
@@ -1923,9 +1923,9 @@ __device__ __forceinline__ void solve_candidate(const BatchParams &P, int ci, in
     }
 }
 
-// The kernels.  Workgroup groups: workgroup b takes entry `ticket` of the launch list P.order (their members).  Everybody else (list 4: class 1, all
-// candidates, largest first; lists 0 .. 3: the classes beyond 1): a bounded number of RESIDENT workgroups pop entries of the
-// launch list (head counter BatchParams.cls_count[LIST]) until it is exhausted and solve the candidates that belong to their class.
+// The kernels.  Workgroup groups: workgroup b takes entry `ticket` of the launch list P.order (their members).  Everybody else (LIST_1: class 1, all
+// candidates, largest first; LIST_1B .. LIST_3: the classes beyond 1; sdsm_launch.h): a bounded number of RESIDENT workgroups pop entries of the
+// launch list (head counter BatchParams.cls_count[list]) until it is exhausted and solve the candidates that belong to their class.
 // The host knows only an upper bound of M, so the lists of these classes are upper bounds -- candidates that COULD belong, largest
 // first; most do not.  One workgroup per entry meant thousands of 512-thread workgroups that exit at once but each need a whole free
 // compute unit first: they kept three hardware queues busy for milliseconds (and class 2b waited 4.5 ms behind the empty global-memory
@@ -1939,7 +1939,7 @@ __global__ __launch_bounds__(WGSIZE, WPE) void sdsm_k_solve(BatchParams P, int h
     // picks an instruction, the pixel passes of the other candidates of the compute unit fill the gaps (+2 % on the 8-image launch).
     __builtin_amdgcn_s_setprio(2);
     const int tid = threadIdx.x;
-    if (tid == 0) { KEPT->diag = P.pad2; KEPT->counters = reinterpret_cast<unsigned long long *>(P.cls_count + SDSM_SOLVER_COUNTERS); }   // once per workgroup (a barrier follows)
+    if (tid == 0) { KEPT->diag = P.solver_diag; KEPT->counters = reinterpret_cast<unsigned long long *>(P.cls_count + SDSM_SOLVER_COUNTERS); }   // once per workgroup (a barrier follows)
     load_log_table(tid);
     if constexpr (!WIDE) {                                   // (one call site of the solver per kernel: the groups take entry `ticket`, everybody else pops)
         // Class 1 too (round 4): with one workgroup per candidate the hardware deals workgroup b to compute-unit die b mod 8 IN ORDER -- a die whose
@@ -1960,7 +1960,7 @@ __global__ __launch_bounds__(WGSIZE, WPE) void sdsm_k_solve(BatchParams P, int h
     }
     if constexpr (WIDE) {                                    // members are claimed in start order, not by workgroup index (see wide_barrier)
         int *tk = reinterpret_cast<int *>(SD + L::FLAG);
-        if (tid == 0) *tk = __hip_atomic_fetch_add(P.wide_ticket + (CLS == SDSM_CLS_WIDE_LIGHT ? 2 : CLS == SDSM_CLS_WIDE2B ? 1 : 0), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) *tk = __hip_atomic_fetch_add(P.wide_ticket + group_ticket(CLS), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
         const int slot = uni(*tk);
         __syncthreads();
@@ -2065,28 +2065,70 @@ __global__ __launch_bounds__(WGSIZE) void sdsm_k_eval(BatchParams P, int nprev, 
     for (int j = tid; j < M; j += L::WGS) og[6 + j] = g[6 + j];
 }
 
+// ---- the solve classes, host side ------------------------------------------------------------------
+// class 1:  6 + M <= 128,  envelope <= 2560 doubles, <= P.k1_pixmax pixels   256 threads, LDS ~ 30 KB  (three workgroups / CU)
+// class 1b: 6 + M <= 256,  envelope <= 7168 doubles, <= P.k1_pixmax pixels   256 threads, LDS ~ 79 KB  (two workgroups / CU; 512-thread kernels need
+//           ~200 registers per thread, i.e. a whole compute unit per workgroup whatever their LDS)
+// class 2:  6 + M <= 1024, envelope <= 11000 doubles   512 threads, LDS ~ 157 KB (one workgroup / CU)
+// class 2b: 6 + M <= 512,  envelope <= 15900 doubles   512 threads, LDS ~ 160 KB (one workgroup / CU)
+// class 3:  6 + M <= 1024, any envelope                512 threads, Hessian in global memory (only launched when needed)
+// The classes are independent: they run concurrently on streams forked from the caller's stream.  Measured on the synthetic 4096^2
+// image (10 073 candidates; 2695 of them beyond class 1, 122 beyond class 2) before classes 1b / 2b existed: class 2 alone needed
+// 10.9 s of workgroup time at ONE workgroup per compute unit (43 ms), and the global-memory class, queued behind it on the same
+// stream, another 75 ms (52 ms per candidate: every atomic of the pixel pass goes to memory).
+// One entry per SDSM_CLS_*: the template arguments of its sdsm_k_solve (NMAX, EMAX: the limits sdsm_solve_class tests; wavefronts per SIMD it is compiled for;
+// Hessian in global memory; threads; member of a workgroup group), its SLOT -- the SolveList whose head its resident workgroups pop, for a group layout the
+// GroupTicket its members draw -- and the bound on its RESIDENT workgroups, each of which pops entries of the launch list until the list is exhausted (0: a group
+// layout, one workgroup per list entry).  A 512-thread workgroup needs a whole free compute unit and waits for one while class 1 floods the chip: no more of them
+// than the class can use.  Class 1 has two configurations: throughput mode, and latency mode (LATENCY) at 256 threads.
+template <int NMAX_, int EMAX_, int WPE_, bool GLOBALH_, int THREADS_, bool WIDE_, int SLOT_, int RESIDENT_>
+struct ClassCfg {
+    static constexpr int NMAX = NMAX_, EMAX = EMAX_, WPE = WPE_, THREADS = THREADS_, SLOT = SLOT_, RESIDENT = RESIDENT_;
+    static constexpr bool GLOBALH = GLOBALH_, WIDE = WIDE_;
+    using L = Lay<NMAX_, EMAX_, GLOBALH_, THREADS_>;
+};
+template <int CLS, bool LATENCY = false> struct SolveClass;
+template <> struct SolveClass<SDSM_CLS_1>          : ClassCfg<SDSM_K1_NMAX, SDSM_K1_EMAX, SDSM_K1_WPE, false, SDSM_K1_THREADS, false, LIST_1, 1280> {};   // four (192 threads) or three (256 threads) per compute unit + a margin that starts as slots free up
+template <> struct SolveClass<SDSM_CLS_1, true>    : ClassCfg<SDSM_K1_NMAX, SDSM_K1_EMAX, 3, false, 256, false, LIST_1, 1280> {};
+template <> struct SolveClass<SDSM_CLS_1B>         : ClassCfg<SDSM_K1B_NMAX, SDSM_K1B_EMAX, SDSM_K1B_WPE, false, SDSM_K1B_THREADS, false, LIST_1B, 512> {};   // two per compute unit
+template <> struct SolveClass<SDSM_CLS_2>          : ClassCfg<SDSM_MAX_N_SOLVE, SDSM_K2_EMAX, 2, false, 512, false, LIST_2, 256> {};                    // one per compute unit (synthetic 4096^2: hundreds of candidates)
+template <> struct SolveClass<SDSM_CLS_2B>         : ClassCfg<SDSM_K2B_NMAX, SDSM_K2B_EMAX, 2, false, 512, false, LIST_2B, 128> {};                     // (synthetic 4096^2: 91 candidates)
+template <> struct SolveClass<SDSM_CLS_3>          : ClassCfg<SDSM_MAX_N_GLOBAL, SDSM_MAX_N_GLOBAL * (SDSM_MAX_N_GLOBAL + 1) / 2, 2, true, 512, false, LIST_3, 64> {};   // (34 there, 23-33 ms each: none may wait for another; usually none at all)
+template <> struct SolveClass<SDSM_CLS_WIDE>       : ClassCfg<SDSM_MAX_N_SOLVE, SDSM_K2_EMAX, 2, false, 512, true, TICKET_WIDE, 0> {};
+template <> struct SolveClass<SDSM_CLS_WIDE2B>     : ClassCfg<SDSM_K2B_NMAX, SDSM_K2B_EMAX, 2, false, 512, true, TICKET_WIDE2B, 0> {};
+template <> struct SolveClass<SDSM_CLS_WIDE_LIGHT> : ClassCfg<SDSM_KL_NMAX, SDSM_KL_EMAX, SDSM_KL_WPE, false, SDSM_KL_THREADS, true, TICKET_LIGHT, 0> {};
+
+// An entry agrees with sdsm_solve_class: a candidate exactly at its limits belongs to the class (for a group layout: a group of two), one unknown or one
+// envelope double more does not; a group layout draws the ticket the kernel takes for it.
+template <int CLS, bool LATENCY = false> constexpr bool class_entry_ok()
+{
+    using C = SolveClass<CLS, LATENCY>;
+    const int M = C::NMAX - 6, g = C::WIDE ? 2 : 0, light = CLS == SDSM_CLS_WIDE_LIGHT ? SDSM_KL_EMAX : 0;
+    return sdsm_solve_class(ST_OK, M, C::EMAX, 1, g, INT_MAX, light) == CLS && sdsm_solve_class(ST_OK, M + 1, C::EMAX, 1, g, INT_MAX, light) != CLS
+        && (C::GLOBALH || sdsm_solve_class(ST_OK, M, C::EMAX + 1, 1, g, INT_MAX, light) != CLS) && (C::WIDE ? C::SLOT == group_ticket(CLS) && C::RESIDENT == 0 : C::RESIDENT > 0);
+}
+static_assert(class_entry_ok<SDSM_CLS_1>() && class_entry_ok<SDSM_CLS_1, true>() && class_entry_ok<SDSM_CLS_1B>() && class_entry_ok<SDSM_CLS_2>() && class_entry_ok<SDSM_CLS_2B>() && class_entry_ok<SDSM_CLS_3>()
+              && class_entry_ok<SDSM_CLS_WIDE>() && class_entry_ok<SDSM_CLS_WIDE2B>() && class_entry_ok<SDSM_CLS_WIDE_LIGHT>(), "the table of solve classes and sdsm_solve_class disagree");
+
+// One layout of the point evaluation: class C's, for the candidates that the layout before it (limits nprev, eprev) does not hold.
+template <class C>
+static hipError_t launch_eval_layout(const BatchParams &P, int nprev, int eprev, const double *params, double *out, hipStream_t stream)
+{
+    auto kern = sdsm_k_eval<C::NMAX, C::EMAX, C::GLOBALH, C::THREADS>;
+    constexpr int lds = C::L::TOTAL_BYTES;
+    const hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess) hipLaunchKernelGGL(kern, dim3(P.n), dim3(C::THREADS), lds, stream, P, nprev, eprev, params, out);
+    return e;
+}
+
 extern "C" hipError_t sdsm_launch_eval(const BatchParams &P, const double *params, double *out, hipStream_t stream)
 {
     if (P.n <= 0) return hipSuccess;
+    using C1 = SolveClass<SDSM_CLS_1, true>; using C2 = SolveClass<SDSM_CLS_2>; using C3 = SolveClass<SDSM_CLS_3>;
     hipError_t e;
-    {
-        auto kern = sdsm_k_eval<SDSM_K1_NMAX, SDSM_K1_EMAX, false, 256>;
-        constexpr int lds = Lay<SDSM_K1_NMAX, SDSM_K1_EMAX, false, 256>::TOTAL_BYTES;
-        if ((e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(P.n), dim3(256), lds, stream, P, 0, 0, params, out);
-    }
-    {
-        auto kern = sdsm_k_eval<SDSM_MAX_N_SOLVE, SDSM_K2_EMAX, false, 512>;
-        constexpr int lds = Lay<SDSM_MAX_N_SOLVE, SDSM_K2_EMAX, false, 512>::TOTAL_BYTES;
-        if ((e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(P.n), dim3(512), lds, stream, P, SDSM_K1_NMAX, SDSM_K1_EMAX, params, out);
-    }
-    {
-        auto kern = sdsm_k_eval<SDSM_MAX_N_GLOBAL, SDSM_MAX_N_GLOBAL * (SDSM_MAX_N_GLOBAL + 1) / 2, true, 512>;
-        constexpr int lds = Lay<SDSM_MAX_N_GLOBAL, SDSM_MAX_N_GLOBAL * (SDSM_MAX_N_GLOBAL + 1) / 2, true, 512>::TOTAL_BYTES;
-        if ((e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(P.n), dim3(512), lds, stream, P, SDSM_MAX_N_SOLVE, SDSM_K2_EMAX, params, out);
-    }
+    if ((e = launch_eval_layout<C1>(P, 0, 0, params, out, stream)) != hipSuccess) return e;
+    if ((e = launch_eval_layout<C2>(P, C1::NMAX, C1::EMAX, params, out, stream)) != hipSuccess) return e;
+    if ((e = launch_eval_layout<C3>(P, C2::NMAX, C2::EMAX, params, out, stream)) != hipSuccess) return e;
     return hipGetLastError();
 }
 
@@ -2127,21 +2169,13 @@ extern "C" hipError_t sdsm_launch_probe_loss(long long n, const double *y, const
 }
 
 // ---- launch helper (called from sdsm_api.hip) ----------------------------------------------------
-// class 1:  6 + M <= 128,  envelope <= 2560 doubles, <= P.k1_pixmax pixels   256 threads, LDS ~ 30 KB  (three workgroups / CU)
-// class 1b: 6 + M <= 256,  envelope <= 7168 doubles, <= P.k1_pixmax pixels   256 threads, LDS ~ 79 KB  (two workgroups / CU; 512-thread kernels need
-//           ~200 registers per thread, i.e. a whole compute unit per workgroup whatever their LDS)
-// class 2:  6 + M <= 1024, envelope <= 11000 doubles   512 threads, LDS ~ 157 KB (one workgroup / CU)
-// class 2b: 6 + M <= 512,  envelope <= 15900 doubles   512 threads, LDS ~ 160 KB (one workgroup / CU)
-// class 3:  6 + M <= 1024, any envelope                512 threads, Hessian in global memory (only launched when needed)
-// The classes are independent: they run concurrently on streams forked from the caller's stream.  Measured on the synthetic 4096^2
-// image (10 073 candidates; 2695 of them beyond class 1, 122 beyond class 2) before classes 1b / 2b existed: class 2 alone needed
-// 10.9 s of workgroup time at ONE workgroup per compute unit (43 ms), and the global-memory class, queued behind it on the same
-// stream, another 75 ms (52 ms per candidate: every atomic of the pixel pass goes to memory).
-template <int NMAX, int EMAX, int WPE, bool GLOBALH = false, int WGSIZE = 256, bool WIDE = false, int CLS = SDSM_CLS_1>
-static hipError_t launch_class(const BatchParams &P, int grid, int list, int handles_rest, sdsm_record *records, uint32_t *masks, double *xi_out, hipStream_t stream)
+// One class on one stream.  V: the parameters with the class's launch list (list_view); resident: the bound on its resident workgroups.
+template <int CLS, bool LATENCY = false>
+static hipError_t launch_class(const BatchParams &V, const SolveOutputs &out, hipStream_t stream, int resident = SolveClass<CLS, LATENCY>::RESIDENT)
 {
-    auto kern = sdsm_k_solve<NMAX, EMAX, WPE, GLOBALH, WGSIZE, WIDE, CLS>;
-    constexpr int lds = Lay<NMAX, EMAX, GLOBALH, WGSIZE>::TOTAL_BYTES;
+    using C = SolveClass<CLS, LATENCY>;
+    auto kern = sdsm_k_solve<C::NMAX, C::EMAX, C::WPE, C::GLOBALH, C::THREADS, C::WIDE, CLS>;
+    constexpr int lds = C::L::TOTAL_BYTES;
     static_assert(lds <= 160 * 1024 - 512, "LDS budget");
     static bool attr_set[64] = {};                       // per instantiation and device; the attribute belongs to the function, not to the launch
     int dev = 0;
@@ -2151,12 +2185,12 @@ static hipError_t launch_class(const BatchParams &P, int grid, int list, int han
         if (e != hipSuccess) return e;
         if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
+    const int grid = C::WIDE || V.n < resident ? V.n : resident;
     if (grid <= 0) return hipSuccess;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WGSIZE), lds, stream, P, handles_rest, records, masks, xi_out, list);
+    // (class 1 handles the rest: the candidates without a solve; a group member finds its entry by ticket, not by a list head)
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(C::THREADS), lds, stream, V, CLS == SDSM_CLS_1 ? 1 : 0, out.records, out.masks, out.xi, C::WIDE ? -1 : C::SLOT);
     return hipGetLastError();
 }
-
-extern "C" hipError_t sdsm_launch_setup_rows(const BatchParams &P, hipStream_t stream, const int32_t *order_w, int n_w);
 
 // Gate of class 1: a 512-thread workgroup needs a whole free compute unit, and once the thousands of small workgroups of class 1 flood the
 // chip none becomes free before class 1 is through -- yet the few long candidates of the large classes ARE the end of a launch.  Class 1
@@ -2217,37 +2251,22 @@ extern "C" hipError_t sdsm_launch_queue_probe(int32_t *d_words, const hipStream_
     return hipGetLastError();
 }
 
-// Resident workgroups of the classes beyond 1 (each pops entries of its launch list until the list is exhausted).  A 512-thread
-// workgroup needs a whole free compute unit and waits for one while class 1 floods the chip: no more of them than the class can use.
-#define SDSM_RESIDENT_2 256         // class 2: one per compute unit (synthetic 4096^2: hundreds of candidates)
-#define SDSM_RESIDENT_2B 128        // class 2b (synthetic 4096^2: 91 candidates)
-#define SDSM_RESIDENT_3 64          // global-memory class (34 there, 23-33 ms each: none may wait for another; usually none at all)
-#define SDSM_RESIDENT_1B 512        // class 1b: two per compute unit
-#define SDSM_RESIDENT_1 1280        // class 1: four (192 threads) or three (256 threads) per compute unit + a margin that starts as slots free up
+// class 2b on a queue of its own (side 4): see own_2b below
+extern "C" int sdsm_solve_wants_own_2b(int n_w, int n_d) { return n_w == 0 && n_d >= 2 * SolveClass<SDSM_CLS_2B>::RESIDENT; }
 
-// class 2b on a queue of its own (side4): see own_2b below
-extern "C" int sdsm_solve_wants_own_2b(int n_w, int n_d) { return n_w == 0 && n_d >= 2 * SDSM_RESIDENT_2B; }
-
-extern "C" hipError_t sdsm_launch_solve(const BatchParams &P, sdsm_record *records, uint32_t *masks, double *xi_out,
-                                        hipStream_t stream, hipStream_t side1, hipStream_t side2, hipStream_t side3, hipStream_t side4, hipEvent_t *ev /* 5 */,
-                                        int n_c, int n_d, int n_w, int n_r)
+extern "C" hipError_t sdsm_launch_solve(const BatchParams &P, const SolveOutputs &out, const LaunchStreams &streams, const LaunchLists &lists)
 {
     hipError_t e;
-    // P.order = [all n, largest first | n_c candidates whose bound Mcap admits more than class 1 | the n_d that admit more than class 2 |
-    // (candidate | member << 24) of the workgroup groups].  n_c / n_d only bound the lengths of the device-built work lists.
-    BatchParams Pw = P;
-    Pw.order = P.order + P.n + n_c + n_d; Pw.n = n_w;
-    BatchParams Pc = P, Pd = P;
-    Pc.order = P.order + P.n; Pc.n = n_c;
-    Pd.order = P.order + P.n + n_c; Pd.n = n_d;
-    const int g_c = n_c < SDSM_RESIDENT_2 ? n_c : SDSM_RESIDENT_2, g_d = n_d < SDSM_RESIDENT_2B ? n_d : SDSM_RESIDENT_2B, g_3 = n_d < SDSM_RESIDENT_3 ? n_d : SDSM_RESIDENT_3;
-    const int g_b = n_c < SDSM_RESIDENT_1B ? n_c : SDSM_RESIDENT_1B;
+    const hipStream_t stream = streams.caller;
+    // the lists of the classes beyond 1 only bound the lengths of the device-built work lists (upper bounds of M); P itself views the list of all candidates
+    const BatchParams Pc = list_view(P, lists.beyond_1), Pd = list_view(P, lists.beyond_2), Pw = list_view(P, lists.group_members);
+    const int n_c = Pc.n, n_d = Pd.n, n_w = Pw.n;
     // rows of G~ of the very large regions (one workgroup per member of their workgroup groups), on the caller's stream right behind the
     // setup kernel: a region whose envelope turns out too large for a group belongs to class 2b or the global-memory class, whose kernels
     // therefore wait for them too
-    if (n_r > 0 && (e = sdsm_launch_setup_rows(P, stream, Pw.order + n_w, n_r)) != hipSuccess) return e;
+    if ((e = sdsm_launch_setup_rows(P, stream, lists.row_members)) != hipSuccess) return e;
     // fork: the side streams wait for everything queued on the caller's stream so far (setup kernels)
-    if (n_c > 0 || n_d > 0 || n_w > 0) { if ((e = hipEventRecord(ev[0], stream)) != hipSuccess) return e; }
+    if (lists.forks() && (e = hipEventRecord(streams.ev[0], stream)) != hipSuccess) return e;
     // Queues (kernels of one stream run one after the other; the longest chains first on each):
     //   side1: the global-memory class (one candidate takes tens of milliseconds), then class 2b;
     //   side2: the workgroup groups of the very large regions (the light ones, or those of class-2 layout), then class 2;
@@ -2255,12 +2274,17 @@ extern "C" hipError_t sdsm_launch_solve(const BatchParams &P, sdsm_record *recor
     //   caller's stream: class 1 (all candidates in the host's order, largest first; the others leave at once).
     // The driver maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and kernels of streams that share a queue run one after the other: the caller
     // passes side streams it has probed to run side by side with `stream` and with each other (choose_sides, sdsm_api.hip).  Where it found fewer than three, two of
-    // the arguments are the same stream (side3 == side2: class 1b behind the groups / class 2; then side2 == side1 as well): fork, launches in order, join all hold.
+    // the sides are the same stream (side3 == side2: class 1b behind the groups / class 2; then side2 == side1 as well): fork, launches in order, join all hold.
     // An error while enqueueing (a launch that fails) must not leave forked work behind on the side streams, which all plans of the device share: the first error
     // is kept, nothing further is launched, but every side stream that was forked is still recorded and joined below.
     hipError_t first = hipSuccess;
     auto keep = [&](hipError_t r) { if (first == hipSuccess && r != hipSuccess) first = r; return first == hipSuccess; };
-    bool forked1 = false, forked2 = false, forked3 = false, forked4 = false;
+    struct Side { hipStream_t stream; hipEvent_t joined; bool forked; };
+    Side side[4];
+    for (int i = 0; i < 4; i++) side[i] = {streams.side[i], streams.ev ? streams.ev[1 + i] : nullptr, false};
+    Side &side1 = side[0], &side2 = side[1], &side3 = side[2], &side4 = side[3];
+    auto fork = [&](Side &s) { return s.forked = keep(hipStreamWaitEvent(s.stream, streams.ev[0], 0)); };
+    auto join = [&](Side &s) { if (s.forked) { hipError_t r = hipEventRecord(s.joined, s.stream); if (r == hipSuccess) r = hipStreamWaitEvent(stream, s.joined, 0); keep(r); } };
     const bool light = SDSM_LIGHT_GROUPS && P.light_emax > 0;
     // Plans WITHOUT workgroup groups (synthetic 4096^2: every class has hundreds of candidates of its own): class 2b on a queue of its own instead of behind the
     // global-memory class -- a kernel behind another one starts when class 1 already holds the chip with resident workgroups, and a 512-thread workgroup then gets no
@@ -2268,43 +2292,27 @@ extern "C" hipError_t sdsm_launch_solve(const BatchParams &P, sdsm_record *recor
     // they are (a fourth stream for class 2 beside the groups was measured slower in round 3: its resident workgroups take compute units from the group members).
     // (only where the list is long: on the 8-copies step, whose list of 2b / 3 candidates holds a few dozen upper bounds and no real candidate, the 128 more resident
     // workgroups at the start cost 0.2 of 4.9 ms)
-    const bool own_2b = sdsm_solve_wants_own_2b(n_w, n_d) && side4 != nullptr;
-    if (n_d > 0 || n_w > 0) {
-        if (keep(hipStreamWaitEvent(side1, ev[0], 0))) {
-            forked1 = true;
-            // (the groups whose envelope needs the layout of class 2b: few and short next to the global-memory class behind them)
-            if (n_w > 0 && first == hipSuccess) keep(launch_class<SDSM_K2B_NMAX, SDSM_K2B_EMAX, 2, false, 512, true, SDSM_CLS_WIDE2B>(Pw, n_w, -1, 0, records, masks, xi_out, side1));
-            if (n_d > 0 && first == hipSuccess) keep(launch_class<SDSM_MAX_N_GLOBAL, SDSM_MAX_N_GLOBAL * (SDSM_MAX_N_GLOBAL + 1) / 2, 2, true, 512, false, SDSM_CLS_3>(Pd, g_3, 3, 0, records, masks, xi_out, side1));
-            if (n_d > 0 && !own_2b && first == hipSuccess) keep(launch_class<SDSM_K2B_NMAX, SDSM_K2B_EMAX, 2, false, 512, false, SDSM_CLS_2B>(Pd, g_d, 2, 0, records, masks, xi_out, side1));
-        }
+    const bool own_2b = sdsm_solve_wants_own_2b(n_w, n_d) && side4.stream != nullptr;
+    if ((n_d > 0 || n_w > 0) && fork(side1)) {
+        // (the groups whose envelope needs the layout of class 2b: few and short next to the global-memory class behind them)
+        if (n_w > 0 && first == hipSuccess) keep(launch_class<SDSM_CLS_WIDE2B>(Pw, out, side1.stream));
+        if (n_d > 0 && first == hipSuccess) keep(launch_class<SDSM_CLS_3>(Pd, out, side1.stream));
+        if (n_d > 0 && !own_2b && first == hipSuccess) keep(launch_class<SDSM_CLS_2B>(Pd, out, side1.stream));
     }
-    if (own_2b && first == hipSuccess) {
-        if (keep(hipStreamWaitEvent(side4, ev[0], 0))) {
-            forked4 = true;
-            keep(launch_class<SDSM_K2B_NMAX, SDSM_K2B_EMAX, 2, false, 512, false, SDSM_CLS_2B>(Pd, g_d, 2, 0, records, masks, xi_out, side4));
-        }
+    if (own_2b && first == hipSuccess && fork(side4)) keep(launch_class<SDSM_CLS_2B>(Pd, out, side4.stream));
+    if ((n_w > 0 || n_c > 0) && first == hipSuccess && fork(side2)) {
+        // Light groups (a launch with P.light_emax > 0): THREE wavefronts per SIMD, i.e. at most 168 registers -- a member's two wavefronts per SIMD and the one of a
+        // class-1 workgroup (168 as well) are 504 of the 512 registers of a lane, its LDS leaves class 1's 36 KB free: the compute unit of a member, which waits on LDS
+        // round trips and barriers most of the time, also runs a class-1 candidate.  Every group the light class leaves has the layout of class 2b (side 1) in such
+        // a launch (sdsm_solve_class), so no group kernel stands behind this one.
+        if (n_w > 0 && light && first == hipSuccess) keep(launch_class<SDSM_CLS_WIDE_LIGHT>(Pw, out, side2.stream));
+        // (P.wide_rest: the bound on M of some group admits more unknowns than class 2b holds -- the groups of class-2 layout, if there are any after all, wait behind the light
+        // ones and are not seen by the gate of class 1: slow for them, and 6 + M > 512 at an envelope of at most 11 000 doubles is a region of hundreds of thousands of pixels
+        // a few grid points wide)
+        if (n_w > 0 && (!light || P.wide_rest) && first == hipSuccess) keep(launch_class<SDSM_CLS_WIDE>(Pw, out, side2.stream));
+        if (n_c > 0 && first == hipSuccess) keep(launch_class<SDSM_CLS_2>(Pc, out, side2.stream));
     }
-    if ((n_w > 0 || n_c > 0) && first == hipSuccess) {
-        if (keep(hipStreamWaitEvent(side2, ev[0], 0))) {
-            forked2 = true;
-            // Light groups (a launch with P.light_emax > 0): THREE wavefronts per SIMD, i.e. at most 168 registers -- a member's two wavefronts per SIMD and the one of a
-            // class-1 workgroup (168 as well) are 504 of the 512 registers of a lane, its LDS leaves class 1's 36 KB free: the compute unit of a member, which waits on LDS
-            // round trips and barriers most of the time, also runs a class-1 candidate.  Every group the light class leaves has the layout of class 2b (side 1) in such
-            // a launch (sdsm_solve_class), so no group kernel stands behind this one.
-            if (n_w > 0 && light && first == hipSuccess) keep(launch_class<SDSM_KL_NMAX, SDSM_KL_EMAX, SDSM_KL_WPE, false, SDSM_KL_THREADS, true, SDSM_CLS_WIDE_LIGHT>(Pw, n_w, -1, 0, records, masks, xi_out, side2));
-            // (P.pad3: the bound on M of some group admits more unknowns than class 2b holds -- the groups of class-2 layout, if there are any after all, wait behind the light
-            // ones and are not seen by the gate of class 1: slow for them, and 6 + M > 512 at an envelope of at most 11 000 doubles is a region of hundreds of thousands of pixels
-            // a few grid points wide)
-            if (n_w > 0 && (!light || P.pad3) && first == hipSuccess) keep(launch_class<SDSM_MAX_N_SOLVE, SDSM_K2_EMAX, 2, false, 512, true, SDSM_CLS_WIDE>(Pw, n_w, -1, 0, records, masks, xi_out, side2));
-            if (n_c > 0 && first == hipSuccess) keep(launch_class<SDSM_MAX_N_SOLVE, SDSM_K2_EMAX, 2, false, 512, false, SDSM_CLS_2>(Pc, g_c, 1, 0, records, masks, xi_out, side2));
-        }
-    }
-    if (n_c > 0 && first == hipSuccess) {
-        if (keep(hipStreamWaitEvent(side3, ev[0], 0))) {
-            forked3 = true;
-            keep(launch_class<SDSM_K1B_NMAX, SDSM_K1B_EMAX, SDSM_K1B_WPE, false, SDSM_K1B_THREADS, false, SDSM_CLS_1B>(Pc, g_b, 0, 0, records, masks, xi_out, side3));
-        }
-    }
+    if (n_c > 0 && first == hipSuccess && fork(side3)) keep(launch_class<SDSM_CLS_1B>(Pc, out, side3.stream));
     // class 1 runs THREE wavefronts per SIMD (168 registers).  Measured on the 8-image launch of round 2: 7.4 ms at two wavefronts
     // (240 registers), 5.5 ms at three, 6.6 ms at four (128 registers: 36 spilled) -- the solver is latency bound and a third workgroup
     // per compute unit fills its stalls.
@@ -2316,24 +2324,17 @@ extern "C" hipError_t sdsm_launch_solve(const BatchParams &P, sdsm_record *recor
     // -- no candidates -- "ran" 5.4 ms, class 2b behind it started when class 1 ended, the groups took 9.7 ms instead of 4.7; stream
     // priorities change nothing).  The few long candidates of the large classes ARE the end of the launch: class 1 starts some tens of
     // microseconds after them -- their resident workgroups are in place by then, the ones without work gone again.
-    if ((n_c > 0 || n_d > 0 || n_w > 0) && first == hipSuccess) {
-        // the first kernel of every side queue: side 1: groups of class-2b layout (ticket [1]), else the global-memory class (list 3); side 2: groups of
-        // class-2 layout (ticket [0]) or of the light layout (ticket [2]), else class 2 (list 1); side 3: class 1b (list 0)
-        const int l0 = n_w > 0 ? -2 : 3, c0 = n_w > 0 ? n_w : n_d;
-        const int l1 = n_w > 0 ? (light ? -3 : -1) : 1, c1 = n_w > 0 ? n_w : n_c;
-        hipLaunchKernelGGL(sdsm_k_gate, dim3(1), dim3(64), 0, stream, (const int32_t *)P.cls_count, (const int32_t *)P.wide_ticket, l0, c0, l1, c1, 0, n_c,
+    if (lists.forks() && first == hipSuccess) {
+        // the first kernel of every side queue: side 1: groups of class-2b layout, else the global-memory class; side 2: groups of
+        // the light layout or of class-2 layout, else class 2; side 3: class 1b
+        const int w0 = n_w > 0 ? gate_ticket(TICKET_WIDE2B) : gate_list(LIST_3), c0 = n_w > 0 ? n_w : n_d;
+        const int w1 = n_w > 0 ? gate_ticket(light ? TICKET_LIGHT : TICKET_WIDE) : gate_list(LIST_2), c1 = n_w > 0 ? n_w : n_c;
+        hipLaunchKernelGGL(sdsm_k_gate, dim3(1), dim3(64), 0, stream, (const int32_t *)P.cls_count, (const int32_t *)P.wide_ticket, w0, c0, w1, c1, gate_list(LIST_1B), n_c,
                            (long long)SDSM_GATE_CAP_US * 100, (long long)SDSM_GATE_STALL_US * 100);
     }
-    static const int resident_1 = [] { const char *e = getenv("SDSM_RESIDENT_1"); const int v = e ? atoi(e) : 0; return v > 0 ? v : SDSM_RESIDENT_1; }();   // (diagnostic knob)
-    const int g_1 = P.n < resident_1 ? P.n : resident_1;
-    if (first == hipSuccess) {
-        if (!P.latency) keep(launch_class<SDSM_K1_NMAX, SDSM_K1_EMAX, SDSM_K1_WPE, false, SDSM_K1_THREADS, false, SDSM_CLS_1>(P, g_1, 4, 1, records, masks, xi_out, stream));
-        else keep(launch_class<SDSM_K1_NMAX, SDSM_K1_EMAX, 3, false, 256, false, SDSM_CLS_1>(P, g_1, 4, 1, records, masks, xi_out, stream));
-    }
+    static const int resident_1 = [] { const char *e = getenv("SDSM_RESIDENT_1"); const int v = e ? atoi(e) : 0; return v > 0 ? v : SolveClass<SDSM_CLS_1>::RESIDENT; }();   // (diagnostic knob)
+    if (first == hipSuccess) keep(!P.latency ? launch_class<SDSM_CLS_1>(P, out, stream, resident_1) : launch_class<SDSM_CLS_1, true>(P, out, stream, resident_1));
     // join (also after an error: whatever was forked is recorded and waited for)
-    if (forked1) { hipError_t r = hipEventRecord(ev[1], side1); if (r == hipSuccess) r = hipStreamWaitEvent(stream, ev[1], 0); keep(r); }
-    if (forked2) { hipError_t r = hipEventRecord(ev[2], side2); if (r == hipSuccess) r = hipStreamWaitEvent(stream, ev[2], 0); keep(r); }
-    if (forked3) { hipError_t r = hipEventRecord(ev[3], side3); if (r == hipSuccess) r = hipStreamWaitEvent(stream, ev[3], 0); keep(r); }
-    if (forked4) { hipError_t r = hipEventRecord(ev[4], side4); if (r == hipSuccess) r = hipStreamWaitEvent(stream, ev[4], 0); keep(r); }
+    for (Side &s : side) join(s);
     return first;
 }

@@ -44,6 +44,50 @@ def solve_scene_gpu(scene, footprints=None, want_xi=False, mode=None):
     return out
 
 
+def plan_of_squares(sides):
+    """A host-only plan over one candidate per atom, atoms = squares of the given side lengths on a grid (statistics only: area, extents)."""
+    import ctypes as C
+    from . import _capi
+    lib = _capi.lib()
+    n = len(sides)
+    pitch = max(sides)
+    per_row = 60000 // pitch
+    stats = np.zeros((n + 1, 6), np.int32)
+    for k, sd in enumerate(sides, start=1):
+        r, c = ((k - 1) // per_row) * pitch, ((k - 1) % per_row) * pitch
+        stats[k] = (sd * sd, r, r + sd - 1, c, c + sd - 1, 0)
+    H, W = ((n - 1) // per_row + 1) * pitch, per_row * pitch
+    assert H <= 65535
+    cfg = _capi.make_config(dict(alpha=0.033, smooth_amount=4, smooth_subsample=8, background_margin=0))
+    offs = np.arange(n + 1, dtype=np.int32)
+    labels = np.arange(1, n + 1, dtype=np.int32)
+    plan = lib.sdsm_plan_create(H, W, n, stats.ctypes.data_as(C.c_void_p), C.byref(cfg), n, offs.ctypes.data_as(C.c_void_p), labels.ctypes.data_as(C.c_void_p))
+    assert plan, lib.sdsm_last_error()
+    return plan
+
+
+PLAN_LIST_NAMES = ('all', 'beyond_1', 'beyond_2', 'group_members', 'row_members', 'setup_small', 'setup_big')
+# the plans whose launch lists tests/golden/plan_lists.json records: name -> (sides of plan_of_squares, scheduling modes)
+PLAN_LIST_CASES = {
+    'clusters': ([30] * 200 + [70] * 20 + [100] * 6 + [180] * 2, (0, 1, 2)),      # groups, row members, latency groups; one setup launch
+    'setup_split': ([30] * 300 + [190] * 2, (0,)),                                # the two-launch setup: 300 small regions, 2 beyond the small tables
+    'no_groups': ([70] * 8000 + [120] * 40, (0,)),                                # thousands of mid-size regions: no groups, no row members
+}
+
+
+def plan_lists(plan, mode):
+    """The launch lists of a host-only plan in the given scheduling mode (sdsm_plan_lists): spans as 7 x (first, count), and `order`."""
+    import ctypes as C
+    from . import _capi
+    lib = _capi.lib()
+    _capi.check(lib.sdsm_plan_set_latency_mode(plan, mode), 'sdsm_plan_set_latency_mode')
+    spans = np.zeros((7, 2), np.int32)
+    _capi.check(lib.sdsm_plan_lists(plan, spans.ctypes.data_as(C.c_void_p), None), 'sdsm_plan_lists')
+    order = np.zeros(int(spans[:, 1].sum()), np.int32)
+    _capi.check(lib.sdsm_plan_lists(plan, spans.ctypes.data_as(C.c_void_p), order.ctypes.data_as(C.c_void_p)), 'sdsm_plan_lists')
+    return spans, order
+
+
 def dice(a_off, a_frag, b_off, b_frag, shape):
     fa = np.zeros(shape, bool)
     fb = np.zeros(shape, bool)

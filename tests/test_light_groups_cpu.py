@@ -4,7 +4,8 @@ import ctypes as C
 
 import numpy as np
 
-from test_capi_cpu import _plan_of_squares, _schedule
+from superdsm_amd.testing import plan_of_squares as _plan_of_squares
+from test_capi_cpu import _schedule
 
 CLS_1, CLS_1B, CLS_2, CLS_2B, CLS_3, CLS_WIDE, CLS_WIDE2B, CLS_WIDE_LIGHT = range(8)
 KL_NMAX, KL_EMAX = 288, 12400          # SDSM_KL_NMAX, SDSM_KL_EMAX
