@@ -181,6 +181,11 @@ int sdsm_plan_schedule(const sdsm_plan *plan, int32_t *group_members, int32_t *r
  * workgroups that build rows of G~ | setup by the small class | setup by the large class] in one array of entries; order, if not NULL,
  * receives that array (as many int32 as the counts add up to; member lists hold candidate | member << 24). */
 int sdsm_plan_lists(const sdsm_plan *plan, int32_t spans[14], int32_t *order);
+/* What the plan's kernels are given in its current mode, as raw bytes (host only, diagnostics and tests; read-only).  params receives the
+ * kernel arguments laid over a NULL workspace (params_bytes must be 856, the size of the argument struct): every pointer into the workspace
+ * then holds its block's byte offset, the image pointers are NULL, so the one blob carries all offsets and all scalars.  cand receives the
+ * candidate descriptors (cand_bytes must be 112 times the plan's candidates).  A size that differs is SDSM_ERR_ARGUMENT. */
+int sdsm_plan_image(const sdsm_plan *plan, void *params, size_t params_bytes, void *cand, size_t cand_bytes);
 /* The solve class of every candidate in the plan's current mode (host only, diagnostics and tests), given what the setup kernel found for it
  * (status, M and env_size of its state): 0 class 1, 1 class 1b, 2 class 2, 3 class 2b, 4 the global-memory class, 5 / 6 / 7 a workgroup
  * group with the LDS layout of class 2 / of class 2b / the light layout (at most 288 unknowns and 12 400 envelope doubles: its members

@@ -31,6 +31,32 @@ RECORD_DTYPE = np.dtype([
     ('iters_ell', 'i4'), ('iters_dsm', 'i4'), ('evals_value', 'i4'), ('evals_full', 'i4'),
     ('on_boundary', 'i4'), ('fg_r0', 'i4'), ('fg_c0', 'i4'), ('fg_h', 'i4'), ('fg_w', 'i4'), ('n_positive', 'i4'), ('n_negative', 'i4'), ('reserved', 'i4')])
 assert RECORD_DTYPE.itemsize == 128
+# CandDesc and CandState of csrc/sdsm_common.h, field by field: what the plan uploads per candidate and what the setup kernel writes
+CAND_DESC_DTYPE = np.dtype([
+    ('crop_off', 'i8'), ('ell_off', 'i8'), ('mask_off', 'i8'), ('xi_off', 'i8'),
+    ('N', 'i4'), ('r0', 'i4'), ('c0', 'i4'), ('h', 'i4'), ('w', 'i4'), ('fp_off', 'i4'), ('fp_len', 'i4'), ('Mcap', 'i4'), ('perm_inv', 'u4'), ('wide_g', 'i4'),
+    ('hglob_off', 'i8'), ('wide_off', 'i8'), ('image', 'i4'), ('NRcap', 'i4'), ('run_off', 'i8'), ('rows_g', 'i4'), ('pad1', 'i4')])
+assert CAND_DESC_DTYPE.itemsize == 112
+CAND_STATE_DTYPE = np.dtype([
+    ('M', 'i4'), ('status', 'i4'), ('hc', 'i4'), ('wc', 'i4'), ('npos', 'i4'), ('zmax', 'i4'),
+    ('sum_r', 'u8'), ('sum_c', 'u8'), ('sum_rr', 'u8'), ('sum_cc', 'u8'),
+    ('hzmax', 'i4'), ('env_size', 'i4'), ('nneg', 'i4'), ('yexp', 'i4'), ('NR', 'i4'), ('pad', 'i4', 7)])
+assert CAND_STATE_DTYPE.itemsize == 104
+# the 16 values of sdsm_plan_layout: byte offsets of workspace blocks, then sizes and counts
+PLAN_LAYOUT_NAMES = ('cand', 'state', 'crop_y', 'crop_rc', 'crop_cc', 'run_meta', 'grid_rc', 'ell_im', 'ell_w', 'zcap_run', 'k',
+                     'cand_size', 'total_pixels', 'total_ell', 'state_size', 'total_runs')
+# BatchParams of csrc/sdsm_common.h, the parameter blob of sdsm_plan_image (pointers as u8: over a null workspace they hold byte offsets)
+_IMAGE_REF = np.dtype([('y', 'u8'), ('atoms', 'u8'), ('valid', 'u8'), ('H', 'i4'), ('W', 'i4')])
+PLAN_PARAMS_DTYPE = np.dtype(
+    [('n', 'i4'), ('n_images', 'i4'), ('n_total', 'i4'), ('latency', 'i4'), ('img', _IMAGE_REF, 16)]
+    + [(f, 'i4') for f in ('k', 'R', 'subsample', 'zcap', 'zcap_run', 'zshift', 'no_deform', 'no_trivial_rule', 'init_elliptical', 'max_iters', 'k1_pixmax', 'pad0')]
+    + [(f, 'f8') for f in ('scale', 'epsilon', 'alpha', 'reg_unit')] + [('hess_thr', 'f4')]
+    + [(f, 'i4') for f in ('boost_pixels', 'light_emax', 'wide_rest', 'rows_mcap', 'solver_diag')]
+    + [(f, 'u8') for f in ('cand', 'state', 'fp_labels', 'order', 'crop_y', 'crop_rc', 'run_meta', 'run_q0', 'run_aux', 'tmp_y', 'tmp_rc', 'crop_cc', 'dist', 'inv',
+                           'grid_rc', 'ell_w', 'ell_im', 'env_fst', 'env_rb', 'psf', 'wide_pool', 'wide_ticket')]
+    + [('wide_timeout', 'i8')] + [(f, 'u8') for f in ('cls_count', 'hglob', 'prof', 'prof2', 'x0')])
+PLAN_PARAMS_BYTES = PLAN_PARAMS_DTYPE.itemsize
+assert PLAN_PARAMS_BYTES == 856 and PLAN_PARAMS_DTYPE.fields['wide_rest'][1] == 620 and PLAN_PARAMS_DTYPE.fields['solver_diag'][1] == 628
 POST_RECORD_DTYPE = np.dtype([('contrast', 'f8'), ('interior_mean', 'f8'), ('exterior_mean', 'f8'), ('fg_mean', 'f8'), ('fg_std', 'f8'),
                               ('area', 'i4'), ('status', 'i4'), ('r0', 'i4'), ('c0', 'i4'), ('h', 'i4'), ('w', 'i4')])
 assert POST_RECORD_DTYPE.itemsize == 64
@@ -114,6 +140,7 @@ SYMBOLS = {
     'sdsm_plan_layout': (_i32, [_vp, _vp]),
     'sdsm_plan_schedule': (_i32, [_vp, _vp, _vp]),
     'sdsm_plan_lists': (_i32, [_vp, _vp, _vp]),
+    'sdsm_plan_image': (_i32, [_vp, _vp, _sz, _vp, _sz]),
     'sdsm_plan_solve_classes': (_i32, [_vp, _vp, _vp, _vp, _vp]),
     'sdsm_set_light_envelope_limit': (_i32, [_i32]),
     'sdsm_plan_set_latency_mode': (_i32, [_vp, _i32]),

@@ -1,5 +1,6 @@
-// Host side of a launch, shared by sdsm_api.hip (plan, layout), sdsm_setup.hip and sdsm_solve.hip (launches): the launch lists of a plan,
-// the zeroed words of a launch, the streams a launch runs on.  Each format is defined here and nowhere else.
+// Host side of a launch, shared by sdsm_plan.hip (plan, layout), sdsm_api.hip (entry points), sdsm_setup.hip and sdsm_solve.hip (launches): the
+// launch lists of a plan, the zeroed words of a launch, the limits of the setup classes, the streams a launch runs on.  Each format is defined
+// here and nowhere else (the workspace itself: the table of sdsm_plan.h).
 #pragma once
 #include <cstddef>
 #include "sdsm_common.h"
@@ -44,6 +45,20 @@ __host__ __device__ constexpr int group_ticket(int cls) { return cls == SDSM_CLS
 // What the gate of class 1 (sdsm_k_gate) watches, as its arguments encode it: a list head as it is, a group ticket as -1 - ticket.
 constexpr int gate_list(SolveList l) { return l; }
 constexpr int gate_ticket(GroupTicket t) { return -1 - t; }
+
+// ---- setup classes --------------------------------------------------------------------------------------------------------------
+// Limits of the setup kernel's LDS tables (sdsm_setup.hip): the plan picks the smallest class that holds it (sdsm_setup_class).
+struct SetupLimS { static constexpr int DIM = 512, GRID = 512, PSFW = 1152, LABELS = 32767, WPE = 4, WG = 256; };      // 13 KB: PSF k <= 33
+struct SetupLimM { static constexpr int DIM = 1024, GRID = 1024, PSFW = SDSM_PSF_LDS, LABELS = SDSM_MAX_LABELS, WPE = 4, WG = 1024; };   // 37 KB: PSF k <= 65; plans with regions this large have few candidates: 1024 threads each
+struct SetupLimL { static constexpr int DIM = SDSM_MAX_BBOX_DIM, GRID = SDSM_MAX_GRID, PSFW = SDSM_PSF_LDS, LABELS = SDSM_MAX_LABELS, WPE = 4, WG = 1024; };   // 54 KB
+constexpr bool sdsm_setup_fits_small(int h, int w, int mcap, int max_label, int k)
+{
+    return h <= SetupLimS::DIM && w <= SetupLimS::DIM && mcap <= SetupLimS::GRID && max_label <= SetupLimS::LABELS && k * k <= SetupLimS::PSFW;
+}
+constexpr int sdsm_setup_class(int max_dim, int max_mcap, int max_label, int k)
+{
+    return sdsm_setup_fits_small(max_dim, max_dim, max_mcap, max_label, k) ? 0 : max_dim <= SetupLimM::DIM && max_mcap <= SetupLimM::GRID ? 1 : 2;
+}
 
 // ---- streams and results of a launch --------------------------------------------------------------------------------------------
 // side[0]: the global-memory class and class 2b; side[1]: the groups and class 2; side[2]: class 1b; side[3]: class 2b of plans without groups, or null

@@ -481,30 +481,7 @@ extern "C" size_t sdsm_preprocess_workspace_bytes(int H, int W, double sigma1, d
            + align_up(1024 * 8, 256) + 512;
 }
 
-// numpy pairwise sum (PW_BLOCKSIZE 128), host
-static double np_pairwise(const double *a, long n)
-{
-    if (n < 8) { double r = 0; for (long i = 0; i < n; i++) r += a[i]; return r; }
-    if (n <= 128) {
-        double r[8]; long i;
-        for (int k = 0; k < 8; k++) r[k] = a[k];
-        for (i = 8; i < n - (n % 8); i += 8) for (int k = 0; k < 8; k++) r[k] += a[i + k];
-        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; i++) res += a[i];
-        return res;
-    }
-    long n2 = n / 2; n2 -= n2 % 8;
-    return np_pairwise(a, n2) + np_pairwise(a + n2, n - n2);
-}
-
-// scipy.ndimage._filters._gaussian_kernel1d
-extern "C" void sdsm_gauss_kernel_host(double sigma, int radius, double *w)
-{
-    double s2 = sigma * sigma;
-    for (int i = 0; i <= 2 * radius; i++) { double x = i - radius; w[i] = exp(-0.5 / s2 * (x * x)); }
-    double s = np_pairwise(w, 2 * radius + 1);
-    for (int i = 0; i <= 2 * radius; i++) w[i] = w[i] / s;
-}
+extern "C" void sdsm_gauss_kernel_host(double sigma, int radius, double *w);   // scipy.ndimage._filters._gaussian_kernel1d (sdsm_plan.hip: the PSF needs it too)
 
 // hipFuncSetAttribute costs microseconds per call: the dynamic LDS limit of a kernel is raised only when a launch needs more than before
 static hipError_t need_lds(const void *fn, size_t bytes)

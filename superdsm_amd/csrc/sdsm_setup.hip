@@ -353,10 +353,7 @@ __device__ __forceinline__ int envelope_from_first(const BatchParams &P, const C
 
 }  // namespace
 
-// Limits of the setup kernel's LDS tables: the host picks the smallest class that holds the plan (sdsm_setup_class).
-struct SetupLimS { static constexpr int DIM = 512, GRID = 512, PSFW = 1152, LABELS = 32767, WPE = 4, WG = 256; };      // 13 KB: PSF k <= 33
-struct SetupLimM { static constexpr int DIM = 1024, GRID = 1024, PSFW = SDSM_PSF_LDS, LABELS = SDSM_MAX_LABELS, WPE = 4, WG = 1024; };   // 37 KB: PSF k <= 65; plans with regions this large have few candidates: 1024 threads each
-struct SetupLimL { static constexpr int DIM = SDSM_MAX_BBOX_DIM, GRID = SDSM_MAX_GRID, PSFW = SDSM_PSF_LDS, LABELS = SDSM_MAX_LABELS, WPE = 4, WG = 1024; };   // 54 KB
+// (The limits of the setup kernel's LDS tables, SetupLimS / M / L, and sdsm_setup_class: sdsm_launch.h -- the plan picks its class from them.)
 
 // LDS of the setup kernel is sized by the limits T of a plan's class (SetupLimits below, chosen by the host from the plan's
 // largest bounding box, bound on M, label and PSF): the common plans -- regions of a few hundred pixels across -- then run four
@@ -888,18 +885,6 @@ __global__ __launch_bounds__(SDSM_WG) void sdsm_k_setup_rows(BatchParams P)
         if (P.prof2) { P.prof2[(size_t)ci * 8 + 7] = rt1 - rt0; P.prof2[(size_t)ci * 8 + 5] = rt2 - rt1; P.prof2[(size_t)ci * 8 + 6] = PROF_NOW() - rt2; P.prof2[(size_t)ci * 8 + 0] = rows_t[0] + rows_t[3]; P.prof2[(size_t)ci * 8 + 1] = rows_t[1]; P.prof2[(size_t)ci * 8 + 2] = rows_t[2]; }   // (the last member's: prologue, its runs, meeting + envelope)
 #endif
     }
-}
-
-extern "C" int sdsm_setup_class(int max_dim, int max_mcap, int max_label, int k)
-{
-    if (max_dim <= SetupLimS::DIM && max_mcap <= SetupLimS::GRID && max_label <= SetupLimS::LABELS && k * k <= SetupLimS::PSFW) return 0;
-    if (max_dim <= SetupLimM::DIM && max_mcap <= SetupLimM::GRID) return 1;
-    return 2;
-}
-
-extern "C" int sdsm_setup_fits_small(int h, int w, int mcap, int max_label, int k)
-{
-    return h <= SetupLimS::DIM && w <= SetupLimS::DIM && mcap <= SetupLimS::GRID && max_label <= SetupLimS::LABELS && k * k <= SetupLimS::PSFW;
 }
 
 extern "C" hipError_t sdsm_launch_setup(const BatchParams &P, hipStream_t stream, const LaunchLists &lists, int cls)

@@ -2197,7 +2197,7 @@ static hipError_t launch_class(const BatchParams &V, const SolveOutputs &out, hi
 // therefore starts when the FIRST kernel of every side queue has its work in resident workgroups: one wavefront on the caller's stream polls the
 // heads of their launch lists (a head at the end of its list: every entry has been claimed by a resident workgroup) and the ticket counters
 // of the workgroup groups (all tickets drawn: every member has started), with a cap -- where fewer than three side streams with a queue of their own were found (choose_sides,
-// sdsm_api.hip) class 1b sits behind the groups on its stream and its list is not claimed before they end: the gate then leaves by its stall rule or its cap.  (Rounds 2-3: a fixed wait of 60 / 120 us, tuned on one
+// sdsm_sides.hip) class 1b sits behind the groups on its stream and its list is not claimed before they end: the gate then leaves by its stall rule or its cap.  (Rounds 2-3: a fixed wait of 60 / 120 us, tuned on one
 // workload mix; the wait is now what the launch needs: tens of microseconds for short lists.)
 __global__ void sdsm_k_gate(const int32_t *cls_count, const int32_t *ticket, int l0, int n0, int l1, int n1, int l2, int n2, long long cap_ticks, long long stall_ticks)
 {
@@ -2273,7 +2273,7 @@ extern "C" hipError_t sdsm_launch_solve(const BatchParams &P, const SolveOutputs
     //   side3: class 1b (two workgroups per compute unit);
     //   caller's stream: class 1 (all candidates in the host's order, largest first; the others leave at once).
     // The driver maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and kernels of streams that share a queue run one after the other: the caller
-    // passes side streams it has probed to run side by side with `stream` and with each other (choose_sides, sdsm_api.hip).  Where it found fewer than three, two of
+    // passes side streams it has probed to run side by side with `stream` and with each other (choose_sides, sdsm_sides.hip).  Where it found fewer than three, two of
     // the sides are the same stream (side3 == side2: class 1b behind the groups / class 2; then side2 == side1 as well): fork, launches in order, join all hold.
     // An error while enqueueing (a launch that fails) must not leave forked work behind on the side streams, which all plans of the device share: the first error
     // is kept, nothing further is launched, but every side stream that was forked is still recorded and joined below.

@@ -385,38 +385,39 @@ class Batch:
 
     def inspect_states(self):
         """The per-candidate state words of the setup kernel (M, status, envelope size, runs) without the crops / rows of :meth:`inspect`."""
-        lay = np.zeros(16, np.int64)
+        lay = self.layout()
+        state = self.ws[lay['state']:lay['state'] + lay['state_size'] * self.n].cpu().numpy().view(_capi.CAND_STATE_DTYPE)
+        return [{f: int(r[f]) for f in ('M', 'status', 'zmax', 'hzmax', 'env_size', 'NR')} for r in state]
+
+    def layout(self):
+        """The values of sdsm_plan_layout by name (_capi.PLAN_LAYOUT_NAMES): byte offsets of workspace blocks, then sizes and counts."""
+        lay = np.zeros(len(_capi.PLAN_LAYOUT_NAMES), np.int64)
         _capi.check(_capi.lib().sdsm_plan_layout(self.plan, lay.ctypes.data_as(C.c_void_p)), 'sdsm_plan_layout')
-        ssz = int(lay[14])
-        state = self.ws[int(lay[1]):int(lay[1]) + ssz * self.n].cpu().numpy().view(np.int32).reshape(self.n, ssz // 4)
-        return [dict(M=int(r[0]), status=int(r[1]), zmax=int(r[5]), hzmax=int(r[14]), env_size=int(r[15]), NR=int(r[18])) for r in state]
+        lay = dict(zip(_capi.PLAN_LAYOUT_NAMES, lay.tolist()))
+        assert lay['cand_size'] == _capi.CAND_DESC_DTYPE.itemsize and lay['state_size'] == _capi.CAND_STATE_DTYPE.itemsize
+        return lay
 
     def inspect(self):
         """Setup-phase outputs for parity tests: per candidate (N, M, status, pixel coordinates, grid points,
         CSR-like G~ rows), reconstructed PER PIXEL from the run-packed crop (a run = the region pixels of one image row inside one
         aligned 4-column cell; an entry of a run holds the weights of its four pixels for one grid point).  Reads the workspace back
         to the host."""
-        lay = np.zeros(16, np.int64)
-        _capi.check(_capi.lib().sdsm_plan_layout(self.plan, lay.ctypes.data_as(C.c_void_p)), 'sdsm_plan_layout')
+        lay = self.layout()
         ws = self.ws.cpu().numpy()
-        zcap, csz, nell, ssz, nruns = int(lay[9]), int(lay[11]), int(lay[13]), int(lay[14]), int(lay[15])
-        cand = ws[lay[0]:lay[0] + csz * self.n].reshape(self.n, csz)
-        i64 = lambda c, o: int(cand[c, o:o + 8].view(np.int64)[0])
-        i32 = lambda c, o: int(cand[c, o:o + 4].view(np.int32)[0])
-        state = ws[lay[1]:lay[1] + ssz * self.n].view(np.int32).reshape(self.n, ssz // 4)   # CandState
-        crop_y = ws[lay[2]:lay[2] + 32 * nruns].view(np.float64).reshape(-1, 4)
-        crop_rc = ws[lay[3]:lay[3] + 4 * nruns].view(np.uint32)
-        run_meta = ws[lay[5]:lay[5] + 4 * nruns].view(np.uint32)
+        zcap, nell, nruns = lay['zcap_run'], lay['total_ell'], lay['total_runs']
+        block = lambda name, dtype, count: ws[lay[name]:lay[name] + np.dtype(dtype).itemsize * count].view(dtype)
+        cand, state = block('cand', _capi.CAND_DESC_DTYPE, self.n), block('state', _capi.CAND_STATE_DTYPE, self.n)
+        crop_y = block('crop_y', np.float64, 4 * nruns).reshape(-1, 4)
+        crop_rc, run_meta = block('crop_rc', np.uint32, nruns), block('run_meta', np.uint32, nruns)
         xi_off = self.xi_offsets()
-        grid = ws[lay[6]:].view(np.uint32)
-        ell_im = ws[lay[7]:lay[7] + 4 * nell].view(np.uint32)
-        ell_w = ws[lay[8]:lay[8] + 16 * nell].view(np.float32).reshape(-1, 4)
+        grid = ws[lay['grid_rc']:].view(np.uint32)
+        ell_im = block('ell_im', np.uint32, nell)
+        ell_w = block('ell_w', np.float32, 4 * nell).reshape(-1, 4)
         out = []
         for i in range(self.n):
             N = int(self.n_pixels[i])
-            M, status, hc, wc, npos = (int(v) for v in state[i, :5])
-            NR = int(state[i, 18])
-            ro, eo = i64(i, 96), i64(i, 8)
+            M, status, hc, wc, npos, NR = (int(state[i][f]) for f in ('M', 'status', 'hc', 'wc', 'npos', 'NR'))
+            ro, eo = int(cand[i]['run_off']), int(cand[i]['ell_off'])
             g = grid[xi_off[i]:xi_off[i] + M]
             have_runs = status == 0 and NR > 0
             meta = run_meta[ro:ro + NR] if have_runs else np.zeros(0, np.uint32)
@@ -444,7 +445,7 @@ class Batch:
             take = lambda a, dt: (np.asarray(a, dt)[o] if len(a) else np.zeros(0, dt))
             idx = np.stack(idxs, axis=1)[:, o] if idxs else np.zeros((zc, 0), np.int64)
             w = np.stack(wts, axis=1)[:, o] if wts else np.zeros((zc, 0), np.float32)
-            out.append(dict(N=N, M=M, status=status, hc=hc, wc=wc, npos=npos, zmax=int(state[i, 5]), env_size=int(state[i, 15]), NR=NR,
+            out.append(dict(N=N, M=M, status=status, hc=hc, wc=wc, npos=npos, zmax=int(state[i]['zmax']), env_size=int(state[i]['env_size']), NR=NR,
                             y=take(ys, np.float64), r=rows[o] if len(rows) else rows, c=cols[o] if len(cols) else cols,
                             grid_r=(g >> 16).astype(np.int64), grid_c=(g & 0xffff).astype(np.int64), nnz=take(nnzs, np.int64), hnz=take(hnzs, np.int64),
                             run_nnz=rnnz.copy(), run_hnz=rhz.copy(), run_pixels=np.array([bin(int(v)).count('1') for v in pm], np.int64),

@@ -44,24 +44,49 @@ def solve_scene_gpu(scene, footprints=None, want_xi=False, mode=None):
     return out
 
 
-def plan_of_squares(sides):
-    """A host-only plan over one candidate per atom, atoms = squares of the given side lengths on a grid (statistics only: area, extents)."""
+def plan_inputs(sides, n_images=1, stray=False, **cfg):
+    """The arguments of sdsm_plan_create(_multi) for one candidate per atom, atoms = squares of the given side lengths on a grid (statistics
+    only: area, extents).  ``n_images`` > 1: the candidates are dealt to the images in turn, and the images differ in shape.  ``stray``:
+    every footprint also names label 0, a label above the image's atoms and an atom of area 0 (the plan skips all three).  ``cfg``: dsm/* keys
+    that replace the defaults of these plans."""
+    n = len(sides)
+    pitch = max(list(sides) + [2])
+    per_row = 60000 // pitch
+    mine = [list(range(im, n, n_images)) for im in range(n_images)]
+    H, W, n_atoms, stats, label = [], [], [], [], {}
+    for im, cands in enumerate(mine):
+        st = np.zeros((len(cands) + 1 + bool(stray), 6), np.int32)
+        for k, ci in enumerate(cands, start=1):
+            sd = sides[ci]
+            r, c = ((k - 1) // per_row) * pitch, ((k - 1) % per_row) * pitch
+            st[k] = (sd * sd, r, r + sd - 1, c, c + sd - 1, 0)
+            label[ci] = k
+        H.append(((max(len(cands), 1) - 1) // per_row + 1) * pitch + 7 * im)
+        W.append(per_row * pitch + 13 * im)
+        n_atoms.append(len(st) - 1)
+        stats.append(st)
+    assert max(H) <= 65535
+    fps = [[label[ci]] + ([0, n_atoms[ci % n_images] + 2, n_atoms[ci % n_images]] if stray else []) for ci in range(n)]
+    return dict(H=np.array(H, np.int32), W=np.array(W, np.int32), n_atoms=np.array(n_atoms, np.int32), stats=stats,
+                cfg=dict(dict(alpha=0.033, smooth_amount=4, smooth_subsample=8, background_margin=0), **cfg), n=n,
+                offsets=np.concatenate([[0], np.cumsum([len(f) for f in fps])]).astype(np.int32), labels=np.array(sum(fps, []), np.int32).reshape(-1),
+                image_of=(np.arange(n) % n_images).astype(np.int32))
+
+
+def plan_of_squares(sides, **kw):
+    """A host-only plan over the squares of :func:`plan_inputs` (sdsm_plan_create; with ``n_images`` > 1 sdsm_plan_create_multi)."""
     import ctypes as C
     from . import _capi
     lib = _capi.lib()
-    n = len(sides)
-    pitch = max(sides)
-    per_row = 60000 // pitch
-    stats = np.zeros((n + 1, 6), np.int32)
-    for k, sd in enumerate(sides, start=1):
-        r, c = ((k - 1) // per_row) * pitch, ((k - 1) % per_row) * pitch
-        stats[k] = (sd * sd, r, r + sd - 1, c, c + sd - 1, 0)
-    H, W = ((n - 1) // per_row + 1) * pitch, per_row * pitch
-    assert H <= 65535
-    cfg = _capi.make_config(dict(alpha=0.033, smooth_amount=4, smooth_subsample=8, background_margin=0))
-    offs = np.arange(n + 1, dtype=np.int32)
-    labels = np.arange(1, n + 1, dtype=np.int32)
-    plan = lib.sdsm_plan_create(H, W, n, stats.ctypes.data_as(C.c_void_p), C.byref(cfg), n, offs.ctypes.data_as(C.c_void_p), labels.ctypes.data_as(C.c_void_p))
+    a = plan_inputs(sides, **kw)
+    cfg = _capi.make_config(a['cfg'])
+    ptr = lambda v: v.ctypes.data_as(C.c_void_p)
+    if len(a['stats']) == 1:
+        plan = lib.sdsm_plan_create(int(a['H'][0]), int(a['W'][0]), int(a['n_atoms'][0]), ptr(a['stats'][0]), C.byref(cfg), a['n'], ptr(a['offsets']), ptr(a['labels']))
+    else:
+        tables = (C.c_void_p * len(a['stats']))(*[st.ctypes.data for st in a['stats']])
+        plan = lib.sdsm_plan_create_multi(len(a['stats']), ptr(a['H']), ptr(a['W']), ptr(a['n_atoms']), C.cast(tables, C.c_void_p), C.byref(cfg), a['n'],
+                                          ptr(a['offsets']), ptr(a['labels']), ptr(a['image_of']))
     assert plan, lib.sdsm_last_error()
     return plan
 
@@ -75,6 +100,32 @@ PLAN_LIST_CASES = {
 }
 
 
+# the plans whose workspace layout, kernel arguments and candidate descriptors tests/golden/plan_layout.json records:
+# name -> (sides, scheduling modes, further arguments of plan_inputs).  What each one is there for: tests/test_plan_layout_cpu.py.
+PLAN_LAYOUT_CASES = dict({name: (sides, modes, {}) for name, (sides, modes) in PLAN_LIST_CASES.items()},
+                         two_images=([30] * 40 + [100] * 2, (0,), dict(n_images=2)),
+                         no_deform=([30] * 40 + [100] * 2, (0,), dict(smooth_amount=float('inf'))),
+                         dense_grid=([30] * 10 + [100] * 2, (0,), dict(smooth_amount=8, smooth_subsample=4)),
+                         stray_labels=([30] * 40 + [100] * 2, (0,), dict(stray=True)),
+                         empty=([], (0,), {}))
+
+
+def plan_cases_text():
+    """PLAN_LAYOUT_CASES as the stand-alone check of the plan unit reads them (tests/host/plan_check.cpp): white-space separated numbers, per case
+    its name, modes, images (H, W, atoms, statistics), configuration, footprints and image indices -- the very arrays :func:`plan_of_squares` passes."""
+    from . import _capi
+    words = [len(PLAN_LAYOUT_CASES)]
+    for name, (sides, modes, kw) in PLAN_LAYOUT_CASES.items():
+        a = plan_inputs(sides, **kw)
+        cfg = _capi.make_config(a['cfg'])
+        words += [name, len(modes), *modes, len(a['stats']), *a['H'], *a['W'], *a['n_atoms']]
+        for st in a['stats']:
+            words += st.ravel().tolist()
+        words += [repr(float(getattr(cfg, f))) for f in ('scale', 'epsilon', 'alpha', 'smooth_amount', 'gaussian_shape_multiplier', 'background_margin')]
+        words += [cfg.smooth_subsample, cfg.init_elliptical, cfg.max_iters, cfg.flags, a['n'], *a['offsets'], *a['labels'], *a['image_of']]
+    return ' '.join(str(w) for w in words) + '\n'
+
+
 def plan_lists(plan, mode):
     """The launch lists of a host-only plan in the given scheduling mode (sdsm_plan_lists): spans as 7 x (first, count), and `order`."""
     import ctypes as C
@@ -86,6 +137,37 @@ def plan_lists(plan, mode):
     order = np.zeros(int(spans[:, 1].sum()), np.int32)
     _capi.check(lib.sdsm_plan_lists(plan, spans.ctypes.data_as(C.c_void_p), order.ctypes.data_as(C.c_void_p)), 'sdsm_plan_lists')
     return spans, order
+
+
+def plan_image(plan, n):
+    """sdsm_plan_image of a plan of n candidates in its current mode: the kernel arguments over a null workspace (bytes), the descriptors
+    (_capi.CAND_DESC_DTYPE)."""
+    import ctypes as C
+    from . import _capi
+    params, cand = np.zeros(_capi.PLAN_PARAMS_BYTES, np.uint8), np.zeros(n, _capi.CAND_DESC_DTYPE)
+    _capi.check(_capi.lib().sdsm_plan_image(plan, params.ctypes.data_as(C.c_void_p), params.nbytes, cand.ctypes.data_as(C.c_void_p), cand.nbytes), 'sdsm_plan_image')
+    return params, cand
+
+
+def plan_layout_record(params, cand, sizes, layout):
+    """What tests/golden/plan_layout.json keeps of a plan in one mode: the SHA-256 of the parameter blob, one per CandDesc field (the
+    column's bytes, so that a difference names the field), the four size queries and the 16 values of sdsm_plan_layout."""
+    import hashlib
+    sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+    return dict(params=sha(params), cand={f: sha(cand[f]) for f in cand.dtype.names},
+                workspace_bytes=int(sizes[0]), mask_bytes=int(sizes[1]), total_pixels=int(sizes[2]), xi_count=int(sizes[3]), layout=[int(v) for v in layout])
+
+
+def plan_layout_of(plan, n):
+    """:func:`plan_layout_record` of a host-only plan in its current mode, with the arrays it was made of: (record, params, cand)."""
+    import ctypes as C
+    from . import _capi
+    lib = _capi.lib()
+    params, cand = plan_image(plan, n)
+    lay = np.zeros(16, np.int64)
+    _capi.check(lib.sdsm_plan_layout(plan, lay.ctypes.data_as(C.c_void_p)), 'sdsm_plan_layout')
+    sizes = (lib.sdsm_plan_workspace_bytes(plan), lib.sdsm_plan_mask_bytes(plan), lib.sdsm_plan_total_pixels(plan), lib.sdsm_plan_xi_count(plan))
+    return plan_layout_record(params, cand, sizes, lay), params, cand
 
 
 def dice(a_off, a_frag, b_off, b_frag, shape):

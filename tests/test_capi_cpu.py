@@ -75,7 +75,7 @@ def _schedule(plan, n, mode):
 
 
 def test_scheduling_policy_of_a_plan_is_host_logic():
-    """Workgroup groups and the workgroups that build the rows of G~ (sdsm_api.hip, layout_plan), without a GPU: groups in throughput mode
+    """Workgroup groups and the workgroups that build the rows of G~ (sdsm_plan.hip, layout_plan), without a GPU: groups in throughput mode
     only for regions that are long next to the whole plan, the largest first within a budget of 256 members; latency mode groups the
     mid-size regions too; mode 2 none; rows by several workgroups only while regions above 4096 pixels are few."""
     from superdsm_amd import _capi, testing

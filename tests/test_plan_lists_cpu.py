@@ -1,4 +1,4 @@
-"""The launch lists of a plan (sdsm_api.hip, layout_plan; read through sdsm_plan_lists) are host logic: pinned entry by entry by
+"""The launch lists of a plan (sdsm_plan.hip, layout_plan; read through sdsm_plan_lists) are host logic: pinned entry by entry by
 tests/golden/plan_lists.json for three plans, and checked for the structure every launch relies on.  No GPU."""
 import ctypes as C
 import json

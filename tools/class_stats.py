@@ -22,11 +22,9 @@ _capi.lib().sdsm_enable_kernel_timing(1)
 batch.launch()
 print('solve kernels of the launch: %.2f ms, setup %.2f ms' % (_capi.lib().sdsm_last_solve_kernel_ms(), _capi.lib().sdsm_last_setup_kernel_ms()))
 recs = batch.records()
-lay = np.zeros(16, np.int64)
-_capi.check(_capi.lib().sdsm_plan_layout(batch.plan, lay.ctypes.data_as(C.c_void_p)), 'layout')
-ws = batch.ws.cpu().numpy()
-state = ws[lay[1]:lay[1] + int(lay[14]) * batch.n].view(np.int32).reshape(batch.n, -1)
-env = state[:, 15].astype(np.int64); n = recs['n_deform'] + 6; N = recs['n_pixels']
+lay = batch.layout()
+state = batch.ws[lay['state']:lay['state'] + lay['state_size'] * batch.n].cpu().numpy().view(_capi.CAND_STATE_DTYPE)
+env = state['env_size'].astype(np.int64); n = recs['n_deform'] + 6; N = recs['n_pixels']
 p = prof.cpu().numpy()[:len(fps) * 16].reshape(-1, 16).astype(float)
 tot = p[:, 5] / 2.4e6
 k1 = (n <= 128) & (env <= 2560); k1b = ~k1 & (n <= 256) & (env <= 7168); k2 = ~k1 & ~k1b & (env <= 11000); k2b = ~k1 & ~k1b & ~k2 & (n <= 512) & (env <= 15170); k3 = ~k1 & ~k1b & ~k2 & ~k2b
@@ -67,7 +65,7 @@ for k in np.argsort(-np.where(ok, en, -1))[:15]:
 gcls = np.full(batch.n, -1, np.int32)
 if hasattr(_capi.lib(), 'sdsm_plan_solve_classes'):
     q = lambda a: np.ascontiguousarray(a, np.int32)
-    s_status, s_M, s_env = q(state[:, 1]), q(state[:, 0]), q(state[:, 15])
+    s_status, s_M, s_env = q(state['status']), q(state['M']), q(state['env_size'])
     _capi.check(_capi.lib().sdsm_plan_solve_classes(batch.plan, s_status.ctypes.data_as(C.c_void_p), s_M.ctypes.data_as(C.c_void_p), s_env.ctypes.data_as(C.c_void_p), gcls.ctypes.data_as(C.c_void_p)), 'classes')
 print('groups (class, members, N, M, env, start, end, duration ms), largest first; class -1: a library without sdsm_plan_solve_classes')
 for k in np.argsort(-N):
