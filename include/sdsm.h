@@ -662,6 +662,32 @@ int sdsm_plan_set_start(const sdsm_plan *plan, const double *d_x0);
 int64_t sdsm_plan_eval_param_count(const sdsm_plan *plan);
 int64_t sdsm_plan_eval_out_count(const sdsm_plan *plan);
 int sdsm_batch_eval(const sdsm_plan *plan, void *d_workspace, size_t workspace_bytes, const double *d_params, double *d_out, void *stream);
+/* Parity / debug: ONE damped Newton step as the solver takes it, piece by piece, at caller-given parameters (no reference counterpart:
+ * the reference hands its energy to cvxopt; DESIGN.md "Solver").  Like sdsm_batch_eval it works on the workspace of a previous
+ * sdsm_batch_launch of the same plan and takes d_params in that call's layout; d_dir (same layout, NULL = none) is a search direction.
+ * The solver's own functions run in the LDS layout, thread count and Hessian placement of ONE solve class, `layout`:
+ *   SDSM_STEP_LAYOUT_1 class 1, throughput mode (192 threads)   _1_LATENCY class 1, 256 threads   _1B   _2   _2B
+ *   _3 (Hessian in global memory: only candidates the plan reserved a slot for)   _LIGHT a light group member's layout, alone.
+ * Everything is returned in the candidate's LOCAL frame (coordinates centred on its box and scaled by its half extents -- the frame the
+ * solve kernels work in; theta_local is linear in theta), unknowns in the order theta[6], xi[M], and nothing is computed on top of what
+ * the solver's functions return.  Candidate i's block starts at d_out + i * stride doubles (SDSM_STEP_*), n = 6 + M:
+ *   [SDSM_STEP_RC]        return code of the factorisation (0 ok, 1 not positive definite, 2 non-finite); -1: the candidate has no solve,
+ *                         does not fit the layout, or its block does not fit `stride` -- the rest of its block is then NaN
+ *   [SDSM_STEP_PSI_VALUE] psi by the value-only evaluator   [SDSM_STEP_PSI] psi by the full evaluation (regulariser curvature blended by
+ *                         reg_mu in [0, 1], sums scaled by the bound psi_value)   [SDSM_STEP_LAM2] -g.d of the step (NaN unless RC = 0)
+ *   [SDSM_STEP_N] n   [SDSM_STEP_ENV] E, the doubles of the Hessian envelope (21 for M = 0: the packed lower triangle of the 6 x 6 matrix)
+ *   [SDSM_STEP_LINE .. + 3] psi(x + t d) for t = t0, t0 / 2, t0 / 4, t0 / 8 by the line-search sweep, along d_dir if given, else along
+ *                         the Newton direction (NaN if there is neither)
+ *   [SDSM_STEP_HEAD ..]   gradient[n]; Newton direction[n], the solution of (H + tau diag H) d = -g (NaN unless RC = 0); envelope[E] as the
+ *                         full evaluation left it, BEFORE the factorisation; then, as int32: rb[n], fst[n], rend[ceil(M / 4)] -- unknowns in
+ *                         the envelope's order (xi[M], then theta[6]), row a holds columns fst[a] .. a at envelope[rb[a] + column];
+ *                         rend[p]: the last xi row that reaches the columns of panel p.
+ * A block needs SDSM_STEP_HEAD + 2 n + E + (2 n + ceil(M / 4) + 1) / 2 doubles.  d_out (n_candidates * stride doubles) is filled with
+ * NaN first.  Asynchronous on `stream`. */
+enum { SDSM_STEP_LAYOUT_1 = 0, SDSM_STEP_LAYOUT_1_LATENCY, SDSM_STEP_LAYOUT_1B, SDSM_STEP_LAYOUT_2, SDSM_STEP_LAYOUT_2B, SDSM_STEP_LAYOUT_3, SDSM_STEP_LAYOUT_LIGHT, SDSM_STEP_LAYOUT_N };
+enum { SDSM_STEP_RC = 0, SDSM_STEP_PSI_VALUE = 1, SDSM_STEP_PSI = 2, SDSM_STEP_LAM2 = 3, SDSM_STEP_N = 4, SDSM_STEP_ENV = 5, SDSM_STEP_LINE = 6, SDSM_STEP_HEAD = 10 };
+int sdsm_batch_eval_step(const sdsm_plan *plan, void *d_workspace, size_t workspace_bytes, int layout, double reg_mu, double tau, double t0,
+                         const double *d_params, const double *d_dir, double *d_out, int64_t stride, void *stream);
 /* Parity / debug: the scalar arithmetic every pass over the pixels goes through, element by element -- the device functions of the
  * solve kernels as compiled (no host copy), with the table of the logarithm where those kernels keep it.  d_y, d_S, d_x: n doubles each
  * (device memory), 0 <= n <= SDSM_PROBE_LOSS_MAX; d_out: SDSM_PROBE_N arrays of n doubles, array k at d_out + k * n.  With

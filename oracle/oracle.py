@@ -80,6 +80,8 @@ def lib():
         L.orc_energy_smat.restype = vp
         L.orc_energy_eval.argtypes = [vp, vp, vp, vp]
         L.orc_energy_eval.restype = f64
+        L.orc_energy_eval_thr.argtypes = [vp, vp, vp, vp, f64, f64]
+        L.orc_energy_eval_thr.restype = f64
         L.orc_newton.argtypes = [vp, f64, vp, vp, C.POINTER(SolveInfo)]
         L.orc_moment_init.argtypes = [vp, vp, i32, i32, vp]
         L.orc_cvxprog.argtypes = [vp, vp, i32, i32, C.POINTER(DsmCfg), vp, C.POINTER(CvxprogInfo)]
@@ -211,6 +213,16 @@ class Energy:
         g = np.zeros(self.n)
         H = np.zeros((self.n, self.n))
         v = lib().orc_energy_eval(self.h, _p(p), _p(g), _p(H))
+        return v, g, H
+
+    def eval_thr(self, p, hess_thr=0.1, reg_mu=0.0):
+        """psi, gradient and the solver's approximate Hessian (orc_energy_eval_thr): entries of a G~ row below ``hess_thr`` times the
+        row's maximum (compared in float32) are left out of the Hessian, the regulariser's curvature is blended by ``reg_mu``."""
+        p = _f64(p)
+        assert p.size == self.n
+        g = np.zeros(self.n)
+        H = np.zeros((self.n, self.n))
+        v = lib().orc_energy_eval_thr(self.h, _p(p), _p(g), _p(H), float(hess_thr), float(reg_mu))
         return v, g, H
 
     def newton(self, x0, scale):

@@ -211,6 +211,7 @@ SYMBOLS = {
     'sdsm_plan_eval_param_count': (_i64, [_vp]),
     'sdsm_plan_eval_out_count': (_i64, [_vp]),
     'sdsm_batch_eval': (_i32, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    'sdsm_batch_eval_step': (_i32, [_vp, _vp, _sz, _i32, _f64, _f64, _f64, _vp, _vp, _vp, _i64, _vp]),
     'sdsm_probe_loss_arithmetic': (_i32, [_i64, _vp, _vp, _vp, _vp, _vp]),
     'sdsm_batch_deform_counts': (_i32, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     'sdsm_plan_set_start': (_i32, [_vp, _vp]),

@@ -208,6 +208,26 @@ extern "C" int sdsm_batch_eval(const sdsm_plan *p, void *d_ws, size_t ws_bytes, 
     return SDSM_OK;
 }
 
+// ---- one Newton step, piece by piece, in the layout of one solve class (parity tests) -----------------------
+extern "C" hipError_t sdsm_launch_step_probe(const BatchParams &P, int layout, const double *params, const double *dir, double reg_mu, double tau, double t0, double *out, long long stride, hipStream_t stream);
+
+extern "C" int sdsm_batch_eval_step(const sdsm_plan *p, void *d_ws, size_t ws_bytes, int layout, double reg_mu, double tau, double t0,
+                                    const double *d_params, const double *d_dir, double *d_out, int64_t stride, void *stream)
+{
+    if (!p || !d_ws || !d_params || !d_out) return fail(SDSM_ERR_ARGUMENT, "sdsm_batch_eval_step: null argument");
+    if (layout < 0 || layout >= SDSM_STEP_LAYOUT_N) return fail(SDSM_ERR_ARGUMENT, "sdsm_batch_eval_step: unknown layout");
+    if (!(reg_mu >= 0 && reg_mu <= 1) || !(tau >= 0) || !(t0 > 0) || stride < SDSM_STEP_HEAD) return fail(SDSM_ERR_ARGUMENT, "sdsm_batch_eval_step: reg_mu in [0, 1], tau >= 0, t0 > 0 and stride >= SDSM_STEP_HEAD are required");
+    if (ws_bytes < p->total) return fail(SDSM_ERR_WORKSPACE, "sdsm_batch_eval_step: workspace too small");
+    if (p->n == 0) return SDSM_OK;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e;
+    if (p->uploaded_gen != p->layout_gen || p->uploaded_ws != d_ws) return fail(SDSM_ERR_ARGUMENT, "sdsm_batch_eval_step: needs the workspace of a previous sdsm_batch_launch of this plan");
+    if ((e = hipMemsetAsync(d_out, 0xff, sizeof(double) * (size_t)p->n * (size_t)stride, s)) != hipSuccess) return hipfail(e, "hipMemsetAsync");
+    const BatchParams P = make_params(p, d_ws);
+    if ((e = sdsm_launch_step_probe(P, layout, d_params, d_dir, reg_mu, tau, t0, d_out, (long long)stride, s)) != hipSuccess) return hipfail(e, "launch step probe");
+    return SDSM_OK;
+}
+
 // ---- the scalar loss arithmetic of the solve kernels, element by element (parity tests) ---------------------
 extern "C" hipError_t sdsm_launch_probe_loss(long long n, const double *y, const double *S, const double *x, double *out, hipStream_t stream);
 

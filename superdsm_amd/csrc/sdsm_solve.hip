@@ -637,14 +637,17 @@ __device__ __forceinline__ void eval_line(const Cand &c, int M, double t0, doubl
         load_run(c, pl, active, rp);
         double S0[SDSM_RUN], Sd[SDSM_RUN];
         {
+            // The multiply-adds are written out, in the form the compiler gives poly_surface in eval_value: v^2 x1 + v b + a leaves it the choice of the
+            // product it fuses, per call site, and it chose the other one here -- S(x) of the sweep then differed from eval_value's in the last bit
+            // of some pixels, and a sweep along d = 0 from eval_value's psi by one unit in the last place (tests/test_newton_step_gpu.py).
             const double uu = rp.u * rp.u, u2 = 2 * rp.u;
-            const double a0 = uu * xd[0] + u2 * xd[6] + xd[10], a1 = uu * xd[1] + u2 * xd[7] + xd[11];
-            const double b0 = u2 * xd[4] + 2 * xd[8], b1 = u2 * xd[5] + 2 * xd[9];
+            const double a0 = fma(uu, xd[0], u2 * xd[6]) + xd[10], a1 = fma(uu, xd[1], u2 * xd[7]) + xd[11];
+            const double b0 = fma(u2, xd[4], 2 * xd[8]), b1 = fma(u2, xd[5], 2 * xd[9]);
 #pragma unroll
             for (int k = 0; k < SDSM_RUN; k++) {
                 const double vv = rp.v[k] * rp.v[k];
-                S0[k] = vv * xd[2] + rp.v[k] * b0 + a0;
-                Sd[k] = vv * xd[3] + rp.v[k] * b1 + a1;
+                S0[k] = fma(vv, xd[2], rp.v[k] * b0) + a0;
+                Sd[k] = fma(vv, xd[3], rp.v[k] * b1) + a1;
             }
         }
         if (M > 0) smooth_add2(c, xd, pl, chunk_entries(c, __builtin_amdgcn_readfirstlane(p)), S0, Sd);
@@ -2065,6 +2068,122 @@ __global__ __launch_bounds__(WGSIZE) void sdsm_k_eval(BatchParams P, int nprev, 
     for (int j = tid; j < M; j += L::WGS) og[6 + j] = g[6 + j];
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// One Newton step for parity tests (sdsm_batch_eval_step): what the solver sees at caller-given parameters, in the candidate's LOCAL
+// frame and with no arithmetic of its own -- the functions of newton<> called as they stand, in the LDS layout of one solve class:
+//   eval_value, eval_full(reg_mu, bound = that value, a new point)   psi, the gradient and the envelope of the approximate Hessian as
+//                                                                    stored (copied out BEFORE the factorisation destroys it), with rb, fst, rend
+//   factor_solve(tau)                                                its return code, lam2 and the direction at L::D
+//   eval_line(t0)                                                    along the caller's direction if there is one (written to L::D only after
+//                                                                    the Newton direction has been copied out), else along the Newton direction
+// Envelope set-up (rb, fst, rend) as in solve_candidate: factor_solve reads rend for every panel.  Never same_point (no kept sums here).
+// A candidate the layout does not hold (or whose block does not fit `stride`) keeps the host's NaN fill and gets the return code -1.
+// Block of candidate ci at out + ci * stride (SDSM_STEP_* of include/sdsm.h): 10 head words, gradient[n], direction[n] (theta first, then
+// xi), envelope[E], then rb[n], fst[n], rend[ceil(M / SDSM_PANEL)] as int32.
+// ---------------------------------------------------------------------------------------------------------
+template <int NMAX, int EMAX, bool GLOBALH, int WGSIZE>
+__global__ __launch_bounds__(WGSIZE) void sdsm_k_step_probe(BatchParams P, const double *params, const double *dir, double reg_mu, double tau, double t0, double *out, long long stride)
+{
+    using L = Lay<NMAX, EMAX, GLOBALH, WGSIZE>;
+    const int tid = threadIdx.x;
+    const int ci = blockIdx.x;
+    load_log_table(tid);
+    const CandDesc cd = uniform_desc(P.cand[ci]);
+    const CandState st = uniform_state(P.state[ci]);
+    double *ob = out + (size_t)ci * (size_t)stride;
+    if (stride >= 1 && tid == 0) ob[SDSM_STEP_RC] = -1.0;
+    if (st.status != ST_OK || st.M < 0 || 6 + st.M > SDSM_MAX_N_GLOBAL) return;
+    const int M = st.M, n = 6 + M;
+    const int efull = M > 0 ? st.env_size : 21;
+    const int npan = (M + SDSM_PANEL - 1) / SDSM_PANEL;
+    if (!(n <= NMAX && efull <= EMAX)) return;
+    if (GLOBALH && cd.hglob_off < 0) return;
+    if ((long long)SDSM_STEP_HEAD + 2ll * n + efull + (2ll * n + npan + 1) / 2 > stride) return;
+    Cand c;
+    c.N = cd.N; c.NR = st.NR; c.hzmax = M > 0 ? st.hzmax : 0; c.env_size = efull;
+    c.p_lo = 0; c.p_hi = st.NR; c.wg = 0; c.wG = 1; c.wpool = nullptr; c.wtimeout = 0;
+    c.crop_y2 = (g_cf64x2_p)(P.crop_y + cd.run_off * SDSM_RUN); c.crop_rc = (g_cu32_p)(P.crop_rc + cd.run_off); c.meta = (g_cu32_p)(P.run_meta + cd.run_off);
+    c.aux = (g_cu32_p)(P.run_aux + cd.run_off);
+    c.ell_im = (g_cu32_p)(P.ell_im + cd.ell_off); c.ell_w4 = (g_cf32x4_p)(reinterpret_cast<const f32x4 *>(P.ell_w) + cd.ell_off);
+    c.hglob = (GLOBALH && cd.hglob_off >= 0) ? P.hglob + cd.hglob_off : nullptr;
+    c.scale = P.scale / cd.N; c.epsilon = P.epsilon; c.alpha = P.alpha; c.reg0 = P.reg_unit * M;
+    c.yexp = st.yexp; c.boost = 0;
+    const double half_r = 0.5 * (cd.h - 1), half_c = 0.5 * (cd.w - 1);
+    c.rmid = cd.r0 + half_r; c.cmid = cd.c0 + half_c;
+    c.inv_hr = 1.0 / (half_r < 1 ? 1 : half_r); c.inv_hc = 1.0 / (half_c < 1 ? 1 : half_c);
+    const int imH = P.img[cd.image].H, imW = P.img[cd.image].W;
+    const double z0 = imH > 1 ? imH - 1.0 : 1.0, z1 = imW > 1 ? imW - 1.0 : 1.0;
+    const double P0 = 1.0 / (c.inv_hr * z0), P1 = 1.0 / (c.inv_hc * z1), O0 = c.rmid / z0, O1 = c.cmid / z1;
+    c = uniform_cand(c);
+    double *x = SD + L::X, *g = SD + L::G, *d = SD + L::D, *Hp = hess_ptr<L>(c);
+    const double *pin = params + (size_t)6 * ci + cd.xi_off;
+    if (tid == 0) {
+        *WIDE_PHASE = 0; *WIDE_OPS = 0;
+        KEPT->diag = 0; KEPT->counters = nullptr;              // (never read: no evaluation here is a second one at its point)
+        double thg[6], thl[6];
+        for (int i = 0; i < 6; i++) thg[i] = pin[i];
+        reparam(thg, P0, P1, O0, O1, thl);
+        for (int i = 0; i < 6; i++) x[i] = thl[i];
+    }
+    for (int j = tid; j < M; j += L::WGS) x[6 + j] = pin[6 + j];
+    int *rbp = RBP, *fstp = FSTP, *rendp = RENDP;
+    if (M > 0) {                                                 // envelope of the Hessian: solve_candidate's set-up, panel by panel
+        const int exi = efull - 6 * M - 21;
+        for (int a = tid; a < M; a += L::WGS) { rbp[a] = P.env_rb[cd.xi_off + a]; fstp[a] = P.env_fst[cd.xi_off + a]; }
+        if (tid < 6) { rbp[M + tid] = exi + tid * M + tid * (tid + 1) / 2; fstp[M + tid] = 0; }
+        __syncthreads();
+        for (int pnl = tid; SDSM_PANEL * pnl < M; pnl += L::WGS) {
+            int lo = SDSM_PANEL * pnl, hi = M - 1;
+            while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (fstp[mid] <= SDSM_PANEL * pnl) lo = mid; else hi = mid - 1; }
+            rendp[pnl] = lo;
+        }
+    }
+    __syncthreads();
+#ifdef SDSM_PROFILE
+    long long prof_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+    const double psi_value = eval_value<L>(c, L::X, M);
+    const double psi_full = eval_full<L>(c, M, reg_mu, psi_value, false PROF_ARG);
+    __syncthreads();
+    double *og = ob + SDSM_STEP_HEAD, *od = og + n, *oe = od + n;
+    int *oi = reinterpret_cast<int *>(oe + efull);
+    for (int i = tid; i < n; i += L::WGS) og[i] = g[i];
+    for (int e = tid; e < efull; e += L::WGS) oe[e] = Hp[e];
+    if (M > 0) {
+        for (int i = tid; i < n; i += L::WGS) { oi[i] = rbp[i]; oi[n + i] = fstp[i]; }
+        for (int pnl = tid; pnl < npan; pnl += L::WGS) oi[2 * n + pnl] = rendp[pnl];
+    } else {
+        for (int i = tid; i < 6; i += L::WGS) { oi[i] = i * (i + 1) / 2; oi[n + i] = 0; }
+    }
+    __syncthreads();                                             // the envelope is out: the factorisation may destroy it
+    double lam2 = NAN;
+    const int rc = factor_solve<L>(c, M, tau, &lam2 PROF_ARG);   // (uniform: every thread gets the same code)
+    if (rc == 0) for (int i = tid; i < n; i += L::WGS) od[i] = d[i];
+    __syncthreads();                                             // the Newton direction is out: L::D may take the caller's
+    if (dir) {
+        const double *din = dir + (size_t)6 * ci + cd.xi_off;
+        if (tid == 0) {
+            double thg[6], thl[6];
+            for (int i = 0; i < 6; i++) thg[i] = din[i];
+            reparam(thg, P0, P1, O0, O1, thl);                  // (linear in theta: a direction maps as a point does)
+            for (int i = 0; i < 6; i++) d[i] = thl[i];
+        }
+        for (int j = tid; j < M; j += L::WGS) d[6 + j] = din[6 + j];
+    }
+    __syncthreads();
+    double line[LS_K];
+#pragma unroll
+    for (int k = 0; k < LS_K; k++) line[k] = NAN;
+    if (dir != nullptr || rc == 0) eval_line<L>(c, M, t0, line);  // (uniform)
+    if (tid == 0) {
+        ob[SDSM_STEP_PSI_VALUE] = psi_value; ob[SDSM_STEP_PSI] = psi_full; ob[SDSM_STEP_LAM2] = rc == 0 ? lam2 : NAN;
+        ob[SDSM_STEP_N] = (double)n; ob[SDSM_STEP_ENV] = (double)efull;
+#pragma unroll
+        for (int k = 0; k < LS_K; k++) ob[SDSM_STEP_LINE + k] = line[k];
+        ob[SDSM_STEP_RC] = (double)rc;
+    }
+}
+
 // ---- the solve classes, host side ------------------------------------------------------------------
 // class 1:  6 + M <= 128,  envelope <= 2560 doubles, <= P.k1_pixmax pixels   256 threads, LDS ~ 30 KB  (three workgroups / CU)
 // class 1b: 6 + M <= 256,  envelope <= 7168 doubles, <= P.k1_pixmax pixels   256 threads, LDS ~ 79 KB  (two workgroups / CU; 512-thread kernels need
@@ -2130,6 +2249,34 @@ extern "C" hipError_t sdsm_launch_eval(const BatchParams &P, const double *param
     if ((e = launch_eval_layout<C2>(P, C1::NMAX, C1::EMAX, params, out, stream)) != hipSuccess) return e;
     if ((e = launch_eval_layout<C3>(P, C2::NMAX, C2::EMAX, params, out, stream)) != hipSuccess) return e;
     return hipGetLastError();
+}
+
+// The step probe in one layout: class C's limits, LDS layout and thread count (one workgroup per candidate, no group).
+template <class C>
+static hipError_t launch_step_layout(const BatchParams &P, const double *params, const double *dir, double reg_mu, double tau, double t0, double *out, long long stride, hipStream_t stream)
+{
+    auto kern = sdsm_k_step_probe<C::NMAX, C::EMAX, C::GLOBALH, C::THREADS>;
+    constexpr int lds = C::L::TOTAL_BYTES;
+    static_assert(lds <= 160 * 1024 - 512, "LDS budget");
+    const hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(P.n), dim3(C::THREADS), lds, stream, P, params, dir, reg_mu, tau, t0, out, stride);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t sdsm_launch_step_probe(const BatchParams &P, int layout, const double *params, const double *dir, double reg_mu, double tau, double t0, double *out, long long stride, hipStream_t stream)
+{
+    if (P.n <= 0) return hipSuccess;
+    switch (layout) {
+    case SDSM_STEP_LAYOUT_1:         return launch_step_layout<SolveClass<SDSM_CLS_1>>(P, params, dir, reg_mu, tau, t0, out, stride, stream);
+    case SDSM_STEP_LAYOUT_1_LATENCY: return launch_step_layout<SolveClass<SDSM_CLS_1, true>>(P, params, dir, reg_mu, tau, t0, out, stride, stream);
+    case SDSM_STEP_LAYOUT_1B:        return launch_step_layout<SolveClass<SDSM_CLS_1B>>(P, params, dir, reg_mu, tau, t0, out, stride, stream);
+    case SDSM_STEP_LAYOUT_2:         return launch_step_layout<SolveClass<SDSM_CLS_2>>(P, params, dir, reg_mu, tau, t0, out, stride, stream);
+    case SDSM_STEP_LAYOUT_2B:        return launch_step_layout<SolveClass<SDSM_CLS_2B>>(P, params, dir, reg_mu, tau, t0, out, stride, stream);
+    case SDSM_STEP_LAYOUT_3:         return launch_step_layout<SolveClass<SDSM_CLS_3>>(P, params, dir, reg_mu, tau, t0, out, stride, stream);
+    case SDSM_STEP_LAYOUT_LIGHT:     return launch_step_layout<SolveClass<SDSM_CLS_WIDE_LIGHT>>(P, params, dir, reg_mu, tau, t0, out, stride, stream);   // (the member's layout, alone: wG = 1)
+    default:                         return hipErrorInvalidValue;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------

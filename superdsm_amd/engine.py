@@ -383,6 +383,51 @@ class Batch:
             res.append(dict(psi=float(out[2 * i]), psi_value=float(out[2 * i + 1]), grad=out[g0:g0 + m].copy(), hess_theta=H))
         return res
 
+    STEP_LAYOUTS = ('class 1', 'class 1 latency', 'class 1b', 'class 2', 'class 2b', 'class 3', 'light')     # SDSM_STEP_LAYOUT_* of include/sdsm.h, in order
+
+    def evaluate_step(self, layout, params, direction=None, reg_mu=0.0, tau=0.0, t0=1.0, dense=True):
+        """One Newton step of the solver, piece by piece, in the layout of one solve class (sdsm_batch_eval_step; ``layout``: a name of
+        ``STEP_LAYOUTS``): ``params[i]`` as for :meth:`evaluate`, ``direction`` (same shapes, or None) a search direction for the
+        line-search sweep.  Needs a previous :meth:`launch`.  Returns a list of dicts, everything in the candidate's local frame, unknowns
+        theta (6) then xi (M): ``rc`` (0 ok, 1 not positive definite, 2 non-finite, -1: not in this layout -- then nothing else),
+        ``psi_value``, ``psi``, ``lam2``, ``line`` (4), ``grad``, ``dir`` (the Newton direction), ``env`` (the envelope as stored before
+        the factorisation), ``rb``, ``fst``, ``rend`` (int32; envelope order: xi, then theta) and, expanded from those on the host,
+        ``hess`` (dense, symmetric, theta first) with ``stored`` (which entries the envelope holds; :func:`expand_envelope`, None
+        unless ``dense``)."""
+        L = _capi.lib()
+        xo = self.xi_offsets()
+        states = self.inspect_states()
+        need = [10 + 2 * (6 + s['M']) + (s['env_size'] if s['M'] > 0 else 21) + (2 * (6 + s['M']) + (s['M'] + 3) // 4 + 1) // 2 if s['status'] == 0 and s['M'] >= 0 else 10 for s in states]
+        stride = max(need)
+
+        def pack(vectors):
+            buf = np.zeros(L.sdsm_plan_eval_param_count(self.plan))
+            for i, p in enumerate(vectors):
+                p = np.asarray(p, np.float64)
+                buf[6 * i + xo[i]:6 * i + xo[i] + p.size] = p
+            return torch.from_numpy(buf).to(self.image.device)
+        d_par, d_dir = pack(params), (pack(direction) if direction is not None else None)
+        d_out = torch.empty(self.n * stride, dtype=torch.float64, device=self.image.device)
+        with torch.cuda.device(self.image.device):
+            _capi.check(L.sdsm_batch_eval_step(self.plan, _ptr(self.ws), self.ws_bytes, self.STEP_LAYOUTS.index(layout), float(reg_mu), float(tau), float(t0),
+                                               _ptr(d_par), _ptr(d_dir) if d_dir is not None else None, _ptr(d_out), stride, _stream()), 'sdsm_batch_eval_step')
+        out = d_out.cpu().numpy().reshape(self.n, stride)
+        res = []
+        for i in range(self.n):
+            b = out[i]
+            if not b[0] >= 0:
+                res.append(dict(rc=-1))
+                continue
+            n, E = int(b[4]), int(b[5])
+            M = n - 6
+            ints = b[10 + 2 * n + E:need[i]].view(np.int32)
+            rb, fst, rend = ints[:n].copy(), ints[n:2 * n].copy(), ints[2 * n:2 * n + (M + 3) // 4].copy()
+            env = b[10 + 2 * n:10 + 2 * n + E].copy()
+            hess, stored = expand_envelope(env, rb, fst) if dense else (None, None)
+            res.append(dict(rc=int(b[0]), psi_value=float(b[1]), psi=float(b[2]), lam2=float(b[3]), line=b[6:10].copy(), grad=b[10:10 + n].copy(),
+                            dir=b[10 + n:10 + 2 * n].copy(), env=env, rb=rb, fst=fst, rend=rend, hess=hess, stored=stored))
+        return res
+
     def inspect_states(self):
         """The per-candidate state words of the setup kernel (M, status, envelope size, runs) without the crops / rows of :meth:`inspect`."""
         lay = self.layout()
@@ -399,7 +444,8 @@ class Batch:
 
     def inspect(self):
         """Setup-phase outputs for parity tests: per candidate (N, M, status, pixel coordinates, grid points,
-        CSR-like G~ rows), reconstructed PER PIXEL from the run-packed crop (a run = the region pixels of one image row inside one
+        CSR-like G~ rows and, in ``lead``, which of a row's entries are LEADING ones -- those the approximate Hessian of the solver uses; ``hnz`` counts
+        them per pixel, ``run_hnz`` per run, ``hzmax`` is the setup kernel's maximum over the runs), reconstructed PER PIXEL from the run-packed crop (a run = the region pixels of one image row inside one
         aligned 4-column cell; an entry of a run holds the weights of its four pixels for one grid point).  Reads the workspace back
         to the host."""
         lay = self.layout()
@@ -423,7 +469,7 @@ class Batch:
             meta = run_meta[ro:ro + NR] if have_runs else np.zeros(0, np.uint32)
             rnnz, rhz, pm = (meta & 0xfff).astype(np.int64), ((meta >> 12) & 0xfff).astype(np.int64), (meta >> 24).astype(np.int64)
             rc = crop_rc[ro:ro + len(meta)]
-            rows, cols, ys, nnzs, hnzs, idxs, wts = [], [], [], [], [], [], []
+            rows, cols, ys, nnzs, hnzs, idxs, wts, leads = [], [], [], [], [], [], [], []
             zc = max(zcap, 1)
             for p in range(len(meta)):
                 k = int(rnnz[p]) if M > 0 else 0
@@ -436,20 +482,21 @@ class Batch:
                     sel = w4[:, q] != 0                                  # a grid point outside the pixel's window: weight 0
                     ci, cw = (im[sel] & 0xffff).astype(np.int64), w4[sel, q]
                     o2 = np.argsort(ci, kind='stable')                   # report rows by column index
-                    col = np.zeros(zc, np.int64); wt = np.zeros(zc, np.float32)
-                    col[:len(ci)] = ci[o2]; wt[:len(ci)] = cw[o2]
-                    idxs.append(col); wts.append(wt); nnzs.append(len(ci))
+                    col = np.zeros(zc, np.int64); wt = np.zeros(zc, np.float32); ld = np.zeros(zc, bool)
+                    col[:len(ci)] = ci[o2]; wt[:len(ci)] = cw[o2]; ld[:len(ci)] = (((im[sel] >> (16 + q)) & 1) != 0)[o2]
+                    idxs.append(col); wts.append(wt); nnzs.append(len(ci)); leads.append(ld)
                     hnzs.append(int((((im >> (16 + q)) & 1) != 0).sum()))
             rows, cols = np.asarray(rows, np.int64), np.asarray(cols, np.int64)
             o = np.lexsort((cols, rows))                                   # the crop is stored by runs in sorted scatter order; report it in raster order
             take = lambda a, dt: (np.asarray(a, dt)[o] if len(a) else np.zeros(0, dt))
             idx = np.stack(idxs, axis=1)[:, o] if idxs else np.zeros((zc, 0), np.int64)
             w = np.stack(wts, axis=1)[:, o] if wts else np.zeros((zc, 0), np.float32)
+            lead = np.stack(leads, axis=1)[:, o] if leads else np.zeros((zc, 0), bool)
             out.append(dict(N=N, M=M, status=status, hc=hc, wc=wc, npos=npos, zmax=int(state[i]['zmax']), env_size=int(state[i]['env_size']), NR=NR,
                             y=take(ys, np.float64), r=rows[o] if len(rows) else rows, c=cols[o] if len(cols) else cols,
                             grid_r=(g >> 16).astype(np.int64), grid_c=(g & 0xffff).astype(np.int64), nnz=take(nnzs, np.int64), hnz=take(hnzs, np.int64),
                             run_nnz=rnnz.copy(), run_hnz=rhz.copy(), run_pixels=np.array([bin(int(v)).count('1') for v in pm], np.int64),
-                            idx=idx.copy(), w=w.copy()))
+                            idx=idx.copy(), w=w.copy(), lead=lead.copy(), hzmax=int(state[i]['hzmax'])))
         return out
 
     def fragments(self, records, select=None, masks=None, lazy=False):
@@ -457,6 +504,20 @@ class Batch:
         if masks is None:
             masks = self.masks_dev.cpu().numpy()
         return fragments_from_masks(records, self.mask_info, self.mask_offset, masks, select, lazy)
+
+
+def expand_envelope(env, rb, fst):
+    """The envelope of sdsm_batch_eval_step (row a of the order xi[M], theta[6] holds columns fst[a] .. a at env[rb[a] + column]) as a
+    dense symmetric matrix with the unknowns in the order theta, xi, and the mask of the entries the envelope holds."""
+    n = len(rb)
+    M = n - 6
+    var = np.concatenate([6 + np.arange(M), np.arange(6)])              # envelope order -> variable order
+    hess, stored = np.zeros((n, n)), np.zeros((n, n), bool)
+    for a in range(n):
+        cols = np.arange(fst[a], a + 1)
+        hess[var[a], var[cols]] = hess[var[cols], var[a]] = env[rb[a] + cols]
+        stored[var[a], var[cols]] = stored[var[cols], var[a]] = True
+    return hess, stored
 
 
 def algorithmic_bytes(records, mask_info):

@@ -1064,5 +1064,157 @@ def energy_reference(y, y_mask, atoms, fp, cfg, theta, xi=None, box=None):
         out.update(reg_sum=reg_sum, reg0=reg0)
     ymax = float(np.abs(y[region]).max())
     out.update(psi=psi, grad=grad, hess_theta=hess, y=y[region].copy(), t=t, theta_hat=theta_hat, kappa=kappa, A=A,
-               abs_r=np.abs(r).sum(), abs_d=d.sum(), yexp=int(np.frexp(ymax)[1]) if ymax > 0 else -400)
+               abs_r=np.abs(r).sum(), abs_d=d.sum(), yexp=int(np.frexp(ymax)[1]) if ymax > 0 else -400,
+               rows=rr, cols=cc, u_local=ul, v_local=vl)        # (for hessian_reference: image coordinates and local coordinates of the pixels)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# The Newton step of the solve kernels (sdsm_batch_eval_step): the approximate Hessian, its envelope, the backward error of the
+# factorisation.  NumPy only (and the oracle: test infrastructure).
+# ---------------------------------------------------------------------------------------------------------
+HESS_THR = 0.1                   # the solver's leading rule (BatchParams.hess_thr, ORC_HESS_THR)
+PANEL = 4                        # SDSM_PANEL
+HZREG = 8                        # SDSM_HZREG: leading entries of a run held in registers
+
+
+def leading_entries(indptr, data, hess_thr=HESS_THR):
+    """Which entries of the rows of G~ are LEADING ones: the oracle's rule (sdsm_oracle.c, energy_eval_chunk), compared in float32 --
+    ``(float) w >= (float) hess_thr * (float) wmax`` with wmax the row's largest entry; ``hess_thr`` = 0: all of them."""
+    data = np.asarray(data)
+    if not hess_thr > 0:
+        return np.ones(data.size, bool)
+    w32 = data.astype(np.float32)
+    wmax = np.maximum.reduceat(w32, indptr[:-1]) if data.size else np.zeros(0, np.float32)
+    return w32 >= np.float32(hess_thr) * np.repeat(wmax, np.diff(indptr))
+
+
+def envelope_reference(rows, cols, M, indptr, indices, lead):
+    """The envelope of the approximate Hessian as the setup kernel defines it, from the leading entries of every pixel (region pixels
+    in raster order at image coordinates ``rows``, ``cols``): ``fst[a]`` = the smallest column any pixel couples with a column >= a,
+    rounded down to a multiple of the panel width (non-decreasing by construction), ``rb[a]`` = the row's base so that entry (a, b) is
+    at rb[a] + b, the 6 dense theta rows behind the xi rows, ``rend[p]`` = the last xi row whose first column is <= PANEL p,
+    ``env_size``; ``run_hz``: leading entries per RUN (the region pixels of one image row inside one aligned 4-column cell; an entry
+    counts once if it is a leading one for any pixel of the run) and ``hzmax``, their maximum."""
+    first = np.arange(M)
+    runs = {}
+    for i in range(len(rows)):
+        j = indices[indptr[i]:indptr[i + 1]][lead[indptr[i]:indptr[i + 1]]]
+        if j.size:
+            first[j] = np.minimum(first[j], j.min())
+            runs.setdefault((int(rows[i]), int(cols[i]) >> 2), set()).update(j.tolist())
+    fst = (np.minimum.accumulate(first[::-1])[::-1] // PANEL) * PANEL if M else first
+    width = np.arange(M) - fst + 1
+    start = np.concatenate([[0], np.cumsum(width)])
+    exi = int(start[-1])
+    rb = np.concatenate([start[:-1] - fst, exi + np.arange(6) * M + np.arange(6) * (np.arange(6) + 1) // 2]).astype(np.int64)
+    fst_all = np.concatenate([fst, np.zeros(6, np.int64)]).astype(np.int64)
+    rend = np.array([np.flatnonzero(fst <= PANEL * p).max() for p in range((M + PANEL - 1) // PANEL)], np.int64)
+    run_hz = np.array([len(v) for v in runs.values()], np.int64)
+    return dict(fst=fst_all, rb=rb, rend=rend, env_size=exi + 6 * M + 21, run_hz=run_hz, hzmax=int(run_hz.max()) if run_hz.size else 0)
+
+
+def lead_gram(q, pw, smat, lead, M):
+    """sum_i pw_i J_i J_i^T over the pixels, J_i = (q[:, i], the LEADING entries of row i of G~): the (6 + M)^2 matrix of the solver's
+    approximate Hessian for pixel weights ``pw`` (np.longdouble; unknowns theta, then xi).  theta-theta: all pixels; theta-xi and
+    xi-xi: only over the entries that are leading for the pixel.  ``smat`` = (indptr, indices, data); ``data`` may be replaced by
+    ones to count the pixels that couple two unknowns."""
+    X = np.longdouble
+    q, pw = np.asarray(q, X), np.asarray(pw, X)
+    N, n = q.shape[1], 6 + M
+    Hm = np.zeros((n, n), X)
+    Hm[:6, :6] = np.einsum('ai,bi->ab', q * pw, q)
+    if M == 0:
+        return Hm
+    indptr, indices, data = smat
+    row = np.repeat(np.arange(N), np.diff(indptr))[lead]
+    col, w = np.asarray(indices)[lead].astype(np.int64), np.asarray(data)[lead].astype(X)
+    for k in range(6):
+        tx = np.zeros(M, X)
+        np.add.at(tx, col, q[k, row] * pw[row] * w)
+        Hm[k, 6:], Hm[6:, k] = tx, tx
+    cnt = np.bincount(row, minlength=N)
+    start = np.concatenate([[0], np.cumsum(cnt)])
+    flat = np.zeros(M * M, X)
+    for k in np.unique(cnt[cnt > 0]):                      # pixels with k leading entries: all their pairs at once
+        pix = np.flatnonzero(cnt == k)
+        e = start[pix][:, None] + np.arange(k)[None, :]
+        ck, wk = col[e], w[e]
+        val = pw[pix][:, None, None] * wk[:, :, None] * wk[:, None, :]
+        np.add.at(flat, (ck[:, :, None] * M + ck[:, None, :]).ravel(), val.ravel())
+    Hm[6:, 6:] = flat.reshape(M, M)
+    return Hm
+
+
+def hessian_reference(y, y_mask, atoms, fp, cfg, theta, xi=None, box=None, reg_mu=0.0, hess_thr=HESS_THR):
+    """:func:`energy_reference` and, in the candidate's LOCAL frame (``u_local``, ``v_local``; theta_local = R theta), the gradient
+    ``grad_local`` and the solver's full approximate Hessian ``hess`` ((6 + M)^2, np.longdouble, unknowns theta then xi):
+    theta-theta sum_i d_i q_a q_b over all pixels, q = (u^2, v^2, 2 u v, 2 u, 2 v, 1), d_i = y_i^2 kappa_i; theta-xi and xi-xi only
+    over the entries of G~ that are leading for pixel i (:func:`leading_entries`); xi diagonal plus the regulariser's curvature
+    max(0, alpha eps / (xi^2 + eps)^(3/2)), blended by ``reg_mu`` towards alpha / sqrt(xi^2 + eps) (sdsm_oracle.c, energy_eval_thr).
+    Also ``q_local`` (6 x N), ``r``, ``d`` per pixel, ``lead`` (per entry of ``smat``), ``xi``, ``reg_curv`` (the blended curvature) and
+    ``reg_major`` = alpha / sqrt(xi^2 + eps)."""
+    X = np.longdouble
+    ref = energy_reference(y, y_mask, atoms, fp, cfg, theta, xi, box)
+    N, M = ref['N'], ref['M']
+    ul, vl = ref['u_local'], ref['v_local']
+    ql = np.stack([ul * ul, vl * vl, 2 * ul * vl, 2 * ul, 2 * vl, np.ones(N, X)])
+    yl = ref['y'].astype(X)
+    r, d = -yl * ref['theta_hat'], yl * yl * ref['kappa']
+    lead = leading_entries(ref['smat'][0], ref['smat'][2], hess_thr) if M > 0 else None
+    Hm = lead_gram(ql, d, ref['smat'], lead, M)
+    grad_local = np.concatenate([(ql * r).sum(axis=1), ref['grad'][6:]])
+    ref.update(hess=Hm, grad_local=grad_local, q_local=ql, r=r, d=d, lead=lead, reg_mu=float(reg_mu), xi=np.zeros(0, X))
+    if M > 0:
+        al, ep = X(float(cfg.get('alpha', 0.5))), X(float(cfg.get('epsilon', 1.0)))
+        xil = np.asarray(xi, np.float64).ravel().astype(X)
+        t2 = np.sqrt(xil * xil + ep)
+        gd = np.maximum(al * ep / (t2 * t2 * t2), X(0))
+        gd = gd + X(float(reg_mu)) * (al / t2 - gd)
+        Hm[6 + np.arange(M), 6 + np.arange(M)] += gd
+        ref.update(reg_curv=gd, reg_major=al / t2, xi=xil)
+    return ref
+
+
+# The Newton step (factor_solve of sdsm_solve.hip) is held by its BACKWARD error, so no condition number enters: with the kernel's own
+# float64 H, g and d, r = (H + tau diag H) d + g must satisfy |r_i| <= gamma sqrt(h_ii) sum_j sqrt(h_jj) |d_j|.
+# Where gamma comes from (u = 2^-53; Higham, Accuracy and Stability of Numerical Algorithms, 2nd ed., Lemma 8.4, Theorems 10.3 / 10.4;
+# E_RSQRT = 4.2e-15 is rsqrt_f64's relative error, tests/test_loss_arithmetic_gpu.py):
+#   * a factor entry is l_ik = (a_ik - sum_{m < k} l_im l_km) rho_k with rho_k the reciprocal pivot: at most k <= n multiply-subtracts
+#     (each product and each difference rounds once, or once together as a fused multiply-add) and the scaling -- by Lemma 8.4 the
+#     computed factor reproduces A with |dA| <= gamma_n |L| |L^T|, gamma_k = k u / (1 - k u);
+#   * the forward substitution rides along as row n of the same loops: gamma_n |L|; the back substitution does the same number of
+#     multiply-subtracts per unknown plus two scalings (y~ = y rho, the factor row times rho): gamma_(n + 2) |L^T|;
+#     together (Theorem 10.4) (3 n + 2) u |L| |L^T|, and (|L| |L^T|)_ij <= sqrt(a_ii a_jj) (Cauchy-Schwarz on the rows of L);
+#   * every value passes through a reciprocal pivot at most three times -- when its factor entry is scaled and once in each substitution
+#     --, each within E_RSQRT of 1 / sqrt(pivot): 3 E_RSQRT (an upper bound: the kernel uses the SAME rho_k wherever the pivot
+#     enters, so most of this error is a consistent rescaling that cancels);
+#   * the shifted diagonal a_ii = fl(h_ii (1 + tau)): one more u on the diagonal, and a_ii <= (1 + tau) h_ii (1 + u).
+# gamma = ((3 n + 3) u + 3 E_RSQRT) (1 + tau) (1 + 1e-6); the last factor covers the second-order terms (products of two of the above,
+# each < 1e-12).  The elliptical model (M = 0) solves the Jacobi-scaled system S H S + tau I, S = diag(rsqrt(h_ii)), and returns
+# d = S z: in unscaled terms the same residual with the same bound (the scaled diagonal is 1 + tau, z_j = sqrt(h_jj) d_j; the error
+# of S moves the shift tau h_ii by 2 E_RSQRT of itself, inside the pivot term).
+# lam2 = ||L^-1 g||^2 is compared with -g.d in np.longdouble: 2 gamma (sum_j sqrt(h_jj) |d_j|)^2 + n u sum |g_i d_i|.
+STEP_E_RSQRT = 4.2e-15
+
+
+def step_gamma(n, tau):
+    u = 2.0 ** -53
+    return ((3 * n + 3) * u + 3 * STEP_E_RSQRT) * (1 + tau) * (1 + 1e-6)
+
+
+def step_residual(Hm, g, d, tau):
+    """The backward error of one Newton step in np.longdouble: ``r`` = (H + tau diag H) d + g, its componentwise ``bound``
+    gamma sqrt(h_ii) sum_j sqrt(h_jj) |d_j|, ``ratio`` = max |r_i| / bound_i; ``lam2`` = -g.d with ``lam2_bound`` (see above)."""
+    X = np.longdouble
+    Hm, g, d = np.asarray(Hm, np.float64).astype(X), np.asarray(g, np.float64).astype(X), np.asarray(d, np.float64).astype(X)
+    n = g.size
+    diag = np.diagonal(Hm).copy()
+    r = Hm @ d + X(float(tau)) * diag * d + g
+    sd = np.sqrt(np.maximum(diag, X(0)))
+    s = (sd * np.abs(d)).sum()
+    gamma = X(step_gamma(n, float(tau)))
+    bound = gamma * sd * s
+    with np.errstate(all='ignore'):
+        ratio = np.where(r == 0, X(0), np.abs(r) / bound)
+    return dict(r=r, bound=bound, ratio=float(ratio.max()), lam2=-(g * d).sum(), lam2_bound=2 * gamma * s * s + n * X(2.0) ** -53 * np.abs(g * d).sum())

@@ -238,12 +238,8 @@ REL_D = (3 * E_EXP + 2 * E_RCP + 6 * H) * SECOND_ORDER
 F6 = np.array([1, 1, 2, 2, 2, 1], X)
 
 
-def _eval_bounds(ref):
-    N, M = ref['N'], ref['M']
-    y, t, th, ka, A = np.abs(ref['y']).astype(X), ref['t'], ref['theta_hat'], ref['kappa'], ref['A']
-    dS = (14 + ref['nnz']) * H * A + 16 * H * (F6 * ref['theta_local_abs']).sum()                       # (a)
-    dt = y * dS * (1 + H) + H * np.abs(t)                                                                # (b)
-    assert float(dt.max()) < 1e-6                                                                        # (second-order terms are what they are said to be)
+def _psi_bound(N, M, t, th, dt, phi_sum, reg_sum, reg0, psi):
+    """The bound on psi of a pass whose arguments t_i are within dt_i of the reference's t_i ((c) above and the order of the sums)."""
     E = np.exp(-np.abs(t))
     phi = np.maximum(-t, X(0)) + np.log1p(E)
     b0 = _bound_exp(E) + H / (1 - H) + E_LOG_ABS
@@ -253,13 +249,22 @@ def _eval_bounds(ref):
     # super-chunk is 512 runs and a run holds at least one pixel: at most ceil(N / 512) + 1 of them.  All terms are >= 0, so the sum
     # is off by at most (the longest chain of additions) H (the sum of the terms as computed).
     depth = 4 + 6 + 8 + -(-N // 512) + 1
-    b_psi = pix + depth * H * (ref['phi_sum'] + pix) * SECOND_ORDER
+    b_psi = pix + depth * H * (phi_sum + pix) * SECOND_ORDER
     if M > 0:
         # regulariser alpha sum sqrt(xi^2 + eps) - alpha sqrt(eps) M: a term carries <= 4 roundings (square, sum, a square root within
         # one ulp), every lane adds ceil(M / 64) of them, 6 butterfly levels, the product with alpha, the difference; alpha sqrt(eps) M
         # is formed in float64 on the host (3): (ceil(M / 64) + 14) H of the two magnitudes
-        b_psi = b_psi + (-(-M // 64) + 14) * H * (ref['reg_sum'] + ref['reg0'])
-    b_psi = (b_psi + H * abs(ref['psi'])) * SECOND_ORDER                                                 # pixel part + regulariser
+        b_psi = b_psi + (-(-M // 64) + 14) * H * (reg_sum + reg0)
+    return (b_psi + H * abs(psi)) * SECOND_ORDER                                                         # pixel part + regulariser
+
+
+def _eval_bounds(ref):
+    N, M = ref['N'], ref['M']
+    y, t, th, ka, A = np.abs(ref['y']).astype(X), ref['t'], ref['theta_hat'], ref['kappa'], ref['A']
+    dS = (14 + ref['nnz']) * H * A + 16 * H * (F6 * ref['theta_local_abs']).sum()                       # (a)
+    dt = y * dS * (1 + H) + H * np.abs(t)                                                                # (b)
+    assert float(dt.max()) < 1e-6                                                                        # (second-order terms are what they are said to be)
+    b_psi = _psi_bound(N, M, t, th, dt, ref['phi_sum'], ref['reg_sum'], ref['reg0'], ref['psi'])
     # the fixed-point quanta (fx_exponents; DESIGN, limits: 2^-48 of the largest possible term): gradient terms < 2^(yexp + b), Hessian
     # terms < 2^(2 yexp + min(b, -1)), 2^b >= psi / ln 2 >= every theta (b = 0 from psi >= ln 2 on); a term keeps `bits` bits below that.
     # The evaluation is scaled by the device's own psi, which lies within b_psi of the reference's: the larger exponent of the two.
@@ -291,7 +296,7 @@ def _eval_bounds(ref):
         np.add.at(mag, indices, data.astype(X) * (y * th)[row])
         np.add.at(cnt, indices, (data != 0).astype(X))
         b_grad[6:] = moved + cnt * unit_g / 2 + H * mag + 5 * H * X(ref['alpha']) + H * np.abs(ref['grad'][6:])
-    return dict(psi=b_psi, grad=b_grad * SECOND_ORDER, hess=b_hess * SECOND_ORDER)
+    return dict(psi=b_psi, grad=b_grad * SECOND_ORDER, hess=b_hess * SECOND_ORDER, dt=dt, dr=dr, dd=dd, unit_g=unit_g, unit_h=unit_h)     # (the last five: for tests/test_newton_step_gpu.py)
 
 
 def _blob_scene():
