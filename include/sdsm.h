@@ -537,6 +537,61 @@ int sdsm_measure_labels_multi(const sdsm_set_image *images, int n_images, const 
                               const int32_t *n_labels, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp,
                               sdsm_measure_record *d_out, int32_t *d_bad, void *stream);
 
+/* ---- contour shape tables (no reference counterpart; the definitions are shape_objects_host and shape_labels_host of
+ * superdsm_amd/shape.py) --------------------------------------------------------------------------------------------------------------
+ * One record of exact integers per object, from which superdsm_amd/shape.py derives perimeter, circularity, convex area, solidity and
+ * the Feret diameters on the host, and the vertices of its convex hull.  An object is the set P of the set bits of its fragment;
+ * everything else -- the rest of its box, other objects, the outside of the image -- is outside P (unlike the boundary distances below,
+ * where the image frame makes no boundary).  Conventions as for the measurement tables: objects as sdsm_post_objects takes them, sets
+ * as a HOST table of sdsm_set_image (H, W <= 65535, H * W < 2^31), the single-image form is the set of that one image; every count is an
+ * integer sum and every atomic an integer add / min / max / or, so the bytes do not depend on the order, the launch or the set size.
+ *
+ * border pixel: a pixel of P with a 4-neighbour outside P.  For a border pixel, v = 1 + 2 * (border pixels among its 4 orthogonal
+ * neighbours) + 10 * (border pixels among its 4 diagonal neighbours); perim_n1 counts v in {5, 7, 15, 17, 25, 27}, perim_n2 v in
+ * {21, 33}, perim_n3 v in {13, 23}: the classes of the 4-neighbourhood perimeter estimator n1 + n2 * sqrt(2) + n3 * (1 + sqrt(2)) / 2.
+ * Hull: of the corners of the closed unit squares of the pixels, on the lattice 0 .. H x 0 .. W; vertices (row, column) counter-clockwise
+ * in the (row, column) plane from the smallest (row, column), collinear points dropped.  80 bytes. */
+#define SDSM_SHAPE_MAX_CHAIN 4096       /* vertices of the left or the right chain of a hull that the kernel holds (see DESIGN.md "Limits") */
+#define SDSM_SHAPE_MAX_WINDOW_WORDS (1ll << 26)     /* label form: 32-bit words of all label windows of a call (256 MB) */
+typedef struct {
+    int64_t area;                       /* pixels of P */
+    int64_t border_pixels;              /* border pixels */
+    int64_t edges_r, edges_c;           /* unit edges between a pixel of P and an outside pixel above or below / left or right of it */
+    int64_t perim_n1, perim_n2, perim_n3;
+    int64_t hull_area2;                 /* twice the area of the hull (shoelace) */
+    int64_t feret_max_d2;               /* largest squared distance between two hull vertices */
+    int32_t n_vertices;                 /* hull vertices */
+    int32_t flags;                      /* bit 0: the bounding box of P touches the image frame; bit 30: a hull chain passed
+                                           SDSM_SHAPE_MAX_CHAIN vertices (the hull fields and vertices are then not valid) */
+} sdsm_shape_record;
+/* Host helper (no device access): the vertex slots an object with an h x w box needs in d_slots, 2 * min(h + 1, 2 * w + 2); 0 for an
+ * empty box. */
+int64_t sdsm_shape_vertex_slots(int h, int w);
+/* d_out[i] for object i of d_boxes / d_bits_off (n of them; d_obj_image int32, NULL for one image), one workgroup each.  The bits of a
+ * fragment past h * w are ignored, a box larger than the tight box changes nothing; a fragment without a set bit, and an object whose box
+ * is empty or leaves its image, give the zero record and no vertex.  Hull vertices: object i writes (row, column) int32 pairs, image
+ * coordinates, from pair d_slot_off[i] (int64) of d_slots on, sdsm_shape_vertex_slots(h, w) pairs at most (workspace of the caller);
+ * then d_vert_off (n + 1 int64) receives the exclusive sum of n_vertices and d_verts the vertices of all objects one behind the other
+ * (d_vert_off[n] pairs; room for as many pairs as d_slots holds is enough). */
+int sdsm_shape_objects(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, const int64_t *d_slot_off,
+                       int32_t *d_slots, sdsm_shape_record *d_out, int64_t *d_vert_off, int32_t *d_verts, void *stream);
+int sdsm_shape_objects_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                             const int64_t *d_bits_off, const uint32_t *d_bits, const int64_t *d_slot_off, int32_t *d_slots,
+                             sdsm_shape_record *d_out, int64_t *d_vert_off, int32_t *d_verts, void *stream);
+/* The same for labels of label maps (d_labels int32, packed): the caller names n windows (d_obj_image, d_boxes, d_bits_off into the
+ * workspace d_bits of window_words <= SDSM_SHAPE_MAX_WINDOW_WORDS words, which the call clears) and, per image, the window of every label:
+ * d_label_obj[rec_off[i] + l] is the window of label l of image i, or negative for a label that is not measured (rec_off, n_labels: HOST
+ * arrays as for sdsm_measure_labels, whose records give the boxes).  A first kernel sets the bit of every pixel in the window of its
+ * label -- a pixel of another label stays outside --, then the windows are measured as objects.  A pixel outside the box of its label's
+ * window is skipped; a label outside 0 .. n_labels[i] - 1 is counted in d_bad[i] (int32 per image, cleared by the call) and skipped. */
+int sdsm_shape_labels(int H, int W, const int32_t *d_labels, int n_labels, const int32_t *d_label_obj, int n, const int32_t *d_boxes,
+                      const int64_t *d_bits_off, int64_t window_words, uint32_t *d_bits, const int64_t *d_slot_off, int32_t *d_slots,
+                      sdsm_shape_record *d_out, int64_t *d_vert_off, int32_t *d_verts, int32_t *d_bad, void *stream);
+int sdsm_shape_labels_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int64_t *rec_off, const int32_t *n_labels,
+                            const int32_t *d_label_obj, int n, const int32_t *d_obj_image, const int32_t *d_boxes, const int64_t *d_bits_off,
+                            int64_t window_words, uint32_t *d_bits, const int64_t *d_slot_off, int32_t *d_slots, sdsm_shape_record *d_out,
+                            int64_t *d_vert_off, int32_t *d_verts, int32_t *d_bad, void *stream);
+
 /* ---- contingency table of two label maps (no reference counterpart; the definition is overlap_pairs_host of superdsm_amd/compare.py) --
  * For two label maps of one image (d_a, d_b: int32, packed as the table of the set says) the number of pixels of every pair of labels
  * (a, b) that occurs, background members included, in a hash table per image: image i owns the slots table_off[i] .. table_off[i] +

@@ -14,3 +14,4 @@ if 'GPU_MAX_HW_QUEUES' not in _os.environ and _os.environ.get('SDSM_SET_HW_QUEUE
 from .c2freganal import C2F_RegionAnalysis  # noqa: E402,F401
 from . import compare  # noqa: E402,F401
 from . import boundary  # noqa: E402,F401
+from . import shape  # noqa: E402,F401

@@ -83,6 +83,13 @@ PAIR_DISTANCE_DTYPE = np.dtype([('a', '<i4'), ('b', '<i4'), ('boundary_a', '<i4'
                                 ('flags', '<i4'), ('reserved', '<i4'), ('sum_q_ab', '<i8'), ('sum_q_ba', '<i8'), ('nsd_num', '<i8'),
                                 ('nsd_den', '<i8')])                                 # sdsm_pair_distance
 assert PAIR_DISTANCE_DTYPE.itemsize == 64
+SHAPE_MAX_CHAIN = 4096              # SDSM_SHAPE_MAX_CHAIN: vertices of one chain of a hull
+SHAPE_MAX_WINDOW_WORDS = 1 << 26    # SDSM_SHAPE_MAX_WINDOW_WORDS: words of all label windows of a call of the label form of the shape tables
+SHAPE_CHAIN_OVERFLOW = 1 << 30      # flag bit 30 of sdsm_shape_record
+_SHAPE_FIELDS = [('area', 'i8'), ('border_pixels', 'i8'), ('edges_r', 'i8'), ('edges_c', 'i8'), ('perim_n1', 'i8'), ('perim_n2', 'i8'), ('perim_n3', 'i8'),
+                 ('hull_area2', 'i8'), ('feret_max_d2', 'i8'), ('n_vertices', 'i4'), ('flags', 'i4')]
+SHAPE_RECORD_DTYPE = np.dtype(_SHAPE_FIELDS)                                       # sdsm_shape_record
+assert SHAPE_RECORD_DTYPE.itemsize == 80
 
 
 class MeasureRecord(C.Structure):
@@ -194,6 +201,12 @@ SYMBOLS = {
     'sdsm_measure_objects_multi': (_i32, [C.POINTER(SetImage), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sdsm_measure_labels': (_i32, [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sdsm_measure_labels_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_shape_vertex_slots': (_i64, [_i32, _i32]),
+    'sdsm_shape_objects': (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_shape_objects_multi': (_i32, [C.POINTER(SetImage), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_shape_labels': (_i32, [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_shape_labels_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp]),
     'sdsm_overlap_pairs': (_i32, [_i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     'sdsm_overlap_pairs_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _vp, _vp, _vp, _vp]),
     'sdsm_label_pixel_counts': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp]),

@@ -779,6 +779,66 @@ extern "C" int sdsm_measure_labels(int H, int W, const int32_t *d_labels, int n_
     return sdsm_measure_labels_multi(&one, 1, d_labels, &off, &n_labels, d_g, d_gmax_abs, d_scale_exp, d_out, d_bad, stream);
 }
 
+// ---- contour shape tables (sdsm_shape.hip) ----------------------------------------------------------------------------------------------
+extern "C" hipError_t sdsm_shape_objects_impl(const sdsm_set_image *images, int n_images, int n, const int32_t *obj_image, const int32_t *boxes,
+                                              const int64_t *bits_off, const uint32_t *bits, const int64_t *slot_off, int32_t *slots,
+                                              sdsm_shape_record *out, int64_t *vert_off, int32_t *verts, hipStream_t stream);
+extern "C" hipError_t sdsm_shape_scatter_impl(const sdsm_set_image *images, int n_images, const int32_t *labels, const int64_t *rec_off,
+                                              const int32_t *n_labels, const int32_t *label_obj, int n, const int32_t *boxes, const int64_t *bits_off,
+                                              int64_t window_words, uint32_t *bits, int32_t *bad, hipStream_t stream);
+
+extern "C" int sdsm_shape_objects_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                                        const int64_t *d_bits_off, const uint32_t *d_bits, const int64_t *d_slot_off, int32_t *d_slots,
+                                        sdsm_shape_record *d_out, int64_t *d_vert_off, int32_t *d_verts, void *stream)
+{
+    SET_TABLE("sdsm_shape_objects", SET_SIDES | SET_PIXELS);
+    if (n < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_shape_objects: n < 0");
+    if (!d_vert_off || (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_slot_off || !d_slots || !d_out || !d_verts || (n_images > 1 && !d_obj_image))))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_shape_objects: null argument");
+    hipError_t e = sdsm_shape_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_slot_off, d_slots, d_out, d_vert_off, d_verts,
+                                           (hipStream_t)stream);
+    SET_DONE("sdsm_shape_objects");
+}
+
+extern "C" int sdsm_shape_objects(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, const int64_t *d_slot_off,
+                                  int32_t *d_slots, sdsm_shape_record *d_out, int64_t *d_vert_off, int32_t *d_verts, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_shape_objects_multi(&one, 1, n, nullptr, d_boxes, d_bits_off, d_bits, d_slot_off, d_slots, d_out, d_vert_off, d_verts, stream);
+}
+
+extern "C" int sdsm_shape_labels_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int64_t *rec_off, const int32_t *n_labels,
+                                       const int32_t *d_label_obj, int n, const int32_t *d_obj_image, const int32_t *d_boxes, const int64_t *d_bits_off,
+                                       int64_t window_words, uint32_t *d_bits, const int64_t *d_slot_off, int32_t *d_slots, sdsm_shape_record *d_out,
+                                       int64_t *d_vert_off, int32_t *d_verts, int32_t *d_bad, void *stream)
+{
+    SET_TABLE("sdsm_shape_labels", SET_SIDES | SET_PIXELS);
+    if (n < 0 || window_words < 0 || window_words > SDSM_SHAPE_MAX_WINDOW_WORDS)
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_shape_labels: n >= 0 and 0 <= window_words <= SDSM_SHAPE_MAX_WINDOW_WORDS required");
+    if (!d_labels || !rec_off || !n_labels || !d_label_obj || !d_vert_off || !d_bad ||
+        (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_slot_off || !d_slots || !d_out || !d_verts || (n_images > 1 && !d_obj_image))))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_shape_labels: null argument");
+    for (int i = 0; i < n_images; i++)
+        if (n_labels[i] < 1 || n_labels[i] > SDSM_MEASURE_MAX_LABELS || rec_off[i] < 0)
+            return fail(SDSM_ERR_ARGUMENT, "sdsm_shape_labels: 1 <= n_labels <= 65536 and rec_off >= 0 required");
+    hipError_t e = sdsm_shape_scatter_impl(images, n_images, d_labels, rec_off, n_labels, d_label_obj, n, d_boxes, d_bits_off, window_words, d_bits, d_bad,
+                                           (hipStream_t)stream);
+    if (e == hipSuccess)
+        e = sdsm_shape_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_slot_off, d_slots, d_out, d_vert_off, d_verts,
+                                    (hipStream_t)stream);
+    SET_DONE("sdsm_shape_labels");
+}
+
+extern "C" int sdsm_shape_labels(int H, int W, const int32_t *d_labels, int n_labels, const int32_t *d_label_obj, int n, const int32_t *d_boxes,
+                                 const int64_t *d_bits_off, int64_t window_words, uint32_t *d_bits, const int64_t *d_slot_off, int32_t *d_slots,
+                                 sdsm_shape_record *d_out, int64_t *d_vert_off, int32_t *d_verts, int32_t *d_bad, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    const int64_t off = 0;
+    return sdsm_shape_labels_multi(&one, 1, d_labels, &off, &n_labels, d_label_obj, n, nullptr, d_boxes, d_bits_off, window_words, d_bits, d_slot_off, d_slots,
+                                   d_out, d_vert_off, d_verts, d_bad, stream);
+}
+
 // ---- contingency table of two label maps (sdsm_measure.hip) ---------------------------------------------------------------------------
 extern "C" hipError_t sdsm_overlap_pairs_impl(const sdsm_set_image *images, int n_images, const int32_t *d_a, const int32_t *d_b,
                                               const int64_t *table_off, const int64_t *capacity, uint64_t *d_keys, uint64_t *d_counts,
