@@ -592,6 +592,71 @@ int sdsm_shape_labels_multi(const sdsm_set_image *images, int n_images, const in
                             int64_t window_words, uint32_t *d_bits, const int64_t *d_slot_off, int32_t *d_slots, sdsm_shape_record *d_out,
                             int64_t *d_vert_off, int32_t *d_verts, int32_t *d_bad, void *stream);
 
+/* ---- intensity distribution tables (no reference counterpart; the definitions are intensity_objects_host and intensity_labels_host of
+ * superdsm_amd/intensity.py) ----------------------------------------------------------------------------------------------------------
+ * Per object, over the FINITE intensities of its pixels (d_g, float64, required; a non-finite pixel sets flag bit 1 and is counted
+ * out): extremes, an exact spread centred on the object's own minimum, exact order statistics for up to SDSM_INTENSITY_MAX_QUANTILES
+ * quantiles, and the two middle order statistics of |g - median|.  superdsm_amd/intensity.py derives standard deviation, mean,
+ * median, quantiles, interquartile range and median absolute deviation on the host.  Conventions as for the measurement tables (objects
+ * as sdsm_post_objects takes them, sets as a HOST table of sdsm_set_image, H, W <= 65535, H * W < 2^31); every sum is an integer sum and
+ * every order statistic an element of the input, so the bytes do not depend on the order, the launch or the set size.  -0.0 reads +0.0
+ * everywhere.
+ *
+ * Spread: d = gmax - gmin (one IEEE subtraction); range_exp e is the smallest exponent with d < 2^e, clamped to -960 .. 1024, 0 when
+ * d == 0.  A finite pixel adds p = rint(ldexp(g - gmin, 30 - e)) (one IEEE subtraction, ties to even; 0 <= p <= 2^30): p to sum_p, bits
+ * 0 .. 31 of p * p to sum_pp_lo, p * p >> 32 to sum_pp_hi.  With S2 = sum_pp_hi * 2^32 + sum_pp_lo the variance is
+ * (n_finite * S2 - sum_p^2) / n_finite^2 * 4^(e - 30); its root is within 2^(e - 30) of the population standard deviation of the doubles.
+ * If d is not finite (gmin and gmax further apart than the largest double), flag bit 3 is set, range_exp is 1024 and the three sums
+ * stay 0.
+ * Order statistics: quantile q = num[q] / den[q] (HOST arrays, launch arguments; 0 <= num <= den, 1 <= den <= SDSM_INTENSITY_MAX_DEN)
+ * of an object with n = n_finite >= 1 has the ranks of sdsm_quantile_ranks; d_order[(i * n_q + q) * 2 + 0 / 1] receive the elements at
+ * the ranks lo / hi of the sorted finite intensities, bit for bit.  With n == 0 both hold the quiet NaN 0x7ff8000000000000.
+ * MAD: med_lo, med_hi are the order statistics at the ranks of 1 / 2, whatever the caller's quantiles, and med = 0.5 * med_lo + 0.5 *
+ * med_hi (two products, one sum, no fused multiply-add); mad_lo, mad_hi are the order statistics at those ranks of the keys |g - med|
+ * (one IEEE subtraction each; +inf where it overflows); all four NaN with n == 0.
+ * Objects with at most SDSM_INTENSITY_LDS_KEYS finite pixels are selected from a copy in LDS; larger ones re-read their pixels in every
+ * round of the selection: the same bytes, more slowly (see DESIGN.md "Limits").  96 bytes. */
+#define SDSM_INTENSITY_MAX_QUANTILES 8
+#define SDSM_INTENSITY_MAX_DEN 1000000  /* largest denominator of a quantile */
+#define SDSM_INTENSITY_LDS_KEYS 4096    /* finite pixels of an object whose keys are staged in LDS (32 KB) */
+typedef struct {
+    int64_t area;                       /* pixels */
+    int64_t n_finite;                   /* pixels with a finite intensity */
+    int64_t sum_p;                      /* sum of p, < 2^61 */
+    uint64_t sum_pp_lo, sum_pp_hi;      /* sums of the low 32 bits and of the rest of p * p, each < 2^63 */
+    double gmin, gmax;                  /* over the finite pixels; +inf / -inf when there are none */
+    double med_lo, med_hi;              /* the two middle order statistics of g (the ranks of 1 / 2); quiet NaN without a finite pixel */
+    double mad_lo, mad_hi;              /* the two middle order statistics of |g - med|; quiet NaN without a finite pixel */
+    int32_t range_exp;                  /* e */
+    int32_t flags;                      /* bit 0: the bounding box of the pixels touches the image frame; bit 1: a non-finite intensity
+                                           inside; bit 2: no finite pixel; bit 3: gmax - gmin is not finite */
+} sdsm_intensity_record;
+/* Host helper (no device access): the ranks of the quantile num / den of n sorted values, 1 <= n < 2^31: h = (n - 1) * num, lo = h div
+ * den, rem = h mod den, hi = lo + (rem != 0).  The quantile is v[lo] + (v[hi] - v[lo]) * rem / den.  The kernels use the same inline
+ * function. */
+int sdsm_quantile_ranks(int64_t n, int32_t num, int32_t den, int64_t *lo, int64_t *hi, int64_t *rem);
+/* d_out[i] and d_order[(i * n_q + q) * 2 ..] for object i of d_boxes / d_bits_off (n of them; d_obj_image int32, NULL for one image), one
+ * workgroup each, no global atomics; neither output needs clearing.  0 <= n_q <= SDSM_INTENSITY_MAX_QUANTILES (d_order may be NULL for
+ * n_q == 0).  The bits of a fragment past h * w are ignored, a box larger than the tight box changes nothing.  A fragment without a set
+ * bit, and an object whose box is empty or leaves its image, give the empty record (integers 0, flags bit 2 alone, gmin, gmax +inf, -inf,
+ * med_lo .. mad_hi NaN) and NaN slots.  n == 0: no launch. */
+int sdsm_intensity_objects(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, const double *d_g,
+                           int n_q, const int32_t *num, const int32_t *den, sdsm_intensity_record *d_out, double *d_order, void *stream);
+int sdsm_intensity_objects_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                                 const int64_t *d_bits_off, const uint32_t *d_bits, const double *d_g, int n_q, const int32_t *num,
+                                 const int32_t *den, sdsm_intensity_record *d_out, double *d_order, void *stream);
+/* The same for labels of label maps, by the windows of sdsm_shape_labels: the caller names n windows (d_obj_image, d_boxes, d_bits_off
+ * into the workspace d_bits of window_words <= SDSM_SHAPE_MAX_WINDOW_WORDS words, which the call clears) and d_label_obj; a first kernel
+ * sets the bit of every pixel in the window of its label, then the windows are measured as objects.  d_bad as there. */
+int sdsm_intensity_labels(int H, int W, const int32_t *d_labels, int n_labels, const int32_t *d_label_obj, int n, const int32_t *d_boxes,
+                          const int64_t *d_bits_off, int64_t window_words, uint32_t *d_bits, const double *d_g, int n_q, const int32_t *num,
+                          const int32_t *den, sdsm_intensity_record *d_out, double *d_order, int32_t *d_bad, void *stream);
+int sdsm_intensity_labels_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int64_t *rec_off,
+                                const int32_t *n_labels, const int32_t *d_label_obj, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                                const int64_t *d_bits_off, int64_t window_words, uint32_t *d_bits, const double *d_g, int n_q,
+                                const int32_t *num, const int32_t *den, sdsm_intensity_record *d_out, double *d_order, int32_t *d_bad,
+                                void *stream);
+
 /* ---- contingency table of two label maps (no reference counterpart; the definition is overlap_pairs_host of superdsm_amd/compare.py) --
  * For two label maps of one image (d_a, d_b: int32, packed as the table of the set says) the number of pixels of every pair of labels
  * (a, b) that occurs, background members included, in a hash table per image: image i owns the slots table_off[i] .. table_off[i] +

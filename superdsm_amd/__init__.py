@@ -15,3 +15,4 @@ from .c2freganal import C2F_RegionAnalysis  # noqa: E402,F401
 from . import compare  # noqa: E402,F401
 from . import boundary  # noqa: E402,F401
 from . import shape  # noqa: E402,F401
+from . import intensity  # noqa: E402,F401

@@ -90,6 +90,13 @@ _SHAPE_FIELDS = [('area', 'i8'), ('border_pixels', 'i8'), ('edges_r', 'i8'), ('e
                  ('hull_area2', 'i8'), ('feret_max_d2', 'i8'), ('n_vertices', 'i4'), ('flags', 'i4')]
 SHAPE_RECORD_DTYPE = np.dtype(_SHAPE_FIELDS)                                       # sdsm_shape_record
 assert SHAPE_RECORD_DTYPE.itemsize == 80
+INTENSITY_MAX_QUANTILES = 8         # SDSM_INTENSITY_MAX_QUANTILES: quantiles of one call of the intensity tables
+INTENSITY_MAX_DEN = 10 ** 6         # SDSM_INTENSITY_MAX_DEN: largest denominator of a quantile
+INTENSITY_LDS_KEYS = 4096           # SDSM_INTENSITY_LDS_KEYS: finite pixels of an object that is selected from LDS
+_INTENSITY_FIELDS = [('area', 'i8'), ('n_finite', 'i8'), ('sum_p', 'i8'), ('sum_pp_lo', 'u8'), ('sum_pp_hi', 'u8'), ('gmin', 'f8'), ('gmax', 'f8'),
+                     ('med_lo', 'f8'), ('med_hi', 'f8'), ('mad_lo', 'f8'), ('mad_hi', 'f8'), ('range_exp', 'i4'), ('flags', 'i4')]
+INTENSITY_RECORD_DTYPE = np.dtype(_INTENSITY_FIELDS)                               # sdsm_intensity_record
+assert INTENSITY_RECORD_DTYPE.itemsize == 96
 
 
 class MeasureRecord(C.Structure):
@@ -207,6 +214,14 @@ SYMBOLS = {
     'sdsm_shape_labels': (_i32, [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sdsm_shape_labels_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                        _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_quantile_ranks': (_i32, [_i64, _i32, _i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'sdsm_intensity_objects': (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp]),
+    'sdsm_intensity_objects_multi': (_i32, [C.POINTER(SetImage), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp,
+                                            _vp]),
+    'sdsm_intensity_labels': (_i32, [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp,
+                                     _vp]),
+    'sdsm_intensity_labels_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp,
+                                           _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp, _vp]),
     'sdsm_overlap_pairs': (_i32, [_i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     'sdsm_overlap_pairs_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _vp, _vp, _vp, _vp]),
     'sdsm_label_pixel_counts': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp]),

@@ -839,6 +839,76 @@ extern "C" int sdsm_shape_labels(int H, int W, const int32_t *d_labels, int n_la
                                    d_out, d_vert_off, d_verts, d_bad, stream);
 }
 
+// ---- intensity distribution tables (sdsm_intensity.hip; the label form fills its windows with the scatter step of sdsm_shape.hip) -------
+extern "C" hipError_t sdsm_intensity_objects_impl(const sdsm_set_image *images, int n_images, int n, const int32_t *obj_image, const int32_t *boxes,
+                                                  const int64_t *bits_off, const uint32_t *bits, const double *d_g, int n_q, const int32_t *num,
+                                                  const int32_t *den, sdsm_intensity_record *out, double *order, hipStream_t stream);
+
+static bool quantiles_ok(int n_q, const int32_t *num, const int32_t *den)
+{
+    if (n_q < 0 || n_q > SDSM_INTENSITY_MAX_QUANTILES || (n_q > 0 && (!num || !den))) return false;
+    for (int q = 0; q < n_q; q++)
+        if (den[q] < 1 || den[q] > SDSM_INTENSITY_MAX_DEN || num[q] < 0 || num[q] > den[q]) return false;
+    return true;
+}
+
+extern "C" int sdsm_intensity_objects_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                                            const int64_t *d_bits_off, const uint32_t *d_bits, const double *d_g, int n_q, const int32_t *num,
+                                            const int32_t *den, sdsm_intensity_record *d_out, double *d_order, void *stream)
+{
+    SET_TABLE("sdsm_intensity_objects", SET_SIDES | SET_PIXELS);
+    if (n < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_intensity_objects: n < 0");
+    if (!quantiles_ok(n_q, num, den))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_intensity_objects: 0 <= n_q <= 8 quantiles with 0 <= num <= den, 1 <= den <= 1000000 required");
+    if (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_g || !d_out || (n_q > 0 && !d_order) || (n_images > 1 && !d_obj_image)))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_intensity_objects: null argument");
+    hipError_t e = sdsm_intensity_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_g, n_q, num, den, d_out, d_order,
+                                               (hipStream_t)stream);
+    SET_DONE("sdsm_intensity_objects");
+}
+
+extern "C" int sdsm_intensity_objects(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, const double *d_g,
+                                      int n_q, const int32_t *num, const int32_t *den, sdsm_intensity_record *d_out, double *d_order, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_intensity_objects_multi(&one, 1, n, nullptr, d_boxes, d_bits_off, d_bits, d_g, n_q, num, den, d_out, d_order, stream);
+}
+
+extern "C" int sdsm_intensity_labels_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int64_t *rec_off,
+                                           const int32_t *n_labels, const int32_t *d_label_obj, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                                           const int64_t *d_bits_off, int64_t window_words, uint32_t *d_bits, const double *d_g, int n_q,
+                                           const int32_t *num, const int32_t *den, sdsm_intensity_record *d_out, double *d_order, int32_t *d_bad,
+                                           void *stream)
+{
+    SET_TABLE("sdsm_intensity_labels", SET_SIDES | SET_PIXELS);
+    if (n < 0 || window_words < 0 || window_words > SDSM_SHAPE_MAX_WINDOW_WORDS)
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_intensity_labels: n >= 0 and 0 <= window_words <= SDSM_SHAPE_MAX_WINDOW_WORDS required");
+    if (!quantiles_ok(n_q, num, den))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_intensity_labels: 0 <= n_q <= 8 quantiles with 0 <= num <= den, 1 <= den <= 1000000 required");
+    if (!d_labels || !rec_off || !n_labels || !d_label_obj || !d_bad ||
+        (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_g || !d_out || (n_q > 0 && !d_order) || (n_images > 1 && !d_obj_image))))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_intensity_labels: null argument");
+    for (int i = 0; i < n_images; i++)
+        if (n_labels[i] < 1 || n_labels[i] > SDSM_MEASURE_MAX_LABELS || rec_off[i] < 0)
+            return fail(SDSM_ERR_ARGUMENT, "sdsm_intensity_labels: 1 <= n_labels <= 65536 and rec_off >= 0 required");
+    hipError_t e = sdsm_shape_scatter_impl(images, n_images, d_labels, rec_off, n_labels, d_label_obj, n, d_boxes, d_bits_off, window_words, d_bits, d_bad,
+                                           (hipStream_t)stream);
+    if (e == hipSuccess)
+        e = sdsm_intensity_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_g, n_q, num, den, d_out, d_order,
+                                        (hipStream_t)stream);
+    SET_DONE("sdsm_intensity_labels");
+}
+
+extern "C" int sdsm_intensity_labels(int H, int W, const int32_t *d_labels, int n_labels, const int32_t *d_label_obj, int n, const int32_t *d_boxes,
+                                     const int64_t *d_bits_off, int64_t window_words, uint32_t *d_bits, const double *d_g, int n_q, const int32_t *num,
+                                     const int32_t *den, sdsm_intensity_record *d_out, double *d_order, int32_t *d_bad, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    const int64_t off = 0;
+    return sdsm_intensity_labels_multi(&one, 1, d_labels, &off, &n_labels, d_label_obj, n, nullptr, d_boxes, d_bits_off, window_words, d_bits, d_g, n_q,
+                                       num, den, d_out, d_order, d_bad, stream);
+}
+
 // ---- contingency table of two label maps (sdsm_measure.hip) ---------------------------------------------------------------------------
 extern "C" hipError_t sdsm_overlap_pairs_impl(const sdsm_set_image *images, int n_images, const int32_t *d_a, const int32_t *d_b,
                                               const int64_t *table_off, const int64_t *capacity, uint64_t *d_keys, uint64_t *d_counts,

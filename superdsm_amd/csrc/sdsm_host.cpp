@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/sdsm.h"
+#include "sdsm_quantile.h"
 
 namespace {
 
@@ -259,5 +260,13 @@ extern "C" int sdsm_flood_sparse(int64_t n, const int32_t *idx, const int32_t *l
             heap.emplace(dist[j], age++, q, (int32_t)j);
         }
     }
+    return SDSM_OK;
+}
+
+// The ranks of the quantile num / den of n sorted values, as the intensity kernels take them (sdsm_quantile.h: the same inline function).
+extern "C" int sdsm_quantile_ranks(int64_t n, int32_t num, int32_t den, int64_t *lo, int64_t *hi, int64_t *rem)
+{
+    if (n < 1 || n > INT32_MAX || den < 1 || den > SDSM_INTENSITY_MAX_DEN || num < 0 || num > den || !lo || !hi || !rem) return SDSM_ERR_ARGUMENT;
+    sdsm_quantile_ranks_inline(n, num, den, lo, hi, rem);
     return SDSM_OK;
 }

@@ -10,7 +10,8 @@ bytes of the ``*_host`` definitions below, whatever the launch or the set size. 
 radii, eccentricity, axis lengths, mean intensities -- is computed in ONE place, :func:`derive`, on the host from those integers.
 
 The standard deviation of the intensities is not part of a table: a one-pass sum of squares minus the squared mean loses the digits
-that post-processing was changed to keep; it needs a second pass."""
+that post-processing was changed to keep.  The second pass it needs is :mod:`intensity`, which centres the squares on each object's own
+minimum and adds the median, quantiles and the median absolute deviation."""
 import csv
 import math
 from fractions import Fraction

@@ -239,49 +239,64 @@ class _ShapeSet:
         return self._download(B, n)
 
     def labels(self, labels, background_label):
-        """Per image (labels measured, records, offsets, vertices) of the label maps of the set: the boxes of the labels from
-        sdsm_measure_labels, their windows sized here, then sdsm_shape_labels."""
-        S, M = self.S, self.M
-        d_labels = S.pack(labels, np.int32)
-        rng = M.label_range(d_labels)
+        """Per image (labels measured, records, offsets, vertices) of the label maps of the set: the windows of the labels
+        (``_LabelWindows``), then sdsm_shape_labels."""
+        S = self.S
+        w = _LabelWindows(self.M, labels, background_label, 'shape')
+        n = len(w.idx)
+        B = self._buffers(w.boxes)
+        S.capi.check(S.L.sdsm_shape_labels_multi(S.table, self.n_im, S._p(w.d_labels), w.c_off, w.c_n, S._p(w.d_label_obj), n, S._p(w.d_image),
+                                                 S._p(w.d_boxes), S._p(w.d_off), w.total, S._p(w.d_bits), S._p(B['d_slot_off']),
+                                                 S._p(B['d_slots']), S._p(B['d_out']), S._p(B['d_vert_off']), S._p(B['d_verts']), S._p(w.d_bad), S._stream()),
+                     'sdsm_shape_labels_multi')
+        recs, offsets, vertices = self._download(B, n)
+        return [(ls, n_labels) + _split(recs, offsets, vertices, a, b) for ls, n_labels, a, b in w.per_image()]
+
+
+class _LabelWindows:
+    """The windows of the labels of a set of label maps (``M``: its ``measure._MeasureSet``), as the label forms of the shape and the
+    intensity tables take them: the boxes of the present labels without ``background_label`` from sdsm_measure_labels (one download),
+    one window of ceil(h w / 32) words per label, and the device arrays that name them.  Raises before any kernel of the caller's is
+    launched where the labels or the windows pass the limits."""
+
+    def __init__(self, M, labels, background_label, what):
+        S = self.S = M.S
+        n_im = self.n_im = len(S.shapes)
+        self.d_labels = S.pack(labels, np.int32)
+        rng = M.label_range(self.d_labels)
         if (rng[:, 0] < 0).any() or (rng[:, 1] >= _capi.MEASURE_MAX_LABELS).any():
-            raise ValueError(f'labels {rng[:, 0].min()} .. {rng[:, 1].max()}: the shape tables take the labels 0 .. {_capi.MEASURE_MAX_LABELS - 1}, '
+            raise ValueError(f'labels {rng[:, 0].min()} .. {rng[:, 1].max()}: the {what} tables take the labels 0 .. {_capi.MEASURE_MAX_LABELS - 1}, '
                              'see DESIGN.md "Limits"')
-        n_labels = (rng[:, 1] + 1).astype(np.int64)
-        rec_off = _exclusive(n_labels)
-        c_off, c_n = (S.C.c_int64 * self.n_im)(*[int(v) for v in rec_off]), (S.C.c_int32 * self.n_im)(*[int(v) for v in n_labels])
-        d_bad = S.torch.empty(self.n_im, dtype=S.torch.int32, device=S.dev)
+        self.n_labels = n_labels = (rng[:, 1] + 1).astype(np.int64)
+        self.rec_off = rec_off = _exclusive(n_labels)
+        self.c_off, self.c_n = (S.C.c_int64 * n_im)(*[int(v) for v in rec_off]), (S.C.c_int32 * n_im)(*[int(v) for v in n_labels])
+        self.d_bad = S.torch.empty(n_im, dtype=S.torch.int32, device=S.dev)
         d_rec = M.record_buffer(int(n_labels.sum()))
-        S.capi.check(S.L.sdsm_measure_labels_multi(S.table, self.n_im, S._p(d_labels), c_off, c_n, None, None, None, S._p(d_rec), S._p(d_bad), S._stream()),
-                     'sdsm_measure_labels_multi')
+        S.capi.check(S.L.sdsm_measure_labels_multi(S.table, n_im, S._p(self.d_labels), self.c_off, self.c_n, None, None, None, S._p(d_rec), S._p(self.d_bad),
+                                                   S._stream()), 'sdsm_measure_labels_multi')
         mrec = M._records(d_rec, int(n_labels.sum()))
         keep = mrec['area'] > 0
         if background_label is not None:
-            for i in range(self.n_im):
+            for i in range(n_im):
                 if 0 <= background_label < n_labels[i]:
                     keep[rec_off[i] + background_label] = False
-        idx = np.nonzero(keep)[0]
-        boxes = np.stack([mrec['r0'][idx], mrec['c0'][idx], mrec['r1'][idx] - mrec['r0'][idx], mrec['c1'][idx] - mrec['c0'][idx]], axis=1).astype(np.int32)
-        obj_image = (np.searchsorted(rec_off, idx, side='right') - 1).astype(np.int32)
+        self.idx = idx = np.nonzero(keep)[0]
+        self.boxes = boxes = np.stack([mrec['r0'][idx], mrec['c0'][idx], mrec['r1'][idx] - mrec['r0'][idx], mrec['c1'][idx] - mrec['c0'][idx]], axis=1).astype(np.int32)
+        self.obj_image = obj_image = (np.searchsorted(rec_off, idx, side='right') - 1).astype(np.int32)
         words = (boxes[:, 2].astype(np.int64) * boxes[:, 3] + 31) // 32
-        total = int(words.sum())
-        if total > _capi.SHAPE_MAX_WINDOW_WORDS:                               # (nothing of the shape kernels has been launched)
-            raise ValueError(f'the windows of the labels take {total} words: the label form of the shape tables takes up to {_capi.SHAPE_MAX_WINDOW_WORDS} '
+        self.total = total = int(words.sum())
+        if total > _capi.SHAPE_MAX_WINDOW_WORDS:                               # (nothing of the caller's kernels has been launched)
+            raise ValueError(f'the windows of the labels take {total} words: the label form of the {what} tables takes up to {_capi.SHAPE_MAX_WINDOW_WORDS} '
                              'per set, see DESIGN.md "Limits"')
         label_obj = np.full(int(n_labels.sum()), -1, np.int32)
         label_obj[idx] = np.arange(len(idx), dtype=np.int32)
-        n = len(idx)
-        B = self._buffers(boxes)
-        d_bits = S.torch.empty(max(1, total), dtype=S.torch.int32, device=S.dev)
-        d_label_obj, d_image, d_boxes, d_off = S._up(label_obj), S._up(obj_image), S._up(boxes.reshape(-1, 4)), S._up(_exclusive(words))
-        S.capi.check(S.L.sdsm_shape_labels_multi(S.table, self.n_im, S._p(d_labels), c_off, c_n, S._p(d_label_obj), n, S._p(d_image),
-                                                 S._p(d_boxes), S._p(d_off), total, S._p(d_bits), S._p(B['d_slot_off']),
-                                                 S._p(B['d_slots']), S._p(B['d_out']), S._p(B['d_vert_off']), S._p(B['d_verts']), S._p(d_bad), S._stream()),
-                     'sdsm_shape_labels_multi')
-        recs, offsets, vertices = self._download(B, n)
-        first = np.searchsorted(obj_image, np.arange(self.n_im + 1))
-        return [((idx[a:b] - rec_off[i]).astype(np.int64), int(n_labels[i])) + _split(recs, offsets, vertices, a, b)
-                for i, (a, b) in enumerate(zip(first[:-1], first[1:]))]
+        self.d_bits = S.torch.empty(max(1, total), dtype=S.torch.int32, device=S.dev)
+        self.d_label_obj, self.d_image, self.d_boxes, self.d_off = S._up(label_obj), S._up(obj_image), S._up(boxes.reshape(-1, 4)), S._up(_exclusive(words))
+
+    def per_image(self):
+        """Per image (labels measured, number of labels, first window, end of its windows)."""
+        first = np.searchsorted(self.obj_image, np.arange(self.n_im + 1))
+        return [((self.idx[a:b] - self.rec_off[i]).astype(np.int64), int(self.n_labels[i]), a, b) for i, (a, b) in enumerate(zip(first[:-1], first[1:]))]
 
 
 def _split(recs, offsets, vertices, a, b):

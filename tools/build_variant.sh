@@ -10,7 +10,7 @@ flags="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -munsafe-fp-atomics $*"
 echo "$flags" > "$out/flags.new"
 if ! cmp -s "$out/flags.new" "$out/flags" 2>/dev/null; then rm -f "$out"/*.o; mv "$out/flags.new" "$out/flags"; fi
 pids=()
-for f in sdsm_api.hip sdsm_plan.hip sdsm_sides.hip sdsm_prepare.hip sdsm_setup.hip sdsm_solve.hip sdsm_post.hip sdsm_c2f.hip sdsm_render.hip sdsm_measure.hip sdsm_shape.hip sdsm_host.cpp; do
+for f in sdsm_api.hip sdsm_plan.hip sdsm_sides.hip sdsm_prepare.hip sdsm_setup.hip sdsm_solve.hip sdsm_post.hip sdsm_c2f.hip sdsm_render.hip sdsm_measure.hip sdsm_shape.hip sdsm_intensity.hip sdsm_host.cpp; do
   o=$out/${f%.*}.o
   if [ ! -f "$o" ] || [ "$src/$f" -nt "$o" ] || [ "$src/sdsm_common.h" -nt "$o" ] || [ "$root/include/sdsm.h" -nt "$o" ] || { [ -f "$src/sdsm_logtab.h" ] && [ "$src/sdsm_logtab.h" -nt "$o" ]; }; then
     /opt/rocm/bin/hipcc $flags -c "$src/$f" -o "$o" & pids+=($!)
