@@ -657,6 +657,81 @@ int sdsm_intensity_labels_multi(const sdsm_set_image *images, int n_images, cons
                                 const int32_t *num, const int32_t *den, sdsm_intensity_record *d_out, double *d_order, int32_t *d_bad,
                                 void *stream);
 
+/* ---- texture tables: grey-level co-occurrence per object (no reference counterpart; the definitions are texture_objects_host and
+ * texture_labels_host of superdsm_amd/texture.py) --------------------------------------------------------------------------------------
+ * Per object and offset the non-zero cells of the grey-level co-occurrence matrix as exact integer counts, from which
+ * superdsm_amd/texture.py derives the Haralick features on the host.  Conventions as for the intensity tables (objects as
+ * sdsm_post_objects takes them, sets as a HOST table of sdsm_set_image, H, W <= 65535, H * W < 2^31; d_g float64, required).
+ *
+ * Levels: image i has levels - 1 edges, d_edges[i * (levels - 1) ..] (float64 on the device, finite and strictly increasing: the
+ * caller's duty, the device cannot be checked from here); the level of a finite pixel g is the number of edges <= g
+ * (sdsm_texture_level), 0 .. levels - 1; -0.0 compares as 0.0.  A non-finite pixel has no level, takes part in no pair and sets flag
+ * bit 1.  1 <= levels <= SDSM_TEXTURE_MAX_LEVELS; with levels == 1 d_edges may be NULL.
+ * Offsets: n_offsets pairs (d_row, d_col) (HOST array, launch arguments), 1 <= n_offsets <= SDSM_TEXTURE_MAX_OFFSETS, none (0, 0), each
+ * with max(|d_row|, |d_col|) <= SDSM_TEXTURE_MAX_REACH, none twice and none together with its negative.
+ * Counts: for object k and offset o every pixel p with p and p + o both in the object and both finite adds 1 to the cell
+ * (min(a, b), max(a, b)) of the levels a of p and b of p + o: the UNORDERED counts c(i, j), i <= j, each below 2^31.  The symmetric
+ * matrix of the literature is c(i, j) off the diagonal and 2 c(i, i) on it.  Every count is an integer sum, and the cells are written in
+ * ascending (i, j) order by a scan, so the bytes do not depend on the order, the launch or the set size. */
+#define SDSM_TEXTURE_MAX_LEVELS 256
+#define SDSM_TEXTURE_MAX_OFFSETS 8
+#define SDSM_TEXTURE_MAX_REACH 32
+#define SDSM_TEXTURE_MAX_SLOTS (1ll << 26)      /* entries of the padded list of a call, all objects and offsets (512 MB) */
+typedef struct {
+    int64_t area;                       /* pixels */
+    int64_t n_finite;                   /* pixels with a finite intensity */
+    int32_t level_min, level_max;       /* over the finite pixels; levels and -1 when there are none */
+    int32_t flags;                      /* bit 0: the bounding box of the pixels touches the image frame; bit 1: a non-finite intensity
+                                           inside; bit 2: no finite pixel */
+    int32_t reserved;                   /* 0 */
+} sdsm_texture_record;                  /* 32 bytes */
+typedef struct {
+    int64_t n_pairs;                    /* pairs of (object, offset): the sum of its counts */
+    int64_t first;                      /* its first entry in d_entries: the running sum of n_entries */
+    int32_t n_entries;                  /* its non-zero cells */
+    int32_t reserved;                   /* 0 */
+} sdsm_texture_pairs;                   /* 24 bytes */
+typedef struct {
+    uint16_t i, j;                      /* the cell, i <= j */
+    uint32_t count;                     /* c(i, j) > 0 */
+} sdsm_texture_entry;                   /* 8 bytes */
+/* Host helpers (no device access), the inline functions the kernels use (csrc/sdsm_texture.h).  sdsm_texture_level: the level of g among
+ * n_edges edges, -1 for a bad argument (n_edges outside 0 .. 255, edges NULL with n_edges > 0) or a non-finite g.  sdsm_texture_cell: the
+ * place of the cell (i, j), 0 <= i <= j < levels, in the packed upper triangle, i * (2 levels - i + 1) / 2 + j - i; -1 otherwise. */
+int sdsm_texture_level(const double *edges, int n_edges, double g);
+int sdsm_texture_cell(int levels, int i, int j);
+/* d_out[k] (n records), d_pairs[k * n_offsets + o] and the entries for object k of d_boxes / d_bits_off (n of them; d_obj_image int32,
+ * NULL for one image), one workgroup per object and offset, no global atomics; no output needs clearing.  (k, o) writes its cells in
+ * ascending (i, j) order into d_slots from entry d_slot_off[k * n_offsets + o] on, d_slot_off[k * n_offsets + o + 1] -
+ * d_slot_off[k * n_offsets + o] at most (n * n_offsets + 1 int64, ascending, workspace of the caller; min(h * w, levels * (levels + 1) /
+ * 2) entries are always enough; d_slot_off[n * n_offsets] <= SDSM_TEXTURE_MAX_SLOTS is the caller's to check); then `first` receives the
+ * exclusive sum of n_entries and d_entries the cells of all (k, o) one behind the other (room for as many entries as d_slots holds is
+ * enough).  The bits of a fragment past h * w are ignored, a box larger than the tight box changes nothing; nothing outside the box is
+ * read.  A fragment without a set bit, and an object whose box is empty or leaves its image, give the empty record (integers 0,
+ * level_min = levels, level_max = -1, flags bit 2 alone) and no pair.  n == 0: no launch. */
+int sdsm_texture_objects(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, const double *d_g,
+                         int levels, const double *d_edges, int n_offsets, const int32_t *offsets, const int64_t *d_slot_off,
+                         sdsm_texture_entry *d_slots, sdsm_texture_record *d_out, sdsm_texture_pairs *d_pairs, sdsm_texture_entry *d_entries,
+                         void *stream);
+int sdsm_texture_objects_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                               const int64_t *d_bits_off, const uint32_t *d_bits, const double *d_g, int levels, const double *d_edges,
+                               int n_offsets, const int32_t *offsets, const int64_t *d_slot_off, sdsm_texture_entry *d_slots,
+                               sdsm_texture_record *d_out, sdsm_texture_pairs *d_pairs, sdsm_texture_entry *d_entries, void *stream);
+/* The same for labels of label maps, by the windows of sdsm_shape_labels: the caller names n windows (d_obj_image, d_boxes, d_bits_off
+ * into the workspace d_bits of window_words <= SDSM_SHAPE_MAX_WINDOW_WORDS words, which the call clears) and d_label_obj; a first kernel
+ * sets the bit of every pixel in the window of its label -- so a pair across two labels is not counted --, then the windows are measured
+ * as objects.  d_bad as there. */
+int sdsm_texture_labels(int H, int W, const int32_t *d_labels, int n_labels, const int32_t *d_label_obj, int n, const int32_t *d_boxes,
+                        const int64_t *d_bits_off, int64_t window_words, uint32_t *d_bits, const double *d_g, int levels, const double *d_edges,
+                        int n_offsets, const int32_t *offsets, const int64_t *d_slot_off, sdsm_texture_entry *d_slots,
+                        sdsm_texture_record *d_out, sdsm_texture_pairs *d_pairs, sdsm_texture_entry *d_entries, int32_t *d_bad, void *stream);
+int sdsm_texture_labels_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int64_t *rec_off,
+                              const int32_t *n_labels, const int32_t *d_label_obj, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                              const int64_t *d_bits_off, int64_t window_words, uint32_t *d_bits, const double *d_g, int levels,
+                              const double *d_edges, int n_offsets, const int32_t *offsets, const int64_t *d_slot_off,
+                              sdsm_texture_entry *d_slots, sdsm_texture_record *d_out, sdsm_texture_pairs *d_pairs,
+                              sdsm_texture_entry *d_entries, int32_t *d_bad, void *stream);
+
 /* ---- contingency table of two label maps (no reference counterpart; the definition is overlap_pairs_host of superdsm_amd/compare.py) --
  * For two label maps of one image (d_a, d_b: int32, packed as the table of the set says) the number of pixels of every pair of labels
  * (a, b) that occurs, background members included, in a hash table per image: image i owns the slots table_off[i] .. table_off[i] +

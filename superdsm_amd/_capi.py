@@ -97,6 +97,15 @@ _INTENSITY_FIELDS = [('area', 'i8'), ('n_finite', 'i8'), ('sum_p', 'i8'), ('sum_
                      ('med_lo', 'f8'), ('med_hi', 'f8'), ('mad_lo', 'f8'), ('mad_hi', 'f8'), ('range_exp', 'i4'), ('flags', 'i4')]
 INTENSITY_RECORD_DTYPE = np.dtype(_INTENSITY_FIELDS)                               # sdsm_intensity_record
 assert INTENSITY_RECORD_DTYPE.itemsize == 96
+TEXTURE_MAX_LEVELS = 256            # SDSM_TEXTURE_MAX_LEVELS: grey levels of the texture tables
+TEXTURE_MAX_OFFSETS = 8             # SDSM_TEXTURE_MAX_OFFSETS: offsets of one call of the texture tables
+TEXTURE_MAX_REACH = 32              # SDSM_TEXTURE_MAX_REACH: largest |d_row|, |d_col| of an offset
+TEXTURE_MAX_SLOTS = 1 << 26         # SDSM_TEXTURE_MAX_SLOTS: entries of the padded list of a call of the texture tables
+_TEXTURE_FIELDS = [('area', 'i8'), ('n_finite', 'i8'), ('level_min', 'i4'), ('level_max', 'i4'), ('flags', 'i4'), ('reserved', 'i4')]
+TEXTURE_RECORD_DTYPE = np.dtype(_TEXTURE_FIELDS)                                   # sdsm_texture_record
+TEXTURE_PAIRS_DTYPE = np.dtype([('n_pairs', 'i8'), ('first', 'i8'), ('n_entries', 'i4'), ('reserved', 'i4')])   # sdsm_texture_pairs
+TEXTURE_ENTRY_DTYPE = np.dtype([('i', 'u2'), ('j', 'u2'), ('count', 'u4')])        # sdsm_texture_entry
+assert TEXTURE_RECORD_DTYPE.itemsize == 32 and TEXTURE_PAIRS_DTYPE.itemsize == 24 and TEXTURE_ENTRY_DTYPE.itemsize == 8
 
 
 class MeasureRecord(C.Structure):
@@ -222,6 +231,15 @@ SYMBOLS = {
                                      _vp]),
     'sdsm_intensity_labels_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp,
                                            _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp, _vp]),
+    'sdsm_texture_level': (_i32, [C.POINTER(C.c_double), _i32, _f64]),
+    'sdsm_texture_cell': (_i32, [_i32, _i32, _i32]),
+    'sdsm_texture_objects': (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_texture_objects_multi': (_i32, [C.POINTER(SetImage), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp,
+                                          _vp, _vp]),
+    'sdsm_texture_labels': (_i32, [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _i32, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp]),
+    'sdsm_texture_labels_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp,
+                                         _i32, _vp, _i32, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sdsm_overlap_pairs': (_i32, [_i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     'sdsm_overlap_pairs_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _vp, _vp, _vp, _vp]),
     'sdsm_label_pixel_counts': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp]),

@@ -909,6 +909,94 @@ extern "C" int sdsm_intensity_labels(int H, int W, const int32_t *d_labels, int 
                                        num, den, d_out, d_order, d_bad, stream);
 }
 
+// ---- texture tables (sdsm_texture.hip; the label form fills its windows with the scatter step of sdsm_shape.hip) -----------------------
+extern "C" hipError_t sdsm_texture_objects_impl(const sdsm_set_image *images, int n_images, int n, const int32_t *obj_image, const int32_t *boxes,
+                                                const int64_t *bits_off, const uint32_t *bits, const double *d_g, int levels, const double *d_edges,
+                                                int n_offsets, const int32_t *offsets, const int64_t *slot_off, sdsm_texture_entry *slots,
+                                                sdsm_texture_record *out, sdsm_texture_pairs *pairs, sdsm_texture_entry *entries, hipStream_t stream);
+
+// the offsets of a call: 1 .. 8 pairs, none (0, 0), reach <= 32, none twice or together with its negative
+static bool texture_offsets_ok(int n_offsets, const int32_t *offsets)
+{
+    if (n_offsets < 1 || n_offsets > SDSM_TEXTURE_MAX_OFFSETS || !offsets) return false;
+    for (int o = 0; o < n_offsets; o++) {
+        const int dr = offsets[2 * o], dc = offsets[2 * o + 1];
+        if ((dr == 0 && dc == 0) || dr < -SDSM_TEXTURE_MAX_REACH || dr > SDSM_TEXTURE_MAX_REACH || dc < -SDSM_TEXTURE_MAX_REACH || dc > SDSM_TEXTURE_MAX_REACH)
+            return false;
+        for (int p = 0; p < o; p++)
+            if ((offsets[2 * p] == dr && offsets[2 * p + 1] == dc) || (offsets[2 * p] == -dr && offsets[2 * p + 1] == -dc)) return false;
+    }
+    return true;
+}
+
+#define TEXTURE_ARGS(name) \
+    if (n < 0 || n > INT_MAX / SDSM_TEXTURE_MAX_OFFSETS) return fail(SDSM_ERR_ARGUMENT, name ": 0 <= n <= (2^31 - 1) / 8 required"); \
+    if (levels < 1 || levels > SDSM_TEXTURE_MAX_LEVELS) return fail(SDSM_ERR_ARGUMENT, name ": 1 <= levels <= 256 required"); \
+    if (!texture_offsets_ok(n_offsets, offsets)) \
+        return fail(SDSM_ERR_ARGUMENT, name ": 1 <= n_offsets <= 8 offsets, none (0, 0), |d_row|, |d_col| <= 32, none twice or with its negative required")
+
+extern "C" int sdsm_texture_objects_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                                          const int64_t *d_bits_off, const uint32_t *d_bits, const double *d_g, int levels, const double *d_edges,
+                                          int n_offsets, const int32_t *offsets, const int64_t *d_slot_off, sdsm_texture_entry *d_slots,
+                                          sdsm_texture_record *d_out, sdsm_texture_pairs *d_pairs, sdsm_texture_entry *d_entries, void *stream)
+{
+    SET_TABLE("sdsm_texture_objects", SET_SIDES | SET_PIXELS);
+    TEXTURE_ARGS("sdsm_texture_objects");
+    if (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_g || (levels > 1 && !d_edges) || !d_slot_off || !d_slots || !d_out || !d_pairs || !d_entries ||
+                  (n_images > 1 && !d_obj_image)))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_texture_objects: null argument");
+    hipError_t e = sdsm_texture_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_g, levels, d_edges, n_offsets, offsets,
+                                             d_slot_off, d_slots, d_out, d_pairs, d_entries, (hipStream_t)stream);
+    SET_DONE("sdsm_texture_objects");
+}
+
+extern "C" int sdsm_texture_objects(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, const double *d_g,
+                                    int levels, const double *d_edges, int n_offsets, const int32_t *offsets, const int64_t *d_slot_off,
+                                    sdsm_texture_entry *d_slots, sdsm_texture_record *d_out, sdsm_texture_pairs *d_pairs, sdsm_texture_entry *d_entries,
+                                    void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_texture_objects_multi(&one, 1, n, nullptr, d_boxes, d_bits_off, d_bits, d_g, levels, d_edges, n_offsets, offsets, d_slot_off, d_slots, d_out,
+                                      d_pairs, d_entries, stream);
+}
+
+extern "C" int sdsm_texture_labels_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int64_t *rec_off,
+                                         const int32_t *n_labels, const int32_t *d_label_obj, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                                         const int64_t *d_bits_off, int64_t window_words, uint32_t *d_bits, const double *d_g, int levels,
+                                         const double *d_edges, int n_offsets, const int32_t *offsets, const int64_t *d_slot_off,
+                                         sdsm_texture_entry *d_slots, sdsm_texture_record *d_out, sdsm_texture_pairs *d_pairs,
+                                         sdsm_texture_entry *d_entries, int32_t *d_bad, void *stream)
+{
+    SET_TABLE("sdsm_texture_labels", SET_SIDES | SET_PIXELS);
+    TEXTURE_ARGS("sdsm_texture_labels");
+    if (window_words < 0 || window_words > SDSM_SHAPE_MAX_WINDOW_WORDS)
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_texture_labels: 0 <= window_words <= SDSM_SHAPE_MAX_WINDOW_WORDS required");
+    if (!d_labels || !rec_off || !n_labels || !d_label_obj || !d_bad ||
+        (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_g || (levels > 1 && !d_edges) || !d_slot_off || !d_slots || !d_out || !d_pairs || !d_entries ||
+                   (n_images > 1 && !d_obj_image))))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_texture_labels: null argument");
+    for (int i = 0; i < n_images; i++)
+        if (n_labels[i] < 1 || n_labels[i] > SDSM_MEASURE_MAX_LABELS || rec_off[i] < 0)
+            return fail(SDSM_ERR_ARGUMENT, "sdsm_texture_labels: 1 <= n_labels <= 65536 and rec_off >= 0 required");
+    hipError_t e = sdsm_shape_scatter_impl(images, n_images, d_labels, rec_off, n_labels, d_label_obj, n, d_boxes, d_bits_off, window_words, d_bits, d_bad,
+                                           (hipStream_t)stream);
+    if (e == hipSuccess)
+        e = sdsm_texture_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_g, levels, d_edges, n_offsets, offsets, d_slot_off,
+                                      d_slots, d_out, d_pairs, d_entries, (hipStream_t)stream);
+    SET_DONE("sdsm_texture_labels");
+}
+
+extern "C" int sdsm_texture_labels(int H, int W, const int32_t *d_labels, int n_labels, const int32_t *d_label_obj, int n, const int32_t *d_boxes,
+                                   const int64_t *d_bits_off, int64_t window_words, uint32_t *d_bits, const double *d_g, int levels,
+                                   const double *d_edges, int n_offsets, const int32_t *offsets, const int64_t *d_slot_off, sdsm_texture_entry *d_slots,
+                                   sdsm_texture_record *d_out, sdsm_texture_pairs *d_pairs, sdsm_texture_entry *d_entries, int32_t *d_bad, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    const int64_t off = 0;
+    return sdsm_texture_labels_multi(&one, 1, d_labels, &off, &n_labels, d_label_obj, n, nullptr, d_boxes, d_bits_off, window_words, d_bits, d_g, levels,
+                                     d_edges, n_offsets, offsets, d_slot_off, d_slots, d_out, d_pairs, d_entries, d_bad, stream);
+}
+
 // ---- contingency table of two label maps (sdsm_measure.hip) ---------------------------------------------------------------------------
 extern "C" hipError_t sdsm_overlap_pairs_impl(const sdsm_set_image *images, int n_images, const int32_t *d_a, const int32_t *d_b,
                                               const int64_t *table_off, const int64_t *capacity, uint64_t *d_keys, uint64_t *d_counts,

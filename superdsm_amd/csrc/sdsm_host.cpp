@@ -15,6 +15,7 @@
 
 #include "../../include/sdsm.h"
 #include "sdsm_quantile.h"
+#include "sdsm_texture.h"
 
 namespace {
 
@@ -269,4 +270,17 @@ extern "C" int sdsm_quantile_ranks(int64_t n, int32_t num, int32_t den, int64_t 
     if (n < 1 || n > INT32_MAX || den < 1 || den > SDSM_INTENSITY_MAX_DEN || num < 0 || num > den || !lo || !hi || !rem) return SDSM_ERR_ARGUMENT;
     sdsm_quantile_ranks_inline(n, num, den, lo, hi, rem);
     return SDSM_OK;
+}
+
+// The level of a value and the place of a cell, as the texture kernels take them (sdsm_texture.h: the same inline functions).
+extern "C" int sdsm_texture_level(const double *edges, int n_edges, double g)
+{
+    if (n_edges < 0 || n_edges > SDSM_TEXTURE_MAX_LEVELS - 1 || (n_edges > 0 && !edges) || !(g - g == 0)) return -1;
+    return sdsm_texture_level_inline(edges, n_edges, g);
+}
+
+extern "C" int sdsm_texture_cell(int levels, int i, int j)
+{
+    if (levels < 1 || levels > SDSM_TEXTURE_MAX_LEVELS || i < 0 || j < i || j >= levels) return -1;
+    return sdsm_texture_cell_inline(levels, i, j);
 }
