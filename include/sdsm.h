@@ -806,6 +806,56 @@ int sdsm_pair_distances(int H, int W, const int32_t *d_a, const int32_t *d_b, co
  * until r * r <= d2 * 2^32 < (r + 1) * (r + 1)); a negative d2 gives 0. */
 int sdsm_quantised_distance(const int32_t *d2, int64_t n, int64_t *out);
 
+/* ---- neighbourhood tables of one label map (no reference counterpart; the definitions are neighbour_pairs_host and
+ * neighbour_labels_host of superdsm_amd/neighbours.py) -------------------------------------------------------------------------------
+ * How the objects of one label map lie to each other, in integers only.  Two pixels are WITHIN REACH iff their squared Euclidean
+ * distance is <= max_d2, 1 <= max_d2 <= SDSM_NEIGHBOUR_MAX_D2 (a reach of 64 pixels; 1 sees edge contacts only, 2 the 8-connected ones).
+ * Pairs: an unordered pair of labels a < b, both >= 1, has an entry iff some pixel of a and some pixel of b are within reach; min_d2 is
+ * the smallest squared distance between a pixel of a and a pixel of b, contact_edges the number of crack edges between them (4-adjacent
+ * pixel pairs with one pixel in each, counted once).  Labels: per label the pixels, the boundary pixels as sdsm_label_pixel_counts
+ * defines them (the image frame makes no boundary), the boundary pixels with a pixel of another label >= 1 within reach, and the pixel
+ * sides by what they face.  Label 0's record holds its area and zeros.
+ * Conventions as for the tables above: sets as a HOST table of sdsm_set_image, d_labels int32 packed as the table says, the
+ * single-image form is the set of that one image; every atomic is an integer min, add or compare-and-swap, so after a sort of the pair
+ * table by key the bytes do not depend on the arrival order, the launch, the set size or the capacity.
+ * Limits: labels 0 .. n_labels - 1 <= 65535 (others are counted and skipped: they count for nothing of their own and the other pixels
+ * see them as label 0), H * H + W * W < 2^31 per image, 1 .. SDSM_MAX_SET_IMAGES images. */
+#define SDSM_NEIGHBOUR_MAX_D2 4096
+typedef struct {
+    int64_t edges_background;           /* pixel sides of the label that face label 0 */
+    int64_t edges_labels;               /* ... that face another label >= 1: the sum of contact_edges over the label's pairs */
+    int64_t edges_frame;                /* ... that lie on the image frame */
+    int32_t area;                       /* pixels */
+    int32_t boundary;                   /* boundary pixels */
+    int32_t close;                      /* boundary pixels with a pixel of another label >= 1 within reach; <= boundary */
+    int32_t reserved;                   /* 0 */
+} sdsm_neighbour_label;                 /* 40 bytes */
+typedef struct {
+    int32_t a, b;                       /* the two labels, 1 <= a < b */
+    int32_t min_d2;                     /* 1 .. max_d2 */
+    int32_t contact_edges;              /* > 0 iff min_d2 == 1 */
+} sdsm_neighbour_pair;                  /* 16 bytes: a row of the sorted table the host makes of the occupied slots */
+/* Host helpers (no device access), the inline functions the kernel uses (csrc/sdsm_neighbours.h).  sdsm_neighbour_halfwidth: the largest
+ * |d_col| with d_row^2 + d_col^2 <= max_d2, by an integer root; -1 when the row lies outside the disk or max_d2 is outside
+ * 1 .. SDSM_NEIGHBOUR_MAX_D2.  sdsm_neighbour_slot: the slot a key is tried at first in a table of `capacity` slots (linear probing
+ * from there); -1 unless capacity is a power of two >= 1. */
+int sdsm_neighbour_halfwidth(int max_d2, int d_row);
+int64_t sdsm_neighbour_slot(uint64_t key, int64_t capacity);
+/* d_label_out[rec_off[i] + l] for the labels 0 <= l < n_labels[i] of image i (rec_off, n_labels: HOST arrays, as
+ * sdsm_measure_labels_multi takes them; 1 <= n_labels <= 65536; the ranges must not overlap), and the pairs of image i in the slots
+ * table_off[i] .. table_off[i] + capacity[i] - 1 of d_keys, d_min_d2 and d_contact (HOST arrays; the per-image open-addressing table of
+ * sdsm_overlap_pairs_multi with two uint32 values instead of one count): an occupied slot holds the key (uint64_t)a << 32 | b, a < b,
+ * with its min_d2 and contact_edges; a free one the key ~0, min_d2 0xffffffff and contact_edges 0.  The call clears everything it
+ * writes into, on the stream.
+ * d_status: 2 int32 per image.  [0]: pixels with a label < 0 or >= n_labels; they are skipped.  [1]: insertions that found every slot
+ * of the table taken; they are dropped, so the table is then incomplete and the caller launches again with a larger one (the label
+ * records are complete all the same).  The kernel never waits for a slot. */
+int sdsm_neighbours_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, int max_d2, const int64_t *rec_off,
+                          const int32_t *n_labels, sdsm_neighbour_label *d_label_out, const int64_t *table_off, const int64_t *capacity,
+                          uint64_t *d_keys, uint32_t *d_min_d2, uint32_t *d_contact, int32_t *d_status, void *stream);
+int sdsm_neighbours(int H, int W, const int32_t *d_labels, int max_d2, int n_labels, sdsm_neighbour_label *d_label_out, int64_t capacity,
+                    uint64_t *d_keys, uint32_t *d_min_d2, uint32_t *d_contact, int32_t *d_status, void *stream);   /* the set of one image */
+
 /* ---- host-side combinatorial steps of the stage (no device access) -------------------------------------------------------------
  * Approximate min-weight set cover (superdsm/minsetcover.py:4-88: greedy + merge phase, retried with beta * gamma on up to max_iter
  * levels) and greedy max-weight set packing (superdsm/maxsetpack.py:8-24) over n objects whose footprints are bit sets of `words`

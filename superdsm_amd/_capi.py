@@ -106,6 +106,11 @@ TEXTURE_RECORD_DTYPE = np.dtype(_TEXTURE_FIELDS)                                
 TEXTURE_PAIRS_DTYPE = np.dtype([('n_pairs', 'i8'), ('first', 'i8'), ('n_entries', 'i4'), ('reserved', 'i4')])   # sdsm_texture_pairs
 TEXTURE_ENTRY_DTYPE = np.dtype([('i', 'u2'), ('j', 'u2'), ('count', 'u4')])        # sdsm_texture_entry
 assert TEXTURE_RECORD_DTYPE.itemsize == 32 and TEXTURE_PAIRS_DTYPE.itemsize == 24 and TEXTURE_ENTRY_DTYPE.itemsize == 8
+NEIGHBOUR_MAX_D2 = 4096             # SDSM_NEIGHBOUR_MAX_D2: largest squared reach of the neighbourhood tables (64 pixels)
+NEIGHBOUR_LABEL_DTYPE = np.dtype([('edges_background', '<i8'), ('edges_labels', '<i8'), ('edges_frame', '<i8'), ('area', '<i4'), ('boundary', '<i4'),
+                                  ('close', '<i4'), ('reserved', '<i4')])                  # sdsm_neighbour_label
+NEIGHBOUR_PAIR_DTYPE = np.dtype([('a', '<i4'), ('b', '<i4'), ('min_d2', '<i4'), ('contact_edges', '<i4')])   # sdsm_neighbour_pair
+assert NEIGHBOUR_LABEL_DTYPE.itemsize == 40 and NEIGHBOUR_PAIR_DTYPE.itemsize == 16
 
 
 class MeasureRecord(C.Structure):
@@ -242,6 +247,11 @@ SYMBOLS = {
                                          _i32, _vp, _i32, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sdsm_overlap_pairs': (_i32, [_i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     'sdsm_overlap_pairs_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _vp, _vp, _vp, _vp]),
+    'sdsm_neighbour_halfwidth': (_i32, [_i32, _i32]),
+    'sdsm_neighbour_slot': (_i64, [C.c_uint64, _i64]),
+    'sdsm_neighbours': (_i32, [_i32, _i32, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_neighbours_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _i32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_int64), _vp, _vp, _vp, _vp, _vp]),
     'sdsm_label_pixel_counts': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp]),
     'sdsm_label_pixel_counts_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, _vp, _vp]),
     'sdsm_label_pixel_lists': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1026,6 +1026,48 @@ extern "C" int sdsm_overlap_pairs(int H, int W, const int32_t *d_a, const int32_
     return sdsm_overlap_pairs_multi(&one, 1, d_a, d_b, &off, &capacity, d_keys, d_counts, d_status, stream);
 }
 
+// ---- neighbourhood tables of one label map (sdsm_neighbours.hip) -----------------------------------------------------------------------
+extern "C" hipError_t sdsm_neighbours_impl(const sdsm_set_image *images, int n_images, const int32_t *d_labels, int max_d2, const int64_t *rec_off,
+                                           const int32_t *n_labels, sdsm_neighbour_label *d_label_out, const int64_t *table_off,
+                                           const int64_t *capacity, uint64_t *d_keys, uint32_t *d_min_d2, uint32_t *d_contact, int32_t *d_status,
+                                           hipStream_t stream);
+
+extern "C" int sdsm_neighbours_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, int max_d2, const int64_t *rec_off,
+                                     const int32_t *n_labels, sdsm_neighbour_label *d_label_out, const int64_t *table_off, const int64_t *capacity,
+                                     uint64_t *d_keys, uint32_t *d_min_d2, uint32_t *d_contact, int32_t *d_status, void *stream)
+{
+    if (max_d2 < 1 || max_d2 > SDSM_NEIGHBOUR_MAX_D2) return fail(SDSM_ERR_ARGUMENT, "sdsm_neighbours: 1 <= max_d2 <= 4096 required");
+    SET_TABLE("sdsm_neighbours", 0);
+    for (int i = 0; i < n_images; i++)
+        if ((int64_t)images[i].H * images[i].H + (int64_t)images[i].W * images[i].W >= (int64_t)1 << 31)
+            return fail(SDSM_ERR_ARGUMENT, "sdsm_neighbours: H * H + W * W < 2^31 required");
+    if (!d_labels || !rec_off || !n_labels || !d_label_out || !table_off || !capacity || !d_keys || !d_min_d2 || !d_contact || !d_status)
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_neighbours: null argument");
+    for (int i = 0; i < n_images; i++) {
+        if (n_labels[i] < 1 || n_labels[i] > SDSM_MEASURE_MAX_LABELS || rec_off[i] < 0)
+            return fail(SDSM_ERR_ARGUMENT, "sdsm_neighbours: 1 <= n_labels <= 65536 and rec_off >= 0 required");
+        if (capacity[i] < 1 || (capacity[i] & (capacity[i] - 1)) != 0 || table_off[i] < 0)
+            return fail(SDSM_ERR_ARGUMENT, "sdsm_neighbours: capacity a power of two >= 1 and table_off >= 0 required");
+        for (int j = 0; j < i; j++) {
+            if (rec_off[i] < rec_off[j] + n_labels[j] && rec_off[j] < rec_off[i] + n_labels[i])
+                return fail(SDSM_ERR_ARGUMENT, "sdsm_neighbours: the records of two images overlap");
+            if (table_off[i] < table_off[j] + capacity[j] && table_off[j] < table_off[i] + capacity[i])
+                return fail(SDSM_ERR_ARGUMENT, "sdsm_neighbours: the tables of two images overlap");
+        }
+    }
+    hipError_t e = sdsm_neighbours_impl(images, n_images, d_labels, max_d2, rec_off, n_labels, d_label_out, table_off, capacity, d_keys, d_min_d2,
+                                        d_contact, d_status, (hipStream_t)stream);
+    SET_DONE("sdsm_neighbours");
+}
+
+extern "C" int sdsm_neighbours(int H, int W, const int32_t *d_labels, int max_d2, int n_labels, sdsm_neighbour_label *d_label_out, int64_t capacity,
+                               uint64_t *d_keys, uint32_t *d_min_d2, uint32_t *d_contact, int32_t *d_status, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    const int64_t off = 0;
+    return sdsm_neighbours_multi(&one, 1, d_labels, max_d2, &off, &n_labels, d_label_out, &off, &capacity, d_keys, d_min_d2, d_contact, d_status, stream);
+}
+
 // ---- boundary distances between two label maps (sdsm_measure.hip) ---------------------------------------------------------------------
 extern "C" hipError_t sdsm_label_pixel_counts_impl(const sdsm_set_image *images, int n_images, const int32_t *labels, int32_t *counts, int32_t *bad,
                                                    hipStream_t stream);

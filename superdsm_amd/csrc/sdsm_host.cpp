@@ -15,6 +15,7 @@
 
 #include "../../include/sdsm.h"
 #include "sdsm_quantile.h"
+#include "sdsm_neighbours.h"
 #include "sdsm_texture.h"
 
 namespace {
@@ -283,4 +284,19 @@ extern "C" int sdsm_texture_cell(int levels, int i, int j)
 {
     if (levels < 1 || levels > SDSM_TEXTURE_MAX_LEVELS || i < 0 || j < i || j >= levels) return -1;
     return sdsm_texture_cell_inline(levels, i, j);
+}
+
+// The half-width of a row of the disk and the first probe position of a pair, as the neighbourhood kernel takes them (sdsm_neighbours.h:
+// the same inline functions).
+static_assert(SDSM_NEIGHBOUR_MAX_D2 == SDSM_NEIGHBOUR_MAX_D2_INLINE, "the limit of the header and of the inline helpers");
+
+extern "C" int sdsm_neighbour_halfwidth(int max_d2, int d_row)
+{
+    return sdsm_neighbour_halfwidth_inline(max_d2, d_row);
+}
+
+extern "C" int64_t sdsm_neighbour_slot(uint64_t key, int64_t capacity)
+{
+    if (capacity < 1 || (capacity & (capacity - 1)) != 0) return -1;
+    return (int64_t)sdsm_neighbour_slot_inline(key, (uint64_t)capacity);
 }
