@@ -385,6 +385,43 @@ template <class Image> static bool set_table_ok(const Image *images, int n_image
                                        ((limits) & SET_SIDES ? " <= 65535" : "") + ((limits) & SET_PIXELS ? ", H * W < 2^31)" : ")"))
 #define SET_DONE(name) return e == hipSuccess ? SDSM_OK : hipfail(e, name)
 
+// H^2 + W^2 < 2^31: every squared distance fits int32 (and so every side 16 bits, H * W 30 bits)
+static bool boundary_shapes_ok(const sdsm_set_image *images, int n_images)
+{
+    for (int i = 0; i < n_images; i++)
+        if ((int64_t)images[i].H * images[i].H + (int64_t)images[i].W * images[i].W >= (int64_t)1 << 31) return false;
+    return true;
+}
+
+// The ranges [off[i], off[i] + len[i]) that the images of a set own in a shared buffer.  The walk goes image by image: image i's own range
+// (len_ok, off >= 0), then its overlap with every image j before it.  Where it stops, *why is what the message says behind the entry's name
+// and *at a number that grows along the walk, so that an entry with two tables (sdsm_neighbours) reports what comes first.
+template <class Len, class Ok>
+static bool ranges_ok(int n_images, const int64_t *off, const Len *len, Ok len_ok, bool check_overlap, const char *bad_range, const char *overlap,
+                      const char **why, int *at)
+{
+    for (int i = 0; i < n_images; i++) {
+        if (!len_ok(len[i]) || off[i] < 0) { *why = bad_range; if (at) *at = i * (SDSM_MAX_SET_IMAGES + 1); return false; }
+        for (int j = 0; check_overlap && j < i; j++)
+            if (off[i] < off[j] + len[j] && off[j] < off[i] + len[i]) { *why = overlap; if (at) *at = i * (SDSM_MAX_SET_IMAGES + 1) + j + 1; return false; }
+    }
+    return true;
+}
+
+// the label records of a set: n_labels[i] records from rec_off[i] on
+static bool label_records_ok(int n_images, const int32_t *n_labels, const int64_t *rec_off, bool check_overlap, const char **why, int *at = nullptr)
+{
+    return ranges_ok(n_images, rec_off, n_labels, [](int32_t n) { return n >= 1 && n <= SDSM_MEASURE_MAX_LABELS; }, check_overlap,
+                     "1 <= n_labels <= 65536 and rec_off >= 0 required", "the records of two images overlap", why, at);
+}
+
+// the pair tables of a set: capacity[i] slots from table_off[i] on
+static bool pair_tables_ok(int n_images, const int64_t *table_off, const int64_t *capacity, const char **why, int *at = nullptr)
+{
+    return ranges_ok(n_images, table_off, capacity, [](int64_t c) { return c >= 1 && (c & (c - 1)) == 0; }, true,
+                     "capacity a power of two >= 1 and table_off >= 0 required", "the tables of two images overlap", why, at);
+}
+
 extern "C" size_t sdsm_c2f_markers_workspace_bytes_multi(const sdsm_set_image *images, int n_images)
 {
     return set_table_ok(images, n_images, SET_PIXELS) ? sdsm_c2f_markers_workspace_bytes_multi_impl(images, n_images) : 0;
@@ -760,13 +797,8 @@ extern "C" int sdsm_measure_labels_multi(const sdsm_set_image *images, int n_ima
     SET_TABLE("sdsm_measure_labels", SET_SIDES | SET_PIXELS);
     if (!d_labels || !rec_off || !n_labels || !d_out || !d_bad) return fail(SDSM_ERR_ARGUMENT, "sdsm_measure_labels: null argument");
     if (d_g && !d_gmax_abs) return fail(SDSM_ERR_ARGUMENT, "sdsm_measure_labels: intensities need d_gmax_abs");
-    for (int i = 0; i < n_images; i++) {
-        if (n_labels[i] < 1 || n_labels[i] > SDSM_MEASURE_MAX_LABELS || rec_off[i] < 0)
-            return fail(SDSM_ERR_ARGUMENT, "sdsm_measure_labels: 1 <= n_labels <= 65536 and rec_off >= 0 required");
-        for (int j = 0; j < i; j++)
-            if (rec_off[i] < rec_off[j] + n_labels[j] && rec_off[j] < rec_off[i] + n_labels[i])
-                return fail(SDSM_ERR_ARGUMENT, "sdsm_measure_labels: the records of two images overlap");
-    }
+    const char *why;
+    if (!label_records_ok(n_images, n_labels, rec_off, true, &why)) return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_measure_labels: ") + why);
     hipError_t e = sdsm_measure_labels_impl(images, n_images, d_labels, rec_off, n_labels, d_g, d_gmax_abs, d_scale_exp, d_out, d_bad, (hipStream_t)stream);
     SET_DONE("sdsm_measure_labels");
 }
@@ -818,9 +850,8 @@ extern "C" int sdsm_shape_labels_multi(const sdsm_set_image *images, int n_image
     if (!d_labels || !rec_off || !n_labels || !d_label_obj || !d_vert_off || !d_bad ||
         (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_slot_off || !d_slots || !d_out || !d_verts || (n_images > 1 && !d_obj_image))))
         return fail(SDSM_ERR_ARGUMENT, "sdsm_shape_labels: null argument");
-    for (int i = 0; i < n_images; i++)
-        if (n_labels[i] < 1 || n_labels[i] > SDSM_MEASURE_MAX_LABELS || rec_off[i] < 0)
-            return fail(SDSM_ERR_ARGUMENT, "sdsm_shape_labels: 1 <= n_labels <= 65536 and rec_off >= 0 required");
+    const char *why;
+    if (!label_records_ok(n_images, n_labels, rec_off, false, &why)) return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_shape_labels: ") + why);
     hipError_t e = sdsm_shape_scatter_impl(images, n_images, d_labels, rec_off, n_labels, d_label_obj, n, d_boxes, d_bits_off, window_words, d_bits, d_bad,
                                            (hipStream_t)stream);
     if (e == hipSuccess)
@@ -888,9 +919,8 @@ extern "C" int sdsm_intensity_labels_multi(const sdsm_set_image *images, int n_i
     if (!d_labels || !rec_off || !n_labels || !d_label_obj || !d_bad ||
         (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_g || !d_out || (n_q > 0 && !d_order) || (n_images > 1 && !d_obj_image))))
         return fail(SDSM_ERR_ARGUMENT, "sdsm_intensity_labels: null argument");
-    for (int i = 0; i < n_images; i++)
-        if (n_labels[i] < 1 || n_labels[i] > SDSM_MEASURE_MAX_LABELS || rec_off[i] < 0)
-            return fail(SDSM_ERR_ARGUMENT, "sdsm_intensity_labels: 1 <= n_labels <= 65536 and rec_off >= 0 required");
+    const char *why;
+    if (!label_records_ok(n_images, n_labels, rec_off, false, &why)) return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_intensity_labels: ") + why);
     hipError_t e = sdsm_shape_scatter_impl(images, n_images, d_labels, rec_off, n_labels, d_label_obj, n, d_boxes, d_bits_off, window_words, d_bits, d_bad,
                                            (hipStream_t)stream);
     if (e == hipSuccess)
@@ -975,9 +1005,8 @@ extern "C" int sdsm_texture_labels_multi(const sdsm_set_image *images, int n_ima
         (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_g || (levels > 1 && !d_edges) || !d_slot_off || !d_slots || !d_out || !d_pairs || !d_entries ||
                    (n_images > 1 && !d_obj_image))))
         return fail(SDSM_ERR_ARGUMENT, "sdsm_texture_labels: null argument");
-    for (int i = 0; i < n_images; i++)
-        if (n_labels[i] < 1 || n_labels[i] > SDSM_MEASURE_MAX_LABELS || rec_off[i] < 0)
-            return fail(SDSM_ERR_ARGUMENT, "sdsm_texture_labels: 1 <= n_labels <= 65536 and rec_off >= 0 required");
+    const char *why;
+    if (!label_records_ok(n_images, n_labels, rec_off, false, &why)) return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_texture_labels: ") + why);
     hipError_t e = sdsm_shape_scatter_impl(images, n_images, d_labels, rec_off, n_labels, d_label_obj, n, d_boxes, d_bits_off, window_words, d_bits, d_bad,
                                            (hipStream_t)stream);
     if (e == hipSuccess)
@@ -1007,13 +1036,8 @@ extern "C" int sdsm_overlap_pairs_multi(const sdsm_set_image *images, int n_imag
 {
     SET_TABLE("sdsm_overlap_pairs", SET_PIXELS);
     if (!d_a || !d_b || !table_off || !capacity || !d_keys || !d_counts || !d_status) return fail(SDSM_ERR_ARGUMENT, "sdsm_overlap_pairs: null argument");
-    for (int i = 0; i < n_images; i++) {
-        if (capacity[i] < 1 || (capacity[i] & (capacity[i] - 1)) != 0 || table_off[i] < 0)
-            return fail(SDSM_ERR_ARGUMENT, "sdsm_overlap_pairs: capacity a power of two >= 1 and table_off >= 0 required");
-        for (int j = 0; j < i; j++)
-            if (table_off[i] < table_off[j] + capacity[j] && table_off[j] < table_off[i] + capacity[i])
-                return fail(SDSM_ERR_ARGUMENT, "sdsm_overlap_pairs: the tables of two images overlap");
-    }
+    const char *why;
+    if (!pair_tables_ok(n_images, table_off, capacity, &why)) return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_overlap_pairs: ") + why);
     hipError_t e = sdsm_overlap_pairs_impl(images, n_images, d_a, d_b, table_off, capacity, d_keys, d_counts, d_status, (hipStream_t)stream);
     SET_DONE("sdsm_overlap_pairs");
 }
@@ -1038,23 +1062,13 @@ extern "C" int sdsm_neighbours_multi(const sdsm_set_image *images, int n_images,
 {
     if (max_d2 < 1 || max_d2 > SDSM_NEIGHBOUR_MAX_D2) return fail(SDSM_ERR_ARGUMENT, "sdsm_neighbours: 1 <= max_d2 <= 4096 required");
     SET_TABLE("sdsm_neighbours", 0);
-    for (int i = 0; i < n_images; i++)
-        if ((int64_t)images[i].H * images[i].H + (int64_t)images[i].W * images[i].W >= (int64_t)1 << 31)
-            return fail(SDSM_ERR_ARGUMENT, "sdsm_neighbours: H * H + W * W < 2^31 required");
+    if (!boundary_shapes_ok(images, n_images)) return fail(SDSM_ERR_ARGUMENT, "sdsm_neighbours: H * H + W * W < 2^31 required");
     if (!d_labels || !rec_off || !n_labels || !d_label_out || !table_off || !capacity || !d_keys || !d_min_d2 || !d_contact || !d_status)
         return fail(SDSM_ERR_ARGUMENT, "sdsm_neighbours: null argument");
-    for (int i = 0; i < n_images; i++) {
-        if (n_labels[i] < 1 || n_labels[i] > SDSM_MEASURE_MAX_LABELS || rec_off[i] < 0)
-            return fail(SDSM_ERR_ARGUMENT, "sdsm_neighbours: 1 <= n_labels <= 65536 and rec_off >= 0 required");
-        if (capacity[i] < 1 || (capacity[i] & (capacity[i] - 1)) != 0 || table_off[i] < 0)
-            return fail(SDSM_ERR_ARGUMENT, "sdsm_neighbours: capacity a power of two >= 1 and table_off >= 0 required");
-        for (int j = 0; j < i; j++) {
-            if (rec_off[i] < rec_off[j] + n_labels[j] && rec_off[j] < rec_off[i] + n_labels[i])
-                return fail(SDSM_ERR_ARGUMENT, "sdsm_neighbours: the records of two images overlap");
-            if (table_off[i] < table_off[j] + capacity[j] && table_off[j] < table_off[i] + capacity[i])
-                return fail(SDSM_ERR_ARGUMENT, "sdsm_neighbours: the tables of two images overlap");
-        }
-    }
+    const char *why_l, *why_t;                   // both walks; what the walk over the images meets first is reported (labels before tables)
+    int at_l, at_t;
+    const bool l_ok = label_records_ok(n_images, n_labels, rec_off, true, &why_l, &at_l), t_ok = pair_tables_ok(n_images, table_off, capacity, &why_t, &at_t);
+    if (!l_ok || !t_ok) return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_neighbours: ") + (!l_ok && (t_ok || at_l <= at_t) ? why_l : why_t));
     hipError_t e = sdsm_neighbours_impl(images, n_images, d_labels, max_d2, rec_off, n_labels, d_label_out, table_off, capacity, d_keys, d_min_d2,
                                         d_contact, d_status, (hipStream_t)stream);
     SET_DONE("sdsm_neighbours");
@@ -1079,13 +1093,6 @@ extern "C" hipError_t sdsm_pair_distances_impl(const sdsm_set_image *images, int
                                                const int32_t *items, sdsm_pair_distance *recs, hipStream_t stream);
 extern "C" void sdsm_quantised_distance_impl(const int32_t *d2, int64_t n, int64_t *out);
 
-// H^2 + W^2 < 2^31: every squared distance fits int32 (and so every side 16 bits, H * W 30 bits)
-static bool boundary_shapes_ok(const sdsm_set_image *images, int n_images)
-{
-    for (int i = 0; i < n_images; i++)
-        if ((int64_t)images[i].H * images[i].H + (int64_t)images[i].W * images[i].W >= (int64_t)1 << 31) return false;
-    return true;
-}
 #define BOUNDARY_TABLE(name) \
     SET_TABLE(name, 0); \
     if (!boundary_shapes_ok(images, n_images)) return fail(SDSM_ERR_ARGUMENT, name ": H * H + W * W < 2^31 required")

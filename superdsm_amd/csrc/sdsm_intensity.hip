@@ -2,7 +2,7 @@
 // sdsm_shape.hip) and the two order statistics of every quantile, for one image or a set of images.  No reference counterpart; the
 // definition the kernel is tested against is the host code of superdsm_amd/intensity.py.
 //
-//   k_intensity_objects   one workgroup of 256 threads per fragment, which walks the fragment's words by ctz (as k_measure_objects).
+//   k_intensity_objects   one workgroup of 256 threads per fragment, which walks the fragment's set bits (each_set_bit of sdsm_tables.h).
 //     pass A      area, bounding box, n_finite, the monotone keys of gmin and gmax, the flags; every finite pixel's key goes to LDS while
 //                 there is room (the place by an LDS integer add: the order of the keys does not matter to a selection)
 //     pass B      from gmin and range_exp the three integer sums, in registers, then one shuffle and one LDS reduction
@@ -14,7 +14,7 @@
 //   An object with at most SDSM_INTENSITY_LDS_KEYS finite pixels is selected from its keys in LDS (rewritten in place for the MAD); a
 //   larger one walks its fragment and re-reads d_g in every round: the same bytes, more slowly.
 // No float atomics, no global atomics, no output that needs clearing.
-#include "sdsm_common.h"
+#include "sdsm_tables.h"
 #include "sdsm_quantile.h"
 #include <climits>
 
@@ -24,15 +24,6 @@ constexpr int ITPB = 256;                        // threads of a workgroup = bin
 constexpr int KCAP = SDSM_INTENSITY_LDS_KEYS;
 constexpr int NQ = SDSM_INTENSITY_MAX_QUANTILES;
 constexpr int IWAVES = ITPB / 64;
-
-typedef unsigned long long u64;
-typedef long long i64;
-
-struct ISet {                                    // the images of a launch
-    int32_t n;
-    int32_t H[SDSM_MAX_SET_IMAGES], W[SDSM_MAX_SET_IMAGES];
-    int64_t off[SDSM_MAX_SET_IMAGES];            // first pixel of the image in the packed buffers
-};
 
 struct IQuant {                                  // the quantiles of a launch
     int32_t n_q;
@@ -51,29 +42,11 @@ struct ILds {
 struct Src {                                     // where the keys of the object come from
     const uint32_t *bits;
     const double *g;
-    uint32_t n_words, n_bits, n;                 // n: staged keys
-    int r0, c0, w, W;
+    Fragment box;
+    uint32_t n;                                  // staged keys
     bool staged, mad;
     double med;
 };
-
-// the monotone 64-bit key of a double (as in sdsm_measure.hip): a < b iff key(a) < key(b); -0.0 is made +0.0 first
-__device__ __forceinline__ u64 dkey(double v)
-{
-    if (v == 0.0) v = 0.0;
-    const u64 b = (u64)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | (1ull << 63));
-}
-
-__device__ __forceinline__ double dkey_inv(u64 k)
-{
-    return __longlong_as_double((i64)((k >> 63) ? (k & ~(1ull << 63)) : ~k));
-}
-
-__device__ __forceinline__ bool finite_bits(double g)
-{
-    return (((u64)__double_as_longlong(g) >> 52) & 0x7ff) != 0x7ff;
-}
 
 // 0.5 a + 0.5 b as two products and one sum.  Contraction is switched off for these statements: a fused multiply-add rounds once where
 // this rounds twice, which shows for subnormals (the compiler contracts __dadd_rn(__dmul_rn(..), ..) as well: they are plain operators).
@@ -88,16 +61,7 @@ __device__ __forceinline__ double midpoint(double a, double b)
 template <class F>
 __device__ __forceinline__ void each_pixel(const Src &s, int tid, F f)
 {
-    for (uint32_t k = tid; k < s.n_words; k += ITPB) {
-        uint32_t word = s.bits[k];
-        if (k == s.n_words - 1 && (s.n_bits & 31)) word &= (1u << (s.n_bits & 31)) - 1;         // the bits past h * w are not the object's
-        while (word) {
-            const uint32_t b = (k << 5) + (uint32_t)__builtin_ctz(word);
-            word &= word - 1;
-            const int r = s.r0 + (int)(b / (uint32_t)s.w), c = s.c0 + (int)(b % (uint32_t)s.w);
-            f(r, c, s.g[(int64_t)r * s.W + c]);
-        }
-    }
+    each_set_bit<ITPB>(s.bits, s.box, tid, [&](uint32_t, int r, int c) { f(r, c, s.g[(int64_t)r * s.box.W + c]); });
 }
 
 // f(key) for every key of the object: of g, or of |g - med| once the MAD is being taken
@@ -196,7 +160,7 @@ __device__ __forceinline__ void empty_result(sdsm_intensity_record *out, double 
     for (int q = 0; q < 2 * n_q; q++) order[q] = nan;
 }
 
-__global__ __launch_bounds__(ITPB) void k_intensity_objects(ISet S, IQuant Q, const int32_t *obj_image, const int32_t *boxes, const int64_t *bits_off,
+__global__ __launch_bounds__(ITPB) void k_intensity_objects(SetImages S, IQuant Q, const int32_t *obj_image, const int32_t *boxes, const int64_t *bits_off,
                                                             const uint32_t *bits_, const double *g_, sdsm_intensity_record *out, double *order_)
 {
     __shared__ ILds T;
@@ -206,15 +170,15 @@ __global__ __launch_bounds__(ITPB) void k_intensity_objects(ISet S, IQuant Q, co
     const bool im_ok = im >= 0 && im < S.n;
     const int H = im_ok ? S.H[im] : 0, W = im_ok ? S.W[im] : 0;
     const int br0 = boxes[4 * i], bc0 = boxes[4 * i + 1], h = boxes[4 * i + 2], w = boxes[4 * i + 3];
+    // (fragment_box of sdsm_tables.h, written out: see "What the table kernels share" in DESIGN.md)
     if (!(im_ok && br0 >= 0 && bc0 >= 0 && h >= 1 && w >= 1 && h <= H && w <= W && br0 <= H - h && bc0 <= W - w)) {
         if (tid == 0) empty_result(out + i, order, Q.n_q, 0, 0);                 // (uniform: the whole workgroup leaves; nothing is read)
         return;
     }
     Src s;
+    s.box = {H, W, br0, bc0, h, w};
     s.bits = bits_ + bits_off[i];
     s.g = g_ + S.off[im];
-    s.n_bits = (uint32_t)h * (uint32_t)w; s.n_words = (s.n_bits + 31) >> 5;
-    s.r0 = br0; s.c0 = bc0; s.w = w; s.W = W;
     s.staged = false; s.mad = false; s.med = 0.0; s.n = 0;
     if (tid == 0) T.count = 0;
     __syncthreads();
@@ -324,9 +288,7 @@ extern "C" hipError_t sdsm_intensity_objects_impl(const sdsm_set_image *images, 
                                                   const int32_t *den, sdsm_intensity_record *out, double *order, hipStream_t stream)
 {
     if (n <= 0) return hipSuccess;
-    ISet S{};
-    S.n = n_images;
-    for (int i = 0; i < n_images; i++) { S.H[i] = images[i].H; S.W[i] = images[i].W; S.off[i] = images[i].offset; }
+    const SetImages S = make_set(images, n_images);
     IQuant Q{};
     Q.n_q = n_q;
     for (int q = 0; q < n_q; q++) { Q.num[q] = num[q]; Q.den[q] = den[q]; }

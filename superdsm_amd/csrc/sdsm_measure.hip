@@ -5,18 +5,18 @@
 //
 //   k_absmax            max finite |g| per image (integer atomic on the bits of a non-negative double), from which the measuring
 //                       kernels take the exponent e of the image's intensity quantum 2^(e - 62) without a host round trip
-//   k_measure_objects   one workgroup per object: the set bits of the fragment by ctz, 64-bit sums in registers, one reduction of the
+//   k_measure_objects   one workgroup per object: the set bits of the fragment (each_set_bit of sdsm_tables.h), 64-bit sums in registers, one reduction of the
 //                       workgroup through LDS, no global atomics
 //   k_measure_labels    one workgroup per band of LBAND consecutive pixels (raster order) of one image: a thread owns segments of LSEG
 //                       pixels and keeps the sums of its current label in registers while the label does not change; on a change
-//                       it flushes into an LDS table keyed by label (open addressing, claimed by compare-and-swap, 64-bit LDS adds);
+//                       it flushes into an LDS table keyed by label (lds_label_slot of sdsm_tables.h, 64-bit LDS adds);
 //                       the occupied slots go to the global records by 64-bit integer atomics at the end of the band.  A label
 //                       without a free slot goes straight to the global atomics.
 //   k_labels_init / k_labels_finish   the identities of the atomics before, the record's final form after
 //   k_overlap_pairs     the contingency table of two label maps (superdsm_amd/compare.py): the bands and segments of k_measure_labels over
 //                       both maps; a thread keeps its current pair (a, b) and the length of its run in registers and flushes on a change
 //                       into an LDS table keyed by the 64-bit pair (64-bit LDS compare-and-swap, 32-bit counts); the occupied slots go
-//                       to the image's global hash table (keys claimed by compare-and-swap, 64-bit counts) at the end of the band.  A
+//                       to the image's global hash table (pair_table_slot of sdsm_tables.h, 64-bit counts) at the end of the band.  A
 //                       pair without an LDS slot goes straight there; one without a global slot is counted and dropped, never waited for.
 //
 //   k_label_pixel_counts / k_label_starts / k_label_pixel_lists   boundary distances (superdsm_amd/boundary.py): per label its pixels and
@@ -28,8 +28,7 @@
 //
 // Every sum over pixels is an integer sum and every atomic an integer add / min / max / or, so the bytes do not depend on the order,
 // the launch or the set size.  Intensities enter as q = rint(ldexp(g, 62 - e)) in two limbs (bits 0-31, and q >> 32).
-#include "sdsm_common.h"
-#include "sdsm_set.h"
+#include "sdsm_tables.h"
 #include <climits>
 #include <cmath>
 
@@ -39,7 +38,8 @@ constexpr int MTPB = 256;
 constexpr int ABS_PIX = 2048;                    // k_absmax: pixels per workgroup
 constexpr int LSEG = 16;                         // k_measure_labels: consecutive pixels of a thread's segment (64 B of labels)
 constexpr int LBAND = 16384;                     //   pixels of a band: 4 segments per thread
-constexpr int LSLOTS = 256;                      //   slots of the LDS table (28 KB: 5 workgroups per compute unit)
+constexpr int LBITS = 8;
+constexpr int LSLOTS = 1 << LBITS;               //   slots of the LDS table (28 KB: 5 workgroups per compute unit)
 constexpr int LPROBES = 16;                      //   slots tried before a label goes to the global atomics
 constexpr int FIN_RECS = MTPB;                   // k_labels_init / k_labels_finish: records per workgroup
 // k_overlap_pairs: the LDS table of a band.  A slot is 12 bytes (64-bit key, 32-bit count), so 1024 slots are 12 KB: a compute unit holds
@@ -52,18 +52,6 @@ constexpr int FIN_RECS = MTPB;                   // k_labels_init / k_labels_fin
 constexpr int OBITS = 10;
 constexpr int OSLOTS = 1 << OBITS;               //   slots of the LDS table
 constexpr int OPROBES = 8;                       //   slots tried before a pair goes to the global table
-
-typedef unsigned long long u64;
-typedef long long i64;
-
-struct MSet {                                    // the images of a launch
-    int32_t n;
-    int32_t H[SDSM_MAX_SET_IMAGES], W[SDSM_MAX_SET_IMAGES];
-    int64_t off[SDSM_MAX_SET_IMAGES];            // first pixel of the image in the packed buffers
-    int64_t rec_off[SDSM_MAX_SET_IMAGES];        // labels: first record of the image
-    int32_t n_labels[SDSM_MAX_SET_IMAGES];
-    int32_t start[SDSM_MAX_SET_IMAGES + 1];      // flattened grid: first workgroup of the image
-};
 
 // the sums of a set of pixels, and how two of them combine
 struct Acc {
@@ -78,19 +66,6 @@ __device__ __forceinline__ void acc_clear(Acc &a)
     a.sum_rr = a.sum_rc = a.sum_cc = a.glo = 0;
     a.kmin = ~0ull; a.kmax = 0;
     a.r0 = a.c0 = INT_MAX; a.r1 = a.c1 = 0; a.flags = 0;
-}
-
-// the monotone 64-bit key of a double: a < b iff key(a) < key(b); -0.0 is made +0.0 first
-__device__ __forceinline__ u64 dkey(double v)
-{
-    if (v == 0.0) v = 0.0;
-    const u64 b = (u64)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | (1ull << 63));
-}
-
-__device__ __forceinline__ double dkey_inv(u64 k)
-{
-    return __longlong_as_double((i64)((k >> 63) ? (k & ~(1ull << 63)) : ~k));
 }
 
 // e of an image from the bits of its max finite |g|: the smallest e with max < 2^e, clamped to -960 .. 1024; 0 without a non-zero pixel
@@ -164,7 +139,7 @@ __device__ __forceinline__ void write_record(sdsm_measure_record *out, const Acc
 }
 
 // ---- max finite |g| per image ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(MTPB) void k_absmax(MSet S, const double *g_, u64 *maxbits)
+__global__ __launch_bounds__(MTPB) void k_absmax(SetLabels S, const double *g_, u64 *maxbits)
 {
     const int im = set_find(S.start, S.n, blockIdx.x);
     const int64_t px = (int64_t)S.H[im] * S.W[im];
@@ -188,7 +163,7 @@ __global__ __launch_bounds__(MTPB) void k_scale_exp(int n, const u64 *maxbits, i
 }
 
 // ---- objects: one workgroup per fragment ----------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(MTPB) void k_measure_objects(MSet S, const int32_t *obj_image, const int32_t *boxes, const int64_t *bits_off,
+__global__ __launch_bounds__(MTPB) void k_measure_objects(SetLabels S, const int32_t *obj_image, const int32_t *boxes, const int64_t *bits_off,
                                                           const uint32_t *bits_, const double *g_, const u64 *maxbits, sdsm_measure_record *out)
 {
     __shared__ Acc part[MTPB / 64];
@@ -196,43 +171,29 @@ __global__ __launch_bounds__(MTPB) void k_measure_objects(MSet S, const int32_t 
     const int im = obj_image ? obj_image[i] : 0;
     Acc a;
     acc_clear(a);
-    if (im < 0 || im >= S.n) {                   // (the caller checks this; nothing of another image is read)
-        if (tid == 0) write_record(out + i, a, 0, 0, 0);
-        return;
-    }
-    const int H = S.H[im], W = S.W[im];
-    const int r0 = boxes[4 * i], c0 = boxes[4 * i + 1], h = boxes[4 * i + 2], w = boxes[4 * i + 3];
-    const int e = g_ ? scale_exp(maxbits[im]) : 0;
-    const bool inside = r0 >= 0 && c0 >= 0 && h >= 1 && w >= 1 && h <= H && w <= W && r0 <= H - h && c0 <= W - w;
+    Fragment f;
+    const bool inside = fragment_box(S, im, boxes, i, f);
+    const int e = g_ && f.H > 0 ? scale_exp(maxbits[im]) : 0;                    // (f.H == 0: `im` is no image of the set)
     if (inside) {                                // a box that leaves its image gives the zero record: no pixel outside is read
-        const uint32_t *bits = bits_ + bits_off[i];
         const double *g = g_ ? g_ + S.off[im] : nullptr;
-        const uint32_t n_bits = (uint32_t)h * (uint32_t)w, n_words = (n_bits + 31) >> 5;
-        for (uint32_t k = tid; k < n_words; k += MTPB) {
-            uint32_t word = bits[k];
-            if (k == n_words - 1 && (n_bits & 31)) word &= (1u << (n_bits & 31)) - 1;       // the bits past h * w are not the object's
-            while (word) {
-                const uint32_t b = (k << 5) + (uint32_t)__builtin_ctz(word);
-                word &= word - 1;
-                const int r = r0 + (int)(b / (uint32_t)w), c = c0 + (int)(b % (uint32_t)w);
-                acc_pixel(a, r, c);
-                if (g) acc_intensity(a, g[(int64_t)r * W + c], 62 - e);
-            }
-        }
+        each_set_bit<MTPB>(bits_ + bits_off[i], f, tid, [&](uint32_t, int r, int c) {
+            acc_pixel(a, r, c);
+            if (g) acc_intensity(a, g[(int64_t)r * f.W + c], 62 - e);
+        });
     }
     for (int o = 32; o > 0; o >>= 1) acc_merge(a, acc_shfl_down(a, o));
     if ((tid & 63) == 0) part[tid >> 6] = a;
     __syncthreads();
     if (tid == 0) {
         for (int k = 1; k < MTPB / 64; k++) acc_merge(a, part[k]);
-        write_record(out + i, a, H, W, e);
+        write_record(out + i, a, f.H, f.W, e);
     }
 }
 
 // ---- labels ------------------------------------------------------------------------------------------------------------------------
 // While the atomics run, a record holds their identities and partial results: r0 / c0 INT_MAX, gmin / gmax as keys; k_labels_finish
 // gives it its final form.
-__global__ __launch_bounds__(MTPB) void k_labels_init(MSet S, sdsm_measure_record *recs, int32_t *bad)
+__global__ __launch_bounds__(MTPB) void k_labels_init(SetLabels S, sdsm_measure_record *recs, int32_t *bad)
 {
     const int im = set_find(S.start, S.n, blockIdx.x);
     const int l = (blockIdx.x - S.start[im]) * FIN_RECS + threadIdx.x;
@@ -246,7 +207,7 @@ __global__ __launch_bounds__(MTPB) void k_labels_init(MSet S, sdsm_measure_recor
     recs[S.rec_off[im] + l] = R;
 }
 
-__global__ __launch_bounds__(MTPB) void k_labels_finish(MSet S, sdsm_measure_record *recs, const u64 *maxbits)
+__global__ __launch_bounds__(MTPB) void k_labels_finish(SetLabels S, sdsm_measure_record *recs, const u64 *maxbits)
 {
     const int im = set_find(S.start, S.n, blockIdx.x);
     const int l = (blockIdx.x - S.start[im]) * FIN_RECS + threadIdx.x;
@@ -290,10 +251,7 @@ struct LTable {                                  // the per-workgroup table, one
 
 __device__ __forceinline__ void flush_label(LTable &T, int32_t label, const Acc &a, sdsm_measure_record *recs)
 {
-    uint32_t s = ((uint32_t)label * 2654435761u) >> 24;              // 8 bits = LSLOTS
-    for (int k = 0; k < LPROBES; k++, s = (s + 1) & (LSLOTS - 1)) {
-        const int32_t old = atomicCAS(&T.key[s], -1, label);
-        if (old != -1 && old != label) continue;
+    const bool found = lds_label_slot<LBITS, LPROBES>(T.key, label, [&](uint32_t s) {
         atomicAdd(&T.area[s], (u64)a.area);
         atomicAdd(&T.sum_r[s], (u64)a.sum_r);
         atomicAdd(&T.sum_c[s], (u64)a.sum_c);
@@ -310,16 +268,15 @@ __device__ __forceinline__ void flush_label(LTable &T, int32_t label, const Acc 
             atomicMin(&T.kmin[s], a.kmin);
             atomicMax(&T.kmax[s], a.kmax);
         }
-        return;
-    }
-    emit_global(recs + label, a);                // no slot: correct and slow
+    });
+    if (!found) emit_global(recs + label, a);            // no slot: correct and slow
 }
 
-__global__ __launch_bounds__(MTPB) void k_measure_labels(MSet S, const int32_t *labels_, const double *g_, const u64 *maxbits,
+__global__ __launch_bounds__(MTPB) void k_measure_labels(SetLabels S, const int32_t *labels_, const double *g_, const u64 *maxbits,
                                                          sdsm_measure_record *recs_, int32_t *bad)
 {
     __shared__ LTable T;
-    static_assert(LSLOTS == 256 && LBAND % (LSEG * MTPB) == 0, "hash width and band size");
+    static_assert(LBAND % (LSEG * MTPB) == 0, "band size");
     const int im = set_find(S.start, S.n, blockIdx.x), tid = threadIdx.x;
     const int W = S.W[im], n_labels = S.n_labels[im];
     const int64_t px = (int64_t)S.H[im] * W;
@@ -382,8 +339,6 @@ __global__ __launch_bounds__(MTPB) void k_measure_labels(MSet S, const int32_t *
 }
 
 // ---- contingency table of two label maps ---------------------------------------------------------------------------------------------
-constexpr u64 OFREE = ~0ull;                     // a free slot of either table (no pair has this key: labels are >= 0)
-
 struct OCap { int64_t cap[SDSM_MAX_SET_IMAGES]; };          // slots of each image's global table, a power of two
 
 __device__ __forceinline__ u64 pair_hash(u64 key)           // multiplicative: the high bits depend on every bit of the key
@@ -391,25 +346,16 @@ __device__ __forceinline__ u64 pair_hash(u64 key)           // multiplicative: t
     return key * 0x9E3779B97F4A7C15ull;
 }
 
-// n pixels of the pair `key` into the global table of its image: linear probing from the hashed slot, at most cap tries.  A key is
-// written once (free -> key, by compare-and-swap) and never changes, so a slot read as another pair's stays that pair's.  A pair that
-// finds the table full is counted in status[1] and its pixels are dropped: the host launches again with a larger table.
+// n pixels of the pair `key` into the global table of its image (pair_table_slot); a pair that finds the table full is counted in
+// status[1] and its pixels are dropped
 __device__ __forceinline__ void insert_global(u64 *keys, u64 *counts, int64_t cap, u64 key, u64 n, int32_t *status)
 {
-    const u64 mask = (u64)cap - 1, h = pair_hash(key);
-    u64 s = (h ^ (h >> 31)) & mask;
-    for (int64_t k = 0; k < cap; k++, s = (s + 1) & mask) {
-        u64 old = __hip_atomic_load(keys + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == OFREE) old = atomicCAS(keys + s, OFREE, key);
-        if (old != OFREE && old != key) continue;
-        atomicAdd(counts + s, n);
-        return;
-    }
-    atomicAdd(status + 1, 1);
+    const u64 h = pair_hash(key);
+    if (!pair_table_slot(keys, cap, (h ^ (h >> 31)) & ((u64)cap - 1), key, [&](u64 s) { atomicAdd(counts + s, n); })) atomicAdd(status + 1, 1);
 }
 
 struct OTable {                                  // the per-workgroup table
-    u64 key[OSLOTS];                             // OFREE: free
+    u64 key[OSLOTS];                             // PAIR_FREE: free
     uint32_t count[OSLOTS];                      // a band holds LBAND = 16 384 pixels
 };
 
@@ -417,8 +363,8 @@ __device__ __forceinline__ void flush_pair(OTable &T, u64 key, uint32_t n, u64 *
 {
     uint32_t s = (uint32_t)(pair_hash(key) >> (64 - OBITS));
     for (int k = 0; k < OPROBES; k++, s = (s + 1) & (OSLOTS - 1)) {
-        const u64 old = atomicCAS(&T.key[s], OFREE, key);
-        if (old != OFREE && old != key) continue;
+        const u64 old = atomicCAS(&T.key[s], PAIR_FREE, key);
+        if (old != PAIR_FREE && old != key) continue;
         atomicAdd(&T.count[s], n);
         return;
     }
@@ -426,7 +372,7 @@ __device__ __forceinline__ void flush_pair(OTable &T, u64 key, uint32_t n, u64 *
 }
 
 // S.rec_off: first slot of the image's global table; status: per image [0] pixels with a negative label (skipped), [1] pairs without a slot
-__global__ __launch_bounds__(MTPB) void k_overlap_pairs(MSet S, OCap C, const int32_t *a_, const int32_t *b_, u64 *keys_, u64 *counts_, int32_t *status_)
+__global__ __launch_bounds__(MTPB) void k_overlap_pairs(SetLabels S, OCap C, const int32_t *a_, const int32_t *b_, u64 *keys_, u64 *counts_, int32_t *status_)
 {
     __shared__ OTable T;
     static_assert(LBAND % (LSEG * MTPB) == 0 && LBAND <= 0xffffffffll, "band size and the 32-bit counts of the LDS table");
@@ -437,9 +383,9 @@ __global__ __launch_bounds__(MTPB) void k_overlap_pairs(MSet S, OCap C, const in
     u64 *keys = keys_ + S.rec_off[im], *counts = counts_ + S.rec_off[im];
     const int64_t cap = C.cap[im];
     int32_t *status = status_ + 2 * im;
-    for (int s = tid; s < OSLOTS; s += MTPB) { T.key[s] = OFREE; T.count[s] = 0; }
+    for (int s = tid; s < OSLOTS; s += MTPB) { T.key[s] = PAIR_FREE; T.count[s] = 0; }
     __syncthreads();
-    u64 cur = OFREE;                             // the pair whose run the registers hold; OFREE: none
+    u64 cur = PAIR_FREE;                             // the pair whose run the registers hold; PAIR_FREE: none
     uint32_t run = 0;
     int n_bad = 0;
     for (int it = 0; it < LBAND / (LSEG * MTPB); it++) {
@@ -473,29 +419,21 @@ __global__ __launch_bounds__(MTPB) void k_overlap_pairs(MSet S, OCap C, const in
     if (n_bad) atomicAdd(status, n_bad);
     __syncthreads();
     for (int s = tid; s < OSLOTS; s += MTPB)     // one lane per slot
-        if (T.key[s] != OFREE) insert_global(keys, counts, cap, T.key[s], T.count[s], status);
+        if (T.key[s] != PAIR_FREE) insert_global(keys, counts, cap, T.key[s], T.count[s], status);
 }
 
-MSet make_mset(const sdsm_set_image *images, int n_images)
-{
-    MSet S{};
-    S.n = n_images;
-    for (int i = 0; i < n_images; i++) { S.H[i] = images[i].H; S.W[i] = images[i].W; S.off[i] = images[i].offset; }
-    return S;
-}
-
-void grid_pixels(MSet &S, int per_block)
+void grid_pixels(SetLabels &S, int per_block)
 {
     for (int i = 0; i < S.n; i++) S.start[i + 1] = S.start[i] + (int32_t)(((int64_t)S.H[i] * S.W[i] + per_block - 1) / per_block);
 }
 
-void grid_records(MSet &S)
+void grid_records(SetLabels &S)
 {
     for (int i = 0; i < S.n; i++) S.start[i + 1] = S.start[i] + (S.n_labels[i] + FIN_RECS - 1) / FIN_RECS;
 }
 
 // max finite |g| per image into d_gmax_abs (the bits of a non-negative double are ordered as integers) and e into d_scale_exp
-hipError_t launch_scale(MSet S, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp, hipStream_t stream)
+hipError_t launch_scale(SetLabels S, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp, hipStream_t stream)
 {
     if (d_g) {
         hipError_t e = hipMemsetAsync(d_gmax_abs, 0, (size_t)S.n * sizeof(double), stream);
@@ -530,20 +468,18 @@ struct BTable {                                  // the per-workgroup table of k
 
 __device__ __forceinline__ void flush_counts(BTable &T, int32_t label, uint32_t area, uint32_t edge, int32_t *counts)
 {
-    uint32_t s = ((uint32_t)label * 2654435761u) >> (32 - BBITS);
-    for (int k = 0; k < BPROBES; k++, s = (s + 1) & (BSLOTS - 1)) {
-        const int32_t old = atomicCAS(&T.key[s], -1, label);
-        if (old != -1 && old != label) continue;
+    const bool found = lds_label_slot<BBITS, BPROBES>(T.key, label, [&](uint32_t s) {
         atomicAdd(&T.area[s], area);
         if (edge) atomicAdd(&T.edge[s], edge);
-        return;
+    });
+    if (!found) {                                // no slot: correct and slow
+        atomicAdd(counts + 2 * label, (int32_t)area);
+        if (edge) atomicAdd(counts + 2 * label + 1, (int32_t)edge);
     }
-    atomicAdd(counts + 2 * label, (int32_t)area);            // no slot: correct and slow
-    if (edge) atomicAdd(counts + 2 * label + 1, (int32_t)edge);
 }
 
 // the bands and segments of k_measure_labels; a thread keeps the counts of its current label in registers while the label does not change
-__global__ __launch_bounds__(MTPB) void k_label_pixel_counts(MSet S, const int32_t *labels_, int32_t *counts_, int32_t *bad)
+__global__ __launch_bounds__(MTPB) void k_label_pixel_counts(SetLabels S, const int32_t *labels_, int32_t *counts_, int32_t *bad)
 {
     __shared__ BTable T;
     const int im = set_find(S.start, S.n, blockIdx.x), tid = threadIdx.x;
@@ -615,7 +551,7 @@ __global__ __launch_bounds__(MTPB) void k_label_starts(const int32_t *counts_, i
 
 // A thread walks its segments run by run: the boundary pixels of a run of one label as a bit mask, one atomic per run and part of the
 // label's list, then the coordinates.  An entry past the image's part of the list (counts of another map) is dropped, never written.
-__global__ __launch_bounds__(MTPB) void k_label_pixel_lists(MSet S, const int32_t *labels_, const int32_t *counts_, const int32_t *start_,
+__global__ __launch_bounds__(MTPB) void k_label_pixel_lists(SetLabels S, const int32_t *labels_, const int32_t *counts_, const int32_t *start_,
                                                             int32_t *cursor_, uint32_t *list_)
 {
     static_assert(LSEG <= 32, "the boundary mask of a run");
@@ -680,12 +616,12 @@ struct DArgs {
     const uint32_t *list_a, *list_b;
 };
 
-__device__ __forceinline__ bool pair_ok(const MSet &S, int im, int la, int lb)
+__device__ __forceinline__ bool pair_ok(const SetImages &S, int im, int la, int lb)
 {
     return im >= 0 && im < S.n && la > 0 && la < BMAXL && lb > 0 && lb < BMAXL;
 }
 
-__global__ __launch_bounds__(MTPB) void k_pair_init(MSet S, DArgs A, int n_pairs, const int32_t *pairs, sdsm_pair_distance *recs)
+__global__ __launch_bounds__(MTPB) void k_pair_init(SetLabels S, DArgs A, int n_pairs, const int32_t *pairs, sdsm_pair_distance *recs)
 {
     const int i = blockIdx.x * MTPB + threadIdx.x;
     if (i >= n_pairs) return;
@@ -705,7 +641,7 @@ __global__ __launch_bounds__(MTPB) void k_pair_init(MSet S, DArgs A, int n_pairs
 // One workgroup per item (pair, phase, chunk).  A lane owns DQ query pixels and their running minima; the target's boundary goes through
 // LDS in tiles of DTILE pixels, every lane reading the same entry (a broadcast).  Rows and columns differ by less than 2^16, so the
 // squares are 24-bit multiplies and their sum fits int32.  q is applied once per query pixel, after the last tile.
-__global__ __launch_bounds__(MTPB) void k_pair_distances(MSet S, DArgs A, int n_pairs, const int32_t *pairs, const int32_t *items, sdsm_pair_distance *recs)
+__global__ __launch_bounds__(MTPB) void k_pair_distances(SetLabels S, DArgs A, int n_pairs, const int32_t *pairs, const int32_t *items, sdsm_pair_distance *recs)
 {
     __shared__ int2 tile[DTILE];
     __shared__ u64 red1[MTPB / 64], red2[MTPB / 64];
@@ -796,7 +732,7 @@ __global__ __launch_bounds__(MTPB) void k_pair_distances(MSet S, DArgs A, int n_
 extern "C" hipError_t sdsm_label_pixel_counts_impl(const sdsm_set_image *images, int n_images, const int32_t *labels, int32_t *counts, int32_t *bad,
                                                    hipStream_t stream)
 {
-    MSet S = make_mset(images, n_images);
+    SetLabels S = make_set(images, n_images);
     hipError_t e = hipMemsetAsync(counts, 0, (size_t)n_images * 2 * BMAXL * sizeof(int32_t), stream);
     if (e == hipSuccess) e = hipMemsetAsync(bad, 0, (size_t)n_images * sizeof(int32_t), stream);
     if (e != hipSuccess) return e;
@@ -808,7 +744,7 @@ extern "C" hipError_t sdsm_label_pixel_counts_impl(const sdsm_set_image *images,
 extern "C" hipError_t sdsm_label_pixel_lists_impl(const sdsm_set_image *images, int n_images, const int32_t *labels, const int32_t *counts,
                                                   int32_t *start, int32_t *cursor, uint32_t *list, hipStream_t stream)
 {
-    MSet S = make_mset(images, n_images);
+    SetLabels S = make_set(images, n_images);
     hipLaunchKernelGGL(k_label_starts, dim3(n_images), dim3(MTPB), 0, stream, counts, start, cursor);
     grid_pixels(S, LBAND);
     hipLaunchKernelGGL(k_label_pixel_lists, dim3(S.start[n_images]), dim3(MTPB), 0, stream, S, labels, counts, start, cursor, list);
@@ -820,7 +756,7 @@ extern "C" hipError_t sdsm_pair_distances_impl(const sdsm_set_image *images, int
                                                const uint32_t *list_a, const uint32_t *list_b, int n_pairs, const int32_t *pairs, int64_t n_items,
                                                const int32_t *items, sdsm_pair_distance *recs, hipStream_t stream)
 {
-    MSet S = make_mset(images, n_images);
+    SetLabels S = make_set(images, n_images);
     const DArgs A = {d_a, d_b, counts_a, counts_b, start_a, start_b, list_a, list_b};
     hipLaunchKernelGGL(k_pair_init, dim3((n_pairs + MTPB - 1) / MTPB), dim3(MTPB), 0, stream, S, A, n_pairs, pairs, recs);
     if (n_items > 0) hipLaunchKernelGGL(k_pair_distances, dim3((unsigned)n_items), dim3(MTPB), 0, stream, S, A, n_pairs, pairs, items, recs);
@@ -836,7 +772,7 @@ extern "C" hipError_t sdsm_measure_objects_impl(const sdsm_set_image *images, in
                                                 const int64_t *bits_off, const uint32_t *bits, const double *d_g, double *d_gmax_abs,
                                                 int32_t *d_scale_exp, sdsm_measure_record *out, hipStream_t stream)
 {
-    MSet S = make_mset(images, n_images);
+    SetLabels S = make_set(images, n_images);
     hipError_t e = launch_scale(S, d_g, d_gmax_abs, d_scale_exp, stream);
     if (e != hipSuccess || n == 0) return e;
     hipLaunchKernelGGL(k_measure_objects, dim3(n), dim3(MTPB), 0, stream, S, obj_image, boxes, bits_off, bits, d_g, (const u64 *)d_gmax_abs, out);
@@ -847,11 +783,11 @@ extern "C" hipError_t sdsm_measure_labels_impl(const sdsm_set_image *images, int
                                                const int32_t *n_labels, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp,
                                                sdsm_measure_record *out, int32_t *bad, hipStream_t stream)
 {
-    MSet S = make_mset(images, n_images);
+    SetLabels S = make_set(images, n_images);
     for (int i = 0; i < n_images; i++) { S.rec_off[i] = rec_off[i]; S.n_labels[i] = n_labels[i]; }
     hipError_t e = launch_scale(S, d_g, d_gmax_abs, d_scale_exp, stream);
     if (e != hipSuccess) return e;
-    MSet R = S;
+    SetLabels R = S;
     grid_records(R);
     hipLaunchKernelGGL(k_labels_init, dim3(R.start[n_images]), dim3(MTPB), 0, stream, R, out, bad);
     grid_pixels(S, LBAND);
@@ -860,13 +796,13 @@ extern "C" hipError_t sdsm_measure_labels_impl(const sdsm_set_image *images, int
     return hipGetLastError();
 }
 
-// The tables are cleared here, on the stream: keys to OFREE (bytes 0xFF), counts and status to 0; slots of images that follow each
+// The tables are cleared here, on the stream: keys to PAIR_FREE (bytes 0xFF), counts and status to 0; slots of images that follow each
 // other in the buffers are cleared by one call.
 extern "C" hipError_t sdsm_overlap_pairs_impl(const sdsm_set_image *images, int n_images, const int32_t *d_a, const int32_t *d_b,
                                               const int64_t *table_off, const int64_t *capacity, uint64_t *d_keys, uint64_t *d_counts,
                                               int32_t *d_status, hipStream_t stream)
 {
-    MSet S = make_mset(images, n_images);
+    SetLabels S = make_set(images, n_images);
     OCap C{};
     for (int i = 0; i < n_images; i++) { S.rec_off[i] = table_off[i]; C.cap[i] = capacity[i]; }
     for (int i = 0; i < n_images;) {

@@ -14,15 +14,14 @@
 //          in runs along a row, so it keeps the current other label and its running minimum in registers and commits on a change, into
 //          an LDS table keyed by the pair (64-bit LDS compare-and-swap, 32-bit min and add).  Only boundary pixels search: the closest pair
 //          of pixels of two disjoint labels are boundary pixels of both (neighbours.py proves it, the tests pin it).
-//       4. The occupied slots go to the label records (integer atomic adds) and to the image's global table (key claimed by 64-bit
-//          compare-and-swap, atomicMin / atomicAdd on the two values).  A label or pair without an LDS slot goes straight there; a pair
+//       4. The occupied slots go to the label records (integer atomic adds) and to the image's global table (pair_table_slot of sdsm_tables.h,
+//          atomicMin / atomicAdd on the two values).  A label or pair without an LDS slot goes straight there; a pair
 //          without a global slot is counted and dropped, never waited for.
 //
 // Every atomic is an integer min, add or compare-and-swap, so the bytes (the pair table after a sort by key) do not depend on the order,
 // the launch, the set size or the capacity.  No float, no scratch.
-#include "sdsm_common.h"
+#include "sdsm_tables.h"
 #include "sdsm_neighbours.h"
-#include "sdsm_set.h"
 
 namespace {
 
@@ -41,9 +40,6 @@ static_assert(NTPB * NSEG == NTH * NTW && NTW % NSEG == 0, "phase 2 covers the t
 static_assert(sizeof(sdsm_neighbour_label) == 40 && sizeof(sdsm_neighbour_pair) == 16, "record sizes of include/sdsm.h");
 static_assert(SDSM_NEIGHBOUR_MAX_D2 == SDSM_NEIGHBOUR_MAX_D2_INLINE && SDSM_NEIGHBOUR_MAX_REACH_INLINE * SDSM_NEIGHBOUR_MAX_REACH_INLINE == SDSM_NEIGHBOUR_MAX_D2,
               "the limit of the header and of the inline helpers");
-
-typedef unsigned long long u64;
-constexpr u64 NFREE = ~0ull;                     // a free slot of either pair table (no pair has this key: labels are <= 65535)
 
 struct NSet {                                    // the images of a launch
     int32_t n, max_d2, reach;
@@ -67,7 +63,7 @@ struct NGlobal {                                 // what a workgroup writes into
 template <int HALO> struct NTile {
     static constexpr int PITCH = NTW + 2 * HALO; // staged labels per staged row
     static constexpr int ROWS = NTH + 2 * HALO;
-    u64 pkey[NPSLOTS];                           // NFREE: free
+    u64 pkey[NPSLOTS];                           // PAIR_FREE: free
     uint32_t pmin[NPSLOTS], pcnt[NPSLOTS];
     int32_t lkey[NLSLOTS];                       // -1: free
     uint32_t lval[NFIELDS][NLSLOTS];             // (a tile has 2048 pixels and 8192 sides)
@@ -78,22 +74,15 @@ template <int HALO> struct NTile {
 };
 static_assert(sizeof(NTile<64>) <= 80 * 1024, "two workgroups per compute unit at the largest halo");
 
-// d2 / contact of the pair `key` into the global table of its image: linear probing from sdsm_neighbour_slot, at most cap tries.  A key is
-// written once (free -> key, by compare-and-swap) and never changes.  A pair that finds the table full is counted in status[1] and
-// dropped: the host launches again with a larger table.
+// d2 / contact of the pair `key` into the global table of its image (pair_table_slot, from sdsm_neighbour_slot on); a pair that finds the
+// table full is counted in status[1] and dropped
 __device__ __forceinline__ void pair_global(const NGlobal &G, u64 key, uint32_t d2, uint32_t contact)
 {
-    const u64 mask = (u64)G.cap - 1;
-    u64 s = sdsm_neighbour_slot_inline(key, (u64)G.cap);
-    for (int64_t k = 0; k < G.cap; k++, s = (s + 1) & mask) {
-        u64 old = __hip_atomic_load(G.keys + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == NFREE) old = atomicCAS(G.keys + s, NFREE, key);
-        if (old != NFREE && old != key) continue;
+    const bool found = pair_table_slot(G.keys, G.cap, sdsm_neighbour_slot_inline(key, (u64)G.cap), key, [&](u64 s) {
         atomicMin(G.min_d2 + s, d2);
         if (contact) atomicAdd(G.contact + s, contact);
-        return;
-    }
-    atomicAdd(G.status + 1, 1);
+    });
+    if (!found) atomicAdd(G.status + 1, 1);
 }
 
 template <class Tile> __device__ __forceinline__ void pair_commit(Tile &T, const NGlobal &G, uint32_t l, uint32_t other, uint32_t d2, uint32_t contact)
@@ -101,8 +90,8 @@ template <class Tile> __device__ __forceinline__ void pair_commit(Tile &T, const
     const u64 key = l < other ? ((u64)l << 32) | other : ((u64)other << 32) | l;
     uint32_t s = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - NPBITS));
     for (int k = 0; k < NPPROBES; k++, s = (s + 1) & (NPSLOTS - 1)) {
-        const u64 old = atomicCAS(&T.pkey[s], NFREE, key);
-        if (old != NFREE && old != key) continue;
+        const u64 old = atomicCAS(&T.pkey[s], PAIR_FREE, key);
+        if (old != PAIR_FREE && old != key) continue;
         atomicMin(&T.pmin[s], d2);
         if (contact) atomicAdd(&T.pcnt[s], contact);
         return;
@@ -120,20 +109,9 @@ __device__ __forceinline__ void label_global(sdsm_neighbour_label *rec, int fiel
     else atomicAdd((u64 *)&rec->edges_frame, (u64)v);
 }
 
-// the slot of `label` in the LDS table, claimed if need be; -1 when NLPROBES slots belong to other labels
-template <class Tile> __device__ __forceinline__ int label_slot(Tile &T, int32_t label)
-{
-    uint32_t s = ((uint32_t)label * 2654435761u) >> (32 - NLBITS);
-    for (int k = 0; k < NLPROBES; k++, s = (s + 1) & (NLSLOTS - 1)) {
-        const int32_t old = atomicCAS(&T.lkey[s], -1, label);
-        if (old == -1 || old == label) return (int)s;
-    }
-    return -1;
-}
-
 template <class Tile> __device__ __forceinline__ void label_add(Tile &T, const NGlobal &G, int32_t label, int field, uint32_t v)
 {
-    const int s = label_slot(T, label);
+    const int s = lds_label_slot<NLBITS, NLPROBES>(T.lkey, label);
     if (s >= 0) atomicAdd(&T.lval[field][s], v);
     else label_global(G.recs + label, field, v);             // no slot: correct and slow
 }
@@ -142,7 +120,7 @@ struct NCounts { uint32_t area, boundary, background, labels, frame; };
 
 template <class Tile> __device__ __forceinline__ void counts_flush(Tile &T, const NGlobal &G, int32_t label, const NCounts &c)
 {
-    const int s = label_slot(T, label);
+    const int s = lds_label_slot<NLBITS, NLPROBES>(T.lkey, label);
     if (s >= 0) {
         atomicAdd(&T.lval[F_AREA][s], c.area);
         if (c.boundary) atomicAdd(&T.lval[F_BOUNDARY][s], c.boundary);
@@ -174,7 +152,7 @@ template <int HALO> __global__ __launch_bounds__(NTPB) void k_neighbours(NSet S,
     const NGlobal G = {recs_ + S.rec_off[im], keys_ + S.table_off[im], min_d2_ + S.table_off[im], contact_ + S.table_off[im], S.cap[im], status_ + 2 * im};
 
     // 1. tables, and the tile with its halo.  Staged rows NTH + 2 R, staged columns NTW + 2 R: inside ROWS x PITCH as R <= HALO.
-    for (int s = tid; s < NPSLOTS; s += NTPB) { T.pkey[s] = NFREE; T.pmin[s] = 0xffffffffu; T.pcnt[s] = 0; }
+    for (int s = tid; s < NPSLOTS; s += NTPB) { T.pkey[s] = PAIR_FREE; T.pmin[s] = 0xffffffffu; T.pcnt[s] = 0; }
     for (int s = tid; s < NLSLOTS; s += NTPB) {
         T.lkey[s] = -1;
         for (int f = 0; f < NFIELDS; f++) T.lval[f][s] = 0;
@@ -280,7 +258,7 @@ template <int HALO> __global__ __launch_bounds__(NTPB) void k_neighbours(NSet S,
 
     // 4. one lane per slot
     for (int s = tid; s < NPSLOTS; s += NTPB)
-        if (T.pkey[s] != NFREE) pair_global(G, T.pkey[s], T.pmin[s], T.pcnt[s]);
+        if (T.pkey[s] != PAIR_FREE) pair_global(G, T.pkey[s], T.pmin[s], T.pcnt[s]);
     for (int s = tid; s < NLSLOTS; s += NTPB) {
         const int32_t label = T.lkey[s];
         if (label < 0) continue;

@@ -14,8 +14,7 @@
 //   k_shape_offsets / k_shape_gather   the exclusive sum of n_vertices, and the vertices of all objects one behind the other
 //   k_shape_scatter   label form: every pixel sets its bit in the window of its label (a thread owns 32 consecutive pixels and issues one
 //                     integer atomic or per word and run), after which the windows are fragments like any other
-#include "sdsm_common.h"
-#include "sdsm_set.h"
+#include "sdsm_tables.h"
 #include <climits>
 
 namespace {
@@ -27,18 +26,6 @@ constexpr int BMAX = 254;                        // rows of a band
 constexpr int SL = SDSM_SHAPE_MAX_CHAIN;         // entries of a chain's stack (16 KB each)
 constexpr int SSEG = 32;                         // k_shape_scatter: consecutive pixels of a thread
 constexpr int SBAND = SSEG * STPB;               //   pixels of a workgroup
-
-typedef unsigned long long u64;
-typedef long long i64;
-
-struct SSet {                                    // the images of a launch
-    int32_t n;
-    int32_t H[SDSM_MAX_SET_IMAGES], W[SDSM_MAX_SET_IMAGES];
-    int64_t off[SDSM_MAX_SET_IMAGES];            // first pixel of the image in the packed buffers
-    int64_t rec_off[SDSM_MAX_SET_IMAGES];        // labels: first entry of the image in d_label_obj
-    int32_t n_labels[SDSM_MAX_SET_IMAGES];
-    int32_t start[SDSM_MAX_SET_IMAGES + 1];      // flattened grid: first workgroup of the image
-};
 
 struct ShapeLds {
     uint32_t pe[PE_WORDS];
@@ -96,19 +83,18 @@ __device__ __forceinline__ int64_t vertex_slots(int h, int w)
     return h < 1 || w < 1 ? 0 : 2 * (int64_t)(h + 1 < 2 * w + 2 ? h + 1 : 2 * w + 2);
 }
 
-__global__ __launch_bounds__(STPB) void k_shape_objects(SSet S, const int32_t *obj_image, const int32_t *boxes, const int64_t *bits_off,
+__global__ __launch_bounds__(STPB) void k_shape_objects(SetLabels S, const int32_t *obj_image, const int32_t *boxes, const int64_t *bits_off,
                                                         const uint32_t *bits_, const int64_t *slot_off, int32_t *slots, sdsm_shape_record *out)
 {
     __shared__ ShapeLds T;
     const int i = blockIdx.x, tid = threadIdx.x;
     const int im = obj_image ? obj_image[i] : 0;
-    const bool im_ok = im >= 0 && im < S.n;
-    const int H = im_ok ? S.H[im] : 0, W = im_ok ? S.W[im] : 0;
-    const int br0 = boxes[4 * i], bc0 = boxes[4 * i + 1], h = boxes[4 * i + 2], w = boxes[4 * i + 3];
-    if (!(im_ok && br0 >= 0 && bc0 >= 0 && h >= 1 && w >= 1 && h <= H && w <= W && br0 <= H - h && bc0 <= W - w)) {
+    Fragment f;
+    if (!fragment_box(S, im, boxes, i, f)) {
         if (tid == 0) zero_record(out + i);      // (uniform: the whole workgroup leaves; no bit of the fragment is read)
         return;
     }
+    const int H = f.H, W = f.W, br0 = f.r0, bc0 = f.c0, h = f.h, w = f.w;
     const uint32_t *bits = bits_ + bits_off[i];
     const uint32_t n_words = ((uint32_t)h * (uint32_t)w + 31) >> 5;
     const int WR = (w + 31) >> 5;                // words of a row
@@ -278,7 +264,7 @@ __global__ __launch_bounds__(STPB) void k_shape_gather(const sdsm_shape_record *
 }
 
 // label form: the bit of every pixel in the window of its label
-__global__ __launch_bounds__(STPB) void k_shape_scatter(SSet S, const int32_t *labels_, const int32_t *label_obj_, int n, const int32_t *boxes,
+__global__ __launch_bounds__(STPB) void k_shape_scatter(SetLabels S, const int32_t *labels_, const int32_t *label_obj_, int n, const int32_t *boxes,
                                                         const int64_t *bits_off, int64_t window_words, uint32_t *bits, int32_t *bad)
 {
     const int im = set_find(S.start, S.n, blockIdx.x);
@@ -321,14 +307,6 @@ __global__ __launch_bounds__(STPB) void k_shape_scatter(SSet S, const int32_t *l
     if (n_bad) atomicAdd(bad + im, n_bad);
 }
 
-SSet make_sset(const sdsm_set_image *images, int n_images)
-{
-    SSet S{};
-    S.n = n_images;
-    for (int i = 0; i < n_images; i++) { S.H[i] = images[i].H; S.W[i] = images[i].W; S.off[i] = images[i].offset; }
-    return S;
-}
-
 }  // namespace
 
 extern "C" int64_t sdsm_shape_vertex_slots(int h, int w)
@@ -340,7 +318,7 @@ extern "C" hipError_t sdsm_shape_objects_impl(const sdsm_set_image *images, int 
                                               const int64_t *bits_off, const uint32_t *bits, const int64_t *slot_off, int32_t *slots,
                                               sdsm_shape_record *out, int64_t *vert_off, int32_t *verts, hipStream_t stream)
 {
-    const SSet S = make_sset(images, n_images);
+    const SetLabels S = make_set(images, n_images);
     if (n > 0) hipLaunchKernelGGL(k_shape_objects, dim3(n), dim3(STPB), 0, stream, S, obj_image, boxes, bits_off, bits, slot_off, slots, out);
     hipLaunchKernelGGL(k_shape_offsets, dim3(1), dim3(STPB), 0, stream, n, out, vert_off);
     if (n > 0) hipLaunchKernelGGL(k_shape_gather, dim3(n), dim3(STPB), 0, stream, out, boxes, slot_off, slots, vert_off, verts);
@@ -351,7 +329,7 @@ extern "C" hipError_t sdsm_shape_scatter_impl(const sdsm_set_image *images, int 
                                               const int32_t *n_labels, const int32_t *label_obj, int n, const int32_t *boxes, const int64_t *bits_off,
                                               int64_t window_words, uint32_t *bits, int32_t *bad, hipStream_t stream)
 {
-    SSet S = make_sset(images, n_images);
+    SetLabels S = make_set(images, n_images);
     for (int i = 0; i < n_images; i++) {
         S.rec_off[i] = rec_off[i]; S.n_labels[i] = n_labels[i];
         S.start[i + 1] = S.start[i] + (int32_t)(((int64_t)S.H[i] * S.W[i] + SBAND - 1) / SBAND);

@@ -18,7 +18,7 @@
 //   k_texture_gather   the padded lists one behind the other
 // The record of an object (area, finite pixels, level range, flags) is found by every workgroup of the object on its way and written by
 // that of offset 0.  The only floating-point operations are comparisons; no float atomics, no global atomics, no output needs clearing.
-#include "sdsm_common.h"
+#include "sdsm_tables.h"
 #include "sdsm_texture.h"
 #include <climits>
 
@@ -26,15 +26,6 @@ namespace {
 
 constexpr int TTPB = 256;
 constexpr int TWAVES = TTPB / 64;
-
-typedef unsigned long long u64;
-typedef long long i64;
-
-struct TSet {                                    // the images of a launch
-    int32_t n;
-    int32_t H[SDSM_MAX_SET_IMAGES], W[SDSM_MAX_SET_IMAGES];
-    int64_t off[SDSM_MAX_SET_IMAGES];            // first pixel of the image in the packed buffers
-};
 
 struct TOffsets {                                // the offsets of a launch
     int32_t n;
@@ -46,11 +37,6 @@ struct TRed {
     int32_t r32[TWAVES][7];
     uint32_t scan[TWAVES];
 };
-
-__device__ __forceinline__ bool finite_bits(double g)
-{
-    return (((u64)__double_as_longlong(g) >> 52) & 0x7ff) != 0x7ff;
-}
 
 // word q of the fragment; 0 outside it, and the bits past h * w are not the object's
 __device__ __forceinline__ uint32_t word_at(const uint32_t *bits, i64 q, uint32_t n_words, uint32_t n_bits)
@@ -81,7 +67,7 @@ __device__ __forceinline__ void empty_result(sdsm_texture_record *out, sdsm_text
     P->n_pairs = 0; P->n_entries = 0; P->reserved = 0;                              // (`first` is k_texture_scan's)
 }
 
-__global__ __launch_bounds__(TTPB) void k_texture(TSet S, TOffsets O, int levels, const double *edges_, const int32_t *obj_image, const int32_t *boxes,
+__global__ __launch_bounds__(TTPB) void k_texture(SetImages S, TOffsets O, int levels, const double *edges_, const int32_t *obj_image, const int32_t *boxes,
                                                   const int64_t *bits_off, const uint32_t *bits_, const double *g_, const int64_t *slot_off,
                                                   sdsm_texture_entry *slots, sdsm_texture_record *out, sdsm_texture_pairs *pairs)
 {
@@ -93,6 +79,7 @@ __global__ __launch_bounds__(TTPB) void k_texture(TSet S, TOffsets O, int levels
     const int i = blockIdx.x, o = blockIdx.y, tid = threadIdx.x;
     sdsm_texture_pairs *P = pairs + ((int64_t)i * O.n + o);
     const int im = obj_image ? obj_image[i] : 0;
+    // (fragment_box and each_set_bit of sdsm_tables.h, written out: see "What the table kernels share" in DESIGN.md)
     const bool im_ok = im >= 0 && im < S.n;
     const int H = im_ok ? S.H[im] : 0, W = im_ok ? S.W[im] : 0;
     const int br0 = boxes[4 * i], bc0 = boxes[4 * i + 1], h = boxes[4 * i + 2], w = boxes[4 * i + 3];
@@ -269,9 +256,7 @@ extern "C" hipError_t sdsm_texture_objects_impl(const sdsm_set_image *images, in
                                                 sdsm_texture_record *out, sdsm_texture_pairs *pairs, sdsm_texture_entry *entries, hipStream_t stream)
 {
     if (n <= 0) return hipSuccess;
-    TSet S{};
-    S.n = n_images;
-    for (int i = 0; i < n_images; i++) { S.H[i] = images[i].H; S.W[i] = images[i].W; S.off[i] = images[i].offset; }
+    const SetImages S = make_set(images, n_images);
     TOffsets O{};
     O.n = n_offsets;
     for (int o = 0; o < n_offsets; o++) { O.dr[o] = offsets[2 * o]; O.dc[o] = offsets[2 * o + 1]; }

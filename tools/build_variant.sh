@@ -10,9 +10,12 @@ flags="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -munsafe-fp-atomics $*"
 echo "$flags" > "$out/flags.new"
 if ! cmp -s "$out/flags.new" "$out/flags" 2>/dev/null; then rm -f "$out"/*.o; mv "$out/flags.new" "$out/flags"; fi
 pids=()
-for f in sdsm_api.hip sdsm_plan.hip sdsm_sides.hip sdsm_prepare.hip sdsm_setup.hip sdsm_solve.hip sdsm_post.hip sdsm_c2f.hip sdsm_render.hip sdsm_measure.hip sdsm_shape.hip sdsm_intensity.hip sdsm_host.cpp; do
+sources=$(cd "$root" && python3 -c "import __graft_entry__ as g; print(' '.join(g.SOURCES))")      # the product's own list
+for f in $sources; do
   o=$out/${f%.*}.o
-  if [ ! -f "$o" ] || [ "$src/$f" -nt "$o" ] || [ "$src/sdsm_common.h" -nt "$o" ] || [ "$root/include/sdsm.h" -nt "$o" ] || { [ -f "$src/sdsm_logtab.h" ] && [ "$src/sdsm_logtab.h" -nt "$o" ]; }; then
+  stale=0                                        # every header is a dependency of every object
+  for d in "$src/$f" "$src"/*.h "$root/include/sdsm.h"; do if [ ! -f "$o" ] || [ "$d" -nt "$o" ]; then stale=1; fi; done
+  if [ $stale = 1 ]; then
     /opt/rocm/bin/hipcc $flags -c "$src/$f" -o "$o" & pids+=($!)
   fi
 done
