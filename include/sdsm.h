@@ -856,6 +856,89 @@ int sdsm_neighbours_multi(const sdsm_set_image *images, int n_images, const int3
 int sdsm_neighbours(int H, int W, const int32_t *d_labels, int max_d2, int n_labels, sdsm_neighbour_label *d_label_out, int64_t capacity,
                     uint64_t *d_keys, uint32_t *d_min_d2, uint32_t *d_contact, int32_t *d_status, void *stream);   /* the set of one image */
 
+/* ---- depth tables: inscribed circle, radii, intensity shells (no reference counterpart; the definitions are depth_objects_host and
+ * depth_labels_host of superdsm_amd/depth.py) ---------------------------------------------------------------------------------------------
+ * How far inside its object a pixel lies, in integers only.  An object is the set P of the set bits of its fragment, as in the shape
+ * tables; everything else -- the rest of its box, other objects or labels, the outside of the image -- is outside P.  d2(p) for p in P
+ * is the smallest squared Euclidean distance from p to a lattice place outside P; a place one step beyond the image frame, or beyond the
+ * box, counts like any other outside pixel.  So d2 >= 1 for every p in P, and d2 <= ceil(min(h, w) / 2)^2 over the tight box.
+ * Conventions as for the shape and intensity tables: objects as sdsm_post_objects takes them, sets as a HOST table of sdsm_set_image
+ * (H, W <= 65535, H * W < 2^31), the single-image form is the set of that one image.  Every sum is an integer sum and every LDS atomic an
+ * integer add, there is no global atomic, and every record and shell row is written completely by its own workgroup: the bytes do not
+ * depend on the order, the launch or the set size, and no output needs clearing.
+ *
+ * Ranges: min(h, w) <= 65535 gives d2 <= 32768^2 = 2^30, and area <= h * w < 2^31, so sum_d2 <= area * max_d2 < 2^61; q(d2) =
+ * floor(sqrt(d2 * 2^32)) <= 2^31 (sdsm_quantised_distance, the one function the boundary tables use), so sum_q < 2^62.  Neither sum can
+ * wrap an int64, and neither is split into limbs.
+ * Median: med_d2_lo, med_d2_hi are the order statistics of d2 at the two ranks of the quantile 1 / 2 (sdsm_quantile_ranks(area, 1, 2)).
+ * Shells: with 1 <= n_shells <= SDSM_DEPTH_MAX_SHELLS the shell of a pixel is min(n_shells - 1, isqrt(d2 - 1)), that is ceil(sqrt(d2)) - 1
+ * capped: shell 0 holds d2 == 1, shell 1 d2 in 2 .. 4, shell 2 d2 in 5 .. 9, the last shell every deeper pixel (sdsm_depth_shell).
+ * Intensities (d_g, float64, optional) enter as for the measurement tables: e is the image's scale exponent, found on the device by the
+ * same first kernel (d_gmax_abs, d_scale_exp as sdsm_measure_objects takes them), a finite pixel adds q = rint(ldexp(g, 62 - e)) in two
+ * limbs to its shell, a non-finite pixel is counted in `count` alone.  Without d_g only `count` is filled and scale_exp is 0.
+ * An object whose box holds at most SDSM_DEPTH_LDS_PIXELS pixels is transformed in LDS; a larger one needs
+ * sdsm_depth_workspace_pixels(h, w) pixels of SDSM_DEPTH_WS_PIXEL_BYTES bytes each in the caller's workspace: the same bytes, more slowly
+ * (see DESIGN.md "Limits").  The decision is by the box, not by the pixels in it.  sdsm_depth_record: 80 bytes; sdsm_depth_shell_record:
+ * 32 bytes. */
+#define SDSM_DEPTH_MAX_SHELLS 32
+#define SDSM_DEPTH_LDS_PIXELS 12288     /* pixels of a box whose transform is held in LDS (two uint16 tiles, 48 KB) */
+#define SDSM_DEPTH_WS_PIXEL_BYTES 8     /* bytes of workspace per pixel of a larger box (two uint32) */
+#define SDSM_DEPTH_NO_WORKSPACE (1 << 30)   /* flag bit 30 of sdsm_depth_record */
+typedef struct {
+    int64_t area;                       /* pixels of P */
+    int64_t max_d2;                     /* largest d2: the squared radius of the largest inscribed circle */
+    int32_t max_row, max_col;           /* the pixel with d2 == max_d2 that is smallest in (row, column) order, image coordinates */
+    int64_t n_max;                      /* pixels with d2 == max_d2 */
+    int64_t sum_d2;                     /* sum of d2, < 2^61 */
+    int64_t sum_q;                      /* sum of q(d2), < 2^62 */
+    int64_t med_d2_lo, med_d2_hi;       /* the two middle order statistics of d2 */
+    int64_t n_rim;                      /* pixels with d2 == 1: the border pixels of the shape tables */
+    int32_t flags;                      /* bit 0: the bounding box of P touches the image frame; bit 30: the box needs workspace and the
+                                           call names none for it (the record and its shells are then zero) */
+    int32_t scale_exp;                  /* e of the record's image; 0 without d_g and in the zero record */
+} sdsm_depth_record;
+typedef struct {
+    int64_t count;                      /* pixels of the shell */
+    int64_t n_finite;                   /* those with a finite intensity */
+    uint64_t gsum_lo;                   /* low limb of their intensity sum */
+    int64_t gsum_hi;                    /* high limb */
+} sdsm_depth_shell_record;
+/* Host helpers (no device access).  sdsm_depth_shell: the shell of d2 among n_shells, by the inline function the kernel uses
+ * (csrc/sdsm_depth.h: a float estimate of the root, then integer correction loops); -1 for d2 < 1, d2 >= 2^31 or n_shells outside
+ * 1 .. SDSM_DEPTH_MAX_SHELLS.  sdsm_depth_workspace_pixels: the workspace pixels an object with an h x w box needs, h * w above
+ * SDSM_DEPTH_LDS_PIXELS and 0 for a box that LDS holds or an empty one. */
+int sdsm_depth_shell(int64_t d2, int n_shells);
+int64_t sdsm_depth_workspace_pixels(int h, int w);
+/* d_out[i] and d_shells[i * n_shells + s] for object i of d_boxes / d_bits_off (n of them; d_obj_image int32, NULL for one image), one
+ * workgroup each.  The bits of a fragment past h * w are ignored, a box larger than the tight box changes nothing; a fragment without a
+ * set bit, and an object whose box is empty or leaves its image, give the zero record and zero shells, and nothing is read for them.
+ * Workspace: object i with sdsm_depth_workspace_pixels(h, w) > 0 owns that many pixels of d_ws from pixel d_ws_off[i] on (d_ws_off: n
+ * int64 on the device; entries of smaller objects are not read; the ranges must not overlap, which is the caller's duty: the offsets
+ * live on the device and an overlap is not detected); ws_pixels is the number of pixels the offsets name in all and ws_bytes the size
+ * of d_ws: ws_pixels * SDSM_DEPTH_WS_PIXEL_BYTES > ws_bytes is an argument error before any
+ * launch, and an object whose range does not lie in 0 .. ws_pixels gets flag bit 30.  d_ws_off and d_ws may be NULL with ws_pixels ==
+ * 0.  d_g NULL: d_gmax_abs and d_scale_exp may be NULL.  n == 0: no launch. */
+int sdsm_depth_objects(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, const double *d_g,
+                       double *d_gmax_abs, int32_t *d_scale_exp, int n_shells, const int64_t *d_ws_off, void *d_ws, int64_t ws_pixels,
+                       size_t ws_bytes, sdsm_depth_record *d_out, sdsm_depth_shell_record *d_shells, void *stream);
+int sdsm_depth_objects_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                             const int64_t *d_bits_off, const uint32_t *d_bits, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp,
+                             int n_shells, const int64_t *d_ws_off, void *d_ws, int64_t ws_pixels, size_t ws_bytes, sdsm_depth_record *d_out,
+                             sdsm_depth_shell_record *d_shells, void *stream);
+/* The same for labels of label maps, by the windows of sdsm_shape_labels: the caller names n windows (d_obj_image, d_boxes, d_bits_off
+ * into the workspace d_bits of window_words <= SDSM_SHAPE_MAX_WINDOW_WORDS words, which the call clears) and d_label_obj; a first kernel
+ * sets the bit of every pixel in the window of its label -- a pixel of another label stays outside --, then the windows are measured as
+ * objects.  d_bad as there. */
+int sdsm_depth_labels(int H, int W, const int32_t *d_labels, int n_labels, const int32_t *d_label_obj, int n, const int32_t *d_boxes,
+                      const int64_t *d_bits_off, int64_t window_words, uint32_t *d_bits, const double *d_g, double *d_gmax_abs,
+                      int32_t *d_scale_exp, int n_shells, const int64_t *d_ws_off, void *d_ws, int64_t ws_pixels, size_t ws_bytes,
+                      sdsm_depth_record *d_out, sdsm_depth_shell_record *d_shells, int32_t *d_bad, void *stream);
+int sdsm_depth_labels_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int64_t *rec_off, const int32_t *n_labels,
+                            const int32_t *d_label_obj, int n, const int32_t *d_obj_image, const int32_t *d_boxes, const int64_t *d_bits_off,
+                            int64_t window_words, uint32_t *d_bits, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp, int n_shells,
+                            const int64_t *d_ws_off, void *d_ws, int64_t ws_pixels, size_t ws_bytes, sdsm_depth_record *d_out,
+                            sdsm_depth_shell_record *d_shells, int32_t *d_bad, void *stream);
+
 /* ---- host-side combinatorial steps of the stage (no device access) -------------------------------------------------------------
  * Approximate min-weight set cover (superdsm/minsetcover.py:4-88: greedy + merge phase, retried with beta * gamma on up to max_iter
  * levels) and greedy max-weight set packing (superdsm/maxsetpack.py:8-24) over n objects whose footprints are bit sets of `words`

@@ -111,6 +111,16 @@ NEIGHBOUR_LABEL_DTYPE = np.dtype([('edges_background', '<i8'), ('edges_labels', 
                                   ('close', '<i4'), ('reserved', '<i4')])                  # sdsm_neighbour_label
 NEIGHBOUR_PAIR_DTYPE = np.dtype([('a', '<i4'), ('b', '<i4'), ('min_d2', '<i4'), ('contact_edges', '<i4')])   # sdsm_neighbour_pair
 assert NEIGHBOUR_LABEL_DTYPE.itemsize == 40 and NEIGHBOUR_PAIR_DTYPE.itemsize == 16
+DEPTH_MAX_SHELLS = 32               # SDSM_DEPTH_MAX_SHELLS: shells of one call of the depth tables
+DEPTH_LDS_PIXELS = 12288            # SDSM_DEPTH_LDS_PIXELS: pixels of a box whose distance transform is held in LDS
+DEPTH_WS_PIXEL_BYTES = 8            # SDSM_DEPTH_WS_PIXEL_BYTES: workspace bytes per pixel of a larger box
+DEPTH_NO_WORKSPACE = 1 << 30        # flag bit 30 of sdsm_depth_record
+_DEPTH_FIELDS = [('area', 'i8'), ('max_d2', 'i8'), ('max_row', 'i4'), ('max_col', 'i4'), ('n_max', 'i8'), ('sum_d2', 'i8'), ('sum_q', 'i8'),
+                 ('med_d2_lo', 'i8'), ('med_d2_hi', 'i8'), ('n_rim', 'i8'), ('flags', 'i4'), ('scale_exp', 'i4')]
+_DEPTH_SHELL_FIELDS = [('count', 'i8'), ('n_finite', 'i8'), ('gsum_lo', 'u8'), ('gsum_hi', 'i8')]
+DEPTH_RECORD_DTYPE = np.dtype(_DEPTH_FIELDS)                                       # sdsm_depth_record
+DEPTH_SHELL_DTYPE = np.dtype(_DEPTH_SHELL_FIELDS)                                  # sdsm_depth_shell_record
+assert DEPTH_RECORD_DTYPE.itemsize == 80 and DEPTH_SHELL_DTYPE.itemsize == 32
 
 
 class MeasureRecord(C.Structure):
@@ -245,6 +255,13 @@ SYMBOLS = {
                                    _vp, _vp]),
     'sdsm_texture_labels_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp,
                                          _i32, _vp, _i32, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_depth_shell': (_i32, [_i64, _i32]),
+    'sdsm_depth_workspace_pixels': (_i64, [_i32, _i32]),
+    'sdsm_depth_objects': (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _sz, _vp, _vp, _vp]),
+    'sdsm_depth_objects_multi': (_i32, [C.POINTER(SetImage), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _sz, _vp, _vp, _vp]),
+    'sdsm_depth_labels': (_i32, [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _sz, _vp, _vp, _vp, _vp]),
+    'sdsm_depth_labels_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp,
+                                       _vp, _vp, _i32, _vp, _vp, _i64, _sz, _vp, _vp, _vp, _vp]),
     'sdsm_overlap_pairs': (_i32, [_i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     'sdsm_overlap_pairs_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _vp, _vp, _vp, _vp]),
     'sdsm_neighbour_halfwidth': (_i32, [_i32, _i32]),

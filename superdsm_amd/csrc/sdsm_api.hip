@@ -1026,6 +1026,89 @@ extern "C" int sdsm_texture_labels(int H, int W, const int32_t *d_labels, int n_
                                      d_edges, n_offsets, offsets, d_slot_off, d_slots, d_out, d_pairs, d_entries, d_bad, stream);
 }
 
+// ---- depth tables (sdsm_depth.hip; the scale step of sdsm_measure.hip, the label form fills its windows with the scatter step of
+// sdsm_shape.hip) ---------------------------------------------------------------------------------------------------------------------------
+extern "C" hipError_t sdsm_measure_scale_impl(const sdsm_set_image *images, int n_images, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp,
+                                              hipStream_t stream);
+extern "C" hipError_t sdsm_depth_objects_impl(const sdsm_set_image *images, int n_images, int n, const int32_t *obj_image, const int32_t *boxes,
+                                              const int64_t *bits_off, const uint32_t *bits, const double *d_g, const double *d_gmax_abs, int n_shells,
+                                              const int64_t *d_ws_off, void *d_ws, int64_t ws_pixels, sdsm_depth_record *out,
+                                              sdsm_depth_shell_record *shells, hipStream_t stream);
+
+// the shells, the intensity buffers and the workspace of a call; null: fine
+static const char *depth_args_bad(int n_shells, const double *d_g, const double *d_gmax_abs, const int64_t *d_ws_off, const void *d_ws, int64_t ws_pixels,
+                                  size_t ws_bytes)
+{
+    if (n_shells < 1 || n_shells > SDSM_DEPTH_MAX_SHELLS) return "1 <= n_shells <= 32 required";
+    if (d_g && !d_gmax_abs) return "intensities need d_gmax_abs";
+    if (ws_pixels < 0 || (ws_pixels > 0 && (!d_ws_off || !d_ws))) return "ws_pixels >= 0 and, with ws_pixels > 0, d_ws_off and d_ws required";
+    if ((uint64_t)ws_pixels > ws_bytes / SDSM_DEPTH_WS_PIXEL_BYTES) return "the workspace is too small for the boxes named (8 bytes per pixel)";
+    return nullptr;
+}
+
+extern "C" int sdsm_depth_objects_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                                        const int64_t *d_bits_off, const uint32_t *d_bits, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp,
+                                        int n_shells, const int64_t *d_ws_off, void *d_ws, int64_t ws_pixels, size_t ws_bytes, sdsm_depth_record *d_out,
+                                        sdsm_depth_shell_record *d_shells, void *stream)
+{
+    SET_TABLE("sdsm_depth_objects", SET_SIDES | SET_PIXELS);
+    if (n < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_depth_objects: n < 0");
+    if (const char *why = depth_args_bad(n_shells, d_g, d_gmax_abs, d_ws_off, d_ws, ws_pixels, ws_bytes))
+        return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_depth_objects: ") + why);
+    if (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_out || !d_shells || (n_images > 1 && !d_obj_image)))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_depth_objects: null argument");
+    hipError_t e = sdsm_measure_scale_impl(images, n_images, d_g, d_gmax_abs, d_scale_exp, (hipStream_t)stream);
+    if (e == hipSuccess)
+        e = sdsm_depth_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_g, d_gmax_abs, n_shells, d_ws_off, d_ws, ws_pixels, d_out,
+                                    d_shells, (hipStream_t)stream);
+    SET_DONE("sdsm_depth_objects");
+}
+
+extern "C" int sdsm_depth_objects(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, const double *d_g,
+                                  double *d_gmax_abs, int32_t *d_scale_exp, int n_shells, const int64_t *d_ws_off, void *d_ws, int64_t ws_pixels,
+                                  size_t ws_bytes, sdsm_depth_record *d_out, sdsm_depth_shell_record *d_shells, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_depth_objects_multi(&one, 1, n, nullptr, d_boxes, d_bits_off, d_bits, d_g, d_gmax_abs, d_scale_exp, n_shells, d_ws_off, d_ws, ws_pixels,
+                                    ws_bytes, d_out, d_shells, stream);
+}
+
+extern "C" int sdsm_depth_labels_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int64_t *rec_off, const int32_t *n_labels,
+                                       const int32_t *d_label_obj, int n, const int32_t *d_obj_image, const int32_t *d_boxes, const int64_t *d_bits_off,
+                                       int64_t window_words, uint32_t *d_bits, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp, int n_shells,
+                                       const int64_t *d_ws_off, void *d_ws, int64_t ws_pixels, size_t ws_bytes, sdsm_depth_record *d_out,
+                                       sdsm_depth_shell_record *d_shells, int32_t *d_bad, void *stream)
+{
+    SET_TABLE("sdsm_depth_labels", SET_SIDES | SET_PIXELS);
+    if (n < 0 || window_words < 0 || window_words > SDSM_SHAPE_MAX_WINDOW_WORDS)
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_depth_labels: n >= 0 and 0 <= window_words <= SDSM_SHAPE_MAX_WINDOW_WORDS required");
+    if (const char *why = depth_args_bad(n_shells, d_g, d_gmax_abs, d_ws_off, d_ws, ws_pixels, ws_bytes))
+        return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_depth_labels: ") + why);
+    if (!d_labels || !rec_off || !n_labels || !d_label_obj || !d_bad ||
+        (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_out || !d_shells || (n_images > 1 && !d_obj_image))))
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_depth_labels: null argument");
+    const char *why;
+    if (!label_records_ok(n_images, n_labels, rec_off, false, &why)) return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_depth_labels: ") + why);
+    hipError_t e = sdsm_shape_scatter_impl(images, n_images, d_labels, rec_off, n_labels, d_label_obj, n, d_boxes, d_bits_off, window_words, d_bits, d_bad,
+                                           (hipStream_t)stream);
+    if (e == hipSuccess) e = sdsm_measure_scale_impl(images, n_images, d_g, d_gmax_abs, d_scale_exp, (hipStream_t)stream);
+    if (e == hipSuccess)
+        e = sdsm_depth_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_g, d_gmax_abs, n_shells, d_ws_off, d_ws, ws_pixels, d_out,
+                                    d_shells, (hipStream_t)stream);
+    SET_DONE("sdsm_depth_labels");
+}
+
+extern "C" int sdsm_depth_labels(int H, int W, const int32_t *d_labels, int n_labels, const int32_t *d_label_obj, int n, const int32_t *d_boxes,
+                                 const int64_t *d_bits_off, int64_t window_words, uint32_t *d_bits, const double *d_g, double *d_gmax_abs,
+                                 int32_t *d_scale_exp, int n_shells, const int64_t *d_ws_off, void *d_ws, int64_t ws_pixels, size_t ws_bytes,
+                                 sdsm_depth_record *d_out, sdsm_depth_shell_record *d_shells, int32_t *d_bad, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    const int64_t off = 0;
+    return sdsm_depth_labels_multi(&one, 1, d_labels, &off, &n_labels, d_label_obj, n, nullptr, d_boxes, d_bits_off, window_words, d_bits, d_g, d_gmax_abs,
+                                   d_scale_exp, n_shells, d_ws_off, d_ws, ws_pixels, ws_bytes, d_out, d_shells, d_bad, stream);
+}
+
 // ---- contingency table of two label maps (sdsm_measure.hip) ---------------------------------------------------------------------------
 extern "C" hipError_t sdsm_overlap_pairs_impl(const sdsm_set_image *images, int n_images, const int32_t *d_a, const int32_t *d_b,
                                               const int64_t *table_off, const int64_t *capacity, uint64_t *d_keys, uint64_t *d_counts,

@@ -17,6 +17,7 @@
 #include "sdsm_quantile.h"
 #include "sdsm_neighbours.h"
 #include "sdsm_texture.h"
+#include "sdsm_depth.h"
 
 namespace {
 
@@ -284,6 +285,22 @@ extern "C" int sdsm_texture_cell(int levels, int i, int j)
 {
     if (levels < 1 || levels > SDSM_TEXTURE_MAX_LEVELS || i < 0 || j < i || j >= levels) return -1;
     return sdsm_texture_cell_inline(levels, i, j);
+}
+
+// The shell of a squared depth, as the depth kernel takes it (sdsm_depth.h: the same inline function), and the workspace of a box.
+static_assert(SDSM_DEPTH_MAX_SHELLS == SDSM_DEPTH_MAX_SHELLS_INLINE, "the limit of the header and of the inline helper");
+
+extern "C" int sdsm_depth_shell(int64_t d2, int n_shells)
+{
+    if (d2 < 1 || d2 > INT32_MAX || n_shells < 1 || n_shells > SDSM_DEPTH_MAX_SHELLS) return -1;
+    return sdsm_depth_shell_inline((int32_t)d2, n_shells);
+}
+
+extern "C" int64_t sdsm_depth_workspace_pixels(int h, int w)
+{
+    if (h < 1 || w < 1) return 0;
+    const int64_t px = (int64_t)h * w;
+    return px > SDSM_DEPTH_LDS_PIXELS ? px : 0;
 }
 
 // The half-width of a row of the disk and the first probe position of a pair, as the neighbourhood kernel takes them (sdsm_neighbours.h:

@@ -91,28 +91,7 @@ __device__ __forceinline__ u64 radix_select(const Src &s, ILds &T, int tid, uint
             if ((k & above) == prefix) atomicAdd(&T.hist[(uint32_t)(k >> shift) & 255u], 1u);
         });
         __syncthreads();
-        if (tid < 64) {                          // one wavefront: lane l owns the bins 4 l .. 4 l + 3
-            const uint32_t h0 = T.hist[4 * tid], h1 = T.hist[4 * tid + 1], h2 = T.hist[4 * tid + 2], h3 = T.hist[4 * tid + 3];
-            const uint32_t sum = h0 + h1 + h2 + h3;
-            uint32_t incl = sum;
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t t = __shfl_up(incl, o);
-                if (tid >= o) incl += t;
-            }
-            const uint32_t excl = incl - sum;
-            if (r >= excl && r < incl) {         // exactly one lane
-                uint32_t rr = r - excl, c = h0;
-                int b = 0;
-                if (rr >= h0) {
-                    rr -= h0; b = 1; c = h1;
-                    if (rr >= h1) {
-                        rr -= h1; b = 2; c = h2;
-                        if (rr >= h2) { rr -= h2; b = 3; c = h3; }
-                    }
-                }
-                T.sel_bin = 4 * tid + b; T.sel_r = rr; T.sel_cnt = c;
-            }
-        }
+        if (tid < 64) select_bin(T.hist, tid, r, T.sel_bin, T.sel_r, T.sel_cnt);     // one wavefront
         __syncthreads();
         prefix |= (u64)T.sel_bin << shift;
         r = T.sel_r;

@@ -68,15 +68,6 @@ __device__ __forceinline__ void acc_clear(Acc &a)
     a.r0 = a.c0 = INT_MAX; a.r1 = a.c1 = 0; a.flags = 0;
 }
 
-// e of an image from the bits of its max finite |g|: the smallest e with max < 2^e, clamped to -960 .. 1024; 0 without a non-zero pixel
-__device__ __forceinline__ int scale_exp(u64 maxbits)
-{
-    if (maxbits == 0) return 0;
-    const int E = (int)(maxbits >> 52);
-    const int e = E == 0 ? -960 : E - 1022;
-    return e < -960 ? -960 : e;
-}
-
 __device__ __forceinline__ void acc_pixel(Acc &a, int r, int c)
 {
     a.area++;
@@ -597,20 +588,7 @@ __global__ __launch_bounds__(MTPB) void k_label_pixel_lists(SetLabels S, const i
     }
 }
 
-// q(d2) = floor(sqrt(d2 * 2^32)): a float estimate (relative error below 2^-22), one Newton step from the exact 64-bit residual, which
-// leaves it within a few units, then the correction that makes it the integer root by construction.  d2 < 2^31: x < 2^63, r < 2^32.
-__host__ __device__ inline u64 quantised_distance(int32_t d2)
-{
-    if (d2 <= 0) return 0;
-    const u64 x = (u64)(uint32_t)d2 << 32;
-    u64 r = (u64)(sqrtf((float)d2) * 65536.0f);              // >= 65536
-    const i64 e = (i64)(x - r * r);                          // (the difference of the unsigned products, read as signed)
-    r = (u64)((i64)r + (i64)floorf((float)e / (2.0f * (float)r)));
-    while (r * r > x) r--;
-    while ((r + 1) * (r + 1) <= x) r++;
-    return r;
-}
-
+// (q(d2) = floor(sqrt(d2 * 2^32)) is quantised_distance of sdsm_tables.h, which the depth tables take as well)
 struct DArgs {
     const int32_t *a, *b, *counts_a, *counts_b, *start_a, *start_b;
     const uint32_t *list_a, *list_b;
@@ -766,6 +744,13 @@ extern "C" hipError_t sdsm_pair_distances_impl(const sdsm_set_image *images, int
 extern "C" void sdsm_quantised_distance_impl(const int32_t *d2, int64_t n, int64_t *out)
 {
     for (int64_t k = 0; k < n; k++) out[k] = (int64_t)quantised_distance(d2[k]);
+}
+
+// the scale step alone, for the tables that quantise intensities as these do (sdsm_depth.hip)
+extern "C" hipError_t sdsm_measure_scale_impl(const sdsm_set_image *images, int n_images, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp,
+                                              hipStream_t stream)
+{
+    return launch_scale(make_set(images, n_images), d_g, d_gmax_abs, d_scale_exp, stream);
 }
 
 extern "C" hipError_t sdsm_measure_objects_impl(const sdsm_set_image *images, int n_images, int n, const int32_t *obj_image, const int32_t *boxes,

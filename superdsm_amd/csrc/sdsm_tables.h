@@ -1,9 +1,11 @@
-// What the table kernels share (sdsm_measure.hip, sdsm_shape.hip, sdsm_intensity.hip, sdsm_texture.hip, sdsm_neighbours.hip): the images
-// of a launch, the order key of a double, the guard and the walk of an object's bit-packed fragment, and the slot claims of the LDS label
-// tables and the global pair tables.  Everything is inlined into its kernel.
+// What the table kernels share (sdsm_measure.hip, sdsm_shape.hip, sdsm_intensity.hip, sdsm_texture.hip, sdsm_neighbours.hip,
+// sdsm_depth.hip): the images of a launch, the order key of a double, the scale exponent of an image and the quantised root of a squared
+// distance, the guard and the walk of an object's bit-packed fragment, and the slot claims of the LDS label tables and the global pair
+// tables.  Everything is inlined into its kernel.
 #pragma once
 #include "sdsm_common.h"
 #include "sdsm_set.h"
+#include <cmath>
 
 typedef unsigned long long u64;
 typedef long long i64;
@@ -44,6 +46,56 @@ __device__ __forceinline__ double dkey_inv(u64 k)
 __device__ __forceinline__ bool finite_bits(double g)
 {
     return (((u64)__double_as_longlong(g) >> 52) & 0x7ff) != 0x7ff;
+}
+
+// e of an image from the bits of its max finite |g| (k_absmax of sdsm_measure.hip leaves them in device memory): the smallest e with
+// max < 2^e, clamped to -960 .. 1024; 0 without a non-zero pixel
+__device__ __forceinline__ int scale_exp(u64 maxbits)
+{
+    if (maxbits == 0) return 0;
+    const int E = (int)(maxbits >> 52);
+    const int e = E == 0 ? -960 : E - 1022;
+    return e < -960 ? -960 : e;
+}
+
+// q(d2) = floor(sqrt(d2 * 2^32)): a float estimate (relative error below 2^-22), one Newton step from the exact 64-bit residual, which
+// leaves it within a few units, then the correction that makes it the integer root by construction.  d2 < 2^31: x < 2^63, r < 2^32.
+__host__ __device__ inline u64 quantised_distance(int32_t d2)
+{
+    if (d2 <= 0) return 0;
+    const u64 x = (u64)(uint32_t)d2 << 32;
+    u64 r = (u64)(sqrtf((float)d2) * 65536.0f);              // >= 65536
+    const i64 e = (i64)(x - r * r);                          // (the difference of the unsigned products, read as signed)
+    r = (u64)((i64)r + (i64)floorf((float)e / (2.0f * (float)r)));
+    while (r * r > x) r--;
+    while ((r + 1) * (r + 1) <= x) r++;
+    return r;
+}
+
+// A round of an exact radix select, once its 256-bin histogram stands in LDS: one wavefront (the caller tests tid < 64) scans it, lane l
+// owning the bins 4 l .. 4 l + 3, and the one lane whose bins hold rank r publishes the bin, the rank that remains inside it and its count.
+__device__ __forceinline__ void select_bin(const uint32_t *hist, int tid, uint32_t r, uint32_t &sel_bin, uint32_t &sel_r, uint32_t &sel_cnt)
+{
+    const uint32_t h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
+    const uint32_t sum = h0 + h1 + h2 + h3;
+    uint32_t incl = sum;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(incl, o);
+        if (tid >= o) incl += t;
+    }
+    const uint32_t excl = incl - sum;
+    if (r >= excl && r < incl) {                 // exactly one lane
+        uint32_t rr = r - excl, c = h0;
+        int b = 0;
+        if (rr >= h0) {
+            rr -= h0; b = 1; c = h1;
+            if (rr >= h1) {
+                rr -= h1; b = 2; c = h2;
+                if (rr >= h2) { rr -= h2; b = 3; c = h3; }
+            }
+        }
+        sel_bin = 4 * tid + b; sel_r = rr; sel_cnt = c;
+    }
 }
 
 // ---- an object's fragment: h * w bits, contiguous from bits[0] on, for the box (r0, c0, h, w) of an H x W image ------------------------
