@@ -153,7 +153,7 @@ int sdsm_batch_launch_multi(const sdsm_plan *plan, const double *const *d_y, con
                             void *d_workspace, size_t workspace_bytes, sdsm_record *d_records, uint32_t *d_masks, double *d_xi, void *stream);
 int64_t sdsm_plan_xi_count(const sdsm_plan *plan);
 /* Workspace layout for inspection (parity tests of the crops / grid / G~ rows).  out[16], byte offsets into the
- * workspace: 0 cand table, 1 cand state (M, status, ...), 2 crop_y f64, 3 crop_rc u32, 4 crop_cc u32 (setup order),
+ * workspace: 0 cand table, 1 cand state (M, status, ...), 2 crop_y f64, 3 crop_rc u32, 4 crop_cc u32 (setup only: raster order; unused for regions whose setup state is held in LDS),
  * 5 ell_meta u32 (row entries | Hessian entries << 16), 6 grid u32, 7 ell_idx u16, 8 ell_w f32; then 9 zcap (entries
  * per row, a multiple of 4), 10 k, 11 sizeof(cand entry), 12 total_pixels, 13 total_ell entries, 14 sizeof(cand state);
  * 15 reserved.  Candidate i's blocks start at crop offset sum(n_pixels[:i]), G~ offset that * zcap -- entry s of crop

@@ -92,7 +92,7 @@ enum { ST_OK = 0, ST_TRIVIAL = 2, ST_ERROR = 3, ST_UNSUPPORTED = 4 };
 
 // Host-planned description of one candidate (read-only on the device).
 struct CandDesc {
-    int64_t crop_off;   // first pixel of the candidate's per-pixel setup arrays (tmp_y / tmp_rc / crop_cc / dist / inv)
+    int64_t crop_off;   // first pixel of the candidate's per-pixel setup arrays (tmp_y / tmp_rc / crop_cc / dist / inv), which are indexed by the raster rank of the pixel
     int64_t ell_off;    // first entry of its G~ block (NRcap * zcap_run entries; entry j of run position p at j * NR + p)
     int64_t mask_off;   // first uint32 word of its bit-packed region-bbox mask
     int64_t xi_off;     // first entry of its grid / xi block (Mcap entries)
@@ -100,7 +100,7 @@ struct CandDesc {
     int32_t r0, c0, h, w;   // region bounding box (union of the atoms' valid extents)
     int32_t fp_off, fp_len; // footprint labels
     int32_t Mcap;       // upper bound of M
-    uint32_t perm_inv;  // crop position of the pixel with raster rank i is (i * perm_inv) mod N (low-discrepancy scatter)
+    uint32_t perm_inv;  // multiplier of a low-discrepancy scatter of the pixels ((i * perm_inv) mod N); filled by the plan, no kernel reads it: the setup arrays are in raster order
     int32_t wide_g;     // > 0: solved by a group of this many workgroups (regions of more than SDSM_WIDE_MIN_PIXELS pixels)
     int64_t hglob_off;  // first double of its block in the global Hessian pool (a dense triangle of 6 + min(Mcap, 1018) unknowns; only if 6 + Mcap > SDSM_ENV_DENSE_N: the envelope may not fit LDS), else -1
     int64_t wide_off;   // first double of the candidate's block in the wide pool: SDSM_WIDE_SYNC (counters of the group / of sdsm_k_setup_rows) + 2 * wide_g * SDSM_WIDE_PBUF doubles; -1 if neither wide_g nor rows_g
@@ -167,9 +167,9 @@ struct BatchParams {
     uint32_t *run_meta;                // entries | leading entries << 12 | present pixels (4 bits) << 24
     uint32_t *run_q0;                  // setup only, raster order of the runs: raster rank of the run's first pixel | present pixels << 28
     uint32_t *run_aux;                 // setup only: [chunk of 64 positions] entries of the chunk's first run (padding target of its rows)
-    double *tmp_y;                     // setup only, per pixel: the crop in scan order (low-discrepancy scatter of the raster rank)
-    uint32_t *tmp_rc;                  // setup only, per pixel
-    uint32_t *crop_cc;                 // setup only, per pixel: compressed coordinates (scan order)
+    double *tmp_y;                     // setup only, per pixel: the crop in raster order (index = raster rank of the pixel within its region)
+    uint32_t *tmp_rc;                  // setup only, per pixel: image coordinates
+    uint32_t *crop_cc;                 // setup only, per pixel: compressed coordinates (raster order).  crop_cc, dist, inv and run_q0 stay unused for a region whose state the setup kernel holds in LDS (sdsm_setup.hip, RegionArrays)
     uint32_t *dist;                    // setup only, per pixel: chessboard distance to the nearest grid point; then, per run (scan order of the runs): entries
     uint32_t *inv;                     // setup only, per run (scan order of the runs): final position
     uint32_t *grid_rc;                 // sorted grid points, compressed coordinates

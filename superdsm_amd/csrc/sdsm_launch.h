@@ -48,9 +48,9 @@ constexpr int gate_ticket(GroupTicket t) { return -1 - t; }
 
 // ---- setup classes --------------------------------------------------------------------------------------------------------------
 // Limits of the setup kernel's LDS tables (sdsm_setup.hip): the plan picks the smallest class that holds it (sdsm_setup_class).
-struct SetupLimS { static constexpr int DIM = 512, GRID = 512, PSFW = 1152, LABELS = 32767, WPE = 4, WG = 256; };      // 13 KB: PSF k <= 33
-struct SetupLimM { static constexpr int DIM = 1024, GRID = 1024, PSFW = SDSM_PSF_LDS, LABELS = SDSM_MAX_LABELS, WPE = 4, WG = 1024; };   // 37 KB: PSF k <= 65; plans with regions this large have few candidates: 1024 threads each
-struct SetupLimL { static constexpr int DIM = SDSM_MAX_BBOX_DIM, GRID = SDSM_MAX_GRID, PSFW = SDSM_PSF_LDS, LABELS = SDSM_MAX_LABELS, WPE = 4, WG = 1024; };   // 54 KB
+struct SetupLimS { static constexpr int DIM = 512, GRID = 512, PSFW = 1152, LABELS = 32767, WPE = 4, WG = 256, STATE = 22528; };      // 18 KB of tables (PSF k <= 33) + 22 KB for the state of a region in LDS (STATE bytes, sdsm_setup.hip RegionArrays): 40 KB
+struct SetupLimM { static constexpr int DIM = 1024, GRID = 1024, PSFW = SDSM_PSF_LDS, LABELS = SDSM_MAX_LABELS, WPE = 4, WG = 1024, STATE = 0; };   // 37 KB: PSF k <= 65; plans with regions this large have few candidates: 1024 threads each
+struct SetupLimL { static constexpr int DIM = SDSM_MAX_BBOX_DIM, GRID = SDSM_MAX_GRID, PSFW = SDSM_PSF_LDS, LABELS = SDSM_MAX_LABELS, WPE = 4, WG = 1024, STATE = 0; };   // 54 KB
 constexpr bool sdsm_setup_fits_small(int h, int w, int mcap, int max_label, int k)
 {
     return h <= SetupLimS::DIM && w <= SetupLimS::DIM && mcap <= SetupLimS::GRID && max_label <= SetupLimS::LABELS && k * k <= SetupLimS::PSFW;

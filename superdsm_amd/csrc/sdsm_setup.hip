@@ -143,6 +143,12 @@ __device__ __forceinline__ GridCursor grid_cursor(const uint32_t *keys, int jlo,
     return g;
 }
 
+__device__ __forceinline__ int64_t uni64(int64_t v)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
 __device__ __forceinline__ int cheb(int r0, int c0, int r1, int c1)
 {
     int a = r0 - r1, b = c0 - c1;
@@ -165,38 +171,93 @@ __device__ __forceinline__ uint32_t scatter_mult(uint32_t NR)
     }
 }
 
-// The pixels of raster run rr: present mask, scan indices (into the per-pixel setup arrays) of the present ones.
-struct RunPixels { uint32_t mask; int idx[SDSM_RUN]; };
-__device__ __forceinline__ RunPixels run_pixels(const BatchParams &P, const CandDesc &cd, int rr)
+// Scan index si = (rr * B) mod NR of the raster runs rr0, rr0 + stride, ...: one 64-bit modulo at the start, then an add and a
+// conditional subtract per run (si, step < NR <= 2^28).
+struct ScatterWalk {
+    uint32_t si, step, NR;
+    __device__ __forceinline__ ScatterWalk(int rr0, int stride, uint32_t B, int nr) : NR((uint32_t)nr)
+    {
+        si = (uint32_t)(((unsigned long long)rr0 * B) % (unsigned long long)NR);
+        step = (uint32_t)(((unsigned long long)stride * B) % (unsigned long long)NR);
+    }
+    __device__ __forceinline__ void next() { si += step; si -= si >= NR ? NR : 0u; }
+};
+
+// The setup-only state of one region beside tmp_y / tmp_rc, in one of two layouts.  Global (LDS = false): the candidate's slices of
+// BatchParams.crop_cc / dist / inv / run_q0.  LDS (regions of at most T::STATE bytes of it, setup_state_bytes): a block of the
+// workgroup's LDS -- cc[N] | q0[NRcap] (32 bit), then dist[N] | pos[NRcap] (16 bit) -- and no global memory at all: none of it is a
+// result.  Pixels are indexed by their raster rank, runs by their raster number (q0) or their scan index (cnt, pos).
+typedef uint32_t __attribute__((address_space(3))) *lds_u32_p;
+typedef uint16_t __attribute__((address_space(3))) *lds_u16_p;
+#define SDSM_NO_GRID_POINT 0xffffffffu      // distance of a pixel while the grid is empty (distance_transform_bf without any grid point)
+template <bool LDS>
+struct RegionArrays {
+    const BatchParams &P;
+    const CandDesc &cd;
+    uint32_t *lds;                          // the LDS block (LDS layout only)
+    __device__ __forceinline__ lds_u32_p w32() const { return (lds_u32_p)lds; }
+    __device__ __forceinline__ lds_u16_p w16() const { return (lds_u16_p)(lds + cd.N + cd.NRcap); }
+    // compressed coordinates of a pixel (before step 2 of the LDS layout: its image coordinates)
+    __device__ __forceinline__ uint32_t cc(int i) const { if constexpr (LDS) return w32()[i]; else return P.crop_cc[cd.crop_off + i]; }
+    __device__ __forceinline__ void set_cc(int i, uint32_t v) const { if constexpr (LDS) w32()[i] = v; else P.crop_cc[cd.crop_off + i] = v; }
+    // raster rank of the first pixel of a raster run | present pixels << 28
+    __device__ __forceinline__ uint32_t q0(int rr) const { if constexpr (LDS) return w32()[cd.N + rr]; else return P.run_q0[cd.run_off + rr]; }
+    __device__ __forceinline__ void set_q0(int rr, uint32_t v) const { if constexpr (LDS) w32()[cd.N + rr] = v; else P.run_q0[cd.run_off + rr] = v; }
+    // chessboard distance of a pixel to the nearest grid point, in compressed coordinates (< DIM: 16 bits hold it, 0xffff: no grid point)
+    __device__ __forceinline__ uint32_t dist(int i) const
+    {
+        if constexpr (LDS) { const uint32_t d = w16()[i]; return d == 0xffffu ? SDSM_NO_GRID_POINT : d; }
+        else return P.dist[cd.crop_off + i];
+    }
+    __device__ __forceinline__ void set_dist(int i, uint32_t d) const
+    {
+        if constexpr (LDS) w16()[i] = (uint16_t)(d < 0xffffu ? d : 0xffffu);
+        else P.dist[cd.crop_off + i] = d;
+    }
+    // per run, by scan index: number of G~ entries (in the place of the distances, which step 3 is done with), sort class and then final position
+    __device__ __forceinline__ uint32_t cnt(int si) const { if constexpr (LDS) return w16()[si]; else return P.dist[cd.crop_off + si]; }
+    __device__ __forceinline__ void set_cnt(int si, uint32_t v) const { if constexpr (LDS) w16()[si] = (uint16_t)v; else P.dist[cd.crop_off + si] = v; }
+    __device__ __forceinline__ uint32_t pos(int si) const { if constexpr (LDS) return w16()[cd.N + si]; else return P.inv[cd.crop_off + si]; }
+    __device__ __forceinline__ void set_pos(int si, uint32_t v) const { if constexpr (LDS) w16()[cd.N + si] = (uint16_t)v; else P.inv[cd.crop_off + si] = v; }
+};
+// Bytes of the LDS layout: 6 per pixel and 6 per run (an entry count is at most GRID, a position below N: both below 2^16 in a block of T::STATE bytes).
+__host__ __device__ constexpr long long setup_state_bytes(long long N, long long NRcap) { return 6 * (N + NRcap); }
+
+// The pixels of raster run rr: present mask, raster ranks (the index into the per-pixel setup arrays) of the present ones.
+struct RunPixels { uint32_t mask; int q; int idx[SDSM_RUN]; };     // q: raster rank of the first present pixel
+template <bool LDS>
+__device__ __forceinline__ RunPixels run_pixels(const RegionArrays<LDS> &A, int rr)
 {
     RunPixels rp;
-    const uint32_t q0m = P.run_q0[cd.run_off + rr];
+    const uint32_t q0m = A.q0(rr);
     rp.mask = q0m >> 28;
-    uint32_t q = q0m & 0x0fffffffu;
+    rp.q = (int)(q0m & 0x0fffffffu);
 #pragma unroll
-    for (int k = 0; k < SDSM_RUN; k++) {
-        rp.idx[k] = -1;
-        if ((rp.mask >> k) & 1u) { rp.idx[k] = (int)(((unsigned long long)q * cd.perm_inv) % (unsigned long long)cd.N); q++; }
-    }
+    for (int k = 0; k < SDSM_RUN; k++) rp.idx[k] = (rp.mask >> k) & 1u ? rp.q + __popc(rp.mask & ((1u << k) - 1u)) : -1;
     return rp;
+}
+// (row << 16) | first column of the run's cell, image coordinates: from the coordinates of its first present pixel
+__device__ __forceinline__ uint32_t run_rc0(const BatchParams &P, const CandDesc &cd, const RunPixels &rp)
+{
+    return rp.mask ? P.tmp_rc[cd.crop_off + rp.q] - (uint32_t)(__ffs((int)rp.mask) - 1) : 0u;
 }
 
 // Runs without G~ (null matrix, or more grid points than the solver holds): the final order is the scan order of the runs.
-__device__ __forceinline__ void plain_runs(const BatchParams &P, const CandDesc &cd, int NR, uint32_t B, int tid, int nthreads)
+template <bool LDS>
+__device__ __forceinline__ void plain_runs(const RegionArrays<LDS> &A, int NR, uint32_t B, int tid, int nthreads)
 {
-    for (int rr = tid; rr < NR; rr += nthreads) {
-        const int pos = (int)(((unsigned long long)rr * B) % (unsigned long long)NR);
-        const RunPixels rp = run_pixels(P, cd, rr);
+    const BatchParams &P = A.P;
+    const CandDesc &cd = A.cd;
+    ScatterWalk sw(tid, nthreads, B, NR);
+    for (int rr = tid; rr < NR; rr += nthreads, sw.next()) {
+        const int pos = (int)sw.si;
+        const RunPixels rp = run_pixels(A, rr);
         double yk[SDSM_RUN];
-        uint32_t rc0 = 0;
-        bool first = true;
+        const uint32_t rc0 = run_rc0(P, cd, rp);
 #pragma unroll
         for (int k = 0; k < SDSM_RUN; k++) {
             yk[k] = 0;
-            if (rp.idx[k] >= 0) {
-                yk[k] = P.tmp_y[cd.crop_off + rp.idx[k]];
-                if (first) { rc0 = P.tmp_rc[cd.crop_off + rp.idx[k]] - (uint32_t)k; first = false; }
-            }
+            if (rp.idx[k] >= 0) yk[k] = P.tmp_y[cd.crop_off + rp.idx[k]];
         }
         double *yo = P.crop_y + (cd.run_off + pos) * SDSM_RUN;
 #pragma unroll
@@ -220,29 +281,32 @@ __device__ __forceinline__ void plain_runs(const BatchParams &P, const CandDesc 
 // within R that writes an entry for every point inside the window of at least one of its pixels (weight 0 for the others).
 // Runs are taken in RASTER order: the 64 lanes of a wavefront then sit next to each other in the image, see (almost) the same
 // grid points and take the same branches in the loops over them.  efirst (LDS, M ints, initialised to j): first coupled column.
-template <bool PSF_LDS>
-__device__ __forceinline__ void rows_of_runs(const BatchParams &P, const CandDesc &cd, int NR, uint32_t B, int M, int R, int hc, const uint32_t *gridkeys,
+template <bool PSF_LDS, bool LDS>
+__device__ __forceinline__ void rows_of_runs(const RegionArrays<LDS> &A, int NR, uint32_t B, int M, int R, int hc, const uint32_t *gridkeys,
                                              const uint16_t *growstart, const float *psf_lds, int *efirst, int rr0, int rr1, int step,
                                              bool &bad, int &hzmax ROWS_PROF_PARAM)
 {
+    const BatchParams &P = A.P;
+    const CandDesc &cd = A.cd;
+    const int64_t crop_off = uni64(cd.crop_off);         // (same for all lanes: scalar address arithmetic, no registers per lane for the array bases)
+    ScatterWalk sw(rr0, step, B, NR);
     for (int rr = rr0; rr < rr1; rr += step) {
         ROWS_T(3);
-        const int si = (int)(((unsigned long long)rr * B) % (unsigned long long)NR);
-        const int pos = (int)P.inv[cd.crop_off + si];
-        const int nnz = (int)P.dist[cd.crop_off + si];
-        const RunPixels rp = run_pixels(P, cd, rr);
+        const int si = (int)sw.si;
+        sw.next();
+        const int pos = (int)A.pos(si);
+        const int nnz = (int)A.cnt(si);
+        const RunPixels rp = run_pixels(A, rr);
         int cr = 0, cck[SDSM_RUN];
         double yk[SDSM_RUN];
-        uint32_t rc0 = 0;
-        bool first = true;
+        const uint32_t rc0 = rp.mask ? P.tmp_rc[crop_off + rp.q] - (uint32_t)(__ffs((int)rp.mask) - 1) : 0u;
 #pragma unroll
         for (int k = 0; k < SDSM_RUN; k++) {
             yk[k] = 0; cck[k] = -(1 << 20);              // an absent pixel: no grid point is inside its window
             if (rp.idx[k] >= 0) {
-                yk[k] = P.tmp_y[cd.crop_off + rp.idx[k]];
-                const uint32_t key = P.crop_cc[cd.crop_off + rp.idx[k]];
+                yk[k] = P.tmp_y[crop_off + rp.idx[k]];
+                const uint32_t key = A.cc(rp.idx[k]);
                 cr = key >> 16; cck[k] = key & 0xffffu;
-                if (first) { rc0 = P.tmp_rc[cd.crop_off + rp.idx[k]] - (uint32_t)k; first = false; }
             }
         }
         double *yo = P.crop_y + (cd.run_off + pos) * SDSM_RUN;
@@ -360,24 +424,49 @@ __device__ __forceinline__ int envelope_from_first(const BatchParams &P, const C
 // workgroups per compute unit instead of the two that the largest tables allow (1.58 -> 1.22 ms on the 8-image launch).
 // One candidate by one workgroup (`return` leaves the candidate; every exit is uniform over the workgroup).  A function of its own: with the body written into
 // the kernel the register allocator left 2 / 6 spilled registers (12 / 20 B of scratch per lane) in two of the three instantiations, this way none.
+// The workgroup's LDS: one block, shared by the two layouts of the region state (the kernel declares it once).
 template <class T>
-__device__ __forceinline__ void setup_candidate(const BatchParams &P)
+struct SetupLds {
+    // footprint bitset during the region scan, then the PSF table (k * k floats, if it fits) for the rows of G~
+    uint32_t fp_or_psf[T::PSFW];
+    uint32_t rowbits[T::DIM / 32], colbits[T::DIM / 32];
+    uint16_t rowrank[T::DIM], colrank[T::DIM];
+    uint32_t gridkeys[T::GRID];
+    unsigned long long mom[4];
+    unsigned long long scr64[(T::WG / 64)];
+    int scr32[(T::WG / 64)];
+    unsigned scr32u[(T::WG / 64)];
+    int sh_M, sh_npos, sh_nneg, sh_err, sh_yhi;
+    int cls_cnt[SDSM_MAX_ELL_GROUPS + 1], cls_start[SDSM_MAX_ELL_GROUPS + 1], cls_run[SDSM_MAX_ELL_GROUPS + 1];
+    int wave_cnt[(T::WG / 64)][SDSM_MAX_ELL_GROUPS + 1];
+    int efirst[T::GRID < SDSM_MAX_N_GLOBAL ? T::GRID : SDSM_MAX_N_GLOBAL];   // envelope of the solver's Hessian: first coupled column per grid point
+    CandState state;
+    uint32_t region[T::STATE > 0 ? T::STATE / 4 : 1];                        // the region state in its LDS layout (RegionArrays)
+};
+static_assert(sizeof(SetupLds<SetupLimS>) <= 40 * 1024, "four setup workgroups of the small class per compute unit: 40 KB of LDS each");
+static_assert(SetupLimS::DIM < 0xffff && SetupLimS::GRID < 0xffff && SetupLimS::STATE / 6 < 0xffff && SetupLimS::STATE % 4 == 0, "16-bit fields of the LDS layout");
+
+#ifdef SDSM_PROFILE_WALL
+// (diagnostic build: start and end of the candidate's setup workgroup on the 100 MHz wall clock, behind the 8 n_total cycle counters of prof2)
+#define SETUP_WALL_END() do { if (P.prof2 && threadIdx.x == 0) { long long *_w = P.prof2 + (size_t)8 * P.n_total + (size_t)2 * ci; _w[0] = wall_t0; _w[1] = wall_clock64(); } } while (0)
+#else
+#define SETUP_WALL_END() do { } while (0)
+#endif
+
+template <class T, bool LDS>
+__device__ __forceinline__ void setup_candidate(const BatchParams &P, SetupLds<T> &L)
 {
     static_assert((T::LABELS + 1) / 32 <= T::PSFW && T::DIM % 32 == 0, "setup limits");
-    // footprint bitset during the region scan, then the PSF table (k * k floats, if it fits) for the rows of G~
-    __shared__ uint32_t fp_or_psf[T::PSFW];
+    auto &fp_or_psf = L.fp_or_psf;
     uint32_t *fpbits = fp_or_psf;
-    __shared__ uint32_t rowbits[T::DIM / 32], colbits[T::DIM / 32];
-    __shared__ uint16_t rowrank[T::DIM], colrank[T::DIM];
-    __shared__ uint32_t gridkeys[T::GRID];
-    __shared__ unsigned long long mom[4];
-    __shared__ unsigned long long scr64[(T::WG / 64)];
-    __shared__ int scr32[(T::WG / 64)];
-    __shared__ unsigned scr32u[(T::WG / 64)];
-    __shared__ int sh_M, sh_npos, sh_nneg, sh_err, sh_yhi;
-    __shared__ int cls_cnt[SDSM_MAX_ELL_GROUPS + 1], cls_start[SDSM_MAX_ELL_GROUPS + 1], cls_run[SDSM_MAX_ELL_GROUPS + 1];
-    __shared__ int wave_cnt[(T::WG / 64)][SDSM_MAX_ELL_GROUPS + 1];
-    __shared__ int efirst[T::GRID < SDSM_MAX_N_GLOBAL ? T::GRID : SDSM_MAX_N_GLOBAL];   // envelope of the solver's Hessian: first coupled column per grid point
+    auto &rowbits = L.rowbits; auto &colbits = L.colbits;
+    auto &rowrank = L.rowrank; auto &colrank = L.colrank;
+    auto &gridkeys = L.gridkeys;
+    auto &mom = L.mom; auto &scr64 = L.scr64; auto &scr32 = L.scr32; auto &scr32u = L.scr32u;
+    int &sh_M = L.sh_M, &sh_npos = L.sh_npos, &sh_nneg = L.sh_nneg, &sh_err = L.sh_err, &sh_yhi = L.sh_yhi;
+    auto &cls_cnt = L.cls_cnt; auto &cls_start = L.cls_start; auto &cls_run = L.cls_run;
+    auto &wave_cnt = L.wave_cnt;
+    auto &efirst = L.efirst;
 
 #ifdef SDSM_PROFILE
     long long sp_t = PROF_NOW(), sp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -385,9 +474,13 @@ __device__ __forceinline__ void setup_candidate(const BatchParams &P)
 #else
 #define SETUP_T(k) do { } while (0)
 #endif
+#ifdef SDSM_PROFILE_WALL
+    const long long wall_t0 = wall_clock64();
+#endif
     const int tid = threadIdx.x;
     const int ci = P.order[blockIdx.x];
     const CandDesc cd = P.cand[ci];
+    const RegionArrays<LDS> A = {P, cd, L.region};
     CandState *st = &P.state[ci];
     const ImageRef im = P.img[cd.image];
     const double *__restrict__ y = im.y;
@@ -416,8 +509,8 @@ __device__ __forceinline__ void setup_candidate(const BatchParams &P)
     __syncthreads();
 
     // ---- 1. region scan in raster order over the bounding box, one aligned 4-column cell per thread and step: the region
-    //      pixels of a cell are one RUN; pixels go to the per-pixel setup arrays in scan order (low-discrepancy scatter of the
-    //      raster rank, the order the grid steps work in), runs are numbered in raster order ------------------------------------
+    //      pixels of a cell are one RUN; pixels go to the per-pixel setup arrays by their raster rank (consecutive lanes write
+    //      consecutive addresses), runs are numbered in raster order ----------------------------------------------------------
     const int cb0 = cd.c0 >> 2, ncw = ((cd.c0 + cd.w - 1) >> 2) - cb0 + 1;
     const int ncell = cd.h * ncw;
     int running = 0, nruns = 0;
@@ -460,9 +553,11 @@ __device__ __forceinline__ void setup_candidate(const BatchParams &P)
                 const int c = ccell + k - cd.c0;
                 const double yv = yv4[k];
                 if (q < cd.N) {
-                    const int64_t o = cd.crop_off + (int64_t)(((unsigned long long)q * cd.perm_inv) % (unsigned long long)cd.N);
+                    const int64_t o = cd.crop_off + q;
+                    const uint32_t rc = ((uint32_t)(cd.r0 + r) << 16) | (uint32_t)(cd.c0 + c);
                     P.tmp_y[o] = yv;
-                    P.tmp_rc[o] = ((uint32_t)(cd.r0 + r) << 16) | (uint32_t)(cd.c0 + c);
+                    P.tmp_rc[o] = rc;
+                    if constexpr (LDS) A.set_cc(q, rc);           // (step 2 turns it into the compressed coordinates in place)
                 }
                 q++;
                 if (fits) atomicOr(&colbits[c >> 5], 1u << (c & 31));
@@ -474,7 +569,7 @@ __device__ __forceinline__ void setup_candidate(const BatchParams &P)
                     npos++; m_r += rq; m_c += cq; m_rr += rq * rq; m_cc += cq * cq;
                 }
             }
-            if (rr < cd.NRcap) P.run_q0[cd.run_off + rr] = q0 | (mask << 28);
+            if (rr < cd.NRcap) A.set_q0(rr, q0 | (mask << 28));
         }
         running += (int)(tot2 & 0xffffu);
         nruns += (int)(tot2 >> 16);
@@ -494,7 +589,7 @@ __device__ __forceinline__ void setup_candidate(const BatchParams &P)
         s.NR = NR;
         if (running != cd.N || NR > cd.NRcap || NR < 1) s.status = ST_ERROR;
         else if (s.npos == 1 && !P.no_trivial_rule) s.status = ST_TRIVIAL;
-        else { plain_runs(P, cd, NR, B, tid, T::WG); s.M = SDSM_MAX_N_GLOBAL; s.status = ST_OK; }
+        else { plain_runs(A, NR, B, tid, T::WG); s.M = SDSM_MAX_N_GLOBAL; s.status = ST_OK; }
         if (tid == 0) *st = s;
         return;
     }
@@ -517,40 +612,40 @@ __device__ __forceinline__ void setup_candidate(const BatchParams &P)
     __syncthreads();
 
     // (the state lives in LDS, every thread stores the same values: 26 registers less across the rest of the kernel)
-    __shared__ CandState sh_state;
-    CandState &s = sh_state;
-    if (tid < (int)(sizeof(CandState) / 4)) reinterpret_cast<int *>(&sh_state)[tid] = 0;
+    CandState &s = L.state;
+    if (tid < (int)(sizeof(CandState) / 4)) reinterpret_cast<int *>(&L.state)[tid] = 0;
     __syncthreads();
     s.hc = hc; s.wc = wc; s.npos = sh_npos; s.nneg = sh_nneg;
     s.sum_r = mom[0]; s.sum_c = mom[1]; s.sum_rr = mom[2]; s.sum_cc = mom[3];
     { int ex = ((sh_yhi >> 20) & 0x7ff) - 1022; s.yexp = ex < -400 ? -400 : (ex > 400 ? 400 : ex); }
     s.NR = NR;
     if (running != cd.N || NR > cd.NRcap || NR < 1) { s.status = ST_ERROR; if (tid == 0) *st = s; return; }   // plan / image mismatch
-    if (s.npos == 1 && !P.no_trivial_rule) { s.status = ST_TRIVIAL; if (tid == 0) *st = s; return; }            // objects.py:184-191 (no solve)
+    if (s.npos == 1 && !P.no_trivial_rule) { s.status = ST_TRIVIAL; if (tid == 0) *st = s; SETUP_WALL_END(); return; }            // objects.py:184-191 (no solve)
 
     const int S = P.subsample, R = P.R;
     const bool null_matrix = P.no_deform || hc <= P.k / 2 || wc <= P.k / 2;               // dsm.py:187,225
     for (int i = tid; i < cd.N; i += T::WG) {
-        uint32_t rc = P.tmp_rc[cd.crop_off + i];
+        uint32_t rc = LDS ? A.cc(i) : P.tmp_rc[cd.crop_off + i];
         int r = (int)(rc >> 16) - cd.r0, c = (int)(rc & 0xffffu) - cd.c0;
         uint32_t key = ((uint32_t)rowrank[r] << 16) | (uint32_t)colrank[c];
-        P.crop_cc[cd.crop_off + i] = key;
+        A.set_cc(i, key);
         if (!null_matrix && rowrank[r] % S == 0 && colrank[c] % S == 0) {                   // dsm.py:165-168
             int j = atomicAdd(&sh_M, 1);
             if (j < T::GRID) gridkeys[j] = key;
         }
     }
     if (null_matrix) {                                  // no G~: the final order of the runs is their scan order
-        plain_runs(P, cd, NR, B, tid, T::WG);
+        plain_runs(A, NR, B, tid, T::WG);
         s.M = 0; s.status = ST_OK;
         if (tid == 0) *st = s;
+        SETUP_WALL_END();
         return;
     }
     __syncthreads();
     const int cap = cd.Mcap < T::GRID ? cd.Mcap : T::GRID;
     int M = sh_M;
     // more grid points than this kernel's table (or the host's bound) holds: the elliptical model only, flagged by the solve kernel
-    if (M > cap) { plain_runs(P, cd, NR, B, tid, T::WG); s.M = SDSM_MAX_N_GLOBAL; s.status = ST_OK; if (tid == 0) *st = s; return; }
+    if (M > cap) { plain_runs(A, NR, B, tid, T::WG); s.M = SDSM_MAX_N_GLOBAL; s.status = ST_OK; if (tid == 0) *st = s; return; }
 
     SETUP_T(1);
     // ---- 3. greedy completion of the grid (dsm.py:169-181) --------------------------------------
@@ -571,7 +666,7 @@ __device__ __forceinline__ void setup_candidate(const BatchParams &P)
         }
         __syncthreads();
         for (int i = tid; i < cd.N; i += T::WG) {
-            const uint32_t key = P.crop_cc[cd.crop_off + i];
+            const uint32_t key = A.cc(i);
             const int r = key >> 16, c = key & 0xffffu;
             const int i0 = r / S, j0 = c / S;
             uint32_t d = 0xffffffffu;                   // distance_transform_bf without any grid point
@@ -598,19 +693,19 @@ __device__ __forceinline__ void setup_candidate(const BatchParams &P)
                     d = t < d ? t : d;
                 }
             }
-            P.dist[cd.crop_off + i] = d;
+            A.set_dist(i, d);
         }
         __syncthreads();                                 // (the bitmap's LDS is reused by step 4b)
     } else {
         for (int i = tid; i < cd.N; i += T::WG) {
-            uint32_t key = P.crop_cc[cd.crop_off + i];
+            uint32_t key = A.cc(i);
             int r = key >> 16, c = key & 0xffffu;
             uint32_t d = 0xffffffffu;                       // distance_transform_bf without any grid point
             for (int j = 0; j < M; j++) {
                 uint32_t t = (uint32_t)cheb(r, c, gridkeys[j] >> 16, gridkeys[j] & 0xffffu);
                 d = t < d ? t : d;
             }
-            P.dist[cd.crop_off + i] = d;
+            A.set_dist(i, d);
         }
     }
     bool unsupported = false;
@@ -618,9 +713,9 @@ __device__ __forceinline__ void setup_candidate(const BatchParams &P)
     // added grid point: the pass that lowers the distances to the new point also finds the next candidate.
     unsigned long long best = ~0ull;
     for (int i = tid; i < cd.N; i += T::WG) {
-        uint32_t d = P.dist[cd.crop_off + i];
+        uint32_t d = A.dist(i);
         if (d >= (uint32_t)S) {
-            unsigned long long key = ((unsigned long long)d << 32) | P.crop_cc[cd.crop_off + i];
+            unsigned long long key = ((unsigned long long)d << 32) | A.cc(i);
             best = key < best ? key : best;
         }
     }
@@ -634,20 +729,20 @@ __device__ __forceinline__ void setup_candidate(const BatchParams &P)
         int nr = nk >> 16, nc = nk & 0xffffu;
         best = ~0ull;
         for (int i = tid; i < cd.N; i += T::WG) {
-            const uint32_t key = P.crop_cc[cd.crop_off + i];
+            const uint32_t key = A.cc(i);
             const uint32_t t = (uint32_t)cheb(key >> 16, key & 0xffffu, nr, nc);
-            uint32_t d = P.dist[cd.crop_off + i];
-            if (t < d) { d = t; P.dist[cd.crop_off + i] = t; }
+            uint32_t d = A.dist(i);
+            if (t < d) { d = t; A.set_dist(i, t); }
             if (d >= (uint32_t)S) {
                 unsigned long long k2 = ((unsigned long long)d << 32) | key;
                 best = k2 < best ? k2 : best;
             }
         }
     }
-    if (unsupported) { __syncthreads(); plain_runs(P, cd, NR, B, tid, T::WG); s.M = SDSM_MAX_N_GLOBAL; s.status = ST_OK; if (tid == 0) *st = s; return; }
+    if (unsupported) { __syncthreads(); plain_runs(A, NR, B, tid, T::WG); s.M = SDSM_MAX_N_GLOBAL; s.status = ST_OK; if (tid == 0) *st = s; return; }
     __syncthreads();
     if (6 + M > SDSM_MAX_N_GLOBAL) {                     // the solve kernel only computes the elliptical model (flagged unsupported)
-        plain_runs(P, cd, NR, B, tid, T::WG);
+        plain_runs(A, NR, B, tid, T::WG);
         s.M = M; s.status = ST_OK;
         if (tid == 0) *st = s;
         return;
@@ -683,14 +778,15 @@ __device__ __forceinline__ void setup_candidate(const BatchParams &P)
     for (int k = tid; k <= ngmax; k += T::WG) { cls_cnt[k] = 0; cls_run[k] = 0; }
     __syncthreads();
     int cntmax = 0;
-    for (int rr = tid; rr < NR; rr += T::WG) {          // raster order (coherent wavefronts), see rows_of_runs
-        const int si = (int)(((unsigned long long)rr * B) % (unsigned long long)NR);
-        const RunPixels rp = run_pixels(P, cd, rr);
+    ScatterWalk sw(tid, T::WG, B, NR);
+    for (int rr = tid; rr < NR; rr += T::WG, sw.next()) {          // raster order (coherent wavefronts), see rows_of_runs
+        const int si = (int)sw.si;
+        const RunPixels rp = run_pixels(A, rr);
         int cr = 0, cck[SDSM_RUN];
 #pragma unroll
         for (int k = 0; k < SDSM_RUN; k++) {
             cck[k] = -(1 << 20);
-            if (rp.idx[k] >= 0) { const uint32_t key = P.crop_cc[cd.crop_off + rp.idx[k]]; cr = key >> 16; cck[k] = key & 0xffffu; }
+            if (rp.idx[k] >= 0) { const uint32_t key = A.cc(rp.idx[k]); cr = key >> 16; cck[k] = key & 0xffffu; }
         }
         int cnt = 0;
         const int jlo = growstart[cr - R > 0 ? cr - R : 0], jhi = cr + R + 1 < hc ? growstart[cr + R + 1] : M;
@@ -706,8 +802,8 @@ __device__ __forceinline__ void setup_candidate(const BatchParams &P)
         cntmax = cnt > cntmax ? cnt : cntmax;
         int k = (cnt + (1 << zshift) - 1) >> zshift;
         k = k > ngmax ? ngmax : k;                       // runs with more entries than zcap_run are reported as errors in step 5
-        P.dist[cd.crop_off + si] = (uint32_t)cnt;
-        P.inv[cd.crop_off + si] = (uint32_t)k;
+        A.set_cnt(si, (uint32_t)cnt);
+        A.set_pos(si, (uint32_t)k);
         atomicAdd(&cls_cnt[k], 1);
     }
     __syncthreads();
@@ -722,7 +818,7 @@ __device__ __forceinline__ void setup_candidate(const BatchParams &P)
             for (int e = tid; e < (T::WG / 64) * (ngmax + 1); e += T::WG) wave_cnt[e / (ngmax + 1)][e % (ngmax + 1)] = 0;
             __syncthreads();
             const int i = base + tid;
-            const int k = i < NR ? (int)P.inv[cd.crop_off + i] : -1;
+            const int k = i < NR ? (int)A.pos(i) : -1;
             int within = 0;
             unsigned long long todo = __ballot(k >= 0);
             while (todo) {                               // one pass per distinct class present in the wavefront
@@ -739,7 +835,7 @@ __device__ __forceinline__ void setup_candidate(const BatchParams &P)
             if (k >= 0) {
                 int before = 0;
                 for (int w2 = 0; w2 < wave; w2++) before += wave_cnt[w2][k];
-                P.inv[cd.crop_off + i] = (uint32_t)(cls_start[k] + cls_run[k] + before + within);
+                A.set_pos(i, (uint32_t)(cls_start[k] + cls_run[k] + before + within));
             }
             __syncthreads();
             for (int k2 = tid; k2 <= ngmax; k2 += T::WG) {
@@ -776,6 +872,7 @@ __device__ __forceinline__ void setup_candidate(const BatchParams &P)
 #ifdef SDSM_PROFILE
         if (P.prof2 && tid == 0) for (int k = 0; k < 8; k++) P.prof2[(size_t)ci * 8 + k] = sp_acc[k];
 #endif
+        SETUP_WALL_END();
         return;
     }
 
@@ -792,8 +889,8 @@ __device__ __forceinline__ void setup_candidate(const BatchParams &P)
 #ifdef SDSM_PROFILE
     long long rows_t[5] = {0, 0, 0, 0, PROF_NOW()};
 #endif
-    if (psf_lds) rows_of_runs<true>(P, cd, NR, B, M, R, hc, gridkeys, growstart, psf_lds, efirst, tid, NR, T::WG, bad, hzmax ROWS_PROF_ARG);
-    else rows_of_runs<false>(P, cd, NR, B, M, R, hc, gridkeys, growstart, psf_lds, efirst, tid, NR, T::WG, bad, hzmax ROWS_PROF_ARG);
+    if (psf_lds) rows_of_runs<true>(A, NR, B, M, R, hc, gridkeys, growstart, psf_lds, efirst, tid, NR, T::WG, bad, hzmax ROWS_PROF_ARG);
+    else rows_of_runs<false>(A, NR, B, M, R, hc, gridkeys, growstart, psf_lds, efirst, tid, NR, T::WG, bad, hzmax ROWS_PROF_ARG);
     if (bad) atomicOr(&sh_err, 1);
     hzmax = -block_min_i32<T::WG / 64>(-hzmax, scr32);
     __syncthreads();
@@ -807,19 +904,27 @@ __device__ __forceinline__ void setup_candidate(const BatchParams &P)
 #ifdef SDSM_PROFILE
     if (P.prof2 && tid == 0) for (int k = 0; k < 8; k++) P.prof2[(size_t)ci * 8 + k] = sp_acc[k];
 #endif
+    SETUP_WALL_END();
 }
 
 template <class T>
 __global__ __launch_bounds__(T::WG, T::WPE) void sdsm_k_setup(BatchParams P)
 {
-    setup_candidate<T>(P);
+    __shared__ SetupLds<T> L;
+    if constexpr (T::STATE > 0) {
+        // the layout of the region state, uniform over the workgroup: LDS where the plan's bounds on the region's pixels and runs fit the block
+        // (a region whose rows sdsm_k_setup_rows builds keeps the global arrays, which that kernel reads)
+        const CandDesc &cd = P.cand[P.order[blockIdx.x]];
+        if (cd.N > 0 && cd.rows_g <= 0 && setup_state_bytes(cd.N, cd.NRcap) <= T::STATE) { setup_candidate<T, true>(P, L); return; }
+    }
+    setup_candidate<T, false>(P, L);
 }
 
 // Rows of G~ and envelope of the very large regions: one workgroup per member of the region's workgroup group, each takes
 // a slice of the raster ranks.  The members meet through global atomics only (first coupled columns: atomicMin, largest
 // number of Hessian entries: atomicMax, error flag: atomicOr); the LAST member to finish (a ticket counter, no waiting)
 // builds the envelope and completes the state.
-__global__ __launch_bounds__(SDSM_WG) void sdsm_k_setup_rows(BatchParams P)
+__global__ __launch_bounds__(SDSM_WG, 4) void sdsm_k_setup_rows(BatchParams P)      // (four workgroups per compute unit as before the runs' scan index became a loop variable: <= 128 registers)
 {
     extern __shared__ __align__(16) unsigned char rows_dyn[];            // gridkeys[P.rows_mcap] | efirst[P.rows_mcap]: sized by the plan (launch)
     uint32_t *gridkeys = reinterpret_cast<uint32_t *>(rows_dyn);
@@ -861,8 +966,9 @@ __global__ __launch_bounds__(SDSM_WG) void sdsm_k_setup_rows(BatchParams P)
     rt1 = PROF_NOW();
     long long rows_t[5] = {0, 0, 0, 0, rt1};
 #endif
-    if (psf_lds) rows_of_runs<true>(P, cd, NR, B, M, R, hc, gridkeys, growstart, psf_lds, efirst, q0 + tid, q1, SDSM_WG, bad, hzmax ROWS_PROF_ARG);
-    else rows_of_runs<false>(P, cd, NR, B, M, R, hc, gridkeys, growstart, psf_lds, efirst, q0 + tid, q1, SDSM_WG, bad, hzmax ROWS_PROF_ARG);
+    const RegionArrays<false> A = {P, cd, nullptr};      // (the regions of this kernel keep their state in the global arrays)
+    if (psf_lds) rows_of_runs<true>(A, NR, B, M, R, hc, gridkeys, growstart, psf_lds, efirst, q0 + tid, q1, SDSM_WG, bad, hzmax ROWS_PROF_ARG);
+    else rows_of_runs<false>(A, NR, B, M, R, hc, gridkeys, growstart, psf_lds, efirst, q0 + tid, q1, SDSM_WG, bad, hzmax ROWS_PROF_ARG);
 #ifdef SDSM_PROFILE
     rt2 = PROF_NOW();
 #endif
