@@ -856,6 +856,43 @@ int sdsm_neighbours_multi(const sdsm_set_image *images, int n_images, const int3
 int sdsm_neighbours(int H, int W, const int32_t *d_labels, int max_d2, int n_labels, sdsm_neighbour_label *d_label_out, int64_t capacity,
                     uint64_t *d_keys, uint32_t *d_min_d2, uint32_t *d_contact, int32_t *d_status, void *stream);   /* the set of one image */
 
+/* ---- zone label maps of one label map (no reference counterpart; the definitions are nearest_other_host and zone_maps_host of
+ * superdsm_amd/zones.py) ---------------------------------------------------------------------------------------------------------------
+ * New label maps out of one label map, in integers only.  The map L (labels 0 .. 65535, 0 the background) is extended by label 0
+ * outside the image frame.  NEAREST OTHER: for a pixel p, among the lattice places q with 0 < |p - q|^2 <= max_d2 and L(q) != L(p) the
+ * one with the smallest key (|p - q|^2, L(q)) gives d2(p) and other(p); where there is none both are 0.  1 <= max_d2 <= SDSM_ZONE_MAX_D2
+ * (a reach of 64 pixels).  So for a background pixel `other` is the nearest label >= 1 (the frame never counts), and for a pixel of a
+ * label >= 1 d2 is its squared depth in the convention of the depth tables and `other` what it faces, 0 for background or frame.
+ * ZONES: with depth(p) = d2(p), or SDSM_ZONE_NO_UPPER where nothing was found, a pixel is IN zone z iff lo_d2 < depth(p) <= hi_d2.  A
+ * zone of side SDSM_ZONE_SIDE_BACKGROUND gives a background pixel that is in it other(p); one of side SDSM_ZONE_SIDE_OBJECT gives a
+ * pixel of a label >= 1 that is in it L(p); with keep_own every pixel of a label >= 1 gets L(p); every other pixel gets 0.  So
+ *   grown(hi)     = {BACKGROUND, 1, 0, hi}      ring(lo, hi) = {BACKGROUND, 0, lo, hi}
+ *   core(lo)      = {OBJECT, 0, lo, SDSM_ZONE_NO_UPPER}      rim(hi) = {OBJECT, 0, 0, hi}
+ * Every bound that is not SDSM_ZONE_NO_UPPER must be <= max_d2 (the search ends there); SDSM_ZONE_NO_UPPER is taken as hi_d2 of an
+ * OBJECT zone only.
+ * Conventions as for the tables above: sets as a HOST table of sdsm_set_image, int32 maps packed as the table says, the single-image
+ * form is the set of that one image.  Every pixel of every map asked for is written, by plain stores of values that depend on the label
+ * map alone: no output needs clearing.
+ * Limits: labels 0 .. 65535 (a pixel with another label is counted in its image's status word and taken as label 0), H * H + W * W <
+ * 2^31 per image, 1 .. SDSM_MAX_SET_IMAGES images, 0 .. SDSM_ZONE_MAX_ZONES zones. */
+#define SDSM_ZONE_MAX_D2 4096
+#define SDSM_ZONE_MAX_ZONES 8
+#define SDSM_ZONE_NO_UPPER 0x7fffffff   /* hi_d2 of a zone without an upper bound */
+#define SDSM_ZONE_SIDE_BACKGROUND 0
+#define SDSM_ZONE_SIDE_OBJECT 1
+typedef struct {
+    int32_t side;                       /* SDSM_ZONE_SIDE_BACKGROUND or SDSM_ZONE_SIDE_OBJECT */
+    int32_t keep_own;                   /* 1: every pixel of a label >= 1 keeps its label (BACKGROUND zones only); else 0 */
+    int32_t lo_d2, hi_d2;               /* in the zone: lo_d2 < depth <= hi_d2; 0 <= lo_d2 < hi_d2 */
+} sdsm_zone_spec;                       /* 16 bytes */
+/* zones: a HOST array of n_zones specs.  d_d2, d_other: packed int32 maps as d_labels, either may be NULL (not written).  d_zone_out:
+ * n_zones packed int32 maps, that of zone z from element z * zone_stride on; zone_stride >= offset + H * W of every image.  NULL with
+ * n_zones == 0.  d_status: one int32 per image, cleared by the call: the pixels with a label outside 0 .. 65535. */
+int sdsm_zones_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, int max_d2, int n_zones, const sdsm_zone_spec *zones,
+                     int64_t zone_stride, int32_t *d_d2, int32_t *d_other, int32_t *d_zone_out, int32_t *d_status, void *stream);
+int sdsm_zones(int H, int W, const int32_t *d_labels, int max_d2, int n_zones, const sdsm_zone_spec *zones, int32_t *d_d2, int32_t *d_other,
+               int32_t *d_zone_out, int32_t *d_status, void *stream);   /* the set of one image; zone_stride = H * W */
+
 /* ---- depth tables: inscribed circle, radii, intensity shells (no reference counterpart; the definitions are depth_objects_host and
  * depth_labels_host of superdsm_amd/depth.py) ---------------------------------------------------------------------------------------------
  * How far inside its object a pixel lies, in integers only.  An object is the set P of the set bits of its fragment, as in the shape

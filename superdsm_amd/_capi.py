@@ -111,6 +111,13 @@ NEIGHBOUR_LABEL_DTYPE = np.dtype([('edges_background', '<i8'), ('edges_labels', 
                                   ('close', '<i4'), ('reserved', '<i4')])                  # sdsm_neighbour_label
 NEIGHBOUR_PAIR_DTYPE = np.dtype([('a', '<i4'), ('b', '<i4'), ('min_d2', '<i4'), ('contact_edges', '<i4')])   # sdsm_neighbour_pair
 assert NEIGHBOUR_LABEL_DTYPE.itemsize == 40 and NEIGHBOUR_PAIR_DTYPE.itemsize == 16
+ZONE_MAX_D2 = 4096                  # SDSM_ZONE_MAX_D2: largest squared bound of a zone and largest squared reach of the nearest-other transform
+ZONE_MAX_ZONES = 8                  # SDSM_ZONE_MAX_ZONES: zones of one call
+ZONE_NO_UPPER = 0x7fffffff          # SDSM_ZONE_NO_UPPER: hi_d2 of a zone without an upper bound
+ZONE_SIDE_BACKGROUND, ZONE_SIDE_OBJECT = 0, 1
+_ZONE_FIELDS = [('side', 'i4'), ('keep_own', 'i4'), ('lo_d2', 'i4'), ('hi_d2', 'i4')]
+ZONE_SPEC_DTYPE = np.dtype(_ZONE_FIELDS)                                           # sdsm_zone_spec
+assert ZONE_SPEC_DTYPE.itemsize == 16
 DEPTH_MAX_SHELLS = 32               # SDSM_DEPTH_MAX_SHELLS: shells of one call of the depth tables
 DEPTH_LDS_PIXELS = 12288            # SDSM_DEPTH_LDS_PIXELS: pixels of a box whose distance transform is held in LDS
 DEPTH_WS_PIXEL_BYTES = 8            # SDSM_DEPTH_WS_PIXEL_BYTES: workspace bytes per pixel of a larger box
@@ -269,6 +276,8 @@ SYMBOLS = {
     'sdsm_neighbours': (_i32, [_i32, _i32, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     'sdsm_neighbours_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _i32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, C.POINTER(C.c_int64),
                                      C.POINTER(C.c_int64), _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_zones': (_i32, [_i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_zones_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     'sdsm_label_pixel_counts': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp]),
     'sdsm_label_pixel_counts_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, _vp, _vp]),
     'sdsm_label_pixel_lists': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

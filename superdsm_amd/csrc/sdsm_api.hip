@@ -1165,6 +1165,44 @@ extern "C" int sdsm_neighbours(int H, int W, const int32_t *d_labels, int max_d2
     return sdsm_neighbours_multi(&one, 1, d_labels, max_d2, &off, &n_labels, d_label_out, &off, &capacity, d_keys, d_min_d2, d_contact, d_status, stream);
 }
 
+// ---- zone label maps of one label map (sdsm_zones.hip) -----------------------------------------------------------------------------------
+extern "C" hipError_t sdsm_zones_impl(const sdsm_set_image *images, int n_images, const int32_t *d_labels, int max_d2, int n_zones,
+                                      const sdsm_zone_spec *zones, int64_t zone_stride, int32_t *d_d2, int32_t *d_other, int32_t *d_zone_out,
+                                      int32_t *d_status, hipStream_t stream);
+
+// a bound of a zone: 0 .. max_d2
+static bool zone_bound_ok(int32_t v, int max_d2) { return v >= 0 && v <= max_d2; }
+
+extern "C" int sdsm_zones_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, int max_d2, int n_zones, const sdsm_zone_spec *zones,
+                                int64_t zone_stride, int32_t *d_d2, int32_t *d_other, int32_t *d_zone_out, int32_t *d_status, void *stream)
+{
+    if (max_d2 < 1 || max_d2 > SDSM_ZONE_MAX_D2) return fail(SDSM_ERR_ARGUMENT, "sdsm_zones: 1 <= max_d2 <= 4096 required");
+    if (n_zones < 0 || n_zones > SDSM_ZONE_MAX_ZONES) return fail(SDSM_ERR_ARGUMENT, "sdsm_zones: 0 <= n_zones <= 8 required");
+    SET_TABLE("sdsm_zones", 0);
+    if (!boundary_shapes_ok(images, n_images)) return fail(SDSM_ERR_ARGUMENT, "sdsm_zones: H * H + W * W < 2^31 required");
+    if (!d_labels || !d_status || (n_zones > 0 && (!zones || !d_zone_out))) return fail(SDSM_ERR_ARGUMENT, "sdsm_zones: null argument");
+    for (int z = 0; z < n_zones; z++) {
+        const sdsm_zone_spec &Z = zones[z];
+        const bool object = Z.side == SDSM_ZONE_SIDE_OBJECT;
+        if ((!object && Z.side != SDSM_ZONE_SIDE_BACKGROUND) || (Z.keep_own != 0 && (Z.keep_own != 1 || object)))
+            return fail(SDSM_ERR_ARGUMENT, "sdsm_zones: a zone's side is 0 or 1, keep_own 0 or, on the background side, 1");
+        if (!zone_bound_ok(Z.lo_d2, max_d2) || !(zone_bound_ok(Z.hi_d2, max_d2) || (object && Z.hi_d2 == SDSM_ZONE_NO_UPPER)) || Z.lo_d2 >= Z.hi_d2)
+            return fail(SDSM_ERR_ARGUMENT, "sdsm_zones: 0 <= lo_d2 < hi_d2 <= max_d2 required (hi_d2 of an object zone may be SDSM_ZONE_NO_UPPER)");
+    }
+    for (int i = 0; n_zones > 0 && i < n_images; i++)
+        if (zone_stride < images[i].offset + (int64_t)images[i].H * images[i].W)
+            return fail(SDSM_ERR_ARGUMENT, "sdsm_zones: zone_stride >= offset + H * W of every image required");
+    hipError_t e = sdsm_zones_impl(images, n_images, d_labels, max_d2, n_zones, zones, zone_stride, d_d2, d_other, d_zone_out, d_status, (hipStream_t)stream);
+    SET_DONE("sdsm_zones");
+}
+
+extern "C" int sdsm_zones(int H, int W, const int32_t *d_labels, int max_d2, int n_zones, const sdsm_zone_spec *zones, int32_t *d_d2, int32_t *d_other,
+                          int32_t *d_zone_out, int32_t *d_status, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_zones_multi(&one, 1, d_labels, max_d2, n_zones, zones, (int64_t)H * W, d_d2, d_other, d_zone_out, d_status, stream);
+}
+
 // ---- boundary distances between two label maps (sdsm_measure.hip) ---------------------------------------------------------------------
 extern "C" hipError_t sdsm_label_pixel_counts_impl(const sdsm_set_image *images, int n_images, const int32_t *labels, int32_t *counts, int32_t *bad,
                                                    hipStream_t stream);
