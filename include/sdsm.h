@@ -893,6 +893,73 @@ int sdsm_zones_multi(const sdsm_set_image *images, int n_images, const int32_t *
 int sdsm_zones(int H, int W, const int32_t *d_labels, int max_d2, int n_zones, const sdsm_zone_spec *zones, int32_t *d_d2, int32_t *d_other,
                int32_t *d_zone_out, int32_t *d_status, void *stream);   /* the set of one image; zone_stride = H * W */
 
+/* ---- connected parts of one label map (no reference counterpart; the definitions are parts_host and keep_maps_host of
+ * superdsm_amd/parts.py) ---------------------------------------------------------------------------------------------------------------
+ * Which pixels of a label hang together, in integers only.  The map L (labels 0 .. 65535, 0 the background) is extended by label 0
+ * outside the image frame.  A PART is a maximal set of pixels of one label >= 1 that are connected under the adjacency `connectivity`,
+ * 4 or 8; pixels of different labels are never connected.  The parts of an image are numbered 1 .. K by their first pixel in raster
+ * order (the smallest r * W + c), which for a map with the single label 1 is the numbering of scipy.ndimage.label.  The PART MAP holds
+ * the part number of every pixel, 0 on the background.
+ * Bit quads: q1, q3, qd of label l count, over all (H + 1) * (W + 1) windows of 2 x 2 places of the zero-padded mask L == l, those with
+ * exactly one place of the mask, with exactly three, and with exactly the two places of a diagonal (sdsm_parts_quad).  The Euler number
+ * of the mask is (q1 - q3 + 2 qd) / 4 under connectivity 4 and (q1 - q3 - 2 qd) / 4 under 8, and its holes are n_parts - Euler.
+ * Conventions as for the zone maps: sets as a HOST table of sdsm_set_image, int32 maps packed as the table says, the single-image form
+ * is the set of that one image.  Every pixel of every map is written by plain stores, every record by integer add / min / max atomics
+ * on cleared records: the bytes do not depend on the order, the tiling, the launch or the set size.  No kernel waits for another
+ * thread's progress.
+ * Limits: labels 0 .. n_labels - 1, n_labels <= 65536 (a pixel with another label is counted in its image's status word and taken as
+ * label 0), H * H + W * W < 2^31 per image, 1 .. SDSM_MAX_SET_IMAGES images, 0 .. SDSM_PARTS_MAX_KEEPS selections.  K is bounded by the
+ * pixels alone; a part map goes into the other label-map entry points only while K <= 65535. */
+#define SDSM_PARTS_MAX_KEEPS 8
+#define SDSM_KEEP_SPLIT 0               /* a pixel of a label >= 1 gets its part number */
+#define SDSM_KEEP_LARGEST 1             /* ... its label, if its part is largest_part of its label */
+#define SDSM_KEEP_MIN_AREA 2            /* ... its label, if the area of its part is >= min_area */
+typedef struct {
+    int32_t label;                      /* the label of the part's pixels */
+    int32_t area;
+    int32_t first;                      /* raster index r * W + c of the part's first pixel */
+    int32_t r0, c0, r1, c1;             /* the tight box, r1 and c1 exclusive */
+    int32_t index_in_label;             /* NOT written by the device (0): the parts of a label counted in part order, by the caller */
+} sdsm_part_record;                     /* 32 bytes */
+typedef struct {
+    int32_t n_parts;
+    int32_t area;
+    int32_t largest_area;
+    int32_t largest_part;               /* the part number; of several parts of the largest area the smallest number */
+    int32_t q1, q3, qd;                 /* bit-quad counts: at most (H + 1) * (W + 1) < 2^31 windows (H * W < 2^30, H + W < 2^17) */
+    int32_t reserved;
+} sdsm_part_label_record;               /* 32 bytes; the record of label 0 stays all zero */
+typedef struct {
+    int32_t kind;                       /* SDSM_KEEP_SPLIT, SDSM_KEEP_LARGEST or SDSM_KEEP_MIN_AREA */
+    int32_t min_area;                   /* SDSM_KEEP_MIN_AREA: >= 1; else 0 */
+} sdsm_keep_spec;                       /* 8 bytes */
+/* Host helper (no device access), the inline function the tile kernel uses (csrc/sdsm_parts.h): the class of the window  a b / c d
+ * against the mask of `label`: 0 none, 1 q1, 2 q3, 3 qd. */
+int sdsm_parts_quad(int32_t a, int32_t b, int32_t c, int32_t d, int32_t label);
+/* LABELLING.  d_label_out[rec_off[i] + l] for the labels 0 <= l < n_labels[i] of image i (rec_off, n_labels: HOST arrays, as
+ * sdsm_neighbours_multi takes them), complete; d_part_map: the packed int32 part maps; d_count: one int32 per image, its K; d_status:
+ * one int32 per image, the pixels with a label < 0 or >= n_labels.  The call clears what it adds into, on the stream.  d_ws: at least
+ * sdsm_parts_workspace_bytes_multi bytes, 8-byte aligned (parents, part areas, scan chunks, the keys of the largest parts).
+ * K is not known before the scan, so the part table is a call of its own, once the caller has read d_count. */
+size_t sdsm_parts_workspace_bytes_multi(const sdsm_set_image *images, int n_images, const int64_t *rec_off, const int32_t *n_labels);
+int sdsm_parts_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, int connectivity, const int64_t *rec_off,
+                     const int32_t *n_labels, sdsm_part_label_record *d_label_out, int32_t *d_part_map, int32_t *d_count, int32_t *d_status,
+                     void *d_ws, size_t ws_bytes, void *stream);
+int sdsm_parts(int H, int W, const int32_t *d_labels, int connectivity, int n_labels, sdsm_part_label_record *d_label_out, int32_t *d_part_map,
+               int32_t *d_count, int32_t *d_status, void *d_ws, size_t ws_bytes, void *stream);   /* the set of one image */
+/* PART TABLE.  d_part_out[part_off[i] + k - 1] for the parts 1 <= k <= n_parts[i] of image i (part_off, n_parts: HOST arrays; n_parts as
+ * read from d_count; the ranges must not overlap), from the label map and the part map of sdsm_parts_multi.  A pixel whose part number
+ * lies outside 1 .. n_parts is passed over.  The call initialises the records on the stream. */
+int sdsm_parts_table_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int32_t *d_part_map, const int64_t *part_off,
+                           const int32_t *n_parts, sdsm_part_record *d_part_out, void *stream);
+/* SELECTIONS.  keeps: a HOST array of n_keeps specs.  d_keep_out: n_keeps packed int32 maps, that of selection z from element
+ * z * keep_stride on; keep_stride >= offset + H * W of every image.  Reads the two maps and the two tables of the calls above; every pixel
+ * of every map is written.  A pixel whose label lies outside 1 .. n_labels - 1 or whose part lies outside 1 .. n_parts gets 0. */
+int sdsm_parts_keep_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int32_t *d_part_map, const int64_t *rec_off,
+                          const int32_t *n_labels, const sdsm_part_label_record *d_label_recs, const int64_t *part_off, const int32_t *n_parts,
+                          const sdsm_part_record *d_part_recs, int n_keeps, const sdsm_keep_spec *keeps, int64_t keep_stride, int32_t *d_keep_out,
+                          void *stream);
+
 /* ---- depth tables: inscribed circle, radii, intensity shells (no reference counterpart; the definitions are depth_objects_host and
  * depth_labels_host of superdsm_amd/depth.py) ---------------------------------------------------------------------------------------------
  * How far inside its object a pixel lies, in integers only.  An object is the set P of the set bits of its fragment, as in the shape

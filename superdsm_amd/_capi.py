@@ -118,6 +118,15 @@ ZONE_SIDE_BACKGROUND, ZONE_SIDE_OBJECT = 0, 1
 _ZONE_FIELDS = [('side', 'i4'), ('keep_own', 'i4'), ('lo_d2', 'i4'), ('hi_d2', 'i4')]
 ZONE_SPEC_DTYPE = np.dtype(_ZONE_FIELDS)                                           # sdsm_zone_spec
 assert ZONE_SPEC_DTYPE.itemsize == 16
+PARTS_MAX_KEEPS = 8                 # SDSM_PARTS_MAX_KEEPS: selections of one call of the connected parts
+KEEP_SPLIT, KEEP_LARGEST, KEEP_MIN_AREA = 0, 1, 2
+_PART_FIELDS = [('label', '<i4'), ('area', '<i4'), ('first', '<i4'), ('r0', '<i4'), ('c0', '<i4'), ('r1', '<i4'), ('c1', '<i4'), ('index_in_label', '<i4')]
+_PART_LABEL_FIELDS = [('n_parts', '<i4'), ('area', '<i4'), ('largest_area', '<i4'), ('largest_part', '<i4'), ('q1', '<i4'), ('q3', '<i4'), ('qd', '<i4'),
+                      ('reserved', '<i4')]
+PART_DTYPE = np.dtype(_PART_FIELDS)                                                # sdsm_part_record
+PART_LABEL_DTYPE = np.dtype(_PART_LABEL_FIELDS)                                    # sdsm_part_label_record
+KEEP_SPEC_DTYPE = np.dtype([('kind', '<i4'), ('min_area', '<i4')])                 # sdsm_keep_spec
+assert PART_DTYPE.itemsize == 32 and PART_LABEL_DTYPE.itemsize == 32 and KEEP_SPEC_DTYPE.itemsize == 8
 DEPTH_MAX_SHELLS = 32               # SDSM_DEPTH_MAX_SHELLS: shells of one call of the depth tables
 DEPTH_LDS_PIXELS = 12288            # SDSM_DEPTH_LDS_PIXELS: pixels of a box whose distance transform is held in LDS
 DEPTH_WS_PIXEL_BYTES = 8            # SDSM_DEPTH_WS_PIXEL_BYTES: workspace bytes per pixel of a larger box
@@ -278,6 +287,13 @@ SYMBOLS = {
                                      C.POINTER(C.c_int64), _vp, _vp, _vp, _vp, _vp]),
     'sdsm_zones': (_i32, [_i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sdsm_zones_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_parts_quad': (_i32, [_i32, _i32, _i32, _i32, _i32]),
+    'sdsm_parts_workspace_bytes_multi': (_sz, [C.POINTER(SetImage), _i32, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    'sdsm_parts': (_i32, [_i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sdsm_parts_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _i32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sdsm_parts_table_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, _vp]),
+    'sdsm_parts_keep_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_int32), _vp, _i32, _vp, _i64, _vp, _vp]),
     'sdsm_label_pixel_counts': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp]),
     'sdsm_label_pixel_counts_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, _vp, _vp]),
     'sdsm_label_pixel_lists': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1203,6 +1203,98 @@ extern "C" int sdsm_zones(int H, int W, const int32_t *d_labels, int max_d2, int
     return sdsm_zones_multi(&one, 1, d_labels, max_d2, n_zones, zones, (int64_t)H * W, d_d2, d_other, d_zone_out, d_status, stream);
 }
 
+// ---- connected parts of one label map (sdsm_parts.hip) -----------------------------------------------------------------------------------
+extern "C" size_t sdsm_parts_workspace_bytes_impl(const sdsm_set_image *images, int n_images, const int64_t *rec_off, const int32_t *n_labels);
+extern "C" hipError_t sdsm_parts_impl(const sdsm_set_image *images, int n_images, const int32_t *d_labels, int connectivity, const int64_t *rec_off,
+                                      const int32_t *n_labels, sdsm_part_label_record *d_label_out, int32_t *d_part_map, int32_t *d_count,
+                                      int32_t *d_status, void *d_ws, hipStream_t stream);
+extern "C" hipError_t sdsm_parts_table_impl(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int32_t *d_part_map,
+                                            const int64_t *part_off, const int32_t *n_parts, sdsm_part_record *d_part_out, hipStream_t stream);
+extern "C" hipError_t sdsm_parts_keep_impl(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int32_t *d_part_map,
+                                           const int64_t *rec_off, const int32_t *n_labels, const sdsm_part_label_record *d_label_recs,
+                                           const int64_t *part_off, const int32_t *n_parts, const sdsm_part_record *d_part_recs, int n_keeps,
+                                           const sdsm_keep_spec *keeps, int64_t keep_stride, int32_t *d_keep_out, hipStream_t stream);
+
+// the part records of a set: n_parts[i] >= 0 records from part_off[i] on
+static bool part_records_ok(int n_images, const int32_t *n_parts, const int64_t *part_off, bool check_overlap, const char **why)
+{
+    return ranges_ok(n_images, part_off, n_parts, [](int32_t n) { return n >= 0; }, check_overlap, "n_parts >= 0 and part_off >= 0 required",
+                     "the part records of two images overlap", why, nullptr);
+}
+
+extern "C" size_t sdsm_parts_workspace_bytes_multi(const sdsm_set_image *images, int n_images, const int64_t *rec_off, const int32_t *n_labels)
+{
+    const char *why;
+    if (!set_table_ok(images, n_images, 0) || !boundary_shapes_ok(images, n_images) || !rec_off || !n_labels) return 0;
+    return label_records_ok(n_images, n_labels, rec_off, true, &why) ? sdsm_parts_workspace_bytes_impl(images, n_images, rec_off, n_labels) : 0;
+}
+
+extern "C" int sdsm_parts_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, int connectivity, const int64_t *rec_off,
+                                const int32_t *n_labels, sdsm_part_label_record *d_label_out, int32_t *d_part_map, int32_t *d_count, int32_t *d_status,
+                                void *d_ws, size_t ws_bytes, void *stream)
+{
+    if (connectivity != 4 && connectivity != 8) return fail(SDSM_ERR_ARGUMENT, "sdsm_parts: connectivity 4 or 8 required");
+    SET_TABLE("sdsm_parts", 0);
+    if (!boundary_shapes_ok(images, n_images)) return fail(SDSM_ERR_ARGUMENT, "sdsm_parts: H * H + W * W < 2^31 required");
+    if (!d_labels || !rec_off || !n_labels || !d_label_out || !d_part_map || !d_count || !d_status || !d_ws)
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_parts: null argument");
+    const char *why;
+    if (!label_records_ok(n_images, n_labels, rec_off, true, &why)) return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_parts: ") + why);
+    if (((uintptr_t)d_ws & 7) != 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_parts: the workspace must be 8-byte aligned");
+    if (ws_bytes < sdsm_parts_workspace_bytes_impl(images, n_images, rec_off, n_labels)) return fail(SDSM_ERR_WORKSPACE, "sdsm_parts: workspace too small");
+    hipError_t e = sdsm_parts_impl(images, n_images, d_labels, connectivity, rec_off, n_labels, d_label_out, d_part_map, d_count, d_status, d_ws,
+                                   (hipStream_t)stream);
+    SET_DONE("sdsm_parts");
+}
+
+extern "C" int sdsm_parts(int H, int W, const int32_t *d_labels, int connectivity, int n_labels, sdsm_part_label_record *d_label_out, int32_t *d_part_map,
+                          int32_t *d_count, int32_t *d_status, void *d_ws, size_t ws_bytes, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    const int64_t off = 0;
+    return sdsm_parts_multi(&one, 1, d_labels, connectivity, &off, &n_labels, d_label_out, d_part_map, d_count, d_status, d_ws, ws_bytes, stream);
+}
+
+extern "C" int sdsm_parts_table_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int32_t *d_part_map, const int64_t *part_off,
+                                      const int32_t *n_parts, sdsm_part_record *d_part_out, void *stream)
+{
+    SET_TABLE("sdsm_parts_table", 0);
+    if (!boundary_shapes_ok(images, n_images)) return fail(SDSM_ERR_ARGUMENT, "sdsm_parts_table: H * H + W * W < 2^31 required");
+    if (!d_labels || !d_part_map || !part_off || !n_parts || !d_part_out) return fail(SDSM_ERR_ARGUMENT, "sdsm_parts_table: null argument");
+    const char *why;
+    if (!part_records_ok(n_images, n_parts, part_off, true, &why)) return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_parts_table: ") + why);
+    hipError_t e = sdsm_parts_table_impl(images, n_images, d_labels, d_part_map, part_off, n_parts, d_part_out, (hipStream_t)stream);
+    SET_DONE("sdsm_parts_table");
+}
+
+extern "C" int sdsm_parts_keep_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int32_t *d_part_map, const int64_t *rec_off,
+                                     const int32_t *n_labels, const sdsm_part_label_record *d_label_recs, const int64_t *part_off, const int32_t *n_parts,
+                                     const sdsm_part_record *d_part_recs, int n_keeps, const sdsm_keep_spec *keeps, int64_t keep_stride, int32_t *d_keep_out,
+                                     void *stream)
+{
+    if (n_keeps < 1 || n_keeps > SDSM_PARTS_MAX_KEEPS) return fail(SDSM_ERR_ARGUMENT, "sdsm_parts_keep: 1 <= n_keeps <= 8 required");
+    SET_TABLE("sdsm_parts_keep", 0);
+    if (!boundary_shapes_ok(images, n_images)) return fail(SDSM_ERR_ARGUMENT, "sdsm_parts_keep: H * H + W * W < 2^31 required");
+    if (!d_labels || !d_part_map || !rec_off || !n_labels || !d_label_recs || !part_off || !n_parts || !d_part_recs || !keeps || !d_keep_out)
+        return fail(SDSM_ERR_ARGUMENT, "sdsm_parts_keep: null argument");
+    const char *why;
+    if (!label_records_ok(n_images, n_labels, rec_off, false, &why) || !part_records_ok(n_images, n_parts, part_off, false, &why))
+        return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_parts_keep: ") + why);
+    for (int z = 0; z < n_keeps; z++) {
+        const sdsm_keep_spec &K = keeps[z];
+        if (K.kind != SDSM_KEEP_SPLIT && K.kind != SDSM_KEEP_LARGEST && K.kind != SDSM_KEEP_MIN_AREA)
+            return fail(SDSM_ERR_ARGUMENT, "sdsm_parts_keep: a selection's kind is 0, 1 or 2");
+        if (K.kind == SDSM_KEEP_MIN_AREA ? K.min_area < 1 : K.min_area != 0)
+            return fail(SDSM_ERR_ARGUMENT, "sdsm_parts_keep: min_area >= 1 for SDSM_KEEP_MIN_AREA, 0 for the other kinds");
+    }
+    for (int i = 0; i < n_images; i++)
+        if (keep_stride < images[i].offset + (int64_t)images[i].H * images[i].W)
+            return fail(SDSM_ERR_ARGUMENT, "sdsm_parts_keep: keep_stride >= offset + H * W of every image required");
+    hipError_t e = sdsm_parts_keep_impl(images, n_images, d_labels, d_part_map, rec_off, n_labels, d_label_recs, part_off, n_parts, d_part_recs, n_keeps, keeps,
+                                        keep_stride, d_keep_out, (hipStream_t)stream);
+    SET_DONE("sdsm_parts_keep");
+}
+
 // ---- boundary distances between two label maps (sdsm_measure.hip) ---------------------------------------------------------------------
 extern "C" hipError_t sdsm_label_pixel_counts_impl(const sdsm_set_image *images, int n_images, const int32_t *labels, int32_t *counts, int32_t *bad,
                                                    hipStream_t stream);

@@ -18,6 +18,7 @@
 #include "sdsm_neighbours.h"
 #include "sdsm_texture.h"
 #include "sdsm_depth.h"
+#include "sdsm_parts.h"
 
 namespace {
 
@@ -316,4 +317,10 @@ extern "C" int64_t sdsm_neighbour_slot(uint64_t key, int64_t capacity)
 {
     if (capacity < 1 || (capacity & (capacity - 1)) != 0) return -1;
     return (int64_t)sdsm_neighbour_slot_inline(key, (uint64_t)capacity);
+}
+
+// The class of a bit quad, as the tile kernel of the connected parts takes it (sdsm_parts.h: the same inline function).
+extern "C" int sdsm_parts_quad(int32_t a, int32_t b, int32_t c, int32_t d, int32_t label)
+{
+    return sdsm_parts_quad_inline(a, b, c, d, label);
 }
