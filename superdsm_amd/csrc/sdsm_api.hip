@@ -769,15 +769,25 @@ extern "C" hipError_t sdsm_measure_labels_impl(const sdsm_set_image *images, int
                                                const int32_t *n_labels, const double *d_g, double *d_gmax_abs, int32_t *d_scale_exp,
                                                sdsm_measure_record *out, int32_t *bad, hipStream_t stream);
 
+// the packed objects of a call, as the nine table entries below take them: n boxes, the offsets of their words and the words, and the image of every
+// object where the set has more than one; null: fine
+static const char *packed_objects_bad(int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes, const int64_t *d_bits_off,
+                                      const uint32_t *d_bits)
+{
+    if (n < 0) return "n < 0";
+    if (n > 0 && (!d_boxes || !d_bits_off || !d_bits || (n_images > 1 && !d_obj_image))) return "null argument";
+    return nullptr;
+}
+
 extern "C" int sdsm_measure_objects_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
                                           const int64_t *d_bits_off, const uint32_t *d_bits, const double *d_g, double *d_gmax_abs,
                                           int32_t *d_scale_exp, sdsm_measure_record *d_out, void *stream)
 {
     SET_TABLE("sdsm_measure_objects", SET_SIDES | SET_PIXELS);
-    if (n < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_measure_objects: n < 0");
+    if (const char *why = packed_objects_bad(n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits))
+        return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_measure_objects: ") + why);
     if (d_g && !d_gmax_abs) return fail(SDSM_ERR_ARGUMENT, "sdsm_measure_objects: intensities need d_gmax_abs");
-    if (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_out || (n_images > 1 && !d_obj_image)))
-        return fail(SDSM_ERR_ARGUMENT, "sdsm_measure_objects: null argument");
+    if (n > 0 && !d_out) return fail(SDSM_ERR_ARGUMENT, "sdsm_measure_objects: null argument");
     hipError_t e = sdsm_measure_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_g, d_gmax_abs, d_scale_exp, d_out,
                                              (hipStream_t)stream);
     SET_DONE("sdsm_measure_objects");
@@ -819,14 +829,30 @@ extern "C" hipError_t sdsm_shape_scatter_impl(const sdsm_set_image *images, int 
                                               const int32_t *n_labels, const int32_t *label_obj, int n, const int32_t *boxes, const int64_t *bits_off,
                                               int64_t window_words, uint32_t *bits, int32_t *bad, hipStream_t stream);
 
+// The label form of `who` (shape, intensity, texture, depth): the arguments that name the label maps and the windows of their labels are checked,
+// then the windows are filled (the scatter step).  SDSM_OK: the entry goes on with its *_objects_impl on the windows.
+static int label_windows(const char *who, const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int64_t *rec_off, const int32_t *n_labels,
+                         const int32_t *d_label_obj, int n, const int32_t *d_obj_image, const int32_t *d_boxes, const int64_t *d_bits_off,
+                         int64_t window_words, uint32_t *d_bits, int32_t *d_bad, void *stream)
+{
+    if (n < 0 || window_words < 0 || window_words > SDSM_SHAPE_MAX_WINDOW_WORDS)
+        return fail(SDSM_ERR_ARGUMENT, std::string(who) + ": n >= 0 and 0 <= window_words <= SDSM_SHAPE_MAX_WINDOW_WORDS required");
+    const char *why = !d_labels || !rec_off || !n_labels || !d_label_obj || !d_bad ? "null argument"
+                                                                                    : packed_objects_bad(n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits);
+    if (why || !label_records_ok(n_images, n_labels, rec_off, false, &why)) return fail(SDSM_ERR_ARGUMENT, std::string(who) + ": " + why);
+    hipError_t e = sdsm_shape_scatter_impl(images, n_images, d_labels, rec_off, n_labels, d_label_obj, n, d_boxes, d_bits_off, window_words, d_bits, d_bad,
+                                           (hipStream_t)stream);
+    SET_DONE(who);
+}
+
 extern "C" int sdsm_shape_objects_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
                                         const int64_t *d_bits_off, const uint32_t *d_bits, const int64_t *d_slot_off, int32_t *d_slots,
                                         sdsm_shape_record *d_out, int64_t *d_vert_off, int32_t *d_verts, void *stream)
 {
     SET_TABLE("sdsm_shape_objects", SET_SIDES | SET_PIXELS);
-    if (n < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_shape_objects: n < 0");
-    if (!d_vert_off || (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_slot_off || !d_slots || !d_out || !d_verts || (n_images > 1 && !d_obj_image))))
-        return fail(SDSM_ERR_ARGUMENT, "sdsm_shape_objects: null argument");
+    if (const char *why = packed_objects_bad(n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits))
+        return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_shape_objects: ") + why);
+    if (!d_vert_off || (n > 0 && (!d_slot_off || !d_slots || !d_out || !d_verts))) return fail(SDSM_ERR_ARGUMENT, "sdsm_shape_objects: null argument");
     hipError_t e = sdsm_shape_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_slot_off, d_slots, d_out, d_vert_off, d_verts,
                                            (hipStream_t)stream);
     SET_DONE("sdsm_shape_objects");
@@ -845,18 +871,12 @@ extern "C" int sdsm_shape_labels_multi(const sdsm_set_image *images, int n_image
                                        int64_t *d_vert_off, int32_t *d_verts, int32_t *d_bad, void *stream)
 {
     SET_TABLE("sdsm_shape_labels", SET_SIDES | SET_PIXELS);
-    if (n < 0 || window_words < 0 || window_words > SDSM_SHAPE_MAX_WINDOW_WORDS)
-        return fail(SDSM_ERR_ARGUMENT, "sdsm_shape_labels: n >= 0 and 0 <= window_words <= SDSM_SHAPE_MAX_WINDOW_WORDS required");
-    if (!d_labels || !rec_off || !n_labels || !d_label_obj || !d_vert_off || !d_bad ||
-        (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_slot_off || !d_slots || !d_out || !d_verts || (n_images > 1 && !d_obj_image))))
-        return fail(SDSM_ERR_ARGUMENT, "sdsm_shape_labels: null argument");
-    const char *why;
-    if (!label_records_ok(n_images, n_labels, rec_off, false, &why)) return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_shape_labels: ") + why);
-    hipError_t e = sdsm_shape_scatter_impl(images, n_images, d_labels, rec_off, n_labels, d_label_obj, n, d_boxes, d_bits_off, window_words, d_bits, d_bad,
+    if (!d_vert_off || (n > 0 && (!d_slot_off || !d_slots || !d_out || !d_verts))) return fail(SDSM_ERR_ARGUMENT, "sdsm_shape_labels: null argument");
+    if (int rc = label_windows("sdsm_shape_labels", images, n_images, d_labels, rec_off, n_labels, d_label_obj, n, d_obj_image, d_boxes, d_bits_off, window_words,
+                               d_bits, d_bad, stream))
+        return rc;
+    hipError_t e = sdsm_shape_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_slot_off, d_slots, d_out, d_vert_off, d_verts,
                                            (hipStream_t)stream);
-    if (e == hipSuccess)
-        e = sdsm_shape_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_slot_off, d_slots, d_out, d_vert_off, d_verts,
-                                    (hipStream_t)stream);
     SET_DONE("sdsm_shape_labels");
 }
 
@@ -888,11 +908,11 @@ extern "C" int sdsm_intensity_objects_multi(const sdsm_set_image *images, int n_
                                             const int32_t *den, sdsm_intensity_record *d_out, double *d_order, void *stream)
 {
     SET_TABLE("sdsm_intensity_objects", SET_SIDES | SET_PIXELS);
-    if (n < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_intensity_objects: n < 0");
+    if (const char *why = packed_objects_bad(n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits))
+        return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_intensity_objects: ") + why);
     if (!quantiles_ok(n_q, num, den))
         return fail(SDSM_ERR_ARGUMENT, "sdsm_intensity_objects: 0 <= n_q <= 8 quantiles with 0 <= num <= den, 1 <= den <= 1000000 required");
-    if (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_g || !d_out || (n_q > 0 && !d_order) || (n_images > 1 && !d_obj_image)))
-        return fail(SDSM_ERR_ARGUMENT, "sdsm_intensity_objects: null argument");
+    if (n > 0 && (!d_g || !d_out || (n_q > 0 && !d_order))) return fail(SDSM_ERR_ARGUMENT, "sdsm_intensity_objects: null argument");
     hipError_t e = sdsm_intensity_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_g, n_q, num, den, d_out, d_order,
                                                (hipStream_t)stream);
     SET_DONE("sdsm_intensity_objects");
@@ -912,20 +932,14 @@ extern "C" int sdsm_intensity_labels_multi(const sdsm_set_image *images, int n_i
                                            void *stream)
 {
     SET_TABLE("sdsm_intensity_labels", SET_SIDES | SET_PIXELS);
-    if (n < 0 || window_words < 0 || window_words > SDSM_SHAPE_MAX_WINDOW_WORDS)
-        return fail(SDSM_ERR_ARGUMENT, "sdsm_intensity_labels: n >= 0 and 0 <= window_words <= SDSM_SHAPE_MAX_WINDOW_WORDS required");
     if (!quantiles_ok(n_q, num, den))
         return fail(SDSM_ERR_ARGUMENT, "sdsm_intensity_labels: 0 <= n_q <= 8 quantiles with 0 <= num <= den, 1 <= den <= 1000000 required");
-    if (!d_labels || !rec_off || !n_labels || !d_label_obj || !d_bad ||
-        (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_g || !d_out || (n_q > 0 && !d_order) || (n_images > 1 && !d_obj_image))))
-        return fail(SDSM_ERR_ARGUMENT, "sdsm_intensity_labels: null argument");
-    const char *why;
-    if (!label_records_ok(n_images, n_labels, rec_off, false, &why)) return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_intensity_labels: ") + why);
-    hipError_t e = sdsm_shape_scatter_impl(images, n_images, d_labels, rec_off, n_labels, d_label_obj, n, d_boxes, d_bits_off, window_words, d_bits, d_bad,
-                                           (hipStream_t)stream);
-    if (e == hipSuccess)
-        e = sdsm_intensity_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_g, n_q, num, den, d_out, d_order,
-                                        (hipStream_t)stream);
+    if (n > 0 && (!d_g || !d_out || (n_q > 0 && !d_order))) return fail(SDSM_ERR_ARGUMENT, "sdsm_intensity_labels: null argument");
+    if (int rc = label_windows("sdsm_intensity_labels", images, n_images, d_labels, rec_off, n_labels, d_label_obj, n, d_obj_image, d_boxes, d_bits_off,
+                               window_words, d_bits, d_bad, stream))
+        return rc;
+    hipError_t e = sdsm_intensity_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_g, n_q, num, den, d_out, d_order,
+                                               (hipStream_t)stream);
     SET_DONE("sdsm_intensity_labels");
 }
 
@@ -963,7 +977,9 @@ static bool texture_offsets_ok(int n_offsets, const int32_t *offsets)
     if (n < 0 || n > INT_MAX / SDSM_TEXTURE_MAX_OFFSETS) return fail(SDSM_ERR_ARGUMENT, name ": 0 <= n <= (2^31 - 1) / 8 required"); \
     if (levels < 1 || levels > SDSM_TEXTURE_MAX_LEVELS) return fail(SDSM_ERR_ARGUMENT, name ": 1 <= levels <= 256 required"); \
     if (!texture_offsets_ok(n_offsets, offsets)) \
-        return fail(SDSM_ERR_ARGUMENT, name ": 1 <= n_offsets <= 8 offsets, none (0, 0), |d_row|, |d_col| <= 32, none twice or with its negative required")
+        return fail(SDSM_ERR_ARGUMENT, name ": 1 <= n_offsets <= 8 offsets, none (0, 0), |d_row|, |d_col| <= 32, none twice or with its negative required"); \
+    if (n > 0 && (!d_g || (levels > 1 && !d_edges) || !d_slot_off || !d_slots || !d_out || !d_pairs || !d_entries)) \
+        return fail(SDSM_ERR_ARGUMENT, name ": null argument")
 
 extern "C" int sdsm_texture_objects_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
                                           const int64_t *d_bits_off, const uint32_t *d_bits, const double *d_g, int levels, const double *d_edges,
@@ -972,9 +988,8 @@ extern "C" int sdsm_texture_objects_multi(const sdsm_set_image *images, int n_im
 {
     SET_TABLE("sdsm_texture_objects", SET_SIDES | SET_PIXELS);
     TEXTURE_ARGS("sdsm_texture_objects");
-    if (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_g || (levels > 1 && !d_edges) || !d_slot_off || !d_slots || !d_out || !d_pairs || !d_entries ||
-                  (n_images > 1 && !d_obj_image)))
-        return fail(SDSM_ERR_ARGUMENT, "sdsm_texture_objects: null argument");
+    if (const char *why = packed_objects_bad(n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits))
+        return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_texture_objects: ") + why);
     hipError_t e = sdsm_texture_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_g, levels, d_edges, n_offsets, offsets,
                                              d_slot_off, d_slots, d_out, d_pairs, d_entries, (hipStream_t)stream);
     SET_DONE("sdsm_texture_objects");
@@ -999,19 +1014,13 @@ extern "C" int sdsm_texture_labels_multi(const sdsm_set_image *images, int n_ima
 {
     SET_TABLE("sdsm_texture_labels", SET_SIDES | SET_PIXELS);
     TEXTURE_ARGS("sdsm_texture_labels");
-    if (window_words < 0 || window_words > SDSM_SHAPE_MAX_WINDOW_WORDS)
+    if (window_words < 0 || window_words > SDSM_SHAPE_MAX_WINDOW_WORDS)      // (n is checked above: this entry's text names the words alone)
         return fail(SDSM_ERR_ARGUMENT, "sdsm_texture_labels: 0 <= window_words <= SDSM_SHAPE_MAX_WINDOW_WORDS required");
-    if (!d_labels || !rec_off || !n_labels || !d_label_obj || !d_bad ||
-        (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_g || (levels > 1 && !d_edges) || !d_slot_off || !d_slots || !d_out || !d_pairs || !d_entries ||
-                   (n_images > 1 && !d_obj_image))))
-        return fail(SDSM_ERR_ARGUMENT, "sdsm_texture_labels: null argument");
-    const char *why;
-    if (!label_records_ok(n_images, n_labels, rec_off, false, &why)) return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_texture_labels: ") + why);
-    hipError_t e = sdsm_shape_scatter_impl(images, n_images, d_labels, rec_off, n_labels, d_label_obj, n, d_boxes, d_bits_off, window_words, d_bits, d_bad,
-                                           (hipStream_t)stream);
-    if (e == hipSuccess)
-        e = sdsm_texture_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_g, levels, d_edges, n_offsets, offsets, d_slot_off,
-                                      d_slots, d_out, d_pairs, d_entries, (hipStream_t)stream);
+    if (int rc = label_windows("sdsm_texture_labels", images, n_images, d_labels, rec_off, n_labels, d_label_obj, n, d_obj_image, d_boxes, d_bits_off,
+                               window_words, d_bits, d_bad, stream))
+        return rc;
+    hipError_t e = sdsm_texture_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_g, levels, d_edges, n_offsets, offsets, d_slot_off,
+                                             d_slots, d_out, d_pairs, d_entries, (hipStream_t)stream);
     SET_DONE("sdsm_texture_labels");
 }
 
@@ -1035,14 +1044,15 @@ extern "C" hipError_t sdsm_depth_objects_impl(const sdsm_set_image *images, int 
                                               const int64_t *d_ws_off, void *d_ws, int64_t ws_pixels, sdsm_depth_record *out,
                                               sdsm_depth_shell_record *shells, hipStream_t stream);
 
-// the shells, the intensity buffers and the workspace of a call; null: fine
-static const char *depth_args_bad(int n_shells, const double *d_g, const double *d_gmax_abs, const int64_t *d_ws_off, const void *d_ws, int64_t ws_pixels,
-                                  size_t ws_bytes)
+// the shells, the intensity buffers, the workspace and the outputs of a call for n objects; null: fine
+static const char *depth_args_bad(int n, int n_shells, const double *d_g, const double *d_gmax_abs, const int64_t *d_ws_off, const void *d_ws, int64_t ws_pixels,
+                                  size_t ws_bytes, const void *d_out, const void *d_shells)
 {
     if (n_shells < 1 || n_shells > SDSM_DEPTH_MAX_SHELLS) return "1 <= n_shells <= 32 required";
     if (d_g && !d_gmax_abs) return "intensities need d_gmax_abs";
     if (ws_pixels < 0 || (ws_pixels > 0 && (!d_ws_off || !d_ws))) return "ws_pixels >= 0 and, with ws_pixels > 0, d_ws_off and d_ws required";
     if ((uint64_t)ws_pixels > ws_bytes / SDSM_DEPTH_WS_PIXEL_BYTES) return "the workspace is too small for the boxes named (8 bytes per pixel)";
+    if (n > 0 && (!d_out || !d_shells)) return "null argument";
     return nullptr;
 }
 
@@ -1052,11 +1062,9 @@ extern "C" int sdsm_depth_objects_multi(const sdsm_set_image *images, int n_imag
                                         sdsm_depth_shell_record *d_shells, void *stream)
 {
     SET_TABLE("sdsm_depth_objects", SET_SIDES | SET_PIXELS);
-    if (n < 0) return fail(SDSM_ERR_ARGUMENT, "sdsm_depth_objects: n < 0");
-    if (const char *why = depth_args_bad(n_shells, d_g, d_gmax_abs, d_ws_off, d_ws, ws_pixels, ws_bytes))
-        return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_depth_objects: ") + why);
-    if (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_out || !d_shells || (n_images > 1 && !d_obj_image)))
-        return fail(SDSM_ERR_ARGUMENT, "sdsm_depth_objects: null argument");
+    const char *why = packed_objects_bad(n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits);
+    if (!why) why = depth_args_bad(n, n_shells, d_g, d_gmax_abs, d_ws_off, d_ws, ws_pixels, ws_bytes, d_out, d_shells);
+    if (why) return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_depth_objects: ") + why);
     hipError_t e = sdsm_measure_scale_impl(images, n_images, d_g, d_gmax_abs, d_scale_exp, (hipStream_t)stream);
     if (e == hipSuccess)
         e = sdsm_depth_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_g, d_gmax_abs, n_shells, d_ws_off, d_ws, ws_pixels, d_out,
@@ -1080,18 +1088,12 @@ extern "C" int sdsm_depth_labels_multi(const sdsm_set_image *images, int n_image
                                        sdsm_depth_shell_record *d_shells, int32_t *d_bad, void *stream)
 {
     SET_TABLE("sdsm_depth_labels", SET_SIDES | SET_PIXELS);
-    if (n < 0 || window_words < 0 || window_words > SDSM_SHAPE_MAX_WINDOW_WORDS)
-        return fail(SDSM_ERR_ARGUMENT, "sdsm_depth_labels: n >= 0 and 0 <= window_words <= SDSM_SHAPE_MAX_WINDOW_WORDS required");
-    if (const char *why = depth_args_bad(n_shells, d_g, d_gmax_abs, d_ws_off, d_ws, ws_pixels, ws_bytes))
+    if (const char *why = depth_args_bad(n, n_shells, d_g, d_gmax_abs, d_ws_off, d_ws, ws_pixels, ws_bytes, d_out, d_shells))
         return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_depth_labels: ") + why);
-    if (!d_labels || !rec_off || !n_labels || !d_label_obj || !d_bad ||
-        (n > 0 && (!d_boxes || !d_bits_off || !d_bits || !d_out || !d_shells || (n_images > 1 && !d_obj_image))))
-        return fail(SDSM_ERR_ARGUMENT, "sdsm_depth_labels: null argument");
-    const char *why;
-    if (!label_records_ok(n_images, n_labels, rec_off, false, &why)) return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_depth_labels: ") + why);
-    hipError_t e = sdsm_shape_scatter_impl(images, n_images, d_labels, rec_off, n_labels, d_label_obj, n, d_boxes, d_bits_off, window_words, d_bits, d_bad,
-                                           (hipStream_t)stream);
-    if (e == hipSuccess) e = sdsm_measure_scale_impl(images, n_images, d_g, d_gmax_abs, d_scale_exp, (hipStream_t)stream);
+    if (int rc = label_windows("sdsm_depth_labels", images, n_images, d_labels, rec_off, n_labels, d_label_obj, n, d_obj_image, d_boxes, d_bits_off, window_words,
+                               d_bits, d_bad, stream))
+        return rc;
+    hipError_t e = sdsm_measure_scale_impl(images, n_images, d_g, d_gmax_abs, d_scale_exp, (hipStream_t)stream);
     if (e == hipSuccess)
         e = sdsm_depth_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_g, d_gmax_abs, n_shells, d_ws_off, d_ws, ws_pixels, d_out,
                                     d_shells, (hipStream_t)stream);

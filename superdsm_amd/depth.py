@@ -37,14 +37,15 @@ and adds nothing to the sums.  An object without a pixel has the zero row and ze
 import csv
 import math
 from fractions import Fraction
+from functools import partial
 
 import numpy as np
 
 from . import _capi
-from .imageset import in_sets
 from .intensity import quantile_ranks
-from .measure import _check_intensity, _check_labels, _check_shape, _label_count, _object_boxes, _scaled, quantize, scale_exponent
-from .postprocess import _check_boxes, _exclusive, pack_fragments
+from .measure import (_check_intensity, _check_labels, _check_shape, _keep_absent, _label_count, _label_sets, _label_table, _LabelWindows, _MeasureSet,
+                      _object_boxes, _object_sets, _result_inputs, _scaled, quantize, scale_exponent)
+from .postprocess import _check_boxes, _exclusive
 
 TABLE_DTYPE = np.dtype([('label', 'i4')] + _capi._DEPTH_FIELDS)        # 'label': the label, or the index of the object in its image
 DEFAULT_SHELLS = 8
@@ -115,12 +116,7 @@ def _fill_record(rec, shells, mask, offset, shape, g, e):
             shells['gsum_hi'][t] = int((qt >> 32).sum(dtype=np.int64))
 
 
-def _table(labels, recs):
-    table = np.zeros(len(recs), TABLE_DTYPE)
-    table['label'] = labels
-    for name in _capi.DEPTH_RECORD_DTYPE.names:
-        table[name] = recs[name]
-    return table
+_table = partial(_label_table, TABLE_DTYPE)                            # _table(labels, recs)
 
 
 def depth_objects_host(objects, shape, intensity=None, n_shells=DEFAULT_SHELLS):
@@ -238,7 +234,6 @@ class _DepthSet:
     the depth kernel."""
 
     def __init__(self, shapes, intensities):
-        from .measure import _MeasureSet
         self.M = _MeasureSet(shapes, intensities)     # (the intensities packed; the label form takes the boxes of the labels from there)
         self.S = self.M.S
         self.n_im = len(self.S.shapes)
@@ -248,11 +243,9 @@ class _DepthSet:
         S, n = self.S, len(boxes)
         ws = workspace_pixels(boxes)
         total = int(ws.sum())
-        u8 = dict(dtype=S.torch.uint8, device=S.dev)
-        return dict(d_out=S.torch.empty(max(1, n) * _capi.DEPTH_RECORD_DTYPE.itemsize, **u8),
-                    d_shells=S.torch.empty(max(1, n * n_shells) * _capi.DEPTH_SHELL_DTYPE.itemsize, **u8),
+        return dict(d_out=S.record_buffer(n, _capi.DEPTH_RECORD_DTYPE), d_shells=S.record_buffer(n * n_shells, _capi.DEPTH_SHELL_DTYPE),
                     d_ws_off=S._up(_exclusive(ws)) if total else None, ws_pixels=total,
-                    d_ws=S.torch.empty(total * _capi.DEPTH_WS_PIXEL_BYTES, **u8) if total else None)
+                    d_ws=S.torch.empty(total * _capi.DEPTH_WS_PIXEL_BYTES, dtype=S.torch.uint8, device=S.dev) if total else None)
 
     def _workspace(self, B, ws_bytes):
         """The four workspace arguments; ``ws_bytes``: the size named to the call instead of the buffer's own."""
@@ -261,8 +254,8 @@ class _DepthSet:
         return S._p(B['d_ws_off']), S._p(B['d_ws']), B['ws_pixels'], own if ws_bytes is None else int(ws_bytes)
 
     def _download(self, B, n, n_shells):
-        recs = B['d_out'].cpu().numpy()[:n * _capi.DEPTH_RECORD_DTYPE.itemsize].view(_capi.DEPTH_RECORD_DTYPE).copy()
-        shells = B['d_shells'].cpu().numpy()[:n * n_shells * _capi.DEPTH_SHELL_DTYPE.itemsize].view(_capi.DEPTH_SHELL_DTYPE).reshape(n, n_shells).copy()
+        recs = self.S.records(B['d_out'], n, _capi.DEPTH_RECORD_DTYPE)
+        shells = self.S.records(B['d_shells'], n * n_shells, _capi.DEPTH_SHELL_DTYPE).reshape(n, n_shells)
         if (recs['flags'] & _capi.DEPTH_NO_WORKSPACE).any():
             raise _capi.SdsmError('an object above the LDS tile was named no workspace, see DESIGN.md "Limits"')
         return recs, shells
@@ -271,56 +264,33 @@ class _DepthSet:
         """(records, shells) of the objects of the set (``packed``: the bit-packed fragments, one uint8 array of whole words each)."""
         S, n = self.S, len(boxes)
         B = self.buffers(boxes, n_shells) if B is None else B
-        d_image, d_boxes, d_off = S._up(np.asarray(obj_image, np.int32)), S._up(np.asarray(boxes, np.int32).reshape(-1, 4)), S._up(_exclusive(words))
-        d_bits = S._up(np.concatenate(packed) if len(packed) else np.zeros(4, np.uint8))
-        S.capi.check(S.L.sdsm_depth_objects_multi(S.table, self.n_im, n, S._p(d_image), S._p(d_boxes), S._p(d_off), S._p(d_bits), S._p(self.M.d_g),
-                                                  S._p(self.M.d_gmax), S._p(self.M.d_exp), n_shells, *self._workspace(B, ws_bytes), S._p(B['d_out']),
-                                                  S._p(B['d_shells']), S._stream()), 'sdsm_depth_objects_multi')
+        d_objects = S.upload_objects(obj_image, boxes, words, packed)
+        S.capi.check(S.L.sdsm_depth_objects_multi(S.table, self.n_im, n, *map(S._p, d_objects), S._p(self.M.d_g), S._p(self.M.d_gmax), S._p(self.M.d_exp), n_shells,
+                                                  *self._workspace(B, ws_bytes), S._p(B['d_out']), S._p(B['d_shells']), S._stream()), 'sdsm_depth_objects_multi')
         return self._download(B, n, n_shells)
 
     def labels(self, labels, background_label, n_shells):
-        """Per image (labels measured, number of labels, records, shells) of the label maps of the set: the windows of the labels as the
-        shape tables size them (``shape._LabelWindows``), then sdsm_depth_labels."""
-        from .shape import _LabelWindows
+        """Per image (labels measured, number of labels, records, shells) of the label maps of the set: the windows of the labels
+        (``measure._LabelWindows``), then sdsm_depth_labels."""
         S = self.S
         w = _LabelWindows(self.M, labels, background_label, 'depth')
         n = len(w.idx)
         B = self.buffers(w.boxes, n_shells)
-        S.capi.check(S.L.sdsm_depth_labels_multi(S.table, self.n_im, S._p(w.d_labels), w.c_off, w.c_n, S._p(w.d_label_obj), n, S._p(w.d_image), S._p(w.d_boxes),
-                                                 S._p(w.d_off), w.total, S._p(w.d_bits), S._p(self.M.d_g), S._p(self.M.d_gmax), S._p(self.M.d_exp), n_shells,
+        S.capi.check(S.L.sdsm_depth_labels_multi(S.table, self.n_im, *w.args(), S._p(self.M.d_g), S._p(self.M.d_gmax), S._p(self.M.d_exp), n_shells,
                                                  *self._workspace(B, None), S._p(B['d_out']), S._p(B['d_shells']), S._p(w.d_bad), S._stream()),
                      'sdsm_depth_labels_multi')
         recs, shells = self._download(B, n, n_shells)
         return [(ls, n_labels, recs[a:b], shells[a:b]) for ls, n_labels, a, b in w.per_image()]
 
 
-def _intensities(intensities, shapes):
-    if intensities is None:
-        return None
-    intensities = list(intensities)
-    if len(intensities) != len(shapes) or any(g is None for g in intensities):
-        raise ValueError('intensities: None, or one image per label map / list of objects')
-    return [_check_intensity(g, s) for g, s in zip(intensities, shapes)]
-
-
 def depth_objects_many(objects_per_image, shapes, intensities=None, n_shells=DEFAULT_SHELLS):
     """:func:`depth_objects` for a list of images: one launch per ``_capi.MAX_SET_IMAGES`` images (larger lists are split).  Per image the
     bytes of :func:`depth_objects_host`."""
-    objs = [list(o) for o in objects_per_image]
-    shapes = [_check_shape(s) for s in shapes]
-    if len(shapes) != len(objs):
-        raise ValueError('shapes: one per list of objects')
-    for o, s in zip(objs, shapes):
-        _check_boxes(_object_boxes(o), s)
-    gs = _intensities(intensities, shapes)
+    sets = _object_sets(objects_per_image, shapes, intensities)
     n_shells = check_shells(n_shells)
     out = []
-    for part in in_sets(len(objs)):
-        packs = [pack_fragments(o) for o in objs[part]]
-        recs, shells = _DepthSet(shapes[part], gs[part] if gs is not None else None).objects(
-            np.concatenate([np.full(len(pk[0]), i, np.int32) for i, pk in enumerate(packs)]), np.concatenate([pk[0] for pk in packs]),
-            np.concatenate([pk[1] for pk in packs]), [b for pk in packs for b in pk[2]], n_shells)
-        first = np.concatenate([[0], np.cumsum([len(pk[0]) for pk in packs])])
+    for _, shapes_part, gs, packed, first in sets:
+        recs, shells = _DepthSet(shapes_part, gs).objects(*packed, n_shells)
         out += [(_table(np.arange(b - a), recs[a:b]), shells[a:b]) for a, b in zip(first[:-1], first[1:])]
     return out
 
@@ -333,18 +303,15 @@ def depth_objects(objects, shape, intensity=None, n_shells=DEFAULT_SHELLS):
 
 def depth_labels_many(labels_list, intensities=None, n_shells=DEFAULT_SHELLS, background_label=0, keep_absent=False):
     """:func:`depth_labels` for a list of label maps, one launch per ``_capi.MAX_SET_IMAGES`` images."""
-    from .render import _int32_labels
-    labels_list = [_check_labels(l) for l in labels_list]
-    gs = _intensities(intensities, [l.shape for l in labels_list])
-    l32 = [_int32_labels(l) for l in labels_list]
+    sets = _label_sets(labels_list, intensities)
     n_shells = check_shells(n_shells)
     out = []
-    for part in in_sets(len(l32)):
-        for ls, n_labels, recs, shells in _DepthSet([l.shape for l in l32[part]], gs[part] if gs is not None else None).labels(l32[part], background_label, n_shells):
+    for _, l32, shapes, gs in sets:
+        for ls, n_labels, recs, shells in _DepthSet(shapes, gs).labels(l32, background_label, n_shells):
             if keep_absent:
                 full, full_shells = _zero(n_labels, n_shells)
-                full[ls], full_shells[ls] = recs, shells
-                ls, recs, shells = np.arange(n_labels), full, full_shells
+                full_shells[ls] = shells
+                (ls, recs), shells = _keep_absent(full, ls, recs), full_shells
             out.append((_table(ls, recs), shells))
     return out
 
@@ -358,6 +325,4 @@ def depth_labels(labels, intensity=None, n_shells=DEFAULT_SHELLS, background_lab
 def depth_result(data, objects='postprocessed_objects', intensity='g_raw', n_shells=DEFAULT_SHELLS):
     """The depth table of the objects of pipeline data: ``objects`` an output name or a list of objects, ``intensity`` a key of ``data``,
     an image, or None."""
-    objs = list(data[objects]) if isinstance(objects, str) else list(objects)
-    g = data[intensity] if isinstance(intensity, str) else intensity
-    return depth_objects(objs, data['g_raw'].shape, g, n_shells)
+    return depth_objects(*_result_inputs(data, objects, intensity), n_shells)

@@ -30,13 +30,14 @@ exact rational interpolation (where v_hi - v_lo does not overflow); it is not pr
 import csv
 import math
 from fractions import Fraction
+from functools import partial
 
 import numpy as np
 
 from . import _capi
-from .imageset import in_sets
-from .measure import SCALE_EXP_MAX, SCALE_EXP_MIN, _check_intensity, _check_labels, _check_shape, _label_count, _object_boxes
-from .postprocess import _check_boxes, _exclusive, pack_fragments
+from .measure import (SCALE_EXP_MAX, SCALE_EXP_MIN, _check_labels, _check_shape, _keep_absent, _label_count, _label_sets, _label_table, _LabelWindows,
+                      _MeasureSet, _object_boxes, _object_sets, _require_intensity, _result_inputs)
+from .postprocess import _check_boxes
 
 TABLE_DTYPE = np.dtype([('label', 'i4')] + _capi._INTENSITY_FIELDS)   # 'label': the label, or the index of the object in its image
 DEFAULT_QUANTILES = (0.25, 0.5, 0.75)
@@ -111,18 +112,7 @@ def _fill_record(rec, order, rr, cc, shape, g, fracs):
     rec['med_lo'], rec['med_hi'], rec['mad_lo'], rec['mad_hi'], rec['flags'] = v[lo], v[hi], keys[lo], keys[hi], flags
 
 
-def _require_intensity(intensity, shape):
-    if intensity is None:
-        raise ValueError('intensity: the intensity tables need an image')
-    return _check_intensity(intensity, shape)
-
-
-def _table(labels, recs):
-    table = np.zeros(len(recs), TABLE_DTYPE)
-    table['label'] = labels
-    for name in _capi.INTENSITY_RECORD_DTYPE.names:
-        table[name] = recs[name]
-    return table
+_table = partial(_label_table, TABLE_DTYPE)                           # _table(labels, recs)
 
 
 def _empty_order(n, n_q):
@@ -247,7 +237,6 @@ class _IntensitySet:
     kernel."""
 
     def __init__(self, shapes, intensities):
-        from .measure import _MeasureSet
         self.M = _MeasureSet(shapes, intensities)     # (the intensities packed; the label form takes the boxes of the labels from there)
         self.S = self.M.S
         self.n_im = len(self.S.shapes)
@@ -255,69 +244,47 @@ class _IntensitySet:
     def buffers(self, n, n_q):
         """The two outputs of a call; their contents do not matter."""
         S = self.S
-        return dict(d_out=S.torch.empty(max(1, n) * _capi.INTENSITY_RECORD_DTYPE.itemsize, dtype=S.torch.uint8, device=S.dev),
-                    d_order=S.torch.empty(max(1, n * n_q * 2), dtype=S.torch.float64, device=S.dev))
+        return dict(d_out=S.record_buffer(n, _capi.INTENSITY_RECORD_DTYPE), d_order=S.torch.empty(max(1, n * n_q * 2), dtype=S.torch.float64, device=S.dev))
 
     def _quantiles(self, fracs):
         C = self.S.C
         return len(fracs), (C.c_int32 * max(1, len(fracs)))(*[f[0] for f in fracs]), (C.c_int32 * max(1, len(fracs)))(*[f[1] for f in fracs])
 
     def _download(self, B, n, n_q):
-        recs = B['d_out'].cpu().numpy()[:n * _capi.INTENSITY_RECORD_DTYPE.itemsize].view(_capi.INTENSITY_RECORD_DTYPE).copy()
-        return recs, B['d_order'].cpu().numpy()[:n * n_q * 2].reshape(n, n_q, 2).copy()
+        return self.S.records(B['d_out'], n, _capi.INTENSITY_RECORD_DTYPE), B['d_order'].cpu().numpy()[:n * n_q * 2].reshape(n, n_q, 2).copy()
 
     def objects(self, obj_image, boxes, words, packed, fracs, B=None):
         """(records, order) of the objects of the set (``packed``: the bit-packed fragments, one uint8 array of whole words each)."""
         S, n = self.S, len(boxes)
         n_q, num, den = self._quantiles(fracs)
         B = self.buffers(n, n_q) if B is None else B
-        d_image, d_boxes, d_off = S._up(np.asarray(obj_image, np.int32)), S._up(np.asarray(boxes, np.int32).reshape(-1, 4)), S._up(_exclusive(words))
-        d_bits = S._up(np.concatenate(packed) if len(packed) else np.zeros(4, np.uint8))
-        S.capi.check(S.L.sdsm_intensity_objects_multi(S.table, self.n_im, n, S._p(d_image), S._p(d_boxes), S._p(d_off), S._p(d_bits), S._p(self.M.d_g),
-                                                      n_q, num, den, S._p(B['d_out']), S._p(B['d_order']), S._stream()), 'sdsm_intensity_objects_multi')
+        d_objects = S.upload_objects(obj_image, boxes, words, packed)
+        S.capi.check(S.L.sdsm_intensity_objects_multi(S.table, self.n_im, n, *map(S._p, d_objects), S._p(self.M.d_g), n_q, num, den, S._p(B['d_out']),
+                                                      S._p(B['d_order']), S._stream()), 'sdsm_intensity_objects_multi')
         return self._download(B, n, n_q)
 
     def labels(self, labels, background_label, fracs):
-        """Per image (labels measured, number of labels, records, order) of the label maps of the set: the windows of the labels as the
-        shape tables size them (``shape._LabelWindows``), then sdsm_intensity_labels."""
-        from .shape import _LabelWindows
+        """Per image (labels measured, number of labels, records, order) of the label maps of the set: the windows of the labels
+        (``measure._LabelWindows``), then sdsm_intensity_labels."""
         S = self.S
         w = _LabelWindows(self.M, labels, background_label, 'intensity')
         n = len(w.idx)
         n_q, num, den = self._quantiles(fracs)
         B = self.buffers(n, n_q)
-        S.capi.check(S.L.sdsm_intensity_labels_multi(S.table, self.n_im, S._p(w.d_labels), w.c_off, w.c_n, S._p(w.d_label_obj), n, S._p(w.d_image), S._p(w.d_boxes),
-                                                     S._p(w.d_off), w.total, S._p(w.d_bits), S._p(self.M.d_g), n_q, num, den, S._p(B['d_out']), S._p(B['d_order']),
+        S.capi.check(S.L.sdsm_intensity_labels_multi(S.table, self.n_im, *w.args(), S._p(self.M.d_g), n_q, num, den, S._p(B['d_out']), S._p(B['d_order']),
                                                      S._p(w.d_bad), S._stream()), 'sdsm_intensity_labels_multi')
         recs, order = self._download(B, n, n_q)
         return [(ls, n_labels, recs[a:b], order[a:b]) for ls, n_labels, a, b in w.per_image()]
 
 
-def _intensities(intensities, shapes):
-    intensities = list(intensities) if intensities is not None else []
-    if len(intensities) != len(shapes):
-        raise ValueError('intensities: one image per label map / list of objects')
-    return [_require_intensity(g, s) for g, s in zip(intensities, shapes)]
-
-
 def intensity_objects_many(objects_per_image, shapes, intensities, quantiles=DEFAULT_QUANTILES):
     """:func:`intensity_objects` for a list of images: one launch per ``_capi.MAX_SET_IMAGES`` images (larger lists are split).  Per image
     the bytes of :func:`intensity_objects_host`."""
-    objs = [list(o) for o in objects_per_image]
-    shapes = [_check_shape(s) for s in shapes]
-    if len(shapes) != len(objs):
-        raise ValueError('shapes: one per list of objects')
-    for o, s in zip(objs, shapes):
-        _check_boxes(_object_boxes(o), s)
-    gs = _intensities(intensities, shapes)
+    sets = _object_sets(objects_per_image, shapes, intensities, required=True)
     fracs = quantile_fractions(quantiles)
     out = []
-    for part in in_sets(len(objs)):
-        packs = [pack_fragments(o) for o in objs[part]]
-        recs, order = _IntensitySet(shapes[part], gs[part]).objects(
-            np.concatenate([np.full(len(pk[0]), i, np.int32) for i, pk in enumerate(packs)]), np.concatenate([pk[0] for pk in packs]),
-            np.concatenate([pk[1] for pk in packs]), [b for pk in packs for b in pk[2]], fracs)
-        first = np.concatenate([[0], np.cumsum([len(pk[0]) for pk in packs])])
+    for _, shapes_part, gs, packed, first in sets:
+        recs, order = _IntensitySet(shapes_part, gs).objects(*packed, fracs)
         out += [(_table(np.arange(b - a), recs[a:b]), order[a:b]) for a, b in zip(first[:-1], first[1:])]
     return out
 
@@ -330,18 +297,15 @@ def intensity_objects(objects, shape, intensity, quantiles=DEFAULT_QUANTILES):
 
 def intensity_labels_many(labels_list, intensities, quantiles=DEFAULT_QUANTILES, background_label=0, keep_absent=False):
     """:func:`intensity_labels` for a list of label maps, one launch per ``_capi.MAX_SET_IMAGES`` images."""
-    from .render import _int32_labels
-    labels_list = [_check_labels(l) for l in labels_list]
-    gs = _intensities(intensities, [l.shape for l in labels_list])
-    l32 = [_int32_labels(l) for l in labels_list]
+    sets = _label_sets(labels_list, intensities, required=True)
     fracs = quantile_fractions(quantiles)
     out = []
-    for part in in_sets(len(l32)):
-        for ls, n_labels, recs, order in _IntensitySet([l.shape for l in l32[part]], gs[part]).labels(l32[part], background_label, fracs):
+    for _, l32, shapes, gs in sets:
+        for ls, n_labels, recs, order in _IntensitySet(shapes, gs).labels(l32, background_label, fracs):
             if keep_absent:
-                full, full_order = _empty_records(n_labels), _empty_order(n_labels, len(fracs))
-                full[ls], full_order[ls] = recs, order
-                ls, recs, order = np.arange(n_labels), full, full_order
+                full_order = _empty_order(n_labels, len(fracs))
+                full_order[ls] = order
+                (ls, recs), order = _keep_absent(_empty_records(n_labels), ls, recs), full_order
             out.append((_table(ls, recs), order))
     return out
 
@@ -355,6 +319,4 @@ def intensity_labels(labels, intensity, quantiles=DEFAULT_QUANTILES, background_
 def intensity_result(data, objects='postprocessed_objects', intensity='g_raw', quantiles=DEFAULT_QUANTILES):
     """The intensity table of the objects of pipeline data: ``objects`` an output name or a list of objects, ``intensity`` a key of
     ``data`` or an image."""
-    objs = list(data[objects]) if isinstance(objects, str) else list(objects)
-    g = data[intensity] if isinstance(intensity, str) else intensity
-    return intensity_objects(objs, data['g_raw'].shape, g, quantiles)
+    return intensity_objects(*_result_inputs(data, objects, intensity), quantiles)

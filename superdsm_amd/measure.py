@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _capi
 from .imageset import in_sets
-from .postprocess import _check_boxes, _exclusive, pack_fragments
+from .postprocess import _check_boxes, _exclusive, pack_object_sets
 
 TABLE_DTYPE = np.dtype([('label', 'i4')] + _capi._MEASURE_FIELDS)     # 'label': the label, or the index of the object in its image
 SCALE_EXP_MIN, SCALE_EXP_MAX = -960, 1024
@@ -89,6 +89,12 @@ def _check_intensity(intensity, shape):
     return np.ascontiguousarray(g, np.float64)
 
 
+def _require_intensity(intensity, shape):
+    if intensity is None:
+        raise ValueError('intensity: the intensity tables need an image')
+    return _check_intensity(intensity, shape)
+
+
 def _check_shape(shape):
     shape = tuple(int(v) for v in shape)
     if len(shape) != 2 or min(shape) < 1 or max(shape) > 65535 or shape[0] * shape[1] >= 2 ** 31 - 1:
@@ -100,12 +106,17 @@ def _object_boxes(objects):
     return np.array([(int(o.fg_offset[0]), int(o.fg_offset[1])) + tuple(o.fg_fragment.shape) for o in objects], np.int64).reshape(-1, 4)
 
 
-def _as_table(recs, labels):
-    table = np.zeros(len(recs), TABLE_DTYPE)
+def _label_table(dtype, labels, recs):
+    """The table of ``dtype`` -- a 'label' column in front of the fields of the records -- of the records ``recs`` of ``labels``."""
+    table = np.zeros(len(recs), dtype)
     table['label'] = labels
-    for name in _capi.MEASURE_RECORD_DTYPE.names:
+    for name in dtype.names[1:]:
         table[name] = recs[name]
     return table
+
+
+def _as_table(recs, labels):
+    return _label_table(TABLE_DTYPE, labels, recs)
 
 
 def measure_objects_host(objects, shape, intensity=None):
@@ -246,19 +257,18 @@ class _MeasureSet:
         self.d_exp = S.torch.empty(self.n_im, dtype=S.torch.int32, device=S.dev)
 
     def _records(self, d_out, n):
-        return d_out.cpu().numpy()[:n * _capi.MEASURE_RECORD_DTYPE.itemsize].view(_capi.MEASURE_RECORD_DTYPE).copy()
+        return self.S.records(d_out, n, _capi.MEASURE_RECORD_DTYPE)
 
     def record_buffer(self, n):
-        return self.S.torch.empty(max(1, n) * _capi.MEASURE_RECORD_DTYPE.itemsize, dtype=self.S.torch.uint8, device=self.S.dev)
+        return self.S.record_buffer(n, _capi.MEASURE_RECORD_DTYPE)
 
     def objects(self, obj_image, boxes, words, packed):
         """The records of the objects of the set (``packed``: the bit-packed fragments, one uint8 array of whole words each)."""
         S, n = self.S, len(boxes)
         d_out = self.record_buffer(n)
-        d_image, d_boxes, d_off = S._up(np.asarray(obj_image, np.int32)), S._up(np.asarray(boxes, np.int32).reshape(-1, 4)), S._up(_exclusive(words))
-        d_bits = S._up(np.concatenate(packed) if len(packed) else np.zeros(4, np.uint8))
-        S.capi.check(S.L.sdsm_measure_objects_multi(S.table, self.n_im, n, S._p(d_image), S._p(d_boxes), S._p(d_off), S._p(d_bits), S._p(self.d_g),
-                                                    S._p(self.d_gmax), S._p(self.d_exp), S._p(d_out), S._stream()), 'sdsm_measure_objects_multi')
+        d_objects = S.upload_objects(obj_image, boxes, words, packed)
+        S.capi.check(S.L.sdsm_measure_objects_multi(S.table, self.n_im, n, *map(S._p, d_objects), S._p(self.d_g), S._p(self.d_gmax), S._p(self.d_exp),
+                                                    S._p(d_out), S._stream()), 'sdsm_measure_objects_multi')
         return self._records(d_out, n)
 
     def label_range(self, d_labels):
@@ -296,33 +306,116 @@ class _MeasureSet:
         return self.d_exp.cpu().numpy()
 
 
-def _intensities(intensities, shapes):
-    if intensities is None:
+class _LabelWindows:
+    """The windows of the labels of a set of label maps (``M``: its ``_MeasureSet``), as the label forms of the shape, intensity, texture
+    and depth tables take them: the boxes of the present labels without ``background_label`` from sdsm_measure_labels (one download),
+    one window of ceil(h w / 32) words per label, and the device arrays that name them.  Raises before any kernel of the caller's is
+    launched where the labels or the windows pass the limits."""
+
+    def __init__(self, M, labels, background_label, what):
+        S = self.S = M.S
+        n_im = self.n_im = len(S.shapes)
+        self.d_labels = S.pack(labels, np.int32)
+        rng = M.label_range(self.d_labels)
+        if (rng[:, 0] < 0).any() or (rng[:, 1] >= _capi.MEASURE_MAX_LABELS).any():
+            raise ValueError(f'labels {rng[:, 0].min()} .. {rng[:, 1].max()}: the {what} tables take the labels 0 .. {_capi.MEASURE_MAX_LABELS - 1}, '
+                             'see DESIGN.md "Limits"')
+        self.n_labels = n_labels = (rng[:, 1] + 1).astype(np.int64)
+        self.rec_off = rec_off = _exclusive(n_labels)
+        self.c_off, self.c_n = (S.C.c_int64 * n_im)(*[int(v) for v in rec_off]), (S.C.c_int32 * n_im)(*[int(v) for v in n_labels])
+        self.d_bad = S.torch.empty(n_im, dtype=S.torch.int32, device=S.dev)
+        d_rec = M.record_buffer(int(n_labels.sum()))
+        S.capi.check(S.L.sdsm_measure_labels_multi(S.table, n_im, S._p(self.d_labels), self.c_off, self.c_n, None, None, None, S._p(d_rec), S._p(self.d_bad),
+                                                   S._stream()), 'sdsm_measure_labels_multi')
+        mrec = M._records(d_rec, int(n_labels.sum()))
+        keep = mrec['area'] > 0
+        if background_label is not None:
+            for i in range(n_im):
+                if 0 <= background_label < n_labels[i]:
+                    keep[rec_off[i] + background_label] = False
+        self.idx = idx = np.nonzero(keep)[0]
+        self.boxes = boxes = np.stack([mrec['r0'][idx], mrec['c0'][idx], mrec['r1'][idx] - mrec['r0'][idx], mrec['c1'][idx] - mrec['c0'][idx]], axis=1).astype(np.int32)
+        self.obj_image = obj_image = (np.searchsorted(rec_off, idx, side='right') - 1).astype(np.int32)
+        words = (boxes[:, 2].astype(np.int64) * boxes[:, 3] + 31) // 32
+        self.total = total = int(words.sum())
+        if total > _capi.SHAPE_MAX_WINDOW_WORDS:                               # (nothing of the caller's kernels has been launched)
+            raise ValueError(f'the windows of the labels take {total} words: the label form of the {what} tables takes up to {_capi.SHAPE_MAX_WINDOW_WORDS} '
+                             'per set, see DESIGN.md "Limits"')
+        label_obj = np.full(int(n_labels.sum()), -1, np.int32)
+        label_obj[idx] = np.arange(len(idx), dtype=np.int32)
+        self.d_label_obj = S._up(label_obj)
+        self.d_image, self.d_boxes, self.d_off, self.d_bits = S.upload_objects(obj_image, boxes, words, None)      # (the call fills the windows)
+
+    def args(self):
+        """The ten arguments that follow the image table in every ``sdsm_*_labels_multi`` call: d_labels, rec_off, n_labels, d_label_obj,
+        n, d_obj_image, d_boxes, d_bits_off, window_words, d_bits."""
+        p = self.S._p
+        return p(self.d_labels), self.c_off, self.c_n, p(self.d_label_obj), len(self.idx), p(self.d_image), p(self.d_boxes), p(self.d_off), self.total, p(self.d_bits)
+
+    def per_image(self):
+        """Per image (labels measured, number of labels, first window, end of its windows)."""
+        first = np.searchsorted(self.obj_image, np.arange(self.n_im + 1))
+        return [((self.idx[a:b] - self.rec_off[i]).astype(np.int64), int(self.n_labels[i]), a, b) for i, (a, b) in enumerate(zip(first[:-1], first[1:]))]
+
+
+# ---- what the GPU forms of the table families share in front of their sets (shape, intensity, texture and depth import it from here) ----
+def _intensities(intensities, shapes, required=False):
+    """One checked float64 image per shape.  ``required``: the family needs them (intensity, texture); otherwise (measure, depth) None
+    stands for no intensities at all and is returned."""
+    if intensities is None and not required:
         return None
-    intensities = list(intensities)
-    if len(intensities) != len(shapes) or any(g is None for g in intensities):
-        raise ValueError('intensities: None, or one image per label map / list of objects')
-    return [_check_intensity(g, s) for g, s in zip(intensities, shapes)]
+    intensities = [] if intensities is None else list(intensities)
+    if len(intensities) != len(shapes) or (not required and any(g is None for g in intensities)):
+        raise ValueError('intensities: ' + ('' if required else 'None, or ') + 'one image per label map / list of objects')
+    return [_require_intensity(g, s) for g, s in zip(intensities, shapes)]
 
 
-def measure_objects_many(objects_per_image, shapes, intensities=None):
-    """:func:`measure_objects` for a list of images: one launch per ``_capi.MAX_SET_IMAGES`` images (larger lists are split).  Per image
-    the bytes of :func:`measure_objects_host`."""
+def _object_sets(objects_per_image, shapes, intensities=None, required=False):
+    """The front of every ``*_objects_many``: the lists checked -- all of them, before anything touches the device --, then per set of up
+    to ``_capi.MAX_SET_IMAGES`` images ``(part, shapes, intensities or None, packed, first)``: its slice of the lists, the packed objects
+    and the split by image of ``postprocess.pack_object_sets``.  A set is packed when the caller's loop comes to it."""
     objs = [list(o) for o in objects_per_image]
     shapes = [_check_shape(s) for s in shapes]
     if len(shapes) != len(objs):
         raise ValueError('shapes: one per list of objects')
     for o, s in zip(objs, shapes):
         _check_boxes(_object_boxes(o), s)
-    gs = _intensities(intensities, shapes)
+    gs = _intensities(intensities, shapes, required)
+    return ((part, shapes[part], gs[part] if gs is not None else None) + pack_object_sets(objs[part])[:2] for part in in_sets(len(objs)))
+
+
+def _label_sets(labels_list, intensities=None, required=False):
+    """The front of every ``*_labels_many``: the label maps checked and as int32, then per set ``(part, label maps, shapes, intensities or
+    None)``."""
+    from .render import _int32_labels
+    labels_list = [_check_labels(l) for l in labels_list]
+    gs = _intensities(intensities, [l.shape for l in labels_list], required)
+    l32 = [_int32_labels(l) for l in labels_list]
+    return [(part, l32[part], [l.shape for l in l32[part]], gs[part] if gs is not None else None) for part in in_sets(len(l32))]
+
+
+def _keep_absent(empty, ls, recs):
+    """``keep_absent`` of a label form: (labels, records) with one record per label 0 .. n - 1 -- the n ``empty`` records with the measured
+    ``recs`` written at the labels ``ls``."""
+    empty[ls] = recs
+    return np.arange(len(empty)), empty
+
+
+def _result_inputs(data, objects, intensity=None):
+    """What every ``*_result`` hands on: (objects, shape, intensities) of pipeline data -- ``objects`` an output name or a list of
+    objects, ``intensity`` a key of ``data``, an image, or None."""
+    objs = list(data[objects]) if isinstance(objects, str) else list(objects)
+    g = data[intensity] if isinstance(intensity, str) else intensity
+    return objs, data['g_raw'].shape, g
+
+
+def measure_objects_many(objects_per_image, shapes, intensities=None):
+    """:func:`measure_objects` for a list of images: one launch per ``_capi.MAX_SET_IMAGES`` images (larger lists are split).  Per image
+    the bytes of :func:`measure_objects_host`."""
     out = []
-    for part in in_sets(len(objs)):
-        packs = [pack_fragments(o) for o in objs[part]]
-        M = _MeasureSet(shapes[part], gs[part] if gs is not None else None)
-        recs = M.objects(np.concatenate([np.full(len(pk[0]), i, np.int32) for i, pk in enumerate(packs)]), np.concatenate([pk[0] for pk in packs]),
-                         np.concatenate([pk[1] for pk in packs]), [b for pk in packs for b in pk[2]])
-        first = _exclusive([len(pk[0]) for pk in packs] + [0])
-        out += [_as_table(recs[first[i]:first[i] + len(pk[0])], np.arange(len(pk[0]))) for i, pk in enumerate(packs)]
+    for _, shapes_part, gs, packed, first in _object_sets(objects_per_image, shapes, intensities):
+        recs = _MeasureSet(shapes_part, gs).objects(*packed)
+        out += [_as_table(recs[a:b], np.arange(b - a)) for a, b in zip(first[:-1], first[1:])]
     return out
 
 
@@ -335,18 +428,15 @@ def measure_objects(objects, shape, intensity=None):
 def measure_labels_many(labels_list, intensities=None, background_label=0, n_labels=None):
     """:func:`measure_labels` for a list of label maps, one launch per ``_capi.MAX_SET_IMAGES`` images.  ``n_labels``: None, or per image
     the number of labels 0 .. n - 1 the caller vouches for (a label outside raises ``ValueError``)."""
-    from .render import _int32_labels
-    labels_list = [_check_labels(l) for l in labels_list]
-    gs = _intensities(intensities, [l.shape for l in labels_list])
-    l32 = [_int32_labels(l) for l in labels_list]
+    labels_list = list(labels_list)
+    sets = _label_sets(labels_list, intensities)
     if n_labels is not None:
         n_labels = [int(n) for n in n_labels]
-        if len(n_labels) != len(l32) or not all(1 <= n <= _capi.MEASURE_MAX_LABELS for n in n_labels):
+        if len(n_labels) != len(labels_list) or not all(1 <= n <= _capi.MEASURE_MAX_LABELS for n in n_labels):
             raise ValueError(f'n_labels: one count in 1 .. {_capi.MEASURE_MAX_LABELS} per label map, see DESIGN.md "Limits"')
     out = []
-    for part in in_sets(len(l32)):
-        M = _MeasureSet([l.shape for l in l32[part]], gs[part] if gs is not None else None)
-        recs, bad = M.labels(l32[part], n_labels[part] if n_labels is not None else None)
+    for part, l32, shapes, gs in sets:
+        recs, bad = _MeasureSet(shapes, gs).labels(l32, n_labels[part] if n_labels is not None else None)
         if bad.any():
             raise ValueError(f'{int(bad.sum())} pixels of images {(part.start + np.nonzero(bad)[0]).tolist()} carry a label outside 0 .. n_labels - 1')
         out += [_present(r, background_label) for r in recs]
@@ -362,9 +452,7 @@ def measure_labels(labels, intensity=None, background_label=0, n_labels=None):
 def measure_result(data, objects='postprocessed_objects', intensity='g_raw'):
     """The table of the objects of pipeline data: ``objects`` an output name or a list of objects, ``intensity`` a key of ``data``, an
     image, or None."""
-    objs = list(data[objects]) if isinstance(objects, str) else list(objects)
-    g = data[intensity] if isinstance(intensity, str) else intensity
-    return measure_objects(objs, data['g_raw'].shape, g)
+    return measure_objects(*_result_inputs(data, objects, intensity))
 
 
 def label_map_rows_many(labels_list):

@@ -102,6 +102,17 @@ def pack_fragments(objects):
     return boxes, words, packed, areas
 
 
+def pack_object_sets(objects_per_image):
+    """The object lists of one set of images in the packed-object format of the ``*_multi`` calls: ``(obj_image, boxes, words, packed)``
+    -- per object its image, and the boxes, word counts and bit-packed fragments of :func:`pack_fragments`, image after image --, then
+    ``first`` (the objects of image i are ``first[i]`` .. ``first[i + 1]`` - 1) and the areas."""
+    packs = [pack_fragments(objs) for objs in objects_per_image]
+    obj_image = np.concatenate([np.full(len(pk[0]), i, np.int32) for i, pk in enumerate(packs)])
+    boxes, words, areas = (np.concatenate([pk[k] for pk in packs]) for k in (0, 1, 3))
+    first = np.concatenate([[0], np.cumsum([len(pk[0]) for pk in packs])])
+    return (obj_image, boxes, words, [b for pk in packs for b in pk[2]]), first, areas
+
+
 def grown_windows(boxes, H, W, m):
     """The windows box +- m clipped to the image, n x 4 int64 (r0, c0, h, w); ``H`` / ``W``: scalars or one value per box."""
     b = np.asarray(boxes, np.int64).reshape(-1, 4)

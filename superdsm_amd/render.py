@@ -16,7 +16,7 @@ import scipy.ndimage as ndi
 
 from . import _morph
 from .imageset import SetLayout, in_sets
-from .postprocess import _exclusive, grown_windows, pack_fragments, window_words
+from .postprocess import _exclusive, grown_windows, pack_object_sets, window_words
 
 
 def render_objects_foregrounds(shape, objects):
@@ -142,6 +142,24 @@ class _DeviceSet:
     def unpack(self, d, channels=1, tail=()):
         return self.layout.unpack(d.cpu().numpy(), channels, tail)
 
+    def upload_objects(self, obj_image, boxes, words, packed):
+        """The packed objects of a call (``postprocess.pack_object_sets``) on the device: ``(d_obj_image, d_boxes, d_bits_off, d_bits)``,
+        the offsets the exclusive scan of the word counts, the bits of no object four bytes nobody reads.  ``packed`` None: room for
+        the words instead, for windows that a call fills on the device.  The caller keeps the arrays until its download."""
+        if packed is None:
+            d_bits = self.torch.empty(max(1, int(np.sum(words))), dtype=self.torch.int32, device=self.dev)
+        else:
+            d_bits = self._up(np.concatenate(packed) if len(packed) else np.zeros(4, np.uint8))
+        return self._up(np.asarray(obj_image, np.int32)), self._up(np.asarray(boxes, np.int32).reshape(-1, 4)), self._up(_exclusive(words)), d_bits
+
+    def record_buffer(self, n, dtype):
+        """Room for ``n`` records of ``dtype`` (for one where n is 0); its contents do not matter."""
+        return self.torch.empty(max(1, n) * dtype.itemsize, dtype=self.torch.uint8, device=self.dev)
+
+    def records(self, d_out, n, dtype):
+        """The first ``n`` records of a record buffer, downloaded."""
+        return d_out.cpu().numpy()[:n * dtype.itemsize].view(dtype).copy()
+
     def pack_bases(self, bases):
         """The images under an overlay, H x W or H x W x 3 each: (packed float64 buffer, channels); grey ones are tripled if any has colour."""
         ch = 3 if any(b.ndim == 3 for b in bases) else 1
@@ -161,10 +179,8 @@ class _GpuSet(_DeviceSet):
 
     def load(self, obj_image, boxes, words, packed):
         self.n = len(boxes)
-        self.obj_image, self.boxes = np.asarray(obj_image, np.int32), np.asarray(boxes, np.int32).reshape(-1, 4)
-        self.bits_off = _exclusive(words)
-        self.d_bits = self._up(np.concatenate(packed) if len(packed) else np.zeros(4, np.uint8))
-        self._objects()
+        self.obj_image, self.boxes, self.bits_off = np.asarray(obj_image, np.int32), np.asarray(boxes, np.int32).reshape(-1, 4), _exclusive(words)     # (for select)
+        self.d_obj_image, self.d_boxes, self.d_bits_off, self.d_bits = self.upload_objects(obj_image, boxes, words, packed)
 
     def _objects(self):
         self.d_obj_image, self.d_boxes, self.d_bits_off = self._up(self.obj_image), self._up(self.boxes), self._up(self.bits_off)
@@ -329,15 +345,13 @@ def _merge_members(n, pairs, inter, areas, merge_overlap_threshold):
 def _labels_set(shapes, objects_per_image, merge_overlap_threshold, dilate, background_label, keep_set=False):
     """rasterize_labels for one set of at most ``_capi.MAX_SET_IMAGES`` images: every phase one call for the whole set."""
     S = _GpuSet(shapes)
-    packs = [pack_fragments(objs) for objs in objects_per_image]
-    obj_image = np.concatenate([np.full(len(pk[0]), i, np.int32) for i, pk in enumerate(packs)])
-    boxes = np.concatenate([pk[0] for pk in packs])
-    areas = np.concatenate([pk[3] for pk in packs])
+    packed_set, _, areas = pack_object_sets(objects_per_image)
+    obj_image, boxes = packed_set[:2]
     Hs, Ws = (np.array([s[k] for s in S.shapes], np.int64)[obj_image] for k in (0, 1))
     b = boxes.astype(np.int64)
     if ((b[:, 0] < 0) | (b[:, 1] < 0) | (b[:, 2] < 0) | (b[:, 3] < 0) | (b[:, 0] + b[:, 2] > Hs) | (b[:, 1] + b[:, 3] > Ws)).any():
         raise ValueError('an object reaches outside its image (fg_offset, fg_fragment.shape against g_raw.shape)')
-    S.load(obj_image, boxes, np.concatenate([pk[1] for pk in packs]), [b for pk in packs for b in pk[2]])
+    S.load(*packed_set)
     if dilate != 0 and len(boxes):                                       # phase 1 (render.py:380-384)
         boxes, areas = S.morph(dilate)
     keep = areas > 0                                                     # render.py:385

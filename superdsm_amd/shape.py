@@ -28,14 +28,15 @@ compact list), as the boundary lists of :mod:`boundary`.
 SciPy statement above, the hull to Qhull (``scipy.spatial.ConvexHull``), by tests/test_shape_cpu.py."""
 import csv
 import math
+from functools import partial
 
 import numpy as np
 import scipy.ndimage as ndi
 
 from . import _capi
-from .imageset import in_sets
-from .measure import _check_labels, _check_shape, _label_count, _object_boxes
-from .postprocess import _check_boxes, _exclusive, pack_fragments
+from .measure import (_check_labels, _check_shape, _keep_absent, _label_count, _label_sets, _label_table, _LabelWindows, _MeasureSet, _object_boxes,
+                      _object_sets, _result_inputs)
+from .postprocess import _check_boxes, _exclusive
 
 TABLE_DTYPE = np.dtype([('label', 'i4')] + _capi._SHAPE_FIELDS)       # 'label': the label, or the index of the object in its image
 DERIVED_DTYPE = np.dtype([('label', 'i4'), ('area', 'i8'), ('on_boundary', '?'), ('perimeter', 'f8'), ('crack_perimeter', 'f8'), ('circularity', 'f8'),
@@ -96,12 +97,7 @@ def _fill_record(rec, mask, offset, shape):
     return hull
 
 
-def _table(labels, recs):
-    table = np.zeros(len(recs), TABLE_DTYPE)
-    table['label'] = labels
-    for name in _capi.SHAPE_RECORD_DTYPE.names:
-        table[name] = recs[name]
-    return table
+_table = partial(_label_table, TABLE_DTYPE)                           # _table(labels, recs)
 
 
 def _result(labels, recs, hulls):
@@ -206,7 +202,6 @@ class _ShapeSet:
     """One set of up to ``_capi.MAX_SET_IMAGES`` images on the current device and the two calls of the shape kernels."""
 
     def __init__(self, shapes):
-        from .measure import _MeasureSet
         self.M = _MeasureSet(shapes, None)       # (the label form takes the boxes of the labels from the measurement kernels)
         self.S = self.M.S
         self.n_im = len(self.S.shapes)
@@ -217,11 +212,10 @@ class _ShapeSet:
         total = max(1, int(slots.sum()))
         i32 = dict(dtype=S.torch.int32, device=S.dev)
         return dict(d_slot_off=S._up(_exclusive(slots)), d_slots=S.torch.empty(2 * total, **i32), d_verts=S.torch.empty(2 * total, **i32),
-                    d_vert_off=S.torch.empty(n + 1, dtype=S.torch.int64, device=S.dev),
-                    d_out=S.torch.empty(max(1, n) * _capi.SHAPE_RECORD_DTYPE.itemsize, dtype=S.torch.uint8, device=S.dev))
+                    d_vert_off=S.torch.empty(n + 1, dtype=S.torch.int64, device=S.dev), d_out=S.record_buffer(n, _capi.SHAPE_RECORD_DTYPE))
 
     def _download(self, B, n):
-        recs = B['d_out'].cpu().numpy()[:n * _capi.SHAPE_RECORD_DTYPE.itemsize].view(_capi.SHAPE_RECORD_DTYPE).copy()
+        recs = self.S.records(B['d_out'], n, _capi.SHAPE_RECORD_DTYPE)
         if (recs['flags'] & _capi.SHAPE_CHAIN_OVERFLOW).any():
             raise _capi.SdsmError(f'a hull chain passed {_capi.SHAPE_MAX_CHAIN} vertices, see DESIGN.md "Limits"')
         offsets = B['d_vert_off'].cpu().numpy().copy()
@@ -231,11 +225,9 @@ class _ShapeSet:
         """(records, offsets, vertices) of the objects of the set (``packed``: the bit-packed fragments, one uint8 array of whole words each)."""
         S, n = self.S, len(boxes)
         B = self._buffers(boxes)
-        d_image, d_boxes, d_off = S._up(np.asarray(obj_image, np.int32)), S._up(np.asarray(boxes, np.int32).reshape(-1, 4)), S._up(_exclusive(words))
-        d_bits = S._up(np.concatenate(packed) if len(packed) else np.zeros(4, np.uint8))
-        S.capi.check(S.L.sdsm_shape_objects_multi(S.table, self.n_im, n, S._p(d_image), S._p(d_boxes), S._p(d_off), S._p(d_bits), S._p(B['d_slot_off']),
-                                                  S._p(B['d_slots']), S._p(B['d_out']), S._p(B['d_vert_off']), S._p(B['d_verts']), S._stream()),
-                     'sdsm_shape_objects_multi')
+        d_objects = S.upload_objects(obj_image, boxes, words, packed)
+        S.capi.check(S.L.sdsm_shape_objects_multi(S.table, self.n_im, n, *map(S._p, d_objects), S._p(B['d_slot_off']), S._p(B['d_slots']), S._p(B['d_out']),
+                                                  S._p(B['d_vert_off']), S._p(B['d_verts']), S._stream()), 'sdsm_shape_objects_multi')
         return self._download(B, n)
 
     def labels(self, labels, background_label):
@@ -245,58 +237,10 @@ class _ShapeSet:
         w = _LabelWindows(self.M, labels, background_label, 'shape')
         n = len(w.idx)
         B = self._buffers(w.boxes)
-        S.capi.check(S.L.sdsm_shape_labels_multi(S.table, self.n_im, S._p(w.d_labels), w.c_off, w.c_n, S._p(w.d_label_obj), n, S._p(w.d_image),
-                                                 S._p(w.d_boxes), S._p(w.d_off), w.total, S._p(w.d_bits), S._p(B['d_slot_off']),
-                                                 S._p(B['d_slots']), S._p(B['d_out']), S._p(B['d_vert_off']), S._p(B['d_verts']), S._p(w.d_bad), S._stream()),
-                     'sdsm_shape_labels_multi')
+        S.capi.check(S.L.sdsm_shape_labels_multi(S.table, self.n_im, *w.args(), S._p(B['d_slot_off']), S._p(B['d_slots']), S._p(B['d_out']),
+                                                 S._p(B['d_vert_off']), S._p(B['d_verts']), S._p(w.d_bad), S._stream()), 'sdsm_shape_labels_multi')
         recs, offsets, vertices = self._download(B, n)
         return [(ls, n_labels) + _split(recs, offsets, vertices, a, b) for ls, n_labels, a, b in w.per_image()]
-
-
-class _LabelWindows:
-    """The windows of the labels of a set of label maps (``M``: its ``measure._MeasureSet``), as the label forms of the shape and the
-    intensity tables take them: the boxes of the present labels without ``background_label`` from sdsm_measure_labels (one download),
-    one window of ceil(h w / 32) words per label, and the device arrays that name them.  Raises before any kernel of the caller's is
-    launched where the labels or the windows pass the limits."""
-
-    def __init__(self, M, labels, background_label, what):
-        S = self.S = M.S
-        n_im = self.n_im = len(S.shapes)
-        self.d_labels = S.pack(labels, np.int32)
-        rng = M.label_range(self.d_labels)
-        if (rng[:, 0] < 0).any() or (rng[:, 1] >= _capi.MEASURE_MAX_LABELS).any():
-            raise ValueError(f'labels {rng[:, 0].min()} .. {rng[:, 1].max()}: the {what} tables take the labels 0 .. {_capi.MEASURE_MAX_LABELS - 1}, '
-                             'see DESIGN.md "Limits"')
-        self.n_labels = n_labels = (rng[:, 1] + 1).astype(np.int64)
-        self.rec_off = rec_off = _exclusive(n_labels)
-        self.c_off, self.c_n = (S.C.c_int64 * n_im)(*[int(v) for v in rec_off]), (S.C.c_int32 * n_im)(*[int(v) for v in n_labels])
-        self.d_bad = S.torch.empty(n_im, dtype=S.torch.int32, device=S.dev)
-        d_rec = M.record_buffer(int(n_labels.sum()))
-        S.capi.check(S.L.sdsm_measure_labels_multi(S.table, n_im, S._p(self.d_labels), self.c_off, self.c_n, None, None, None, S._p(d_rec), S._p(self.d_bad),
-                                                   S._stream()), 'sdsm_measure_labels_multi')
-        mrec = M._records(d_rec, int(n_labels.sum()))
-        keep = mrec['area'] > 0
-        if background_label is not None:
-            for i in range(n_im):
-                if 0 <= background_label < n_labels[i]:
-                    keep[rec_off[i] + background_label] = False
-        self.idx = idx = np.nonzero(keep)[0]
-        self.boxes = boxes = np.stack([mrec['r0'][idx], mrec['c0'][idx], mrec['r1'][idx] - mrec['r0'][idx], mrec['c1'][idx] - mrec['c0'][idx]], axis=1).astype(np.int32)
-        self.obj_image = obj_image = (np.searchsorted(rec_off, idx, side='right') - 1).astype(np.int32)
-        words = (boxes[:, 2].astype(np.int64) * boxes[:, 3] + 31) // 32
-        self.total = total = int(words.sum())
-        if total > _capi.SHAPE_MAX_WINDOW_WORDS:                               # (nothing of the caller's kernels has been launched)
-            raise ValueError(f'the windows of the labels take {total} words: the label form of the {what} tables takes up to {_capi.SHAPE_MAX_WINDOW_WORDS} '
-                             'per set, see DESIGN.md "Limits"')
-        label_obj = np.full(int(n_labels.sum()), -1, np.int32)
-        label_obj[idx] = np.arange(len(idx), dtype=np.int32)
-        self.d_bits = S.torch.empty(max(1, total), dtype=S.torch.int32, device=S.dev)
-        self.d_label_obj, self.d_image, self.d_boxes, self.d_off = S._up(label_obj), S._up(obj_image), S._up(boxes.reshape(-1, 4)), S._up(_exclusive(words))
-
-    def per_image(self):
-        """Per image (labels measured, number of labels, first window, end of its windows)."""
-        first = np.searchsorted(self.obj_image, np.arange(self.n_im + 1))
-        return [((self.idx[a:b] - self.rec_off[i]).astype(np.int64), int(self.n_labels[i]), a, b) for i, (a, b) in enumerate(zip(first[:-1], first[1:]))]
 
 
 def _split(recs, offsets, vertices, a, b):
@@ -307,19 +251,9 @@ def _split(recs, offsets, vertices, a, b):
 def shape_objects_many(objects_per_image, shapes):
     """:func:`shape_objects` for a list of images: one launch per ``_capi.MAX_SET_IMAGES`` images (larger lists are split).  Per image the
     bytes of :func:`shape_objects_host`."""
-    objs = [list(o) for o in objects_per_image]
-    shapes = [_check_shape(s) for s in shapes]
-    if len(shapes) != len(objs):
-        raise ValueError('shapes: one per list of objects')
-    for o, s in zip(objs, shapes):
-        _check_boxes(_object_boxes(o), s)
     out = []
-    for part in in_sets(len(objs)):
-        packs = [pack_fragments(o) for o in objs[part]]
-        recs, offsets, vertices = _ShapeSet(shapes[part]).objects(
-            np.concatenate([np.full(len(pk[0]), i, np.int32) for i, pk in enumerate(packs)]), np.concatenate([pk[0] for pk in packs]),
-            np.concatenate([pk[1] for pk in packs]), [b for pk in packs for b in pk[2]])
-        first = np.concatenate([[0], np.cumsum([len(pk[0]) for pk in packs])])
+    for _, shapes_part, _, packed, first in _object_sets(objects_per_image, shapes):
+        recs, offsets, vertices = _ShapeSet(shapes_part).objects(*packed)
         for a, b in zip(first[:-1], first[1:]):
             r, o, v = _split(recs, offsets, vertices, a, b)
             out.append((_table(np.arange(b - a), r), o, v))
@@ -334,17 +268,14 @@ def shape_objects(objects, shape):
 
 def shape_labels_many(labels_list, background_label=0, keep_absent=False):
     """:func:`shape_labels` for a list of label maps, one launch per ``_capi.MAX_SET_IMAGES`` images."""
-    from .render import _int32_labels
-    l32 = [_int32_labels(_check_labels(l)) for l in labels_list]
     out = []
-    for part in in_sets(len(l32)):
-        for ls, n_labels, recs, offsets, vertices in _ShapeSet([l.shape for l in l32[part]]).labels(l32[part], background_label):
+    for _, l32, shapes, _ in _label_sets(labels_list):
+        for ls, n_labels, recs, offsets, vertices in _ShapeSet(shapes).labels(l32, background_label):
             if keep_absent:
-                full = np.zeros(n_labels, _capi.SHAPE_RECORD_DTYPE)
-                full[ls] = recs
                 counts = np.zeros(n_labels, np.int64)
                 counts[ls] = np.diff(offsets)
-                ls, recs, offsets = np.arange(n_labels), full, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+                offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+                ls, recs = _keep_absent(np.zeros(n_labels, _capi.SHAPE_RECORD_DTYPE), ls, recs)
             out.append((_table(ls, recs), offsets, vertices))
     return out
 
@@ -358,5 +289,4 @@ def shape_labels(labels, background_label=0, keep_absent=False):
 
 def shape_result(data, objects='postprocessed_objects'):
     """The shape table of the objects of pipeline data: ``objects`` an output name or a list of objects."""
-    objs = list(data[objects]) if isinstance(objects, str) else list(objects)
-    return shape_objects(objs, data['g_raw'].shape)
+    return shape_objects(*_result_inputs(data, objects)[:2])

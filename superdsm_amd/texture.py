@@ -30,14 +30,14 @@ A result is ``(table, pairs, entries)``:
 Parity with scikit-image's ``graycoprops``, mahotas' ``haralick`` and CellProfiler's ``MeasureTexture`` is NOT pinned: none of them is
 available to the tests (DESIGN.md section 8 lists the known differences)."""
 import csv
+from functools import partial
 
 import numpy as np
 
 from . import _capi
-from .imageset import in_sets
-from .measure import _check_labels, _check_shape, _label_count, _object_boxes
-from .intensity import _require_intensity, _intensities
-from .postprocess import _check_boxes, _exclusive, pack_fragments
+from .measure import (_check_labels, _check_shape, _keep_absent, _label_count, _label_sets, _label_table, _LabelWindows, _MeasureSet, _object_boxes,
+                      _object_sets, _require_intensity, _result_inputs)
+from .postprocess import _check_boxes, _exclusive
 
 TABLE_DTYPE = np.dtype([('label', 'i4')] + _capi._TEXTURE_FIELDS)   # 'label': the label, or the index of the object in its image
 PAIRS_DTYPE = _capi.TEXTURE_PAIRS_DTYPE
@@ -156,12 +156,7 @@ def _fill(rec, frag, r0, c0, shape, g, edges, offs):
     return out
 
 
-def _table(labels, recs):
-    table = np.zeros(len(recs), TABLE_DTYPE)
-    table['label'] = labels
-    for name in _capi.TEXTURE_RECORD_DTYPE.names:
-        table[name] = recs[name]
-    return table
+_table = partial(_label_table, TABLE_DTYPE)                         # _table(labels, recs)
 
 
 def _assemble(labels, recs, cells, n_o):
@@ -408,7 +403,6 @@ class _TextureSet:
     texture kernels."""
 
     def __init__(self, shapes, intensities, edges_list, offs):
-        from .measure import _MeasureSet
         self.M = _MeasureSet(shapes, intensities)     # (the intensities packed; the label form takes the boxes of the labels from there)
         self.S = S = self.M.S
         self.n_im = len(S.shapes)
@@ -436,8 +430,8 @@ class _TextureSet:
                     d_slots=u8(slots * ENTRY_DTYPE.itemsize), d_entries=u8(slots * ENTRY_DTYPE.itemsize))
 
     def _download(self, B, n):
-        recs = B['d_out'].cpu().numpy()[:n * _capi.TEXTURE_RECORD_DTYPE.itemsize].view(_capi.TEXTURE_RECORD_DTYPE).copy()
-        pairs = B['d_pairs'].cpu().numpy()[:n * self.n_o * PAIRS_DTYPE.itemsize].view(PAIRS_DTYPE).reshape(n, self.n_o).copy()
+        recs = self.S.records(B['d_out'], n, _capi.TEXTURE_RECORD_DTYPE)
+        pairs = self.S.records(B['d_pairs'], n * self.n_o, PAIRS_DTYPE).reshape(n, self.n_o)
         total = int(pairs['n_entries'].sum())                                      # (only the cells that exist are downloaded)
         entries = B['d_entries'][:total * ENTRY_DTYPE.itemsize].cpu().numpy().view(ENTRY_DTYPE).copy()
         return recs, pairs, entries
@@ -447,28 +441,24 @@ class _TextureSet:
         S, n = self.S, len(boxes)
         slot_off = self.slot_offsets(boxes)
         B = self.buffers(n, int(slot_off[-1])) if B is None else B
-        d_image, d_boxes, d_off = S._up(np.asarray(obj_image, np.int32)), S._up(np.asarray(boxes, np.int32).reshape(-1, 4)), S._up(_exclusive(words))
-        d_bits = S._up(np.concatenate(packed) if len(packed) else np.zeros(4, np.uint8))
-        d_slot_off = S._up(slot_off)
-        S.capi.check(S.L.sdsm_texture_objects_multi(S.table, self.n_im, n, S._p(d_image), S._p(d_boxes), S._p(d_off), S._p(d_bits), S._p(self.M.d_g), self.levels,
-                                                    S._p(self.d_edges), self.n_o, self.c_offsets, S._p(d_slot_off), S._p(B['d_slots']), S._p(B['d_out']),
-                                                    S._p(B['d_pairs']), S._p(B['d_entries']), S._stream()), 'sdsm_texture_objects_multi')
+        d_objects, d_slot_off = S.upload_objects(obj_image, boxes, words, packed), S._up(slot_off)
+        S.capi.check(S.L.sdsm_texture_objects_multi(S.table, self.n_im, n, *map(S._p, d_objects), S._p(self.M.d_g), self.levels, S._p(self.d_edges), self.n_o,
+                                                    self.c_offsets, S._p(d_slot_off), S._p(B['d_slots']), S._p(B['d_out']), S._p(B['d_pairs']),
+                                                    S._p(B['d_entries']), S._stream()), 'sdsm_texture_objects_multi')
         return self._download(B, n)
 
     def labels(self, labels, background_label):
         """Per image (labels measured, number of labels, records, pairs, entries) of the label maps of the set: the windows of the labels
-        as the shape tables size them (``shape._LabelWindows``), then sdsm_texture_labels."""
-        from .shape import _LabelWindows
+        (``measure._LabelWindows``), then sdsm_texture_labels."""
         S = self.S
         w = _LabelWindows(self.M, labels, background_label, 'texture')
         n = len(w.idx)
         slot_off = self.slot_offsets(w.boxes)
         B = self.buffers(n, int(slot_off[-1]))
         d_slot_off = S._up(slot_off)
-        S.capi.check(S.L.sdsm_texture_labels_multi(S.table, self.n_im, S._p(w.d_labels), w.c_off, w.c_n, S._p(w.d_label_obj), n, S._p(w.d_image), S._p(w.d_boxes),
-                                                   S._p(w.d_off), w.total, S._p(w.d_bits), S._p(self.M.d_g), self.levels, S._p(self.d_edges), self.n_o,
-                                                   self.c_offsets, S._p(d_slot_off), S._p(B['d_slots']), S._p(B['d_out']), S._p(B['d_pairs']),
-                                                   S._p(B['d_entries']), S._p(w.d_bad), S._stream()), 'sdsm_texture_labels_multi')
+        S.capi.check(S.L.sdsm_texture_labels_multi(S.table, self.n_im, *w.args(), S._p(self.M.d_g), self.levels, S._p(self.d_edges), self.n_o, self.c_offsets,
+                                                   S._p(d_slot_off), S._p(B['d_slots']), S._p(B['d_out']), S._p(B['d_pairs']), S._p(B['d_entries']),
+                                                   S._p(w.d_bad), S._stream()), 'sdsm_texture_labels_multi')
         recs, pairs, entries = self._download(B, n)
         return [(ls, n_labels) + _split(recs, pairs, entries, a, b) for ls, n_labels, a, b in w.per_image()]
 
@@ -484,21 +474,12 @@ def _split(recs, pairs, entries, a, b):
 def texture_objects_many(objects_per_image, shapes, intensities, edges_list, offsets=DEFAULT_OFFSETS):
     """:func:`texture_objects` for a list of images with one list of edges per image (all of the same length): one launch per
     ``_capi.MAX_SET_IMAGES`` images (larger lists are split).  Per image the bytes of :func:`texture_objects_host`."""
-    objs = [list(o) for o in objects_per_image]
-    shapes = [_check_shape(s) for s in shapes]
-    if len(shapes) != len(objs):
-        raise ValueError('shapes: one per list of objects')
-    for o, s in zip(objs, shapes):
-        _check_boxes(_object_boxes(o), s)
-    gs = _intensities(intensities, shapes)
-    edges_list, offs = _edges_many(edges_list, len(shapes)), check_offsets(offsets)
+    objects_per_image = list(objects_per_image)
+    sets = _object_sets(objects_per_image, shapes, intensities, required=True)
+    edges_list, offs = _edges_many(edges_list, len(objects_per_image)), check_offsets(offsets)
     out = []
-    for part in in_sets(len(objs)):
-        packs = [pack_fragments(o) for o in objs[part]]
-        recs, pairs, entries = _TextureSet(shapes[part], gs[part], edges_list[part], offs).objects(
-            np.concatenate([np.full(len(pk[0]), i, np.int32) for i, pk in enumerate(packs)]), np.concatenate([pk[0] for pk in packs]),
-            np.concatenate([pk[1] for pk in packs]), [b for pk in packs for b in pk[2]])
-        first = np.concatenate([[0], np.cumsum([len(pk[0]) for pk in packs])])
+    for part, shapes_part, gs, packed, first in sets:
+        recs, pairs, entries = _TextureSet(shapes_part, gs, edges_list[part], offs).objects(*packed)
         for a, b in zip(first[:-1], first[1:]):
             r, p, e = _split(recs, pairs, entries, a, b)
             out.append((_table(np.arange(b - a), r), p, e))
@@ -514,20 +495,18 @@ def texture_objects(objects, shape, intensity, edges, offsets=DEFAULT_OFFSETS):
 
 def texture_labels_many(labels_list, intensities, edges_list, offsets=DEFAULT_OFFSETS, background_label=0, keep_absent=False):
     """:func:`texture_labels` for a list of label maps with one list of edges per image, one launch per ``_capi.MAX_SET_IMAGES`` images."""
-    from .render import _int32_labels
-    labels_list = [_check_labels(l) for l in labels_list]
-    gs = _intensities(intensities, [l.shape for l in labels_list])
+    labels_list = list(labels_list)
+    sets = _label_sets(labels_list, intensities, required=True)
     edges_list, offs = _edges_many(edges_list, len(labels_list)), check_offsets(offsets)
-    l32 = [_int32_labels(l) for l in labels_list]
     out = []
-    for part in in_sets(len(l32)):
-        T = _TextureSet([l.shape for l in l32[part]], gs[part], edges_list[part], offs)
-        for ls, n_labels, recs, pairs, entries in T.labels(l32[part], background_label):
+    for part, l32, shapes, gs in sets:
+        T = _TextureSet(shapes, gs, edges_list[part], offs)
+        for ls, n_labels, recs, pairs, entries in T.labels(l32, background_label):
             if keep_absent:
-                full, full_pairs = _empty_records(n_labels, T.levels), np.zeros((n_labels, len(offs)), PAIRS_DTYPE)
-                full[ls], full_pairs[ls] = recs, pairs
+                full_pairs = np.zeros((n_labels, len(offs)), PAIRS_DTYPE)
+                full_pairs[ls] = pairs
                 full_pairs['first'] = _exclusive(full_pairs['n_entries'].reshape(-1)).reshape(full_pairs.shape)
-                ls, recs, pairs = np.arange(n_labels), full, full_pairs
+                (ls, recs), pairs = _keep_absent(_empty_records(n_labels, T.levels), ls, recs), full_pairs
             out.append((_table(ls, recs), pairs, entries))
     return out
 
@@ -542,6 +521,5 @@ def texture_labels(labels, intensity, edges, offsets=DEFAULT_OFFSETS, background
 def texture_result(data, objects='postprocessed_objects', intensity='g_raw', levels=DEFAULT_LEVELS, offsets=DEFAULT_OFFSETS, edges=None):
     """The texture table of the objects of pipeline data: ``objects`` an output name or a list of objects, ``intensity`` a key of ``data``
     or an image; ``levels`` equally wide levels over the finite range of that image (:func:`image_edges`), or the caller's ``edges``."""
-    objs = list(data[objects]) if isinstance(objects, str) else list(objects)
-    g = data[intensity] if isinstance(intensity, str) else intensity
-    return texture_objects(objs, data['g_raw'].shape, g, image_edges(g, levels) if edges is None else edges, offsets)
+    objs, shape, g = _result_inputs(data, objects, intensity)
+    return texture_objects(objs, shape, g, image_edges(g, levels) if edges is None else edges, offsets)

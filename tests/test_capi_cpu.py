@@ -116,6 +116,76 @@ def test_scheduling_policy_of_a_plan_is_host_logic():
     lib.sdsm_plan_destroy(plan)
 
 
+_N_AND_WINDOW = b'n >= 0 and 0 <= window_words <= SDSM_SHAPE_MAX_WINDOW_WORDS required'
+_TEXTURE_N = b'0 <= n <= (2^31 - 1) / 8 required'
+# entry (the text of its messages names it without "_multi"): what n = -1 says and, for a label form, what window_words = -1 says
+_TABLE_ENTRIES = {'sdsm_measure_objects': (b'n < 0', None), 'sdsm_shape_objects': (b'n < 0', None), 'sdsm_shape_labels': (_N_AND_WINDOW, _N_AND_WINDOW),
+                  'sdsm_intensity_objects': (b'n < 0', None), 'sdsm_intensity_labels': (_N_AND_WINDOW, _N_AND_WINDOW),
+                  'sdsm_texture_objects': (_TEXTURE_N, None),
+                  'sdsm_texture_labels': (_TEXTURE_N, b'0 <= window_words <= SDSM_SHAPE_MAX_WINDOW_WORDS required'),
+                  'sdsm_depth_objects': (b'n < 0', None), 'sdsm_depth_labels': (_N_AND_WINDOW, _N_AND_WINDOW)}
+
+
+def _table_entry_arguments(entry, keep):
+    """The complete argument list of ``<entry>_multi`` for one 8 x 8 image and n = 1 with one small host buffer as every pointer, and the
+    positions of n, of window_words (None for an object form) and of every pointer the entry cannot do without.  ``keep`` holds the
+    buffers alive."""
+    from superdsm_amd import _capi
+    buf = np.zeros(64, np.int64)
+    one_i64, one_i32, two_i32 = (C.c_int64 * 1)(0), (C.c_int32 * 1)(1), (C.c_int32 * 1)(2)
+    offsets = (C.c_int32 * 2)(0, 1)
+    table = (_capi.SetImage * 1)()
+    table[0].offset, table[0].H, table[0].W = 0, 8, 8
+    keep += [buf, one_i64, one_i32, two_i32, offsets, table]
+    need, free = (C.c_void_p(buf.ctypes.data), True), (C.c_void_p(buf.ctypes.data), False)
+    args = [(table, False), (1, False)]
+    if entry.endswith('_labels'):       # d_labels, rec_off, n_labels, d_label_obj, n, d_obj_image, d_boxes, d_bits_off, window_words, d_bits
+        args += [need, (one_i64, True), (one_i32, True), need, (1, False), free, need, need, (1, False), need]
+        at_n, at_words = 6, 10
+    else:                               # n, d_obj_image, d_boxes, d_bits_off, d_bits
+        args += [(1, False), free, need, need, need]
+        at_n, at_words = 2, None
+    family = entry.split('_')[1]
+    if family == 'measure':             # d_g, d_gmax_abs, d_scale_exp, d_out
+        args += [free, free, free, need]
+    elif family == 'shape':             # d_slot_off, d_slots, d_out, d_vert_off, d_verts
+        args += [need] * 5
+    elif family == 'intensity':         # d_g, n_q, num, den, d_out, d_order
+        args += [need, (1, False), (one_i32, False), (two_i32, False), need, need]
+    elif family == 'texture':           # d_g, levels, d_edges, n_offsets, offsets, d_slot_off, d_slots, d_out, d_pairs, d_entries
+        args += [need, (2, False), need, (1, False), (offsets, False)] + [need] * 5
+    else:                               # d_g, d_gmax_abs, d_scale_exp, n_shells, d_ws_off, d_ws, ws_pixels, ws_bytes, d_out, d_shells
+        args += [free, free, free, (4, False), (None, False), (None, False), (0, False), (0, False), need, need]
+    if entry.endswith('_labels'):
+        args.append(need)               # d_bad
+    args.append((None, False))          # stream
+    return [a for a, _ in args], at_n, at_words, [k for k, (_, required) in enumerate(args) if required]
+
+
+@pytest.mark.parametrize('entry', sorted(_TABLE_ENTRIES))
+def test_the_table_entries_check_their_arguments(entry):
+    """The ``*_multi`` forms of the nine entries that take packed objects or label windows: the complete argument list passes every
+    argument check (without a GPU the call then fails in HIP), every required pointer omitted alone is a null argument, n = -1 and
+    window_words = -1 are argument errors; every message names the entry."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip('a GPU is present: the complete list would launch kernels on host pointers')
+    from superdsm_amd import _capi
+    lib, keep = _capi.lib(), []
+    call = getattr(lib, entry + '_multi')
+    args, at_n, at_words, required = _table_entry_arguments(entry, keep)
+    n_pointers = {'measure': 4, 'shape': 8, 'intensity': 6, 'texture': 10, 'depth': 5}[entry.split('_')[1]] + (5 if entry.endswith('_labels') else 0)
+    assert len(required) == n_pointers
+    assert call(*args) == -2 and b'no ROCm-capable device' in lib.sdsm_last_error(), lib.sdsm_last_error()
+    for k in required:
+        assert call(*args[:k], None, *args[k + 1:]) == -1, (entry, k)
+        assert lib.sdsm_last_error() == entry.encode() + b': null argument', (entry, k, lib.sdsm_last_error())
+    text_n, text_words = _TABLE_ENTRIES[entry]
+    assert call(*args[:at_n], -1, *args[at_n + 1:]) == -1 and lib.sdsm_last_error() == entry.encode() + b': ' + text_n, lib.sdsm_last_error()
+    if at_words is not None:
+        assert call(*args[:at_words], -1, *args[at_words + 1:]) == -1 and lib.sdsm_last_error() == entry.encode() + b': ' + text_words, lib.sdsm_last_error()
+
+
 def test_compute_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

@@ -253,6 +253,37 @@ def test_sets_equal_the_per_image_calls_and_overlapping_objects_are_measured_alo
         same(m, dp.depth_labels_host(lab, g, 6), 'label set against host')
 
 
+def test_a_list_of_33_images_is_split_into_two_sets_and_every_image_equals_the_host(gpu):
+    """One image more than a set holds (``_capi.MAX_SET_IMAGES`` = 32): the last image is a set of its own, and the objects and labels of
+    every image are those of its own place in the list.  8 x 8 images with one small object, or a few labels, each; image 5 has no
+    object and label map 7 no label."""
+    from superdsm_amd import _capi, depth as dp
+    rng = np.random.default_rng(33)
+    n = _capi.MAX_SET_IMAGES + 1
+    assert n == 33
+    shapes = [(8, 8)] * n
+    gs = [rng.normal(size=s) for s in shapes]
+    per_image = [[Obj((rng.integers(0, 4), rng.integers(0, 4)), np.ones((rng.integers(2, 5), rng.integers(2, 5)), bool))] for _ in range(n)]
+    per_image[5] = []
+    many = dp.depth_objects_many(per_image, shapes, gs, 3)
+    assert len(many) == n and [len(m[0]) for m in many] == [len(o) for o in per_image]
+    for i, (objs, g, m) in enumerate(zip(per_image, gs, many)):
+        same(m, dp.depth_objects_host(objs, (8, 8), g, 3), f'objects of image {i}')
+    maps = []
+    for i in range(n):
+        lab = np.zeros((8, 8), np.int32)
+        for l in range(1, 2 + i % 3):                                        # 1 .. 3 labels, later ones over earlier ones
+            r0, c0 = rng.integers(0, 6, size=2)
+            lab[r0:r0 + 3, c0:c0 + 3] = l
+        maps.append(lab)
+    maps[7][:] = 0
+    many = dp.depth_labels_many(maps, gs, 3)
+    assert len(many) == n
+    for i, (lab, g, m) in enumerate(zip(maps, gs, many)):
+        same(m, dp.depth_labels_host(lab, g, 3), f'labels of image {i}')
+    same(dp.depth_labels_many(maps[-2:], None, 3, keep_absent=True)[1], dp.depth_labels_host(maps[-1], None, 3, keep_absent=True), 'absent labels kept')
+
+
 def test_labels_scene_touching_out_of_range_and_absent(gpu):
     from superdsm_amd import depth as dp
     rng = np.random.default_rng(42)
@@ -276,7 +307,7 @@ def test_labels_scene_touching_out_of_range_and_absent(gpu):
 def test_a_label_outside_the_range_is_counted_and_skipped(gpu):
     """The raw label call with n_labels below the highest label: its pixels are counted in d_bad and belong to no window."""
     from superdsm_amd import depth as dp
-    from superdsm_amd.shape import _LabelWindows
+    from superdsm_amd.measure import _LabelWindows
     labels = np.zeros((12, 12), np.int32)
     labels[1:6, 1:6], labels[7:11, 2:9] = 1, 2
     host = dp.depth_labels_host(labels, None, 4)
