@@ -228,6 +228,7 @@ template <class L> __device__ __forceinline__ double *hess_ptr(const Cand &c) { 
 // the next tickets as soon as any compute unit frees up.  K group launches in flight (streams, processes) can hold at most
 // 7 K compute units in incomplete groups, so with K < 36 on 256 compute units somebody always progresses.
 #define WIDE_PHASE (reinterpret_cast<int *>(SD + L::FLAG) + 2)   // all-reduces done so far (LDS, uniform)
+#define WIDE_ERR (reinterpret_cast<int *>(SD + L::FLAG) + 1)     // the group's error word as thread 0 read it at the last rendezvous (the slot is factor_solve's second panel flag: no rendezvous inside a factorisation)
 
 template <class L>
 __device__ __forceinline__ bool wide_barrier(const Cand &c, int phase0)
@@ -240,20 +241,29 @@ __device__ __forceinline__ bool wide_barrier(const Cand &c, int phase0)
         __hip_atomic_fetch_add(&sync[0], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
         const int target = phase * c.wG;
         const long long t0 = wall_clock64();
+        int err = 0;
         while (__hip_atomic_load(&sync[0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < target) {
-            if (__hip_atomic_load(&sync[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-            if (wall_clock64() - t0 > c.wtimeout) { __hip_atomic_store(&sync[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }   // constant 100 MHz clock; default 50 ms
+            if ((err = __hip_atomic_load(&sync[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0) break;
+            if (wall_clock64() - t0 > c.wtimeout) { __hip_atomic_store(&sync[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); err = 1; break; }   // constant 100 MHz clock; default 50 ms
             __builtin_amdgcn_s_sleep(8);
         }
+        // The error word as this lane saw it last (one more read after the loop: a partner may have given up while the last one arrived)
+        // goes to the workgroup through LDS: one global round trip of one lane instead of one of every thread after the rendezvous.
+        if (err == 0) err = __hip_atomic_load(&sync[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *WIDE_ERR = err;
     }
     __syncthreads();
-    return __hip_atomic_load(&sync[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
+    return *WIDE_ERR == 0;                                   // (read by everybody before thread 0 passes the first barrier of the next call)
 }
 
 // One exchange of a workgroup group.  Publication slots alternate per OPERATION (WIDE_OPS): a member can be at most one operation
 // ahead of the slowest one.  A member's block of a slot: [0, WIDE_F0) integer payload, [WIDE_F0] number of psi-type sums that follow.
 #define WIDE_OPS (reinterpret_cast<int *>(SD + L::FLAG) + 3)
 #define WIDE_RS_MIN 512
+#ifndef WIDE_DIRECT_MAX_G
+#define WIDE_DIRECT_MAX_G 3        // largest group that adds long vectors directly (0: reduce-scatter + all-gather for every group)
+#endif
+static_assert(WIDE_DIRECT_MAX_G >= 0 && WIDE_DIRECT_MAX_G <= 8, "a group has at most 8 members");
 #define WIDE_F0 (SDSM_WIDE_PBUF - SDSM_WIDE_FCAP)
 template <class L>
 __device__ __forceinline__ double *wide_mine(const Cand &c)
@@ -284,11 +294,22 @@ __device__ __forceinline__ bool wide_finish(const Cand &c, double (&tot)[K], dou
     bool ok = wide_barrier<L>(c, phase);
     if (tid == 0) *WIDE_OPS = ops + 1;                           // (everybody read it before the barrier above)
     const int nt = n0 + n1 + n2;
-    if (nt < WIDE_RS_MIN) {
-        for (int e = tid; e < nt; e += L::WGS) {
-            u64 v = 0;
-            for (int m = 0; m < c.wG; m++) v += slot[(size_t)m * SDSM_WIDE_PBUF + e];
-            if (e < n0) b0[e] = v; else if (e < n0 + n1) b1[e - n0] = v; else b2[e - n0 - n1] = v;
+    // Short vectors, and groups of at most WIDE_DIRECT_MAX_G members whatever the length: every member adds the wG published blocks over
+    // the whole vector itself -- one rendezvous; the reduce-scatter's second one only pays for larger groups.  The choice depends on nt (the
+    // candidate's sizes) and c.wG alone, which are the same on every member: every member makes the same number of wide_barrier calls and the
+    // phase counters stay in step.  Integer sums: the totals are the same bits either way.
+    if (nt < WIDE_RS_MIN || c.wG <= WIDE_DIRECT_MAX_G) {
+        for (int e0 = tid; e0 < nt; e0 += 4 * L::WGS) {          // (four entries per thread in flight: the loads are requested before the first store)
+            u64 v[4] = {0, 0, 0, 0};
+            for (int m = 0; m < c.wG; m++) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) { const int e = e0 + k * L::WGS; v[k] += e < nt ? slot[(size_t)m * SDSM_WIDE_PBUF + e] : 0; }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int e = e0 + k * L::WGS;
+                if (e < nt) { if (e < n0) b0[e] = v[k]; else if (e < n0 + n1) b1[e - n0] = v[k]; else b2[e - n0 - n1] = v[k]; }
+            }
         }
     } else {
         const int chunk = (((nt + c.wG - 1) / c.wG) + 7) & ~7;
