@@ -271,6 +271,37 @@ __device__ __forceinline__ double *wide_mine(const Cand &c)
     return c.wpool + SDSM_WIDE_SYNC + (size_t)(*WIDE_OPS & 1) * c.wG * SDSM_WIDE_PBUF + (size_t)c.wg * SDSM_WIDE_PBUF;
 }
 
+// Adds the other members' published words to v: pair k is words e[k], e[k] + 1 (e[k] even) of every block of the slot.  All loads of the
+// batch -- KB pairs of up to OPR other members, 16 bytes each -- are requested before the first add; a group with more than OPR other
+// members takes further rounds.  Integer addition: any order gives the same bits.
+#define WIDE_XB 4                  // pairs a thread has in flight per other member: direct path and all-gather (8 entries x (g - 1) loads)
+#define WIDE_RB 2                  // the same in the reduce-scatter, where up to 7 other members are read at once
+typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+typedef const u64x2 SDSM_GLOBAL *g_cu64x2_p;
+template <int KB, int OPR>
+__device__ __forceinline__ void wide_gather_add(g_cu64x2_p slot, int wg, int wG, const int (&e)[KB], const bool (&in)[KB], u64x2 (&v)[KB])
+{
+    for (int o0 = 0; o0 < wG - 1; o0 += OPR) {
+        u64x2 t[OPR][KB];
+#pragma unroll
+        for (int j = 0; j < OPR; j++) {
+            const int o = o0 + j, m = o < wg ? o : o + 1;    // the o-th member that is not this one
+#pragma unroll
+            for (int k = 0; k < KB; k++) {
+                t[j][k].x = 0; t[j][k].y = 0;
+                if (o < wG - 1 && in[k]) t[j][k] = slot[((size_t)m * SDSM_WIDE_PBUF + e[k]) >> 1];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < OPR; j++) {
+#pragma unroll
+            for (int k = 0; k < KB; k++) { v[k].x += t[j][k].x; v[k].y += t[j][k].y; }
+        }
+    }
+}
+static_assert(SDSM_WIDE_PBUF % 2 == 0 && SDSM_WIDE_SYNC % 2 == 0 && (SDSM_WIDE_PBUF - SDSM_WIDE_FCAP) % 2 == 0, "the blocks of a slot start at multiples of 16 bytes");
+static_assert(SDSM_K2B_EMAX + SDSM_MAX_N_SOLVE + 42 < SDSM_WIDE_PBUF - SDSM_WIDE_FCAP, "the word after an odd-length vector is still payload");
+
 // Completes the exchange: (i) up to three arrays of FIXED-POINT sums (raw 64-bit integers, in LDS or global memory) are all-reduced in
 // place by integer addition -- order-free, so the totals do not depend on the number of members; long vectors (the Hessian envelope:
 // ~10 k entries) as reduce-scatter + all-gather: member g adds the wG partials of ITS share of the entries and leaves the totals in its
@@ -288,52 +319,86 @@ __device__ __forceinline__ bool wide_finish(const Cand &c, double (&tot)[K], dou
     u64 *mine = slot + (size_t)c.wg * SDSM_WIDE_PBUF;
     u64 *b0 = reinterpret_cast<u64 *>(a0), *b1 = reinterpret_cast<u64 *>(a1), *b2 = reinterpret_cast<u64 *>(a2);
     const int tid = threadIdx.x;
-    for (int e = tid; e < n0; e += L::WGS) mine[e] = b0[e];
-    for (int e = tid; e < n1; e += L::WGS) mine[n0 + e] = b1[e];
-    for (int e = tid; e < n2; e += L::WGS) mine[n0 + n1 + e] = b2[e];
+    const int nt = n0 + n1 + n2, n01 = n0 + n1;
+    // Word e of the concatenated vector (a0 | a1 | a2) as this member holds it; 0 beyond its end.  A lane owns the PAIR (e, e + 1), e even:
+    // the blocks of a slot start at multiples of 16 bytes, so a pair moves to and from global memory as one 16-byte access.
+    // (one address select and one access per word, no branch per array)
+    auto at = [&](int e) -> u64 * { return e < n0 ? b0 + e : e < n01 ? b1 + (e - n0) : b2 + (e - n01); };
+    auto rd = [&](int e) -> u64 { const u64 w = *at(e < nt ? e : nt - 1); return e < nt ? w : 0ull; };   // (only called with nt > 0)
+    auto wr = [&](int e, u64 v) { if (e < nt) *at(e) = v; };
+    u64x2 SDSM_GLOBAL *gmine = (u64x2 SDSM_GLOBAL *)mine;
+    for (int e = 2 * tid; e < nt; e += 2 * L::WGS) { u64x2 v; v.x = rd(e); v.y = rd(e + 1); gmine[e >> 1] = v; }
     bool ok = wide_barrier<L>(c, phase);
     if (tid == 0) *WIDE_OPS = ops + 1;                           // (everybody read it before the barrier above)
-    const int nt = n0 + n1 + n2;
+    const g_cu64x2_p gslot = (g_cu64x2_p)slot;
     // Short vectors, and groups of at most WIDE_DIRECT_MAX_G members whatever the length: every member adds the wG published blocks over
     // the whole vector itself -- one rendezvous; the reduce-scatter's second one only pays for larger groups.  The choice depends on nt (the
     // candidate's sizes) and c.wG alone, which are the same on every member: every member makes the same number of wide_barrier calls and the
     // phase counters stay in step.  Integer sums: the totals are the same bits either way.
+    // The blocks of the OTHER members lie in memory another die wrote: every load is a far round trip.  A thread requests all of them for a
+    // batch of pairs before it uses the first (wide_gather_add); its own partials never left LDS and are taken from there.
     if (nt < WIDE_RS_MIN || c.wG <= WIDE_DIRECT_MAX_G) {
-        for (int e0 = tid; e0 < nt; e0 += 4 * L::WGS) {          // (four entries per thread in flight: the loads are requested before the first store)
-            u64 v[4] = {0, 0, 0, 0};
-            for (int m = 0; m < c.wG; m++) {
+        for (int q0 = tid; 2 * q0 < nt; q0 += WIDE_XB * L::WGS) {
+            int e[WIDE_XB]; bool in[WIDE_XB]; u64x2 v[WIDE_XB];
 #pragma unroll
-                for (int k = 0; k < 4; k++) { const int e = e0 + k * L::WGS; v[k] += e < nt ? slot[(size_t)m * SDSM_WIDE_PBUF + e] : 0; }
-            }
+            for (int k = 0; k < WIDE_XB; k++) { e[k] = 2 * (q0 + k * L::WGS); in[k] = e[k] < nt; v[k].x = rd(e[k]); v[k].y = rd(e[k] + 1); }
+            wide_gather_add<WIDE_XB, (WIDE_DIRECT_MAX_G > 2 ? WIDE_DIRECT_MAX_G - 1 : 2)>(gslot, c.wg, c.wG, e, in, v);   // (short vectors of larger groups: further rounds)
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int e = e0 + k * L::WGS;
-                if (e < nt) { if (e < n0) b0[e] = v[k]; else if (e < n0 + n1) b1[e - n0] = v[k]; else b2[e - n0 - n1] = v[k]; }
-            }
+            for (int k = 0; k < WIDE_XB; k++) { wr(e[k], v[k].x); wr(e[k] + 1, v[k].y); }
         }
     } else {
-        const int chunk = (((nt + c.wG - 1) / c.wG) + 7) & ~7;
+        const int chunk = (((nt + c.wG - 1) / c.wG) + 7) & ~7;   // (even: a pair never straddles two shares)
         const int lo = c.wg * chunk, hi = lo + chunk < nt ? lo + chunk : nt;
-        for (int e = lo + tid; e < hi; e += L::WGS) {
-            u64 v = 0;
-            for (int m = 0; m < c.wG; m++) v += slot[(size_t)m * SDSM_WIDE_PBUF + e];
-            mine[e] = v;
+        for (int q0 = tid; lo + 2 * q0 < hi; q0 += WIDE_RB * L::WGS) {
+            int e[WIDE_RB]; bool in[WIDE_RB]; u64x2 v[WIDE_RB];
+#pragma unroll
+            for (int k = 0; k < WIDE_RB; k++) { e[k] = lo + 2 * (q0 + k * L::WGS); in[k] = e[k] < hi; v[k].x = in[k] ? rd(e[k]) : 0ull; v[k].y = in[k] ? rd(e[k] + 1) : 0ull; }
+            wide_gather_add<WIDE_RB, SDSM_WIDE_MAX_G - 1>(gslot, c.wg, c.wG, e, in, v);
+#pragma unroll
+            for (int k = 0; k < WIDE_RB; k++) if (in[k]) gmine[e[k] >> 1] = v[k];
         }
         ok = wide_barrier<L>(c, phase + 1) && ok;
-        for (int e = tid; e < nt; e += L::WGS) {
-            const u64 v = slot[(size_t)(e / chunk) * SDSM_WIDE_PBUF + e];
-            if (e < n0) b0[e] = v; else if (e < n0 + n1) b1[e - n0] = v; else b2[e - n0 - n1] = v;
+        for (int q0 = tid; 2 * q0 < nt; q0 += WIDE_XB * L::WGS) {
+            u64x2 v[WIDE_XB];
+#pragma unroll
+            for (int k = 0; k < WIDE_XB; k++) {
+                const int e = 2 * (q0 + k * L::WGS);
+                v[k].x = 0; v[k].y = 0;
+                if (e < nt) v[k] = gslot[((size_t)(e / chunk) * SDSM_WIDE_PBUF + e) >> 1];
+            }
+#pragma unroll
+            for (int k = 0; k < WIDE_XB; k++) { const int e = 2 * (q0 + k * L::WGS); wr(e, v[k].x); wr(e + 1, v[k].y); }
         }
     }
+    // psi-type sums.  Every wavefront for itself, without a barrier: the counts of all members first (one round trip), then lane l fetches
+    // value i0 + l of the concatenation of the members' lists (one round trip per 64 values), then the values are added one by one in that
+    // order, handed from lane to lane: tot[k] takes the values i = k (mod K), member after member and position after position as before.
+    static_assert(64 % K == 0 && (SDSM_WIDE_FCAP - 8) % K == 0, "a batch of 64 values holds whole K-tuples");
+    const g_cdouble_p gf = (g_cdouble_p)slotd + WIDE_F0;
     double run[K];
 #pragma unroll
     for (int k = 0; k < K; k++) run[k] = 0;
-    for (int m = 0; m < c.wG; m++) {
-        const double *f = slotd + (size_t)m * SDSM_WIDE_PBUF + WIDE_F0;
-        const int nf = (int)f[0];
-        for (int j = 0; j < nf; j++) {
+    double nfd[SDSM_WIDE_MAX_G];
 #pragma unroll
-            for (int k = 0; k < K; k++) run[k] += f[1 + j * K + k];
+    for (int m = 0; m < SDSM_WIDE_MAX_G; m++) { nfd[m] = 0; if (m < c.wG) nfd[m] = gf[(size_t)m * SDSM_WIDE_PBUF]; }
+    int nv[SDSM_WIDE_MAX_G], nvt = 0;                            // values of member m (uniform), of all members
+#pragma unroll
+    for (int m = 0; m < SDSM_WIDE_MAX_G; m++) {
+        int nf = uni((int)nfd[m]);
+        nf = nf < 0 ? 0 : nf > (SDSM_WIDE_FCAP - 8) / K ? (SDSM_WIDE_FCAP - 8) / K : nf;   // (run_pass never publishes more: a block is never read beyond its end)
+        nv[m] = nf * K; nvt += nv[m];
+    }
+    for (int i0 = 0; i0 < nvt; i0 += 64) {
+        int r = i0 + (tid & 63), mm = 0;
+#pragma unroll
+        for (int m = 0; m < SDSM_WIDE_MAX_G; m++) if (mm == m && r >= nv[m]) { r -= nv[m]; mm = m + 1; }
+        double val = 0;
+        if (mm < c.wG) val = gf[(size_t)mm * SDSM_WIDE_PBUF + 1 + r];
+        const int hi32 = __double2hiint(val), lo32 = __double2loint(val);
+        const int cnt = nvt - i0 < 64 ? nvt - i0 : 64;
+        for (int i = 0; i < cnt; i += K) {
+#pragma unroll
+            for (int k = 0; k < K; k++) run[k] += __hiloint2double(__builtin_amdgcn_readlane(hi32, i + k), __builtin_amdgcn_readlane(lo32, i + k));
         }
     }
 #pragma unroll
@@ -549,26 +614,72 @@ __device__ __forceinline__ void poly_surface(const RunPix &rp, const double *xv,
 #pragma unroll
     for (int k = 0; k < SDSM_RUN; k++) S[k] = (rp.v[k] * rp.v[k]) * xv[1] + rp.v[k] * b2 + a;
 }
+// The same with the multiply-adds WRITTEN OUT.  poly_surface leaves the compiler the choice of the product it fuses in 2 u x2 + 2 x4 (and takes
+// it per call site, anew whenever the code around the call changes: the solve kernels fused the first product in eval_full and in the mask
+// tail and the second one in eval_value -- results that differ in the last bit of some pixels, and with them the last digits of the energies).
+// The solver's call sites name the form they have always had; the point evaluators (sdsm_k_eval, sdsm_k_step_probe) keep poly_surface.
+enum { POLY_AUTO = 0, POLY_FIRST = 1, POLY_SECOND = 2 };
+template <int FORM>
+__device__ __forceinline__ void poly_surface_as(const RunPix &rp, const double *xv, double (&S)[SDSM_RUN])
+{
+    if constexpr (FORM == POLY_AUTO) poly_surface(rp, xv, S);
+    else {
+        const double uu = rp.u * rp.u, u2 = 2 * rp.u;
+        const double a = fma(uu, xv[0], u2 * xv[3]) + xv[5];
+        const double b2 = FORM == POLY_FIRST ? fma(u2, xv[2], 2 * xv[4]) : fma(2.0, xv[4], u2 * xv[2]);
+#pragma unroll
+        for (int k = 0; k < SDSM_RUN; k++) S[k] = fma(rp.v[k] * rp.v[k], xv[1], rp.v[k] * b2) + a;
+    }
+}
 
 // entries the rows of the chunk of position p are padded to (uniform: one scalar load per wavefront and chunk)
 __device__ __forceinline__ int chunk_entries(const Cand &c, int pb) { return (int)c.aux[pb >> 6]; }
 
 // The entries of a run, EBATCH at a time: entry j of run position pl is element j * NR + pl of the candidate's block -- byte offsets
 // (32 bits) that advance by NR elements per entry.  kh is uniform (the chunk's padded entry count): the tests on it are scalar branches.
+// (The uniform part of the offsets advanced in scalar registers -- base pointers stepped by NR elements, the lane's offset constant -- saves the
+// vector adds but needs four more scalar registers where the solver's uniform state already spills: class 1 then had 20 bytes of scratch.)
 struct EntryCursor { unsigned ow, oi, sw, si; };
 __device__ __forceinline__ EntryCursor entry_cursor(const Cand &c, int pl)
 {
     EntryCursor e; e.ow = (unsigned)pl * 16u; e.oi = (unsigned)pl * 4u; e.sw = (unsigned)c.NR * 16u; e.si = (unsigned)c.NR * 4u;
     return e;
 }
-__device__ __forceinline__ void load_entries(const Cand &c, EntryCursor &e, int j0, int kh, f32x4 (&w)[EBATCH], uint32_t (&im)[EBATCH])
+// A FULL batch (j0 + EBATCH <= kh): straight-line code, no test per entry, nothing to initialise
+__device__ __forceinline__ void load_entries_full(const Cand &c, EntryCursor &e, f32x4 *w, uint32_t *im)
+{
+#pragma unroll
+    for (int t = 0; t < EBATCH; t++) { w[t] = gld(c.ell_w4, e.ow + (unsigned)t * e.sw); im[t] = gld(c.ell_im, e.oi + (unsigned)t * e.si); }
+    e.ow += EBATCH * e.sw; e.oi += EBATCH * e.si;
+}
+// The tail of a run's list (rem < EBATCH entries; rem <= 0: none): the entries beyond it come out as zeros
+__device__ __forceinline__ void load_entries_tail(const Cand &c, EntryCursor &e, int rem, f32x4 *w, uint32_t *im)
 {
 #pragma unroll
     for (int t = 0; t < EBATCH; t++) {
         w[t].x = 0.f; w[t].y = 0.f; w[t].z = 0.f; w[t].w = 0.f; im[t] = 0;
-        if (j0 + t < kh) { w[t] = gld(c.ell_w4, e.ow + (unsigned)t * e.sw); im[t] = gld(c.ell_im, e.oi + (unsigned)t * e.si); }
+        if (t < rem) { w[t] = gld(c.ell_w4, e.ow + (unsigned)t * e.sw); im[t] = gld(c.ell_im, e.oi + (unsigned)t * e.si); }
     }
     e.ow += EBATCH * e.sw; e.oi += EBATCH * e.si;
+}
+// entries [j0, kh) of a run through use(w, im): whole batches, then one guarded tail
+template <class Use>
+__device__ __forceinline__ void for_entries(const Cand &c, EntryCursor &ec, int j0, int kh, Use &&use)
+{
+    for (; j0 + EBATCH <= kh; j0 += EBATCH) {
+        f32x4 w[EBATCH];
+        uint32_t im[EBATCH];
+        load_entries_full(c, ec, w, im);
+#pragma unroll
+        for (int t = 0; t < EBATCH; t++) use(j0 + t, w[t], im[t]);
+    }
+    if (j0 < kh) {
+        f32x4 w[EBATCH];
+        uint32_t im[EBATCH];
+        load_entries_tail(c, ec, kh - j0, w, im);
+#pragma unroll
+        for (int t = 0; t < EBATCH - 1; t++) if (j0 + t < kh) use(j0 + t, w[t], im[t]);
+    }
 }
 
 // S += G~ xi for the four pixels of the run at position pl: all loads of a batch before the first use
@@ -576,43 +687,27 @@ template <int STRIDE>
 __device__ __forceinline__ void smooth_add(const Cand &c, const double *xv, int pl, int kh, double (&S)[SDSM_RUN])
 {
     EntryCursor ec = entry_cursor(c, pl);
-    for (int j0 = 0; j0 < kh; j0 += EBATCH) {
-        f32x4 w[EBATCH];
-        uint32_t im[EBATCH];
-        load_entries(c, ec, j0, kh, w, im);
-#pragma unroll
-        for (int t = 0; t < EBATCH; t++) {
-            if (j0 + t < kh) {
-                const double xi = xv[STRIDE * (6 + (int)(im[t] & 0xffffu))];
-                S[0] += (double)w[t].x * xi; S[1] += (double)w[t].y * xi; S[2] += (double)w[t].z * xi; S[3] += (double)w[t].w * xi;
-            }
-        }
-    }
+    for_entries(c, ec, 0, kh, [&](int, const f32x4 &w, uint32_t im) {
+        const double xi = xv[STRIDE * (6 + (int)(im & 0xffffu))];
+        S[0] += (double)w.x * xi; S[1] += (double)w.y * xi; S[2] += (double)w.z * xi; S[3] += (double)w.w * xi;
+    });
 }
 
 // The same for S(x) and S(d) at once: xd holds the pairs (x_j, d_j), one 16-byte LDS read per entry
 __device__ __forceinline__ void smooth_add2(const Cand &c, const double *xd, int pl, int kh, double (&S0)[SDSM_RUN], double (&Sd)[SDSM_RUN])
 {
     EntryCursor ec = entry_cursor(c, pl);
-    for (int j0 = 0; j0 < kh; j0 += EBATCH) {
-        f32x4 w[EBATCH];
-        uint32_t im[EBATCH];
-        load_entries(c, ec, j0, kh, w, im);
-#pragma unroll
-        for (int t = 0; t < EBATCH; t++) {
-            if (j0 + t < kh) {
-                const double *pr = xd + 2 * (6 + (int)(im[t] & 0xffffu));
-                const double xi = pr[0], di = pr[1];
-                const double w0 = (double)w[t].x, w1 = (double)w[t].y, w2 = (double)w[t].z, w3 = (double)w[t].w;
-                S0[0] += w0 * xi; S0[1] += w1 * xi; S0[2] += w2 * xi; S0[3] += w3 * xi;
-                Sd[0] += w0 * di; Sd[1] += w1 * di; Sd[2] += w2 * di; Sd[3] += w3 * di;
-            }
-        }
-    }
+    for_entries(c, ec, 0, kh, [&](int, const f32x4 &w, uint32_t im) {
+        const double *pr = xd + 2 * (6 + (int)(im & 0xffffu));
+        const double xi = pr[0], di = pr[1];
+        const double w0 = (double)w.x, w1 = (double)w.y, w2 = (double)w.z, w3 = (double)w.w;
+        S0[0] += w0 * xi; S0[1] += w1 * xi; S0[2] += w2 * xi; S0[3] += w3 * xi;
+        Sd[0] += w0 * di; Sd[1] += w1 * di; Sd[2] += w2 * di; Sd[3] += w3 * di;
+    });
 }
 
 // psi only (final step check, start values).  Result broadcast to all threads.
-template <class L>
+template <class L, int POLY = POLY_AUTO>
 __device__ __forceinline__ double eval_value(const Cand &c, int xo, int M)
 {
     const double *xv = SD + xo;
@@ -622,7 +717,7 @@ __device__ __forceinline__ double eval_value(const Cand &c, int xo, int M)
         const int pl = load_pos(c, p, active);
         load_run(c, pl, active, rp);
         double S[SDSM_RUN];
-        poly_surface(rp, xv, S);
+        poly_surface_as<POLY>(rp, xv, S);
         if (M > 0) smooth_add<1>(c, xv, pl, chunk_entries(c, __builtin_amdgcn_readfirstlane(p)), S);
         double ps = 0;
 #pragma unroll
@@ -839,7 +934,7 @@ template <class L> __device__ __forceinline__ bool sums_kept(const Cand &c, int 
     if constexpr (L::GLOBAL_H) return false; else return M > 0 && 2 * c.env_size + 6 + M <= L::EMAX;
 }
 
-template <class L>
+template <class L, int POLY = POLY_AUTO>
 __device__ __forceinline__ double eval_full(const Cand &c, int M, double reg_mu, double psi_bound, bool same_point PROF_PARAM)
 {
     long long pt = PROF_NOW();
@@ -883,7 +978,7 @@ __device__ __forceinline__ double eval_full(const Cand &c, int M, double reg_mu,
         load_run(c, pl, active, rp);
         const int kh = M > 0 ? chunk_entries(c, __builtin_amdgcn_readfirstlane(p)) : 0;
         double S[SDSM_RUN];
-        poly_surface(rp, xv, S);
+        poly_surface_as<POLY>(rp, xv, S);
         if (M > 0) smooth_add<1>(c, xv, pl, kh, S);
         double r[SDSM_RUN], d[SDSM_RUN], psum = 0;
 #pragma unroll
@@ -924,8 +1019,6 @@ __device__ __forceinline__ double eval_full(const Cand &c, int M, double reg_mu,
         // xi part.  Gradient: every entry of the run; Hessian: its leading entries (kept in registers as they pass by)
         f32x4 lw[HZREG];
         uint32_t lim[HZREG];
-#pragma unroll
-        for (int a = 0; a < HZREG; a++) { lw[a].x = 0.f; lw[a].y = 0.f; lw[a].z = 0.f; lw[a].w = 0.f; lim[a] = 0; }
         int p2 = pl;
         asm volatile("" : "+v"(p2));                      // (a second load of the entries, not the first one kept alive across the loss evaluation)
         EntryCursor ec = entry_cursor(c, p2);
@@ -937,25 +1030,18 @@ __device__ __forceinline__ double eval_full(const Cand &c, int M, double reg_mu,
         };
         static_assert(HZREG % EBATCH == 0, "the leading entries are taken from whole batches");
 #pragma unroll
-        for (int jb = 0; jb < HZREG; jb += EBATCH) {          // the first batch(es) in straight-line code: they include the HZREG leading entries
-            f32x4 w[EBATCH];
-            uint32_t im[EBATCH];
-            load_entries(c, ec, jb, kh, w, im);
+        for (int jb = 0; jb < HZREG; jb += EBATCH) {          // the first batch(es) go straight into the registers of the HZREG leading entries
+            if (jb + EBATCH <= kh) {
+                load_entries_full(c, ec, lw + jb, lim + jb);
 #pragma unroll
-            for (int t = 0; t < EBATCH; t++) {
-                if (jb + t < kh) {
-                    if (jb + t < rp.nnz) grad_entry(w[t], im[t]);
-                    if (jb + t < HZREG) { lw[jb + t] = w[t]; lim[jb + t] = im[t]; }
-                }
+                for (int t = 0; t < EBATCH; t++) if (jb + t < rp.nnz) grad_entry(lw[jb + t], lim[jb + t]);
+            } else {                                          // (kh <= jb: nothing is loaded, the registers are zeros)
+                load_entries_tail(c, ec, kh - jb, lw + jb, lim + jb);
+#pragma unroll
+                for (int t = 0; t < EBATCH - 1; t++) if (jb + t < kh && jb + t < rp.nnz) grad_entry(lw[jb + t], lim[jb + t]);
             }
         }
-        for (int j0 = HZREG; j0 < kh; j0 += EBATCH) {
-            f32x4 w[EBATCH];
-            uint32_t im[EBATCH];
-            load_entries(c, ec, j0, kh, w, im);
-#pragma unroll
-            for (int t = 0; t < EBATCH; t++) if (j0 + t < kh && j0 + t < rp.nnz) grad_entry(w[t], im[t]);
-        }
+        for_entries(c, ec, HZREG, kh, [&](int j, const f32x4 &w, uint32_t im) { if (j < rp.nnz) grad_entry(w, im); });
         const double chd = fx_const(fxh_hi);
         const double v2[SDSM_RUN] = {rp.v[0] * rp.v[0], rp.v[1] * rp.v[1], rp.v[2] * rp.v[2], rp.v[3] * rp.v[3]};
         const double u2 = 2 * u;
@@ -969,16 +1055,14 @@ __device__ __forceinline__ double eval_full(const Cand &c, int M, double reg_mu,
             fx_add(&Hp[rbt[3] + ia], m0, u2, fxh_hi); fx_add(&Hp[rbt[4] + ia], m1, 2.0, fxh_hi); fx_add(&Hp[rbt[5] + ia], m0, 1.0, fxh_hi);
         };
         if (hfast) {
-            int rbs[HZREG];                                                          // row bases of the leading entries
-#pragma unroll
-            for (int a = 0; a < HZREG; a++) {
-                rbs[a] = a < rp.hz ? rbp[lim[a] & 0xffffu] : 0;
-                const unsigned la = lim[a] >> 16;                                    // weights of pixels for which the entry is not a leading one: 0
-                lw[a].x = (la & 1u) ? lw[a].x : 0.f; lw[a].y = (la & 2u) ? lw[a].y : 0.f; lw[a].z = (la & 4u) ? lw[a].z : 0.f; lw[a].w = (la & 8u) ? lw[a].w : 0.f;
-            }
+            // Entry a is masked, and its row base looked up, where the lane has that many leading entries (a run has about three): the entries b <= a
+            // it is paired with were masked in their own turn, and nothing reads the registers of the entries beyond rp.hz.
 #pragma unroll
             for (int a = 0; a < HZREG; a++) {
                 if (a < rp.hz) {
+                    const int rba = rbp[lim[a] & 0xffffu];                           // row base of the leading entry
+                    const unsigned la = lim[a] >> 16;                                // weights of pixels for which the entry is not a leading one: 0
+                    lw[a].x = (la & 1u) ? lw[a].x : 0.f; lw[a].y = (la & 2u) ? lw[a].y : 0.f; lw[a].z = (la & 4u) ? lw[a].z : 0.f; lw[a].w = (la & 8u) ? lw[a].w : 0.f;
                     const double dw[SDSM_RUN] = {d[0] * (double)lw[a].x, d[1] * (double)lw[a].y, d[2] * (double)lw[a].z, d[3] * (double)lw[a].w};
                     theta_rows((int)(lim[a] & 0xffffu), dw);
 #pragma unroll
@@ -986,7 +1070,7 @@ __device__ __forceinline__ double eval_full(const Cand &c, int M, double reg_mu,
                         if ((lim[a] >> 16) & (lim[b] >> 16)) {                       // some pixel couples the two
                             double acc = fma(dw[0], (double)lw[b].x, chd);
                             acc = fma(dw[1], (double)lw[b].y, acc); acc = fma(dw[2], (double)lw[b].z, acc); acc = fma(dw[3], (double)lw[b].w, acc);
-                            fx_commit(&Hp[rbs[a] + (int)(lim[b] & 0xffffu)], acc, fxh_hi);
+                            fx_commit(&Hp[rba + (int)(lim[b] & 0xffffu)], acc, fxh_hi);
                         }
                     }
                 }
@@ -1543,7 +1627,7 @@ __device__ __forceinline__ int newton(const Cand &c, int M, int max_iters, doubl
     for (;;) {
         // (EV_RETRY, EV_CHECK: at the point of the last evaluation -- both follow a factor_solve of the Hessian of exactly that evaluation;
         // a rejected speculative step goes on to the line search and a new iterate -- eval_full takes the sums it kept there)
-        const double pe = eval_full<L>(c, M, why == EV_SPEC ? mu_spec : mu, bound, why == EV_RETRY || why == EV_CHECK PROF_ARG);
+        const double pe = eval_full<L, POLY_FIRST>(c, M, why == EV_SPEC ? mu_spec : mu, bound, why == EV_RETRY || why == EV_CHECK PROF_ARG);
         (*ev_full)++;
         long long pt = PROF_NOW();
         bool line = false;
@@ -1586,7 +1670,7 @@ __device__ __forceinline__ int newton(const Cand &c, int M, int max_iters, doubl
                 // vanishing Hessian and the unguarded step can be arbitrarily bad)
                 for (int i = tid; i < n; i += L::WGS) xt[i] = x[i] + d[i];
                 __syncthreads();
-                const double psit = eval_value<L>(c, L::XT, M);
+                const double psit = eval_value<L, POLY_SECOND>(c, L::XT, M);
                 (*ev_value)++;
                 if (isfinite(psit) && c.scale * psit <= f) {
                     for (int i = tid; i < n; i += L::WGS) x[i] = xt[i];
@@ -1780,7 +1864,7 @@ __device__ __forceinline__ void solve_candidate(const BatchParams &P, int ci, in
                 for (int i = 0; i < 6; i++) xt[i] = thl[i];
             }
             __syncthreads();
-            double vinit = eval_value<L>(c, L::XT, 0);
+            double vinit = eval_value<L, POLY_SECOND>(c, L::XT, 0);
             ev_value++;
             if (vinit > psi_ell) continue;                                      // objects.py:341-342
             vinit_keep = uni(vinit);
@@ -1842,7 +1926,7 @@ __device__ __forceinline__ void solve_candidate(const BatchParams &P, int ci, in
                     for (int i = tid; i < NMAX; i += L::WGS) xt[i] = i < 6 ? keep[i] : (x0 && i < 6 + Mfull ? x0[i] : 0);
                 }
                 __syncthreads();
-                const double vi = eval_value<L>(c, L::XT, Mfull);
+                const double vi = eval_value<L, POLY_SECOND>(c, L::XT, Mfull);
                 ev_value++;
                 if (s == 2 || psi > vi * fresh(1 + 1e-12)) {
                     fallback = true;
@@ -1874,7 +1958,7 @@ __device__ __forceinline__ void solve_candidate(const BatchParams &P, int ci, in
             const int pl = load_pos(c, p, active);
             load_run(c, pl, active, rp);
             double Sv[SDSM_RUN];
-            poly_surface(rp, x, Sv);
+            poly_surface_as<POLY_FIRST>(rp, x, Sv);
             if (Mfull > 0) smooth_add<1>(c, x, pl, chunk_entries(c, pb), Sv);
             if (active) {
                 const uint32_t rc = c.crop_rc[p];
