@@ -1043,6 +1043,77 @@ int sdsm_depth_labels_multi(const sdsm_set_image *images, int n_images, const in
                             const int64_t *d_ws_off, void *d_ws, int64_t ws_pixels, size_t ws_bytes, sdsm_depth_record *d_out,
                             sdsm_depth_shell_record *d_shells, int32_t *d_bad, void *stream);
 
+/* ---- skeleton tables: midlines, end and branch points, length (no reference counterpart; the definitions are skeleton_objects_host and
+ * skeleton_labels_host of superdsm_amd/skeleton.py) ----------------------------------------------------------------------------------------
+ * The form of an object along its own midline, in integers only.  An object is the set P of the set bits of its fragment; everything
+ * else -- the rest of its box, other objects or labels, the outside of the image -- is 0.
+ * Neighbourhood code: bit k of code(p) is the pixel at offset k of the ring, clockwise from north: N(-1,0), NE(-1,1), E(0,1), SE(1,1),
+ * S(1,0), SW(1,-1), W(0,-1), NW(-1,-1); x_k is that bit, indices modulo 8.
+ * Removal rule: for a direction d of N, S, E, W (ring bits 0, 4, 2, 6) deletable(code, d) holds iff x_d = 0 (a border pixel on side d),
+ * the 8-connectivity number sum over k in {0, 2, 4, 6} of (1 - x_k) (x_{k+1} | x_{k+2}) is 1 (the pixel is simple), and at least two of
+ * the eight x_k are set (neither an end nor isolated).  41 of the 256 codes are deletable per direction.
+ * Thinning: a subiteration for d removes, simultaneously, every pixel of X with deletable(code, d), the codes taken before any removal
+ * of that subiteration; a cycle is the four subiterations N, S, E, W; the skeleton S of P is X after repeating cycles from X = P until
+ * one whole cycle removes nothing, and `cycles` counts the cycles that removed a pixel.  S is a subset of P with the 8-connected parts
+ * and the holes of P.
+ * The kernel thins a box of at most 64 x 64 in the registers of one wavefront, a box of at most SDSM_SKELETON_LDS_WORDS row-aligned
+ * 64-bit words (h * ceil(w / 64)) in LDS, and a larger one in sdsm_skeleton_workspace_words(h, w) 64-bit words of the caller's workspace:
+ * the same bytes, more slowly (see DESIGN.md "Limits").  The decision is by the box, not by the pixels in it.  Every count is an
+ * integer, there is no atomic, and every record and skeleton window is written completely by its own wavefront or workgroup: the bytes
+ * do not depend on the order, the launch or the set size.  sdsm_skeleton_record: 48 bytes. */
+#define SDSM_SKELETON_LDS_WORDS 3072    /* 64-bit words of a box whose thinning is held in LDS (two planes, 48 KB: three workgroups a CU) */
+#define SDSM_SKELETON_NO_WORKSPACE (1 << 30)   /* flag bit 30 of sdsm_skeleton_record */
+typedef struct {
+    int32_t area;                       /* pixels of P */
+    int32_t n_skeleton;                 /* pixels of S */
+    int32_t n_end;                      /* pixels of S with exactly one ring neighbour in S */
+    int32_t n_isolated;                 /* pixels of S with none */
+    int32_t n_branch;                   /* pixels of S with >= 3 transitions 0 -> 1 around their ring in S */
+    int32_t n_orth;                     /* unordered pairs of 4-adjacent pixels of S */
+    int32_t n_diag;                     /* unordered pairs of diagonally adjacent pixels of S whose two common 4-neighbours are outside S */
+    int32_t cycles;                     /* cycles that removed a pixel */
+    int32_t first_row, first_col;       /* the first pixel of S in raster order, image coordinates */
+    int32_t flags;                      /* bit 0: the bounding box of P touches the image frame; bit 30: the box needs workspace and the call
+                                           names none for it (the record is then zero and its skeleton window is not written) */
+    int32_t reserved;                   /* 0 */
+} sdsm_skeleton_record;
+/* Host helpers (no device access), by the inline functions the kernel uses (csrc/sdsm_skeleton.h).  sdsm_skeleton_deletable: the removal
+ * rule, 1 or 0; -1 for a code outside 0 .. 255 or a direction that is none of 0, 2, 4, 6.  sdsm_skeleton_workspace_words: the 64-bit
+ * workspace words an object with an h x w box needs, 2 h ceil(w / 64) above SDSM_SKELETON_LDS_WORDS and 0 for a box that LDS or a
+ * wavefront holds or an empty one.  sdsm_skeleton_thin: thins one flat-packed h x w window (bit r w + c of ceil(h w / 32) uint32 words;
+ * the bits past h w are ignored) on the CPU with the header's word functions into `skeleton` (the same layout, the bits past h w clear;
+ * it may be `bits` itself); returns `cycles`, or -1 for h < 1, w < 1, h w >= 2^31 or a null argument. */
+int sdsm_skeleton_deletable(int code, int direction);
+int64_t sdsm_skeleton_workspace_words(int h, int w);
+int sdsm_skeleton_thin(int h, int w, const uint32_t *bits, uint32_t *skeleton);
+/* d_out[i] and the skeleton window of object i of d_boxes / d_bits_off (n of them; d_obj_image int32, NULL for one image).  d_skeleton:
+ * as many words as d_bits, the window of object i at d_bits_off[i] in the layout of its fragment; its contents do not matter.  The bits of a
+ * fragment past h * w are ignored; a fragment without a set bit gives the zero record and a clear window; an object whose box is empty or
+ * leaves its image gives the zero record, and nothing is read or written for it.  Workspace: object i with
+ * sdsm_skeleton_workspace_words(h, w) > 0 owns that many 64-bit words of d_ws from word d_ws_off[i] on (d_ws_off: n int64 on the device;
+ * entries of smaller objects are not read; the ranges must not overlap, which is the caller's duty); ws_words is the number of words the
+ * offsets name in all and ws_bytes the size of d_ws: ws_words * 8 > ws_bytes is an argument error before any launch, and an object whose
+ * range does not lie in 0 .. ws_words gets flag bit 30.  d_ws_off and d_ws may be NULL with ws_words == 0.  n == 0: no launch. */
+int sdsm_skeleton_objects(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, const int64_t *d_ws_off,
+                          void *d_ws, int64_t ws_words, size_t ws_bytes, sdsm_skeleton_record *d_out, uint32_t *d_skeleton, void *stream);
+int sdsm_skeleton_objects_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                                const int64_t *d_bits_off, const uint32_t *d_bits, const int64_t *d_ws_off, void *d_ws, int64_t ws_words,
+                                size_t ws_bytes, sdsm_skeleton_record *d_out, uint32_t *d_skeleton, void *stream);
+/* The same for labels of label maps, by the windows of sdsm_shape_labels: the caller names n windows (d_obj_image, d_boxes, d_bits_off
+ * into the workspace d_bits of window_words <= SDSM_SHAPE_MAX_WINDOW_WORDS words, which the call clears) and d_label_obj; a first kernel
+ * sets the bit of every pixel in the window of its label -- a pixel of another label is outside --, then the windows are thinned as
+ * objects.  d_obj_label: the label of window i (n int32).  d_map (int32, the layout of d_labels; may be NULL) is cleared in stream order,
+ * then every skeleton pixel receives its label.  d_bad as there. */
+int sdsm_skeleton_labels(int H, int W, const int32_t *d_labels, int n_labels, const int32_t *d_label_obj, int n, const int32_t *d_boxes,
+                         const int64_t *d_bits_off, int64_t window_words, uint32_t *d_bits, const int32_t *d_obj_label, const int64_t *d_ws_off,
+                         void *d_ws, int64_t ws_words, size_t ws_bytes, sdsm_skeleton_record *d_out, uint32_t *d_skeleton, int32_t *d_map,
+                         int32_t *d_bad, void *stream);
+int sdsm_skeleton_labels_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int64_t *rec_off, const int32_t *n_labels,
+                               const int32_t *d_label_obj, int n, const int32_t *d_obj_image, const int32_t *d_boxes, const int64_t *d_bits_off,
+                               int64_t window_words, uint32_t *d_bits, const int32_t *d_obj_label, const int64_t *d_ws_off, void *d_ws,
+                               int64_t ws_words, size_t ws_bytes, sdsm_skeleton_record *d_out, uint32_t *d_skeleton, int32_t *d_map, int32_t *d_bad,
+                               void *stream);
+
 /* ---- host-side combinatorial steps of the stage (no device access) -------------------------------------------------------------
  * Approximate min-weight set cover (superdsm/minsetcover.py:4-88: greedy + merge phase, retried with beta * gamma on up to max_iter
  * levels) and greedy max-weight set packing (superdsm/maxsetpack.py:8-24) over n objects whose footprints are bit sets of `words`

@@ -137,6 +137,13 @@ _DEPTH_SHELL_FIELDS = [('count', 'i8'), ('n_finite', 'i8'), ('gsum_lo', 'u8'), (
 DEPTH_RECORD_DTYPE = np.dtype(_DEPTH_FIELDS)                                       # sdsm_depth_record
 DEPTH_SHELL_DTYPE = np.dtype(_DEPTH_SHELL_FIELDS)                                  # sdsm_depth_shell_record
 assert DEPTH_RECORD_DTYPE.itemsize == 80 and DEPTH_SHELL_DTYPE.itemsize == 32
+SKELETON_LDS_WORDS = 3072           # SDSM_SKELETON_LDS_WORDS: 64-bit words (h * ceil(w / 64)) of a box whose thinning is held in LDS
+SKELETON_WAVE_SIDE = 64             # a box of at most 64 x 64 is thinned in the registers of one wavefront
+SKELETON_NO_WORKSPACE = 1 << 30     # flag bit 30 of sdsm_skeleton_record
+_SKELETON_FIELDS = [(name, 'i4') for name in ('area', 'n_skeleton', 'n_end', 'n_isolated', 'n_branch', 'n_orth', 'n_diag', 'cycles', 'first_row', 'first_col',
+                                              'flags', 'reserved')]
+SKELETON_RECORD_DTYPE = np.dtype(_SKELETON_FIELDS)                                 # sdsm_skeleton_record
+assert SKELETON_RECORD_DTYPE.itemsize == 48
 
 
 class MeasureRecord(C.Structure):
@@ -278,6 +285,14 @@ SYMBOLS = {
     'sdsm_depth_labels': (_i32, [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _sz, _vp, _vp, _vp, _vp]),
     'sdsm_depth_labels_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp,
                                        _vp, _vp, _i32, _vp, _vp, _i64, _sz, _vp, _vp, _vp, _vp]),
+    'sdsm_skeleton_deletable': (_i32, [_i32, _i32]),
+    'sdsm_skeleton_workspace_words': (_i64, [_i32, _i32]),
+    'sdsm_skeleton_thin': (_i32, [_i32, _i32, _vp, _vp]),
+    'sdsm_skeleton_objects': (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _sz, _vp, _vp, _vp]),
+    'sdsm_skeleton_objects_multi': (_i32, [C.POINTER(SetImage), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _sz, _vp, _vp, _vp]),
+    'sdsm_skeleton_labels': (_i32, [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _sz, _vp, _vp, _vp, _vp, _vp]),
+    'sdsm_skeleton_labels_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp,
+                                          _vp, _vp, _i64, _sz, _vp, _vp, _vp, _vp, _vp]),
     'sdsm_overlap_pairs': (_i32, [_i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     'sdsm_overlap_pairs_multi': (_i32, [C.POINTER(SetImage), _i32, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _vp, _vp, _vp, _vp]),
     'sdsm_neighbour_halfwidth': (_i32, [_i32, _i32]),

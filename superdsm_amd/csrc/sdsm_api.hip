@@ -1111,6 +1111,73 @@ extern "C" int sdsm_depth_labels(int H, int W, const int32_t *d_labels, int n_la
                                    d_scale_exp, n_shells, d_ws_off, d_ws, ws_pixels, ws_bytes, d_out, d_shells, d_bad, stream);
 }
 
+// ---- skeleton tables (sdsm_skeleton.hip; the label form fills its windows with the scatter step of sdsm_shape.hip) --------------------------
+extern "C" hipError_t sdsm_skeleton_objects_impl(const sdsm_set_image *images, int n_images, int n, const int32_t *obj_image, const int32_t *boxes,
+                                                 const int64_t *bits_off, const uint32_t *bits, const int64_t *d_ws_off, void *d_ws, int64_t ws_words,
+                                                 sdsm_skeleton_record *out, uint32_t *skel, const int32_t *obj_label, int32_t *map, hipStream_t stream);
+
+// the workspace and the outputs of a call for n objects; null: fine
+static const char *skeleton_args_bad(int n, const int64_t *d_ws_off, const void *d_ws, int64_t ws_words, size_t ws_bytes, const void *d_out, const void *d_skeleton)
+{
+    if (ws_words < 0 || (ws_words > 0 && (!d_ws_off || !d_ws))) return "ws_words >= 0 and, with ws_words > 0, d_ws_off and d_ws required";
+    if ((uint64_t)ws_words > ws_bytes / 8) return "the workspace is too small for the boxes named (8 bytes per word)";
+    if (n > 0 && (!d_out || !d_skeleton)) return "null argument";
+    return nullptr;
+}
+
+extern "C" int sdsm_skeleton_objects_multi(const sdsm_set_image *images, int n_images, int n, const int32_t *d_obj_image, const int32_t *d_boxes,
+                                           const int64_t *d_bits_off, const uint32_t *d_bits, const int64_t *d_ws_off, void *d_ws, int64_t ws_words,
+                                           size_t ws_bytes, sdsm_skeleton_record *d_out, uint32_t *d_skeleton, void *stream)
+{
+    SET_TABLE("sdsm_skeleton_objects", SET_SIDES | SET_PIXELS);
+    const char *why = packed_objects_bad(n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits);
+    if (!why) why = skeleton_args_bad(n, d_ws_off, d_ws, ws_words, ws_bytes, d_out, d_skeleton);
+    if (why) return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_skeleton_objects: ") + why);
+    hipError_t e = sdsm_skeleton_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_ws_off, d_ws, ws_words, d_out, d_skeleton, nullptr,
+                                              nullptr, (hipStream_t)stream);
+    SET_DONE("sdsm_skeleton_objects");
+}
+
+extern "C" int sdsm_skeleton_objects(int H, int W, int n, const int32_t *d_boxes, const int64_t *d_bits_off, const uint32_t *d_bits, const int64_t *d_ws_off,
+                                     void *d_ws, int64_t ws_words, size_t ws_bytes, sdsm_skeleton_record *d_out, uint32_t *d_skeleton, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    return sdsm_skeleton_objects_multi(&one, 1, n, nullptr, d_boxes, d_bits_off, d_bits, d_ws_off, d_ws, ws_words, ws_bytes, d_out, d_skeleton, stream);
+}
+
+extern "C" int sdsm_skeleton_labels_multi(const sdsm_set_image *images, int n_images, const int32_t *d_labels, const int64_t *rec_off, const int32_t *n_labels,
+                                          const int32_t *d_label_obj, int n, const int32_t *d_obj_image, const int32_t *d_boxes, const int64_t *d_bits_off,
+                                          int64_t window_words, uint32_t *d_bits, const int32_t *d_obj_label, const int64_t *d_ws_off, void *d_ws,
+                                          int64_t ws_words, size_t ws_bytes, sdsm_skeleton_record *d_out, uint32_t *d_skeleton, int32_t *d_map, int32_t *d_bad,
+                                          void *stream)
+{
+    SET_TABLE("sdsm_skeleton_labels", SET_SIDES | SET_PIXELS);
+    const char *why = skeleton_args_bad(n, d_ws_off, d_ws, ws_words, ws_bytes, d_out, d_skeleton);
+    if (!why && n > 0 && !d_obj_label) why = "null argument";
+    if (why) return fail(SDSM_ERR_ARGUMENT, std::string("sdsm_skeleton_labels: ") + why);
+    if (int rc = label_windows("sdsm_skeleton_labels", images, n_images, d_labels, rec_off, n_labels, d_label_obj, n, d_obj_image, d_boxes, d_bits_off,
+                               window_words, d_bits, d_bad, stream))
+        return rc;
+    hipError_t e = hipSuccess;
+    for (int i = 0; d_map && i < n_images && e == hipSuccess; i++)
+        e = hipMemsetAsync(d_map + images[i].offset, 0, sizeof(int32_t) * (size_t)images[i].H * (size_t)images[i].W, (hipStream_t)stream);
+    if (e == hipSuccess)
+        e = sdsm_skeleton_objects_impl(images, n_images, n, d_obj_image, d_boxes, d_bits_off, d_bits, d_ws_off, d_ws, ws_words, d_out, d_skeleton, d_obj_label,
+                                       d_map, (hipStream_t)stream);
+    SET_DONE("sdsm_skeleton_labels");
+}
+
+extern "C" int sdsm_skeleton_labels(int H, int W, const int32_t *d_labels, int n_labels, const int32_t *d_label_obj, int n, const int32_t *d_boxes,
+                                    const int64_t *d_bits_off, int64_t window_words, uint32_t *d_bits, const int32_t *d_obj_label, const int64_t *d_ws_off,
+                                    void *d_ws, int64_t ws_words, size_t ws_bytes, sdsm_skeleton_record *d_out, uint32_t *d_skeleton, int32_t *d_map,
+                                    int32_t *d_bad, void *stream)
+{
+    const sdsm_set_image one = {0, H, W};
+    const int64_t off = 0;
+    return sdsm_skeleton_labels_multi(&one, 1, d_labels, &off, &n_labels, d_label_obj, n, nullptr, d_boxes, d_bits_off, window_words, d_bits, d_obj_label,
+                                      d_ws_off, d_ws, ws_words, ws_bytes, d_out, d_skeleton, d_map, d_bad, stream);
+}
+
 // ---- contingency table of two label maps (sdsm_measure.hip) ---------------------------------------------------------------------------
 extern "C" hipError_t sdsm_overlap_pairs_impl(const sdsm_set_image *images, int n_images, const int32_t *d_a, const int32_t *d_b,
                                               const int64_t *table_off, const int64_t *capacity, uint64_t *d_keys, uint64_t *d_counts,

@@ -19,6 +19,7 @@
 #include "sdsm_texture.h"
 #include "sdsm_depth.h"
 #include "sdsm_parts.h"
+#include "sdsm_skeleton.h"
 
 namespace {
 
@@ -302,6 +303,58 @@ extern "C" int64_t sdsm_depth_workspace_pixels(int h, int w)
     if (h < 1 || w < 1) return 0;
     const int64_t px = (int64_t)h * w;
     return px > SDSM_DEPTH_LDS_PIXELS ? px : 0;
+}
+
+// The removal rule, the workspace of a box and the thinning of one window, by the word functions the skeleton kernel uses
+// (sdsm_skeleton.h: the same inline functions).
+static_assert(SDSM_SKELETON_LDS_WORDS == SDSM_SKELETON_LDS_WORDS_INLINE, "the limit of the header and of the inline helper");
+
+extern "C" int sdsm_skeleton_deletable(int code, int direction)
+{
+    return sdsm_skeleton_deletable_inline(code, direction);
+}
+
+extern "C" int64_t sdsm_skeleton_workspace_words(int h, int w)
+{
+    if (h < 1 || w < 1) return 0;
+    const int64_t words = (int64_t)h * (((int64_t)w + 63) / 64);
+    return (h <= 64 && w <= 64) || words <= SDSM_SKELETON_LDS_WORDS ? 0 : 2 * words;
+}
+
+extern "C" int sdsm_skeleton_thin(int h, int w, const uint32_t *bits, uint32_t *skeleton)
+{
+    if (h < 1 || w < 1 || (int64_t)h * w >= ((int64_t)1 << 31) || !bits || !skeleton) return -1;
+    const uint32_t n_bits = (uint32_t)h * (uint32_t)w, n32 = (n_bits + 31) >> 5;
+    const int nw = (w + 63) / 64;
+    std::vector<sdsm_skel_word> A((size_t)h * nw), B((size_t)h * nw);
+    for (int r = 0; r < h; r++)
+        for (int j = 0; j < nw; j++)
+            A[(size_t)r * nw + j] = sdsm_skeleton_flat_bits(bits, n32, (uint32_t)r * (uint32_t)w + 64u * (uint32_t)j, w - 64 * j < 64 ? w - 64 * j : 64);
+    const int dirs[4] = {0, 4, 2, 6};
+    int cycles = 0;
+    for (;;) {
+        bool removed = false;
+        for (int d : dirs) {
+            for (int r = 0; r < h; r++)
+                for (int j = 0; j < nw; j++) {
+                    const sdsm_skel_word *p = &A[(size_t)r * nw + j];
+                    const bool l = j > 0, rt = j + 1 < nw, u = r > 0, dn = r + 1 < h;
+                    const sdsm_skel_word up[3] = {u && l ? p[-nw - 1] : 0, u ? p[-nw] : 0, u && rt ? p[-nw + 1] : 0};
+                    const sdsm_skel_word row[3] = {l ? p[-1] : 0, p[0], rt ? p[1] : 0};
+                    const sdsm_skel_word down[3] = {dn && l ? p[nw - 1] : 0, dn ? p[nw] : 0, dn && rt ? p[nw + 1] : 0};
+                    sdsm_skel_word n[8];
+                    sdsm_skeleton_planes(up, row, down, n);
+                    const sdsm_skel_word rm = sdsm_skeleton_remove(row[1], n, d);
+                    B[(size_t)r * nw + j] = row[1] & ~rm;
+                    removed |= rm != 0;
+                }
+            A.swap(B);
+        }
+        if (!removed) break;
+        cycles++;
+    }
+    for (uint32_t k = 0; k < n32; k++) skeleton[k] = sdsm_skeleton_flat_word(A.data(), (uint32_t)w, (uint32_t)nw, n_bits, k);
+    return cycles;
 }
 
 // The half-width of a row of the disk and the first probe position of a pair, as the neighbourhood kernel takes them (sdsm_neighbours.h:
